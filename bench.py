@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline bench: faces/sec of 3DMM decode + depth render, batch 64 @ 200x200, fp32 (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,8 +12,11 @@ synthetic assets of SURVEY.md 8(d) (N = 53,215, T = 105,840, 199 + 29 components
 faces (weak scaling; the path has no collective), the K steps are bracketed by barrier + synchronize, the MAX
 over ranks is taken and rank 0 prints ONE JSON line.
 
-The oracle (oracle/) is used only for the `cpu_baseline` leg: its single-thread decode + render of a bounded
-sample of the same workload, timed on the host cores of the same box.
+A plain run does only what the headline needs: set-up, the warm-up, ONE timed block of exactly K steps, the outputs of the
+last step (--dump-outputs DIR) and the line.  --full adds everything else the bench measures and checks: the median of
+--repeats timed blocks with per-kernel event brackets, the serial-plan, Q30 and operator-surface legs, the oracle parity gate,
+the clock probe, the RCCL self-test / all-reduce preflight, and the `cpu_baseline` leg -- the only user of the oracle
+(oracle/): its single-thread decode + render of a bounded sample of the same workload, timed on the host cores of the same box.
 """
 import argparse
 import importlib
@@ -46,6 +49,30 @@ def algorithmic_bytes(N, T, K, H, W, B):
 
 def pkg(name):
     return importlib.import_module("3dfacerecon_amd." + name)
+
+
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs: at most this many bytes in all (a seeded sample of the faces when the batch is larger)
+DUMP_SEED = 0
+
+
+def dump_outputs(path, plan):
+    """What the timed path handed its caller in its last step -- the plan (slot) that ran it: the four output planes and the
+    decoded vertices -- as float32 .npy files under `path`, for a fixed seeded sample of the batch's faces (face_index.npy)
+    sized to stay within DUMP_BYTES."""
+    import numpy as np
+    import torch
+    outs = dict(zip(("depth", "texture_image", "normal", "tri_ind"), plan.outputs()))
+    outs["vertex_proj"] = plan.vertex_proj
+    per_face = sum(4 * t[0].numel() for t in outs.values())
+    n = max(1, min(plan.B, (DUMP_BYTES - 8 * plan.B) // per_face))
+    faces = np.sort(np.random.RandomState(DUMP_SEED).choice(plan.B, n, replace=False))
+    idx = torch.as_tensor(faces, device=plan.device)
+    os.makedirs(path, exist_ok=True)
+    if plan.device.type == "cuda":   # (a slot's planes come from ITS stream: every stream of the device drained)
+        torch.cuda.synchronize(plan.device)
+    np.save(os.path.join(path, "face_index.npy"), faces.astype(np.float64))
+    for name, t in outs.items():
+        np.save(os.path.join(path, name + ".npy"), t.index_select(0, idx).cpu().numpy().astype(np.float32, copy=False))
 
 
 def relaunch_under_torchrun(args):
@@ -253,19 +280,31 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64, help="faces per GPU per step")
     ap.add_argument("--im-size", type=int, default=200)
+    ap.add_argument("--warmup-ms", type=float, default=100.0,
+                    help="the warm-up runs --warmup steps and then, if they took less, goes on stepping until this many "
+                         "milliseconds have passed (the line's warmup_steps_run): the first ~30 ms of GPU work after the "
+                         "host-side set-up run on a chip that is still ramping its clock.  0 = exactly --warmup steps")
     ap.add_argument("--repeats", type=int, default=0,
-                    help="timed K-step blocks; the median block is reported.  0 = auto: max(10, 1600 // K) -- the first "
-                         "~30 ms of GPU work after the host-side set-up run on a chip that is still ramping its clock "
-                         "(blocks_ms_per_step in the line shows it), so the blocks have to span well beyond that for "
-                         "the median to be a steady-state block")
-    ap.add_argument("--cpu-faces", type=int, default=2048, help="faces in the cpu_baseline sample (0 = skip); 2048 ~ 10 s")
-    ap.add_argument("--graph", action="store_true", help="also report hipGraph-replay throughput")
+                    help="timed K-step blocks; the median block is reported.  0 = auto: 1 in a plain run (exactly K timed "
+                         "steps), max(10, 1600 // K) with --full -- the blocks span well beyond the clock ramp for the "
+                         "median to be a steady-state block (blocks_ms_per_step in the line shows them)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: per-kernel event brackets and the roofline "
+                         "object, the serial-plan / Q30 / operator-surface legs, the oracle parity gate, the clock probe, the "
+                         "RCCL self-test (N = 1) or all-reduce preflight (N > 1) and the CPU baseline.  Off: set-up, warm-up, "
+                         "the K timed steps, --dump-outputs and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed route computed in its last step (the four output planes "
+                         "and vertex_proj of the slot that ran it, for a fixed seeded sample of its faces, <= 60 MB in all) as "
+                         "DIR/<name>.npy, float32; rank 0's batch.  Same arguments, same inputs: two builds compare file by file")
+    ap.add_argument("--cpu-faces", type=int, default=2048, help="--full: faces in the cpu_baseline sample (0 = skip); 2048 ~ 10 s")
+    ap.add_argument("--graph", action="store_true", help="with --full: also report hipGraph-replay throughput")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --batch faces per GPU; strong: ONE --batch-face job cut into per-rank shards")
     ap.add_argument("--parity-faces", type=int, default=-1,
-                    help="faces per rank the oracle checks before the line is printed (-1 = all of them; 0 = skip, the "
+                    help="--full: faces per rank the oracle checks before the line is printed (-1 = all of them; 0 = skip, the "
                          "line then carries parity = null and must not be quoted)")
-    ap.add_argument("--no-ops-surface", action="store_true", help="skip the operator-surface leg")
+    ap.add_argument("--no-ops-surface", action="store_true", help="--full: skip the operator-surface leg")
     ap.add_argument("--route", choices=("auto", "inflight", "serial"), default="auto",
                     help="inflight: BatchesInFlight (--in-flight independent batches, each on its own stream, no edge between "
                          "them: consecutive steps go to alternating slots); serial: DecodeRenderPlan (one batch at a time, three "
@@ -275,18 +314,18 @@ def main():
                     help="inflight route: rows per screen strip of the resolver in the slots' plans (FR_PHASES_STRIP_ROWS).  -1 = "
                          "pipeline.BatchesInFlight's own choice (8 where the library alone picks 10: smaller resolver workgroups fill "
                          "the other batch's gaps), 0 = the library's choice, n = n rows.  No result bit depends on it")
-    ap.add_argument("--no-serial-leg", action="store_true", help="skip the serial plan's comparison leg (inflight route)")
+    ap.add_argument("--no-serial-leg", action="store_true", help="--full: skip the serial plan's comparison leg (inflight route)")
     ap.add_argument("--q30-levels", type=int, default=4, choices=(0, 4, 5, 7),
-                    help="also time the in-flight route with the Q30 decode (int8 matrix cores) at this many digit-product "
+                    help="--full: also time the in-flight route with the Q30 decode (int8 matrix cores) at this many digit-product "
                          "levels, parity-gated against ITS oracle, and report it beside `value` as `q30_inflight` (0 = skip; "
                          "skipped anyway when FR_DECODE_ARITH already selects Q30 for the whole run, or off the inflight route)")
     ap.add_argument("--q30-parity-faces", type=int, default=8,
-                    help="faces per slot the Q30 leg's oracle gate checks (its level-by-level oracle takes ~1 s per face)")
+                    help="--full: faces per slot the Q30 leg's oracle gate checks (its level-by-level oracle takes ~1 s per face)")
     ap.add_argument("--allreduce-mb", type=float, default=-1.0,
-                    help="N > 1: time one SUM all-reduce of this many MB on the bench's process group before the timed "
+                    help="--full, N > 1: time one SUM all-reduce of this many MB on the bench's process group before the timed "
                          "region (config 4's gradient is ~302 MB) and report bus GB/s.  -1 = 302 under nccl, 4 under gloo; 0 = skip")
     ap.add_argument("--no-rccl-selftest", action="store_true",
-                    help="N = 1: skip the one-rank RCCL self-test (utils.dist.rccl_selftest: communicator on this GPU + one "
+                    help="--full, N = 1: skip the one-rank RCCL self-test (utils.dist.rccl_selftest: communicator on this GPU + one "
                          "302 MB all-reduce through it, reported as dist.rccl_selftest)")
     ap.add_argument("--config", type=int, default=0, choices=(0, 3, 4, 5),
                     help="3 / 4 / 5: run the caller config of BASELINE.json (examples/coarse_loop.py --config N --steps K) "
@@ -338,8 +377,10 @@ def main():
         params_np = synth.sample_params_batch(B, im_size=H, beta=0.7, seed=3456 + rank)
     L = pkg("_lib").lib()
     inflight = args.route in ("auto", "inflight")
-    serial_plan = pipe.DecodeRenderPlan(net, B, H, W)
-    serial_plan.params.copy_(torch.as_tensor(params_np, device=dev))
+    serial_plan = None
+    if not inflight or args.full:   # (a plain in-flight run never touches the serial plan)
+        serial_plan = pipe.DecodeRenderPlan(net, B, H, W)
+        serial_plan.params.copy_(torch.as_tensor(params_np, device=dev))
     plan = serial_plan
     slot_params = [params_np]
     if inflight:
@@ -355,16 +396,16 @@ def main():
     torch.cuda.synchronize(dev)
 
     K, Wm = args.steps, args.warmup
-    R = args.repeats if args.repeats > 0 else max(10, 1600 // max(1, K))
-    # N > 1: one all-reduce of config 4's gradient size on the bench's own process group, before anything is timed
+    R = args.repeats if args.repeats > 0 else (max(10, 1600 // max(1, K)) if args.full else 1)
+    # N > 1, --full: one all-reduce of config 4's gradient size on the bench's own process group, before anything is timed
     ar_mb = args.allreduce_mb
     if ar_mb < 0:
         ar_mb = 0.0 if world == 1 else (302.0 if args.dist_backend == "nccl" else 4.0)
-    allreduce = dist_u.allreduce_preflight(ar_mb, device=dev) if world > 1 and ar_mb > 0 else None
+    allreduce = dist_u.allreduce_preflight(ar_mb, device=dev) if args.full and world > 1 and ar_mb > 0 else None
 
-    # The timed region -- EXACTLY K steps between barrier + synchronize brackets -- is run R times back to back and the
-    # MEDIAN block is reported (min / max alongside): at ~0.11 ms per step a single K = 20 block is 2.2 ms of wall clock,
-    # short enough for clock ramps and host jitter to move it by several per cent.
+    # The timed region -- EXACTLY K steps between barrier + synchronize brackets -- is run once in a plain run.  With --full it
+    # is run R times back to back and the MEDIAN block is reported (min / max alongside): at ~0.11 ms per step a single K = 20
+    # block is 2.2 ms of wall clock, short enough for clock ramps and host jitter to move it by several per cent.
     # Per-kernel durations are taken live, inside the timed regions, with HIP events on the launch stream -- on every
     # EV_EVERY-th step only: an event pair costs a few microseconds of stream bubble, which at ~110 us per step would
     # otherwise tax every step by ~7 %.
@@ -372,15 +413,30 @@ def main():
     # four cost the in-flight route 0.6: one bracketed step per twenty -- 80 samples per kernel at K = 20, R = 80)
     EV_EVERY, EV_FIRST = 20, 5   # steps 5, 25, 45, ...: never the block's first step (it starts on an idle chip)
 
+    def warm_up(pl):
+        """--warmup steps, then more until --warmup-ms have passed (every rank the same count: MAX over ranks).  Returns the count."""
+        is_fl = hasattr(pl, "slots")
+        t0 = time.perf_counter()
+        done, chunk = 0, Wm
+        while True:
+            for _ in range(chunk):
+                pl.submit() if is_fl else pl.step()
+            done += chunk
+            torch.cuda.synchronize(dev)
+            more = args.warmup_ms > 0 and 1e3 * (time.perf_counter() - t0) < args.warmup_ms
+            if not dist_u.max_over_ranks(1.0 if more else 0.0, device=dev):
+                return done
+            chunk = max(1, done)   # (doubling: the clock is read between rounds only)
+
     def timed_blocks(pl, with_events):
         is_fl = hasattr(pl, "slots")
-        for _ in range(Wm):
-            pl.submit() if is_fl else pl.step()
+        warm = warm_up(pl)
         # (events for every block are created up front and the per-block max over ranks is taken after the last block, so
         # that the host does nothing but barrier + synchronize + clock reads between two timed regions)
         evs = [({k: [torch.cuda.Event(enable_timing=True) for _ in range(4)] for k in range(min(EV_FIRST, K - 1), K, EV_EVERY)}
                 if with_events else {}) for _ in range(R)]
         loc, ev_all = [], []
+        last = pl
         for r in range(R):
             ev = evs[r]
             dist_u.barrier()
@@ -389,7 +445,7 @@ def main():
             for k in range(K):
                 e = ev.get(k)
                 if is_fl:        # step k goes to slot k mod S, on that slot's stream; the events are recorded on that stream
-                    pl.submit(marks=e)
+                    last = pl.submit(marks=e)
                 elif e is None:
                     pl.step()
                 else:            # the same three kernels, each bracketed by events (the render op launched phase by phase)
@@ -408,10 +464,14 @@ def main():
         blk = [dist_u.max_over_ranks(t, device=dev) for t in loc]
         order = sorted(range(R), key=lambda q: blk[q])
         med = order[(R - 1) // 2]              # the median block (lower median for an even R)
-        return blk, blk[med], loc[med], ev_all
+        return blk, blk[med], loc[med], ev_all, last, warm
 
-    blocks, elapsed, local_med, ev_all = timed_blocks(plan, True)
-    clocks = {"after_timed_blocks": clock_probe(L, dev)}   # (straight behind the last timed block: the chip is as warm as it gets)
+    blocks, elapsed, local_med, ev_all, last, warm_steps = timed_blocks(plan, args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    clocks = {}
+    if args.full:   # (straight behind the last timed block: the chip is as warm as it gets)
+        clocks["after_timed_blocks"] = clock_probe(L, dev)
     per_rank_ms = [1e3 * t / K for t in dist_u.gather_over_ranks(local_med, device=dev)]
     dist_info = dist_u.describe(device=dev)
     faces_per_step = int(round(dist_u.sum_over_ranks(B, device=dev)))   # what the ranks actually ran, counted by the group
@@ -419,15 +479,15 @@ def main():
     # the serial plan (three launches per batch, nothing in flight across batches) in the same process, same K / W / R
     serial_elapsed = None
     serial_ev = []
-    if inflight and not args.no_serial_leg:
-        _, serial_elapsed, _, serial_ev = timed_blocks(serial_plan, True)
+    if args.full and inflight and not args.no_serial_leg:
+        _, serial_elapsed, _, serial_ev, _, _ = timed_blocks(serial_plan, True)
         clocks["after_serial_leg"] = clock_probe(L, dev)
 
     # the same in-flight route with the Q30 decode (int8 matrix cores, `--q30-levels` digit-product levels): its own plans,
     # its own oracle gate -- reported BESIDE `value`, never as it
     q30_leg = None
     host = pkg("_lib")
-    if inflight and args.q30_levels and not serial_plan.q30 and net._basis.q30_ws_bytes > 0:
+    if args.full and inflight and args.q30_levels and not serial_plan.q30 and net._basis.q30_ws_bytes > 0:
         prev_arith, prev_lv = host.decode_arith(), host.q30_levels()
         host.set_decode_arith(host.DECODE_ARITH_Q30, args.q30_levels)
         # An AUXILIARY leg: `value` (the f32 route) is already measured at this point and gated below.  Whatever goes wrong
@@ -442,8 +502,8 @@ def main():
             qserial = pipe.DecodeRenderPlan(net, B, H, W)
             qserial.params.copy_(torch.as_tensor(params_np, device=dev))
             torch.cuda.synchronize(dev)
-            qblocks, qelapsed, _, _ = timed_blocks(qplan, True)    # (event-bracketed steps like the f32 leg: equal treatment)
-            _, qs_elapsed, _, qs_ev = timed_blocks(qserial, True)
+            qblocks, qelapsed, _, _, _, _ = timed_blocks(qplan, True)    # (event-bracketed steps like the f32 leg: equal treatment)
+            _, qs_elapsed, _, qs_ev, _, _ = timed_blocks(qserial, True)
             qpar = None
             if args.parity_faces != 0:
                 for _ in range(3 * len(qplan.slots)):
@@ -481,13 +541,13 @@ def main():
 
     # the operator-surface route (allocations + pack_tri every call): same K / W / R, reported beside `value`
     ops_elapsed = ops_same = None
-    if not args.no_ops_surface:
+    if args.full and not args.no_ops_surface:
         serial_plan.step()
         ops_elapsed, ops_same = ops_surface_leg(net, pkg("rendering_layer.ops"), serial_plan, B, H, W, K, Wm, R, dist_u, dev)
 
     # parity gate: the oracle on every face of the timed route's buffers, on every rank
     parity = None
-    if args.parity_faces != 0:
+    if args.full and args.parity_faces != 0:
         nf = B if args.parity_faces < 0 else args.parity_faces
         if inflight:
             # several batches deep on every slot, all slots running beside each other; then every slot's vertices and planes
@@ -520,14 +580,15 @@ def main():
             dist_u.barrier()
             dist_u.finalize()
             sys.exit(3)
-    decode_ms = sum(e[0].elapsed_time(e[1]) for e in ev_all) / len(ev_all)
     in_region = None
-    emit_ms = sum(e[1].elapsed_time(e[2]) for e in ev_all) / len(ev_all)
-    resolve_ms = sum(e[2].elapsed_time(e[3]) for e in ev_all) / len(ev_all)
-    # one batch's parameters-to-planes time inside the timed region (event before its decode -> event behind its resolve)
-    latency_ms = sum(e[0].elapsed_time(e[3]) for e in ev_all) / len(ev_all)
-    serial_latency_ms = (sum(e[0].elapsed_time(e[3]) for e in serial_ev) / len(serial_ev)) if serial_ev else None
     cov = float(((plan.slots[0] if inflight else plan).tri_ind >= 0).float().mean().item())
+    if args.full:
+        decode_ms = sum(e[0].elapsed_time(e[1]) for e in ev_all) / len(ev_all)
+        emit_ms = sum(e[1].elapsed_time(e[2]) for e in ev_all) / len(ev_all)
+        resolve_ms = sum(e[2].elapsed_time(e[3]) for e in ev_all) / len(ev_all)
+        # one batch's parameters-to-planes time inside the timed region (event before its decode -> event behind its resolve)
+        latency_ms = sum(e[0].elapsed_time(e[3]) for e in ev_all) / len(ev_all)
+        serial_latency_ms = (sum(e[0].elapsed_time(e[3]) for e in serial_ev) / len(serial_ev)) if serial_ev else None
     if inflight and serial_ev:
         # Two batches in flight: a kernel's event-bracketed duration in THAT region measures how the two streams share the
         # chip (a kernel of the low-priority stream waits for the other batch's workgroups), not the kernel.  The per-kernel
@@ -539,7 +600,7 @@ def main():
         resolve_ms = sum(e[2].elapsed_time(e[3]) for e in serial_ev) / len(serial_ev)
 
     graph_fps = graph_multi = None
-    if args.graph:   # (the serial plan: three kernel nodes per replay)
+    if args.full and args.graph:   # (the serial plan: three kernel nodes per replay)
         serial_plan.capture()
         for _ in range(Wm):
             serial_plan.replay()
@@ -584,19 +645,64 @@ def main():
             del gs
 
     rccl_st = None
-    if world == 1 and not args.no_rccl_selftest:   # (after everything timed: the one-GPU box's only contact with RCCL)
+    if args.full and world == 1 and not args.no_rccl_selftest:   # (after everything timed: the one-GPU box's only contact with RCCL)
         rccl_st = dist_u.rccl_selftest(dev)
-    if rank == 0:
+    if rank == 0:   # the headline, in a plain run and with --full alike
         N, T, Kc = net.nvert, int(net.tri.shape[1]), net.ndim_shape + net.ndim_exp
-        ab = algorithmic_bytes(N, T, Kc, H, W, B)
         assert faces_per_step == B_global, (faces_per_step, B_global)
         value = faces_per_step * K / elapsed
+        q30 = (plan.slots[0] if inflight else plan).q30   # FR_DECODE_ARITH=q30 (opt-in, frozen experiment; the default is the f32 chain)
+        route = ("inflight: BatchesInFlight -- %d independent batches in flight, each slot a DecodeRenderPlan "
+                 "(fr_decode_render_forward, three launches per batch) on its own stream with no edge between the streams; step k "
+                 "goes to slot k mod %d; a timed block = K such steps, i.e. K batches from parameters to planes between the "
+                 "brackets (both streams drained at either bracket)" % (len(plan.slots), len(plan.slots))) if inflight else \
+                "serial: DecodeRenderPlan / fr_decode_render_forward -- three launches per batch, one batch at a time"
+        out = {
+            "metric": "faces/sec (3DMM decode+depth render), batch 64 @200x200",
+            "value": value, "unit": "faces/s", "n_gpus": world, "steps": K, "warmup": Wm,
+            "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True, "scaling": args.scaling,
+            "repeats": R, "value_is": ("median over %d timed blocks of K steps each" % R) if R > 1 else "one timed block of K steps",
+            "route": route, "full": bool(args.full), "warmup_steps_run": warm_steps,
+            "value_route": "inflight" if inflight else "serial",
+            "value_meaning": ("THROUGHPUT of independent batches: K batches go from parameters to planes between the brackets with "
+                              "%d in flight at any time; ms_per_step is the interval between finished batches, NOT one batch's "
+                              "latency (per_batch_latency_ms).  A dependent loop (CoarseNet -> render -> CoarseNet, "
+                              "nets/network.py:113-116) gets config.value_one_batch_at_a_time, the serial plan's figure, which is "
+                              "also the one comparable with rounds 1-3 (both measured with --full)" % len(plan.slots)) if inflight else
+                             "one batch at a time: ms_per_step is also one batch's parameters-to-planes time",
+            "value_min": faces_per_step * K / max(blocks), "value_max": faces_per_step * K / min(blocks),
+            "ms_per_step_min": 1e3 * min(blocks) / K, "ms_per_step_max": 1e3 * max(blocks) / K,
+            "blocks_ms_per_step": [round(1e3 * t / K, 5) for t in blocks],   # every timed block, in the order they ran
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "configs[1]: batch %d random 235-d params -> 3DMM decode -> depth render, "
+                                   "%dx%d, fp32, all four output planes" % (args.batch, H, W),
+                       "faces_per_gpu": B if args.scaling == "weak" else None, "faces_per_step_all_gpus": faces_per_step,
+                       "value_one_batch_at_a_time": (faces_per_step * K / serial_elapsed) if serial_elapsed is not None else
+                                                    (value if not inflight else None),
+                       "faces_per_gpu_rank0": B, "batches_in_flight": len(plan.slots) if inflight else 1,
+                       "resolver_strip_rows": ({"in_flight_slots": plan.strip_rows or "library default", "serial_plan": "library default"}
+                                               if inflight else "library default"), "nver": N, "ntri": T, "n_shape": net.ndim_shape, "n_exp": net.ndim_exp,
+                       "sampler": "sample_test.py:23-38 beta=0.7 " + ("seed=3456+rank" if args.scaling == "weak" else "seed=3456, one batch for all ranks"), "coverage": cov,
+                       "sharding": ("weak: every rank runs its own %d faces" % B if args.scaling == "weak" else
+                                    "strong: ONE %d-face batch cut into contiguous shards (utils.dist.shard_range)" % args.batch)
+                                   + ", no data-path collective",
+                       "decode_arith": ("q30, %d digit-product levels (fixed point on the int8 MFMA, include/fr_hotpath.h)" % int(q30)) if q30 else "f32 fmaf chain (f32-input MFMA)",
+                       "constants": "the packed basis (fr_decode_pack_basis) and the pre-validated triangle table "
+                                    "(fr_decode_render_forward, phase 4) are built once per plan: both are "
+                                    "tf.constants of the reference model (network.py:41-43, 178); a caller that repacks the "
+                                    "triangle list every call (fr_render_depth_forward) pays one more 5 us kernel per step"},
+            "dist": dict(dist_info, per_rank_ms_per_step=per_rank_ms, launcher_world_size=world),
+        }
+    if rank == 0 and not args.full:
+        sys.stdout.flush()
+        os.write(real_stdout, (json.dumps(out) + "\n").encode())
+    if rank == 0 and args.full:
+        ab = algorithmic_bytes(N, T, Kc, H, W, B)
         flops = 2.0 * 3 * N * Kc * B
         # algorithmic bytes of the render op (1,948,403 B/face) split over its two kernels: the emit kernel
         # owns the vertex / triangle / texture reads, the resolve kernel the four output planes
         emit_bytes = (4.0 * 3 * N + (4.0 * 3 * T + 4.0 * 3 * N) / B) * B
         resolve_bytes = 4.0 * H * W * 8 * B
-        q30 = serial_plan.q30   # FR_DECODE_ARITH=q30 (opt-in, frozen experiment; the default is the f32 chain)
         try:
             pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
         except (OSError, ValueError):
@@ -657,23 +763,7 @@ def main():
                                 "achieved": ab["render"] * B / (render_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
                                 "unit": "GB/s", "frac": ab["render"] * B / (render_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                 "algorithmic_bytes_per_launch": ab["render"] * B}
-        route = ("inflight: BatchesInFlight -- %d independent batches in flight, each slot a DecodeRenderPlan "
-                 "(fr_decode_render_forward, three launches per batch) on its own stream with no edge between the streams; step k "
-                 "goes to slot k mod %d; a timed block = K such steps, i.e. K batches from parameters to planes between the "
-                 "brackets (both streams drained at either bracket)" % (len(plan.slots), len(plan.slots))) if inflight else \
-                "serial: DecodeRenderPlan / fr_decode_render_forward -- three launches per batch, one batch at a time"
-        out = {
-            "metric": "faces/sec (3DMM decode+depth render), batch 64 @200x200",
-            "value": value, "unit": "faces/s", "n_gpus": world, "steps": K, "warmup": Wm,
-            "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True, "scaling": args.scaling,
-            "repeats": R, "value_is": "median over %d timed blocks of K steps each" % R, "route": route,
-            "value_route": "inflight" if inflight else "serial",
-            "value_meaning": ("THROUGHPUT of independent batches: K batches go from parameters to planes between the brackets with "
-                              "%d in flight at any time; ms_per_step is the interval between finished batches, NOT one batch's "
-                              "latency (per_batch_latency_ms).  A dependent loop (CoarseNet -> render -> CoarseNet, "
-                              "nets/network.py:113-116) gets config.value_one_batch_at_a_time, the serial plan's figure, which is "
-                              "also the one comparable with rounds 1-3" % len(plan.slots)) if inflight else
-                             "one batch at a time: ms_per_step is also one batch's parameters-to-planes time",
+        out.update({
             "per_batch_latency_ms": latency_ms,
             "per_batch_latency_is": "mean over the event-bracketed steps of the timed blocks: HIP event before the batch's decode launch "
                                     "-> event behind its resolve, on the batch's own stream" + (
@@ -684,32 +774,10 @@ def main():
                                  "the timed blocks (and behind the serial leg): the clock THIS part holds under matrix load today -- "
                                  "parts differ by several per cent, which is what moves the in-flight figure from box to box "
                                  "(DESIGN.md 4.7)",
-            "value_min": faces_per_step * K / max(blocks), "value_max": faces_per_step * K / min(blocks),
-            "ms_per_step_min": 1e3 * min(blocks) / K, "ms_per_step_max": 1e3 * max(blocks) / K,
-            "blocks_ms_per_step": [round(1e3 * t / K, 5) for t in blocks],   # every timed block, in the order they ran
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "configs[1]: batch %d random 235-d params -> 3DMM decode -> depth render, "
-                                   "%dx%d, fp32, all four output planes" % (args.batch, H, W),
-                       "faces_per_gpu": B if args.scaling == "weak" else None, "faces_per_step_all_gpus": faces_per_step,
-                       "value_one_batch_at_a_time": (faces_per_step * K / serial_elapsed) if serial_elapsed is not None else
-                                                    (value if not inflight else None),
-                       "faces_per_gpu_rank0": B, "batches_in_flight": len(plan.slots) if inflight else 1,
-                       "resolver_strip_rows": ({"in_flight_slots": plan.strip_rows or "library default", "serial_plan": "library default"}
-                                               if inflight else "library default"), "nver": N, "ntri": T, "n_shape": net.ndim_shape, "n_exp": net.ndim_exp,
-                       "sampler": "sample_test.py:23-38 beta=0.7 " + ("seed=3456+rank" if args.scaling == "weak" else "seed=3456, one batch for all ranks"), "coverage": cov,
-                       "sharding": ("weak: every rank runs its own %d faces" % B if args.scaling == "weak" else
-                                    "strong: ONE %d-face batch cut into contiguous shards (utils.dist.shard_range)" % args.batch)
-                                   + ", no data-path collective",
-                       "decode_arith": ("q30, %d digit-product levels (fixed point on the int8 MFMA, include/fr_hotpath.h)" % int(q30)) if q30 else "f32 fmaf chain (f32-input MFMA)",
-                       "constants": "the packed basis (fr_decode_pack_basis) and the pre-validated triangle table "
-                                    "(fr_decode_render_forward, phase 4) are built once per plan: both are "
-                                    "tf.constants of the reference model (network.py:41-43, 178); a caller that repacks the "
-                                    "triangle list every call (fr_render_depth_forward) pays one more 5 us kernel per step"},
             "roofline": dominant,
             "kernels": kernels,
             "parity": parity,
-            "dist": dict(dist_info, per_rank_ms_per_step=per_rank_ms, launcher_world_size=world),
-        }
+        })
         # BASELINE.json configs[2..4] (the caller loops around this path): NOT run here -- `bench.py --config 3|4|5` runs them -- but the
         # round's recorded lines ride along inside `config`, marked as what they are
         try:

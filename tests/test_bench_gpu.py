@@ -9,11 +9,13 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHORT = ["--steps", "3", "--warmup", "1", "--repeats", "2"]
+FULL = SHORT + ["--full"]   # (everything beyond the headline: legs, gates, per-kernel figures, CPU baseline)
 
 
 def _free_port():
@@ -34,7 +36,7 @@ def _line(cmd):
 
 
 def test_bench_line_one_gpu():
-    d = _line([sys.executable, "bench.py"] + SHORT + ["--cpu-faces", "8"])
+    d = _line([sys.executable, "bench.py"] + FULL + ["--cpu-faces", "8"])
     assert d["metric"].startswith("faces/sec") and d["unit"] == "faces/s" and d["n_gpus"] == 1 and d["steps"] == 3
     assert d["value"] > 1e4 and abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
     assert d["dtype"] == "f32" and d["data"] == "synthetic" and d["vs_baseline"] is None and d["higher_is_better"] is True
@@ -112,7 +114,7 @@ def test_bench_q30_leg_failure_does_not_take_the_line_down():
     """the Q30 leg is auxiliary -- an exception in it is reported inside q30_inflight / roofline.q30 and the f32
     line (already measured, still gated) is printed all the same.  FR_BENCH_Q30_FAULT makes the leg raise on purpose."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", FR_BENCH_Q30_FAULT="1")
-    p = subprocess.run([sys.executable, "bench.py"] + SHORT + ["--cpu-faces", "0", "--no-ops-surface", "--no-rccl-selftest", "--parity-faces", "2"],
+    p = subprocess.run([sys.executable, "bench.py"] + FULL + ["--cpu-faces", "0", "--no-ops-surface", "--no-rccl-selftest", "--parity-faces", "2"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
@@ -123,7 +125,7 @@ def test_bench_q30_leg_failure_does_not_take_the_line_down():
 
 def test_bench_line_serial_route():
     """--route serial: one plan, one stream, one batch at a time."""
-    d = _line([sys.executable, "bench.py"] + SHORT + ["--cpu-faces", "0", "--route", "serial", "--no-ops-surface"])
+    d = _line([sys.executable, "bench.py"] + FULL + ["--cpu-faces", "0", "--route", "serial", "--no-ops-surface"])
     assert d["route"].startswith("serial") and d["config"]["batches_in_flight"] == 1 and d["parity"]["ok"]
     assert "serial_plan" not in d and {"decode", "raster_emit", "resolve_write"} <= set(d["kernels"])
     _check_roofline_is_self_contained(d, q30=False)
@@ -134,7 +136,7 @@ def test_bench_line_serial_route():
 def test_bench_two_ranks_walk_the_multi_rank_flow(scaling, global_faces, local_faces):
     d = _line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--dist-backend", "gloo",
-               "--scaling", scaling, "--cpu-faces", "4", "--no-ops-surface", "--q30-levels", "0"] + SHORT)
+               "--scaling", scaling, "--cpu-faces", "4", "--no-ops-surface", "--q30-levels", "0"] + FULL)
     assert d["n_gpus"] == 2 and d["scaling"] == scaling
     assert d["dist"]["backend"] == "gloo" and d["dist"]["world_size"] == 2 and d["dist"]["ranks_reporting"] == 2
     assert len(d["dist"]["per_rank_ms_per_step"]) == 2 and all(t > 0 for t in d["dist"]["per_rank_ms_per_step"])
@@ -160,3 +162,41 @@ def test_bench_two_ranks_walk_the_multi_rank_flow(scaling, global_faces, local_f
     if scaling == "strong":   # (read from the committed shard timings, not literals)
         sp = d["dist"]["strong_scaling_prediction"]
         assert sp["predicted_speedup_vs_1_gpu"]["8"] > 1.5 and sp["us_per_step_at_faces_per_gpu"]["64"] > 50
+
+
+def test_bench_plain_line_and_outputs(tmp_path, oracle, synth):
+    """A plain run (no --full): exactly K timed steps in one block, the headline fields and nothing measured beside them, and
+    --dump-outputs: the planes and vertices of the slot that ran the LAST timed step, for a seeded sample of its faces --
+    the oracle rasteriser on those vertices gives those planes bit for bit, and the vertices are that slot's batch decoded."""
+    out = tmp_path / "outs"
+    K = 7
+    d = _line([sys.executable, "bench.py", "--gpus", "1", "--steps", str(K), "--warmup", "2", "--dump-outputs", str(out)])
+    assert d["metric"].startswith("faces/sec") and d["unit"] == "faces/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == K and d["warmup"] == 2 and d["warmup_steps_run"] >= 2 and d["full"] is False
+    assert d["repeats"] == 1 and len(d["blocks_ms_per_step"]) == 1 and d["value_is"] == "one timed block of K steps"
+    assert d["value"] > 1e4 and abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert abs(d["blocks_ms_per_step"][0] - d["ms_per_step"]) < 1e-4
+    for k in ("cpu_baseline", "parity", "kernels", "roofline", "serial_plan", "q30_inflight", "ops_surface", "clock_GHz_held"):
+        assert k not in d, k
+    assert "rccl_selftest" not in d["dist"] and d["route"].startswith("inflight")
+    names = ("depth", "texture_image", "normal", "tri_ind")
+    files = {f.name[:-4]: np.load(str(f)) for f in out.iterdir()}
+    assert set(files) == set(names) | {"face_index", "vertex_proj"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 * 10 ** 6
+    faces = files["face_index"].astype(np.int64)
+    n = len(faces)
+    assert 16 <= n <= 64 and np.all(np.diff(faces) > 0)
+    assert files["depth"].shape == (n, 200, 200, 1) and files["texture_image"].shape == (n, 200, 200, 3)
+    A = synth.make_assets()
+    assert files["vertex_proj"].shape == (n, 3, A["mu"].size // 3)
+    V = files["vertex_proj"][:2]
+    want = oracle.render_depth(V, A["tri"], A["vertex"][None], 200, 200)
+    for name, w in zip(names, want):
+        assert np.array_equal(files[name][:2], w, equal_nan=True), name
+    assert (files["tri_ind"] >= 0).mean() > 0.05
+    # step k of the run goes to slot k mod 2 (warm-up included); slot i holds the sampler's draw seed 3456 + 1000 i
+    slot = (d["warmup_steps_run"] + K - 1) % 2
+    P = synth.sample_params_batch(64, im_size=200, beta=0.7, seed=3456 + 1000 * slot)[faces[:2]]
+    Vo = oracle.decode_3dmm(P, A["mu"], A["pc_shape"], A["pc_exp"], 200.0, R=oracle.rotation_matrix_batch(P[:, :3]))
+    assert np.allclose(V, Vo, rtol=1e-6, atol=1e-4)   # (in-kernel fp64 rotation: a few ulp, tests/test_decode_gpu.py)

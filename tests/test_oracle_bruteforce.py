@@ -9,13 +9,7 @@ import pytest
 
 from conftest import GOLDEN, kat_inputs
 from ref_bruteforce import render_depth_bruteforce, render_depth_grad_bruteforce
-
-
-@pytest.fixture(scope="module")
-def pit(oracle):
-    if not oracle.ref_point_in_tri_available():
-        pytest.skip("oracle/_ref/libref_pit.so not built (reference tree absent)")
-    return oracle.ref_point_in_tri_batch
+from ref_pit_golden import pit  # noqa: F401  (the reference's PointInTri: the binary, or its recorded answers)
 
 
 def _eq(got, want, what):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from ref_pit_golden import pit  # noqa: F401  (the reference's PointInTri: the binary, or its recorded answers)
 
 
 def _pit_cases():
@@ -40,11 +41,9 @@ def _pit_cases():
     return P
 
 
-def test_point_in_tri_vs_reference_binary(oracle):
-    if not oracle.ref_point_in_tri_available():
-        pytest.skip("oracle/_ref/libref_pit.so not built (reference tree absent)")
+def test_point_in_tri_vs_reference_binary(oracle, pit):
     P = _pit_cases()
-    ref = oracle.ref_point_in_tri_batch(P)
+    ref = pit(P)
     ours = oracle.point_in_tri_op_batch(P)
     assert ref.sum() > 1000 and (~ref).sum() > 1000
     np.testing.assert_array_equal(ours, ref)

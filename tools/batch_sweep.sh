@@ -5,7 +5,7 @@ set -o pipefail
 OUT=${1:-gpurun_out/r6sweep}
 mkdir -p "$OUT"
 for B in 16 32 48 64 128 256; do
-  timeout 300 python3 bench.py --batch $B --steps 50 --warmup 10 --cpu-faces 0 --no-ops-surface --no-rccl-selftest \
+  timeout 300 python3 bench.py --full --batch $B --steps 50 --warmup 10 --cpu-faces 0 --no-ops-surface --no-rccl-selftest \
       > "$OUT/b$B.json" 2> "$OUT/b$B.err" || echo "batch $B: rc $?" >> "$OUT/failures.txt"
 done
 python3 - "$OUT" <<'PY'

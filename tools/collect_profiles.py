@@ -93,7 +93,7 @@ if os.path.exists(f):
         return (fetch_factor * v["FETCH_SIZE"] + v["WRITE_SIZE"]) * 1024.0
     json.dump({
         "source": "rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- "
-                  "python3 bench.py --route serial --steps 10 --warmup 3 --repeats 2 --cpu-faces 0 --no-ops-surface --parity-faces 0 "
+                  "python3 bench.py --full --route serial --steps 10 --warmup 3 --repeats 2 --cpu-faces 0 --no-ops-surface --parity-faces 0 "
                   "--no-rccl-selftest --q30-levels 0, MI355X, %s kernels (profiles/%s_pmc.json); per launch.  bench.py copies these figures "
                   "into its line (`traffic`, `rocprofv3_avg_ms`): they are NOT measured by the run that prints the line" % (tag, tag),
         "source_file": "profiles/pmc_traffic.json <- profiles/%s_pmc.json" % tag,

@@ -6,8 +6,8 @@ mkdir -p $O
 timeout 1800 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | tail -12 > $O/pytest_gpu.log
 echo "pytest rc=$?"; tail -4 $O/pytest_gpu.log
 timeout 300 python -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench.err; echo "bench k20 rc=$?"
-timeout 600 python3 bench.py > $O/bench.json 2>> $O/bench.err; echo "bench rc=$?"
+timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_k20.json 2> $O/bench.err; echo "bench k20 rc=$?"
+timeout 600 python3 bench.py --full > $O/bench.json 2>> $O/bench.err; echo "bench rc=$?"
 python3 - $O <<'PY'
 import json, sys, os
 o = sys.argv[1]

@@ -23,28 +23,28 @@ HF="--offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17"
 # ---- parity, smoke, bench -------------------------------------------------------------------------------------------------
 leg pytest_gpu bash -c "set -o pipefail; python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | tail -12 > $O/pytest_gpu.log"   # (pytest's own exit status: collection / fixture errors fail the leg too)
 leg smoke bash -c "python -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.log 2>&1"
-leg bench bash -c "python bench.py > $O/bench.json 2> $O/bench.err"
-leg bench_k20 bash -c "python bench.py --steps 20 --warmup 5 --cpu-faces 0 > $O/bench_k20.json 2>> $O/bench.err"
-leg bench_serial bash -c "python bench.py --route serial --cpu-faces 0 --no-ops-surface > $O/bench_serial.json 2>> $O/bench.err"
-leg bench_graph bash -c "python bench.py --graph --cpu-faces 0 --no-ops-surface > $O/bench_graph.json 2>> $O/bench.err"
-leg bench_q30 bash -c "FR_DECODE_ARITH=q30 python bench.py --cpu-faces 0 --no-ops-surface > $O/bench_q30.json 2>> $O/bench.err"
-leg bench_q30l5 bash -c "FR_DECODE_ARITH=q30l5 python bench.py --cpu-faces 0 --no-ops-surface > $O/bench_q30l5.json 2>> $O/bench.err"
-leg bench_q30l4 bash -c "FR_DECODE_ARITH=q30l4 python bench.py --cpu-faces 0 --no-ops-surface > $O/bench_q30l4.json 2>> $O/bench.err"
-leg bench_again bash -c "python bench.py --cpu-faces 0 > $O/bench_again.json 2>> $O/bench.err"
+leg bench bash -c "python bench.py --full > $O/bench.json 2> $O/bench.err"
+leg bench_k20 bash -c "python bench.py --full --steps 20 --warmup 5 --cpu-faces 0 > $O/bench_k20.json 2>> $O/bench.err"
+leg bench_serial bash -c "python bench.py --full --route serial --cpu-faces 0 --no-ops-surface > $O/bench_serial.json 2>> $O/bench.err"
+leg bench_graph bash -c "python bench.py --full --graph --cpu-faces 0 --no-ops-surface > $O/bench_graph.json 2>> $O/bench.err"
+leg bench_q30 bash -c "FR_DECODE_ARITH=q30 python bench.py --full --cpu-faces 0 --no-ops-surface > $O/bench_q30.json 2>> $O/bench.err"
+leg bench_q30l5 bash -c "FR_DECODE_ARITH=q30l5 python bench.py --full --cpu-faces 0 --no-ops-surface > $O/bench_q30l5.json 2>> $O/bench.err"
+leg bench_q30l4 bash -c "FR_DECODE_ARITH=q30l4 python bench.py --full --cpu-faces 0 --no-ops-surface > $O/bench_q30l4.json 2>> $O/bench.err"
+leg bench_again bash -c "python bench.py --full --cpu-faces 0 > $O/bench_again.json 2>> $O/bench.err"
 leg phase_test bash -c "python examples/coarse_loop.py --phase test --batch 32 --steps 6 --warmup 2 > $O/phase_test.json 2> $O/phase_test.err"
-leg bench_rows10 bash -c "python bench.py --strip-rows 0 --cpu-faces 0 --no-ops-surface > $O/bench_rows10.json 2>> $O/bench.err"
+leg bench_rows10 bash -c "python bench.py --full --strip-rows 0 --cpu-faces 0 --no-ops-surface > $O/bench_rows10.json 2>> $O/bench.err"
 # ---- rocprofv3: kernel stats + PMC passes of the same command (never --pmc together with a trace domain other than kernel-trace) --
 # (BCMD = the serial route: one batch in flight, the state the line's per-kernel figures and roofline object are measured in;
 #  prof_inflight = the default command, where kernels of two batches share the chip and a kernel's duration measures the sharing)
-BCMD="python3 bench.py --route serial --steps 10 --warmup 3 --repeats 2 --cpu-faces 0 --no-ops-surface --parity-faces 0 --no-rccl-selftest --q30-levels 0"
+BCMD="python3 bench.py --full --route serial --steps 10 --warmup 3 --repeats 2 --cpu-faces 0 --no-ops-surface --parity-faces 0 --no-rccl-selftest --q30-levels 0"
 leg prof_bench bash -c "rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- $BCMD > $O/prof_bench.log 2>&1"
-leg prof_inflight bash -c "rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_inflight -- python3 bench.py --steps 10 --warmup 3 --repeats 2 --cpu-faces 0 --no-ops-surface --parity-faces 0 --no-serial-leg --no-rccl-selftest --q30-levels 0 > $O/prof_inflight.log 2>&1"
+leg prof_inflight bash -c "rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_inflight -- python3 bench.py --full --steps 10 --warmup 3 --repeats 2 --cpu-faces 0 --no-ops-surface --parity-faces 0 --no-serial-leg --no-rccl-selftest --q30-levels 0 > $O/prof_inflight.log 2>&1"
 leg prof_q30l4 bash -c "FR_DECODE_ARITH=q30l4 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_q30l4 -- $BCMD > $O/prof_q30l4.log 2>&1"
 leg pmc_fetch_q30l4 bash -c "FR_DECODE_ARITH=q30l4 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $O/pmc_fetch_q30l4 -- $BCMD > $O/pmc_fetch_q30l4.log 2>&1"
 leg pmc_write_q30l4 bash -c "FR_DECODE_ARITH=q30l4 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $O/pmc_write_q30l4 -- $BCMD > $O/pmc_write_q30l4.log 2>&1"
 leg pmc_sq_q30l4 bash -c "FR_DECODE_ARITH=q30l4 rocprofv3 --kernel-trace --output-format csv --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_LDS SQ_WAIT_ANY -d $O/pmc_sq_q30l4 -- $BCMD > $O/pmc_sq_q30l4.log 2>&1"
 leg pmc_summary_q30l4 bash -c "python tools/pmc_summary.py $O/pmc_summary_q30l4.json $O/pmc_fetch_q30l4 $O/pmc_write_q30l4 $O/pmc_sq_q30l4 > /dev/null 2>> $O/bench.err"
-leg trace_inflight bash -c "rocprofv3 --kernel-trace --output-format csv -d $O/trace_inflight -- python3 bench.py --steps 100 --warmup 10 --repeats 3 --cpu-faces 0 --no-ops-surface --parity-faces 0 --no-serial-leg --q30-levels 0 --no-rccl-selftest > $O/trace_inflight.log 2>&1; python tools/inflight_trace.py $O/trace_inflight $O/inflight_timeline.json > /dev/null"
+leg trace_inflight bash -c "rocprofv3 --kernel-trace --output-format csv -d $O/trace_inflight -- python3 bench.py --full --steps 100 --warmup 10 --repeats 3 --cpu-faces 0 --no-ops-surface --parity-faces 0 --no-serial-leg --q30-levels 0 --no-rccl-selftest > $O/trace_inflight.log 2>&1; python tools/inflight_trace.py $O/trace_inflight $O/inflight_timeline.json > /dev/null"
 leg pmc_fetch bash -c "rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $O/pmc_fetch -- $BCMD > $O/pmc_fetch.log 2>&1"
 leg pmc_write bash -c "rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $O/pmc_write -- $BCMD > $O/pmc_write.log 2>&1"
 leg pmc_sq1 bash -c "rocprofv3 --kernel-trace --output-format csv --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d $O/pmc_sq1 -- $BCMD > $O/pmc_sq1.log 2>&1"
