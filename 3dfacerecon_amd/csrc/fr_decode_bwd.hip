@@ -328,7 +328,10 @@ __global__ __launch_bounds__(256) void bwd_pack_kernel(const float* __restrict__
 // B-fragment order (double buffered; ONE LDS-only barrier per group); the waves then multiply the group's three basis row
 // blocks (twelve 1 KiB fragments per wave, two groups in flight) against them.  dv never exists in global memory: g and
 // vertex_proj are read once, the 41 MB write + re-read and the prepass launch are gone.
-// Summation order: per output, groups ascending, x / y / z row block, k-step -- fixed by the chunking (FR_BWD_CHUNKS) alone.
+// Summation order: per output, groups ascending, x / y / z row block, k-step -- fixed by the chunking (FR_BWD_CHUNKS) alone: CB,
+// NB, the batch size, a face's column and its 64-face pass (b0) change no bit -- with one exception, the mu form's d f, whose
+// per-workgroup share alpha . d alpha + beta . d beta is summed over a wave's CB slot blocks first and then wave by wave, so its
+// association follows CB as well (tests/test_decode_backward_bounds_gpu.py holds both).
 // CB: 16-coefficient blocks per wave.  CB = 2 (eight waves for the model's 15 blocks: two per SIMD, one multiplying while the
 // other waits for its fragments) or 4 (four waves, one per SIMD; also what bases of more than 16 blocks take).
 // Either way the packed path covers bases of at most 16 blocks (256 coefficients: the model has 228); larger ones take the
@@ -692,6 +695,8 @@ struct BwdGeom {
     int cb_p;                                       // packed path: 16-coefficient blocks per wave (2 or 4)
     size_t slab_bytes_p, at_bytes;
 };
+// (tests/test_decode_backward_bounds_gpu.py derives its error bounds from this geometry: it reads it through
+// fr_debug_decode_bwd_geom, never from a copy of these rules)
 static BwdGeom bwd_geom(int N, int ns = 199, int ne = 29) {
     BwdGeom g;
     g.pre_blocks = (N + BW_PV - 1) / BW_PV;
@@ -736,7 +741,28 @@ static BwdGeom bwd_geom(int N, int ns = 199, int ne = 29) {
     return g;
 }
 
+// CB of one pass of nbatch (<= 64) faces: FR_BWD_CB 2 or 4, or 0 = by batch -- four blocks per wave up to 32 live columns,
+// two beyond
+static int bwd_pass_cb(int nbatch) {
+    const int o = opt(OPT_BWD_CB);
+    if (o == 0) return (nbatch + 15) / 16 <= 2 ? 4 : 2;
+    return o == 4 ? 4 : 2;
+}
+
 }  // namespace fr
+
+// test hook (include/fr_hotpath.h): the geometry the decode-backward launcher would choose under the current knobs, without a GPU.
+// out = {vertex groups per fused workgroup, fused workgroups, CB of a pass of min(nbatch, 64) faces, waves per fused workgroup
+// at that CB, rows per reference-layout GEMM workgroup, GEMM workgroups, prepass workgroups}
+extern "C" void fr_debug_decode_bwd_geom(int nbatch, int N, int n_shape, int n_exp, int* out) {
+    for (int i = 0; i < 7; i++) out[i] = 0;
+    if (N <= 0 || n_shape < 0 || n_exp < 0) return;
+    const fr::BwdGeom g = fr::bwd_geom(N, n_shape, n_exp);
+    const int cb = fr::bwd_pass_cb(nbatch < 64 ? nbatch : 64);
+    const int waves = (g.sbt + cb - 1) / cb;
+    out[0] = g.groups_per_block; out[1] = g.gemm_blocks_p; out[2] = cb; out[3] = waves < 4 ? 4 : waves;
+    out[4] = g.rows_per_block; out[5] = g.gemm_blocks; out[6] = g.pre_blocks;
+}
 
 size_t fr_decode_backward_workspace_impl(int N, int ns, int ne) {
     if (N <= 0) return 0;
@@ -803,13 +829,11 @@ int fr_launch_decode_backward(const float* grad_vertex_proj, const float* params
         a.nbatch = min(B - b0, 64);
         const int nbt = (a.nbatch + 15) / 16;
         if (packed) {   // ONE launch: gradient tile -> dv rows in LDS -> MFMA reduction + the pose partial sums
-            if (opt(OPT_BWD_CB) == 0) {   // by batch: four blocks per wave up to 32 live columns, two beyond
-                const int cb = nbt <= 2 ? 4 : 2;
-                if (cb != g.cb_p) {
-                    g.cb_p = cb;
-                    g.block_waves_p = (g.sbt + cb - 1) / cb < 4 ? 4 : (g.sbt + cb - 1) / cb;
-                    a.nslots = 16 * cb * g.block_waves_p;
-                }
+            const int cb = bwd_pass_cb(a.nbatch);
+            if (cb != g.cb_p) {
+                g.cb_p = cb;
+                g.block_waves_p = (g.sbt + cb - 1) / cb < 4 ? 4 : (g.sbt + cb - 1) / cb;
+                a.nslots = 16 * cb * g.block_waves_p;
             }
             const dim3 gb(g.block_waves_p * 64);
 #define FR_BWD_LAUNCH1(NBV, CBV) hipLaunchKernelGGL((bwd_fused_kernel<NBV, CBV>), dim3(a.gemm_blocks), gb, 0, stream, a);

@@ -52,11 +52,13 @@ const char* fr_strerror(int code);
  *   FR_RESOLVE_BLOCK (0 = auto | 256 | 512 | 1024)   FR_RENDER_ROWS (0 = auto | rows per screen strip)
  *   FR_DECODE_STORE (0 | 1 = transposed accumulators, one dword per lane per store: measured +1.1 us, A/B only)
  *   FR_BWD_CHUNKS (row chunks of the packed decode-backward GEMM: 256 = default | 1 .. 512; changes the association of the
- *   partial sums, i.e. the gradient's last bits -- every other knob leaves every result bit unchanged)
- *   FR_BWD_CB (16-coefficient blocks per wave of the fused decode backward: 0 = by batch | 2 | 4)
+ *   partial sums, i.e. the gradient's last bits)
+ *   FR_BWD_CB (16-coefficient blocks per wave of the fused decode backward: 0 = by batch | 2 | 4; changes no result bit except
+ *   d f of fr_decode_3dmm_backward_packed_mu, whose per-workgroup partial it re-associates)
  *   FR_EMIT_ORDER (lane order of a segment's triangles in the emit kernel, fixed by the pack phase: -1 = scored per segment
  *   (default) | 0 = list order | 1 = even triangles, then odd ones; read when the triangle list is packed)
- * None of them changes a result bit (tests/test_render_gpu.py, tests/test_decode_gpu.py hold every setting to the oracle).
+ * Apart from those two, none of them changes a result bit (tests/test_render_gpu.py, tests/test_decode_gpu.py hold every setting to
+ * the oracle; tests/test_decode_backward_bounds_gpu.py the two backward knobs).
  * Returns FR_OK or FR_ERR_INVALID_ARG (unknown name). */
 int fr_set_option(const char* name, int value);
 int fr_get_option(const char* name, int* value);
@@ -291,6 +293,12 @@ int fr_decode_3dmm_backward_packed_mu(const float* grad_vertex_proj, const float
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
  * plays the FR_RENDER_ROWS tuning knob.  Used by tests/test_capi_cpu.py. */
 void fr_debug_render_geom(int B, int ntri, int H, int W, int rows_override, int* out);
+
+/* The decode-backward launch geometry under the current FR_BWD_CHUNKS / FR_BWD_CB (no GPU needed): out[7] = {vertex groups of
+ * 16 per fused workgroup, fused workgroups, CB of a 64-face pass of min(nbatch, 64) faces, waves per fused workgroup, rows per
+ * reference-layout GEMM workgroup, GEMM workgroups, prepass workgroups}.  Used by tests/test_decode_backward_bounds_gpu.py to
+ * derive its rounding-error bounds and by tests/test_capi_cpu.py. */
+void fr_debug_decode_bwd_geom(int nbatch, int N, int n_shape, int n_exp, int* out);
 
 /* The kernels divide by 3.0f (render_depth_op.cc:217, 223, 361) through a 3-instruction exact sequence: this hook
  * compares it with x / 3.0f on the fp32 bit patterns [first, first + count) and writes the number of differing results

@@ -475,6 +475,74 @@ int fr_oracle_decode_3dmm_backward_f64(const float* grad_vertex_proj, const floa
     return 0;
 }
 
+/* The same float64 gradient (the same operations in the same order: with R_override == NULL it is bit for bit the function
+ * above) with two additions:
+ *   R_override [B,9] fp32 (may be NULL): the host-supplied rotation of fr_decode_3dmm_backward*'s R_override -- the reference
+ *     forms R on the host (tf.py_func, network.py:150); NULL: fr_oracle_rotation_matrix of the angles, as above;
+ *   abs_sum [B, 7+ns+ne] (may be NULL): S_k = sum_i |t_i| over output k's float64 terms t_i -- the magnitude an fp32
+ *     evaluation's rounding error is proportional to:  d t3d_i: sum_p |dq_i|;  d f: sum_p sum_i |(R v_p)_i dq_i|;
+ *     d alpha / d beta: |pc|^T |dv|;  the angles: 0. */
+int fr_oracle_decode_3dmm_backward_f64_ex(const float* grad_vertex_proj, const float* params, const float* mu,
+                                          const float* pc_shape, const float* pc_exp, const float* R_override, int B, int N,
+                                          int ns, int ne, double* grad_params, double* abs_sum) {
+    if (B < 0 || N < 0 || ns < 0 || ne < 0) return -1;
+    int nd = 7 + ns + ne;
+    double* dv = (double*)malloc(sizeof(double) * 3 * (size_t)(N > 0 ? N : 1));
+    if (!dv) return -2;
+    for (int b = 0; b < B; b++) {
+        const float* pr = params + (size_t)b * nd;
+        double* gp = grad_params + (size_t)b * nd;
+        double* sa = abs_sum ? abs_sum + (size_t)b * nd : NULL;
+        for (int i = 0; i < nd; i++) gp[i] = 0.0;
+        if (sa)
+            for (int i = 0; i < nd; i++) sa[i] = 0.0;
+        float Rf[9];
+        if (R_override)
+            memcpy(Rf, R_override + 9 * (size_t)b, sizeof(Rf));
+        else
+            fr_oracle_rotation_matrix(pr[0], pr[1], pr[2], Rf);
+        double f = pr[6];
+        const float* gx = grad_vertex_proj + ((size_t)b * 3 + 0) * N;
+        const float* gy = grad_vertex_proj + ((size_t)b * 3 + 1) * N;
+        const float* gz = grad_vertex_proj + ((size_t)b * 3 + 2) * N;
+        for (int p = 0; p < N; p++) {
+            double dq[3] = {(double)gx[p], -(double)gy[p], (double)gz[p]};
+            double v[3];
+            for (int c = 0; c < 3; c++) {
+                size_t r = (size_t)c * N + p;
+                double S = 0, E = 0;
+                for (int k = 0; k < ns; k++) S += (double)pc_shape[r * ns + k] * (double)pr[7 + k];
+                for (int k = 0; k < ne; k++) E += (double)pc_exp[r * ne + k] * (double)pr[7 + ns + k];
+                v[c] = (double)mu[r] + S + E;
+            }
+            for (int i = 0; i < 3; i++) {
+                const double t = ((double)Rf[3 * i] * v[0] + (double)Rf[3 * i + 1] * v[1] + (double)Rf[3 * i + 2] * v[2]) * dq[i];
+                gp[3 + i] += dq[i];
+                gp[6] += t;
+                if (sa) {
+                    sa[3 + i] += fabs(dq[i]);
+                    sa[6] += fabs(t);
+                }
+            }
+            for (int c = 0; c < 3; c++)
+                dv[(size_t)c * N + p] = f * ((double)Rf[c] * dq[0] + (double)Rf[3 + c] * dq[1] + (double)Rf[6 + c] * dq[2]);
+        }
+        for (size_t r = 0; r < (size_t)3 * N; r++) {
+            double d = dv[r];
+            if (sa) {
+                const double ad = fabs(d);
+                for (int k = 0; k < ns; k++) sa[7 + k] += fabs((double)pc_shape[r * ns + k]) * ad;
+                for (int k = 0; k < ne; k++) sa[7 + ns + k] += fabs((double)pc_exp[r * ne + k]) * ad;
+            }
+            if (d == 0.0) continue;
+            for (int k = 0; k < ns; k++) gp[7 + k] += (double)pc_shape[r * ns + k] * d;
+            for (int k = 0; k < ne; k++) gp[7 + ns + k] += (double)pc_exp[r * ne + k] * d;
+        }
+    }
+    free(dv);
+    return 0;
+}
+
 /* ---- Q30 decode: the exact specification of the product's fixed-point basis blend ---------------------------------
  * NOT the reference's arithmetic (the reference runs two fp32 tf.matmuls whose summation order is unknowable,
  * nets/network.py:153-156): this is the written spec of the gfx950 int8-MFMA decode, restated here so that the HIP

@@ -64,6 +64,8 @@ def lib():
         L.fr_oracle_decode_3dmm_f64.restype = ctypes.c_int
         L.fr_oracle_decode_3dmm_backward_f64.argtypes = [_f32p] * 5 + [ctypes.c_int] * 4 + [_f64p]
         L.fr_oracle_decode_3dmm_backward_f64.restype = ctypes.c_int
+        L.fr_oracle_decode_3dmm_backward_f64_ex.argtypes = [_f32p] * 6 + [ctypes.c_int] * 4 + [_f64p, _f64p]
+        L.fr_oracle_decode_3dmm_backward_f64_ex.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -208,9 +210,12 @@ def decode_3dmm_f64(params, mu, pc_shape, pc_exp, im_size):
     return out
 
 
-def decode_3dmm_backward_f64(grad_vertex_proj, params, mu, pc_shape, pc_exp):
+def decode_3dmm_backward_f64(grad_vertex_proj, params, mu, pc_shape, pc_exp, R=None, abs_sum=False):
     """float64 gradient of the parameters given dL/d vertex_proj [B,3,N] (what TF autodiff yields for
-    nets/network.py:140-171: no gradient to the three angles, which pass through tf.py_func)."""
+    nets/network.py:140-171: no gradient to the three angles, which pass through tf.py_func).
+    R: optional fp32 rotations [B,3,3] (the host-supplied R_override of the HIP entry points); None: the rotation of the
+    angles (fr_oracle_rotation_matrix).  abs_sum=True returns (grad, S) with S [B, 7+ns+ne] the sum of the absolute values of
+    each output's float64 terms (fr_oracle_decode_3dmm_backward_f64_ex)."""
     g, gp = _c32(grad_vertex_proj)
     params, pp = _c32(params)
     mu, mp = _c32(np.asarray(mu).reshape(-1))
@@ -218,11 +223,20 @@ def decode_3dmm_backward_f64(grad_vertex_proj, params, mu, pc_shape, pc_exp):
     pc_exp, ep = _c32(pc_exp)
     B, N = params.shape[0], mu.shape[0] // 3
     out = np.empty((B, params.shape[1]), np.float64)
-    rc = lib().fr_oracle_decode_3dmm_backward_f64(gp, pp, mp, sp, ep, B, N, pc_shape.shape[1], pc_exp.shape[1],
-                                                  out.ctypes.data_as(_f64p))
+    if R is None and not abs_sum:
+        rc = lib().fr_oracle_decode_3dmm_backward_f64(gp, pp, mp, sp, ep, B, N, pc_shape.shape[1], pc_exp.shape[1],
+                                                      out.ctypes.data_as(_f64p))
+    else:
+        rp = None
+        if R is not None:
+            R, rp = _c32(np.asarray(R).reshape(B, 9))
+        S = np.empty_like(out) if abs_sum else None
+        rc = lib().fr_oracle_decode_3dmm_backward_f64_ex(gp, pp, mp, sp, ep, rp, B, N, pc_shape.shape[1], pc_exp.shape[1],
+                                                         out.ctypes.data_as(_f64p),
+                                                         S.ctypes.data_as(_f64p) if abs_sum else None)
     if rc != 0:
         raise ValueError("fr_oracle_decode_3dmm_backward_f64 rc=%d" % rc)
-    return out
+    return (out, S) if abs_sum else out
 
 
 # ---- the reference's own PointInTri, compiled from /root/reference into oracle/_ref (if present) ----

@@ -337,3 +337,30 @@ def test_fused_decode_backward_keeps_its_streams_in_registers():
     for b in blocks:
         assert re.search(r"ScratchSize \[bytes/lane\]: 0\b", b), b[:400]
         assert re.search(r"VGPRs Spill: 0\b", b), b[:400]
+
+
+def test_decode_backward_geometry_hook():
+    """fr_debug_decode_bwd_geom: the launch geometry tests/test_decode_backward_bounds_gpu.py derives its bounds from.
+    Full size (N = 53,215, 15 coefficient blocks): 3,326 vertex groups, 13 per fused workgroup (the last one 11) in 256
+    workgroups; CB 4 up to 32 faces and 2 beyond (eight waves); the reference layout takes 312 rows per GEMM workgroup in 512
+    of them and 832 prepass workgroups.  The 70 x 61 mesh: two groups per workgroup, 134 workgroups.  The knobs move it."""
+    host = pkg("_lib")
+    L = host.lib()
+
+    def geom(B, N, ns=199, ne=29):
+        out = (ctypes.c_int * 7)()
+        L.fr_debug_decode_bwd_geom(B, N, ns, ne, out)
+        return list(out)
+
+    with host.options(FR_BWD_CHUNKS=256, FR_BWD_CB=0):
+        assert geom(64, 53215) == [13, 256, 2, 8, 312, 512, 832]
+        assert geom(70, 53215) == geom(64, 53215)
+        assert geom(32, 53215) == [13, 256, 4, 4, 312, 512, 832]
+        assert geom(33, 53215)[2:4] == [2, 8] and geom(1, 53215)[2:4] == [4, 4]
+        assert geom(64, 4270) == [2, 134, 2, 8, 28, 458, 67]
+        assert geom(5, 4270, 240, 16)[2:4] == [4, 4] and geom(64, 4270, 240, 16)[2:4] == [2, 8]
+        assert geom(64, 0) == [0] * 7
+    with host.options(FR_BWD_CHUNKS=512, FR_BWD_CB=4):
+        assert geom(64, 53215)[:4] == [7, 476, 4, 4]
+    with host.options(FR_BWD_CHUNKS=1, FR_BWD_CB=2):
+        assert geom(1, 4270)[:4] == [267, 1, 2, 8]
