@@ -13,6 +13,7 @@ The 235-d layout is unchanged: [phi, gamma, theta, tx, ty, tz, f | shape x199 | 
 import importlib.util
 import os
 import sys
+import threading
 from math import cos, sin
 
 import numpy as np
@@ -73,6 +74,7 @@ class PackedBasis:
         self._packed_ok = None
         self.backward_from_mu = False   # True: the autograd node's backward does not keep the forward's output (see _Decode3DMM)
         self._bwd_ws = {}      # decode-backward workspaces by (device, stream, bytes): backward_workspace()
+        self._bwd_ws_lock = threading.Lock()   # threads on other streams take backwards through one basis at once
 
     def image_t(self):
         """The basis packed for the decode backward (fr_decode_backward_pack_basis), built on first use: callers that never
@@ -113,12 +115,13 @@ class PackedBasis:
         if torch.cuda.is_current_stream_capturing():
             return nws, torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
         key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, nws)
-        buf = self._bwd_ws.pop(key, None)
-        if buf is None:
-            buf = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
-        self._bwd_ws[key] = buf               # (re-inserted last: most recently used)
-        while len(self._bwd_ws) > 4:
-            self._bwd_ws.pop(next(iter(self._bwd_ws)))
+        with self._bwd_ws_lock:
+            buf = self._bwd_ws.pop(key, None)
+            if buf is None:
+                buf = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
+            self._bwd_ws[key] = buf               # (re-inserted last: most recently used)
+            while len(self._bwd_ws) > 4:
+                self._bwd_ws.pop(next(iter(self._bwd_ws)))
         return nws, buf
 
     def use_q30(self):

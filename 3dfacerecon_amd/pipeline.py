@@ -37,10 +37,20 @@ class DecodeRenderPlan:
         """net: nets.network.FaceRecNet (holds the packed basis, tri, vertex_code); texture: (3,N) or (B,3,N)
         tensor, default net.vertex_code (the PNCC colour code, reference network.py:116).  stream: a torch.cuda.Stream
         every launch of this plan goes to (default: whatever torch's current stream is at the call).  strip_rows: rows per
-        screen strip of the resolver (FR_PHASES_STRIP_ROWS in include/fr_hotpath.h; 0 = the library's choice)."""
+        screen strip of the resolver (FR_PHASES_STRIP_ROWS in include/fr_hotpath.h; 0 = the library's choice), 0 .. 255, fixed
+        for the plan's life (a read-only property)."""
         h = _host()
         self.stream = stream
-        self.strip_rows = int(strip_rows) & 0xFF
+        rows = int(strip_rows)
+        if not 0 <= rows <= 255:
+            raise ValueError("strip_rows must be 0 (the library's choice) .. 255, got %d" % rows)
+        self._strip_rows = rows
+        self._hint = rows << 8
+        # the strip geometry the buckets in the workspace were emitted under: the strip hint is the plan's for life, so the launcher
+        # option epoch (_lib.option_epoch) of the last successful call that ran the emit phase names it; None before any -- a
+        # resolve-only call must find the same (_run)
+        self._opts = h._STATE
+        self._emit_epoch = None
         self._h = h
         self._L = L = h.lib()
         self.net = net
@@ -95,13 +105,28 @@ class DecodeRenderPlan:
         self._tri_packed = False
         self.pack_tri()
 
+    @property
+    def strip_rows(self):
+        return self._strip_rows
+
     def _stream(self):
         st = self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
         return ctypes.c_void_p(st.cuda_stream)
 
     def _run(self, phases):
-        """Phase bits of fr_decode_render_forward: 8 = decode, 4 = pack the triangle list, 1 = emit, 2 = resolve."""
-        rc = self._fused_fn(*self._fused_args, self._stream(), phases | (self.strip_rows << 8))
+        """Phase bits of fr_decode_render_forward: 8 = decode, 4 = pack the triangle list, 1 = emit, 2 = resolve.
+        The resolver reads the buckets the emit phase wrote for ONE strip layout, which the strip hint and the process-wide
+        FR_RENDER_ROWS / FR_RENDER_IMPL decide: a resolve without its emit (render_phase(2)) is refused, before anything is
+        launched, unless the last emit of this plan ran under the launcher options in force now (the same option epoch; the
+        strip hint is the plan's for life)."""
+        epoch = self._opts.option_epoch
+        if (phases & 3) == 2 and self._emit_epoch != epoch:
+            raise RuntimeError("DecodeRenderPlan: a resolve without an emit under the same strip geometry (%s): run render_phase(1) "
+                               "or step() first" % ("no emit yet" if self._emit_epoch is None else
+                                                    "the launcher options changed since the last emit"))
+        rc = self._fused_fn(*self._fused_args, self._stream(), phases | self._hint)
+        if phases & 1:
+            self._emit_epoch = epoch if rc == 0 else None
         if rc:
             self._h.check(rc, self._fused_name)
 
@@ -237,9 +262,9 @@ class BatchesInFlight:
         if int(slots) < 1:
             raise ValueError("slots must be >= 1")
         self.device = net.device
-        if strip_rows is None:
+        if strip_rows is None or int(strip_rows) < 0:   # (negative: "auto", as bench.py --strip-rows -1)
             strip_rows = self.strip_rows_in_flight(net, batch, height, width) if int(slots) > 1 else 0
-        self.strip_rows = int(strip_rows)
+        self._strip_rows = int(strip_rows)
         with torch.cuda.device(self.device):
             self.slots = []
             for i in range(int(slots)):
@@ -247,10 +272,15 @@ class BatchesInFlight:
                 # through this API): slot 0 runs at HIGH priority, the others at NORMAL -- one batch entitled to run ahead, the
                 # other filling in (profiles/round4_probes/r4p: equal priorities sometimes lock the streams into step)
                 st = torch.cuda.Stream(device=self.device, priority=(-1 if i == 0 else 0))
-                self.slots.append(_Slot(net, batch, height, width, texture, stream=st, strip_rows=self.strip_rows))
+                self.slots.append(_Slot(net, batch, height, width, texture, stream=st, strip_rows=self._strip_rows))
             torch.cuda.synchronize(self.device)   # every slot's triangle table is packed before anything else touches the slots
         self._next = 0
         self.B = self.slots[0].B
+
+    @property
+    def strip_rows(self):
+        """The strip hint every slot was built with (read-only: the slots' plans keep theirs for life)."""
+        return self._strip_rows
 
     @staticmethod
     def strip_rows_in_flight(net, batch, height=None, width=None):

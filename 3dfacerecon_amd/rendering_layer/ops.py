@@ -61,7 +61,11 @@ _host().lib()
 #     accumulates one 330 MB buffer per stream handle it ever used); clear_workspace_cache() drops them all;
 #   * never used while the current stream is being captured into a hipGraph: a captured launch must not point at a buffer
 #     the cache may later replace, so the capture gets a buffer of its own from the graph's memory pool;
-#   * guarded by a lock (autograd worker threads call the forward too).
+#   * the cache itself is guarded by _WS_LOCK (autograd worker threads call the forward too), and each entry by a lock of its
+#     own, held from the choice of phases through the launch to the record of the packed table: threads that share a stream
+#     (every thread that sets none shares torch's default stream) share its entry, and one thread's pack must not land between
+#     another's choice to skip it and that thread's launch -- nor its kernels between another call's emit and resolve.  The
+#     launch is asynchronous, so the lock is held for microseconds.
 # Each entry also remembers which triangle list its pre-validated triangle table (pack_tri_kernel) was built from -- the
 # tensor OBJECT (held weakly), its torch version counter and the geometry -- so a loop that renders with the same `tri`
 # tensor every call (the reference makes it a tf.constant, network.py:178) packs it once, not once per call.  A new tensor
@@ -74,10 +78,11 @@ _WS_LOCK = threading.Lock()
 
 
 class _WsEntry:
-    __slots__ = ("buf", "tri_ref", "tri_key")
+    __slots__ = ("buf", "tri_ref", "tri_key", "lock")
 
     def __init__(self, buf):
         self.buf = buf
+        self.lock = threading.Lock()   # decide phases -> launch -> record the table, as one step
         self.tri_ref = None   # weakref to the tensor the table was packed from
         self.tri_key = None   # (its version counter, its data_ptr) + geometry
 
@@ -184,12 +189,13 @@ class _RenderDepth(torch.autograd.Function):
             ws_bytes = L.fr_render_depth_workspace_bytes(B, nver, ntri, H, W)
             if ws_bytes:
                 ent, cached = _workspace(dev, ws_bytes)
-                phases, pending = _render_phases(ent, cached, tri_c, (B, nver, ntri, H, W))
-                rc = L.fr_render_depth_forward_phases(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), B, nver, ntri, H, W, 3,
-                                                      tex_batch, h.ptr(depth), h.ptr(tex_img), h.ptr(normal), h.ptr(tri_ind),
-                                                      h.ptr(ent.buf), ws_bytes, h.stream_ptr(dev), phases)
-                if rc == 0:
-                    _table_packed(ent, pending)
+                with ent.lock:
+                    phases, pending = _render_phases(ent, cached, tri_c, (B, nver, ntri, H, W))
+                    rc = L.fr_render_depth_forward_phases(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), B, nver, ntri, H, W, 3,
+                                                          tex_batch, h.ptr(depth), h.ptr(tex_img), h.ptr(normal), h.ptr(tri_ind),
+                                                          h.ptr(ent.buf), ws_bytes, h.stream_ptr(dev), phases)
+                    if rc == 0:
+                        _table_packed(ent, pending)
             else:
                 rc = L.fr_render_depth_forward(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), B, nver, ntri, H, W, 3, tex_batch,
                                                h.ptr(depth), h.ptr(tex_img), h.ptr(normal), h.ptr(tri_ind), None, 0,
@@ -244,15 +250,17 @@ class _RenderingLayerFused(torch.autograd.Function):
         with torch.cuda.device(dev):
             ws_bytes = L.fr_render_depth_workspace_bytes(B, nver, ntri, H, W)
             ent, cached = _workspace(dev, ws_bytes)
-            # the same "pack once while the same `tri` tensor is passed" rule as render_depth (the table is the same table)
-            phases, pending = _render_phases(ent, cached, tri_c, (B, nver, ntri, H, W))
-            rc = L.fr_rendering_layer_forward_phases(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), h.ptr(img_c), B, nver, ntri, H, W,
-                                                     tex_batch, h.ptr(net_in), h.ptr(depth_img), h.ptr(depth), h.ptr(tri_ind),
-                                                     h.ptr(ent.buf), ws_bytes, h.stream_ptr(dev), phases)
+            with ent.lock:
+                # the same "pack once while the same `tri` tensor is passed" rule as render_depth (the table is the same table)
+                phases, pending = _render_phases(ent, cached, tri_c, (B, nver, ntri, H, W))
+                rc = L.fr_rendering_layer_forward_phases(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), h.ptr(img_c), B, nver, ntri, H,
+                                                         W, tex_batch, h.ptr(net_in), h.ptr(depth_img), h.ptr(depth),
+                                                         h.ptr(tri_ind), h.ptr(ent.buf), ws_bytes, h.stream_ptr(dev), phases)
+                if rc == 0:
+                    _table_packed(ent, pending)
         if rc == -4:
             raise NotImplementedError("fused rendering layer: shape only covered by the fallback rasteriser")
         h.check(rc, "fr_rendering_layer_forward")
-        _table_packed(ent, pending)
         ctx.save_for_backward(tri_c, tri_ind, depth, img_c)
         ctx.dims = (B, nver, ntri, H, W)
         ctx.mark_non_differentiable(tri_ind)

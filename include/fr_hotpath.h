@@ -12,9 +12,21 @@
  *   - `hip_stream` is a hipStream_t (NULL = the default stream); all work is enqueued on it, in order;
  *   - return value: FR_OK (0) or a negative FR_ERR_* code (never swallowed, unlike the reference's
  *     printf-and-return at render_depth_op.cu.cc:290-295); fr_strerror() names it;
- *   - reentrant and thread-safe (no static scratch, unlike render_depth_op.cc:125-131).
- *   - calls on DIFFERENT streams with disjoint output / workspace / vertex buffers may run beside each other (the model
- *     constants -- packed basis, triangle list, texture -- are only read): two independent batches in flight on two streams
+ *   - reentrant: no static scratch (unlike render_depth_op.cc:125-131); the only process-wide state is the option table
+ *     (atomics, filled from the environment once under std::call_once) and per-device caches of launch attributes (atomics),
+ *     so any number of host threads may make their first calls at the same moment.  What is supported, exactly
+ *     (tests/test_threads_gpu.py holds each to the single-threaded results, bit for bit):
+ *       * threads calling on DIFFERENT streams with disjoint output / workspace / vertex buffers (the model constants --
+ *         packed basis, triangle list, texture -- are only read);
+ *       * threads sharing ONE stream: each call enqueues its launches in order, but a call of several phases is several
+ *         launches, so calls that share a workspace must be serialised by the caller from the first launch to the last
+ *         (rendering_layer/ops.py holds a lock per cached workspace for this);
+ *       * options (fr_set_option) are process-wide: a change made by any thread applies to the next call of every thread;
+ *       * every phase of ONE workspace's forward -- emit and resolve, and the pack the emit relies on -- must be called under
+ *         one geometry: the same strip hint (FR_PHASES_STRIP_ROWS) and the same FR_RENDER_ROWS / FR_RENDER_IMPL.  A resolve
+ *         under another strip layout than its emit writes wrong planes with no error (pipeline.DecodeRenderPlan refuses such
+ *         a call on the host side);
+ *   - calls on different streams run beside each other: two independent batches in flight on two streams
  *     measure ~100 us per 64-face batch against ~111 us one batch at a time on an MI355X (pipeline.BatchesInFlight,
  *     DESIGN.md 4.7);
  *   - tensors are dense, row-major, fp32; triangle indices and tri_ind stay float-typed at the surface as in
