@@ -185,6 +185,8 @@ def _bind(L):
     L.fr_debug_render_geom.restype = None
     L.fr_debug_decode_bwd_geom.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
     L.fr_debug_decode_bwd_geom.restype = None
+    L.fr_debug_render_bwd_geom.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
+    L.fr_debug_render_bwd_geom.restype = None
     L.fr_debug_div3_sweep.argtypes = [ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _vp]
     L.fr_debug_div3_sweep.restype = _i
     L.fr_debug_clock_probe.argtypes = [_vp, _i, _i, _vp]
@@ -195,7 +197,8 @@ def _bind(L):
 EXPORTS = ["fr_version", "fr_strerror", "fr_render_depth_workspace_bytes", "fr_render_depth_forward",
            "fr_render_depth_backward", "fr_decode_packed_basis_bytes", "fr_decode_pack_basis", "fr_decode_3dmm",
            "fr_decode_backward_workspace_bytes", "fr_decode_3dmm_backward", "fr_rendering_layer_forward",
-           "fr_render_depth_forward_phases", "fr_debug_render_geom", "fr_debug_decode_bwd_geom", "fr_debug_div3_sweep",
+           "fr_render_depth_forward_phases", "fr_debug_render_geom", "fr_debug_decode_bwd_geom", "fr_debug_render_bwd_geom",
+           "fr_debug_div3_sweep",
            "fr_render_depth_backward_workspace_bytes", "fr_render_depth_backward_ws", "fr_set_option", "fr_get_option",
            "fr_decode_q30_image_bytes", "fr_decode_q30_pack", "fr_decode_q30_workspace_bytes", "fr_decode_3dmm_q30",
            "fr_decode_3dmm_q30_lv", "fr_decode_render_forward_q30",

@@ -167,8 +167,7 @@ size_t fr_render_depth_backward_workspace_bytes(int B, int H, int W) {
 int fr_render_depth_backward_ws(const float* depth_grad, const float* tri, const float* tri_ind, float* vertex_grad,
                                 int B, int nver, int ntri, int H, int W, void* workspace, size_t ws_bytes,
                                 void* hip_stream) {
-    if (workspace && (ws_bytes < fr_render_depth_backward_workspace_bytes(B, H, W) || ((uintptr_t)workspace & 15)))
-        return FR_ERR_WORKSPACE;
+    // a workspace that is too small or not 16-byte aligned is never touched: the launcher takes the plain variant (same bits)
     return render_backward_checked(depth_grad, tri, tri_ind, vertex_grad, B, nver, ntri, H, W, workspace, ws_bytes,
                                    hip_stream);
 }

@@ -1780,6 +1780,47 @@ size_t fr_render_backward_workspace_bytes_impl(int B, int H, int W) {
     return (size_t)B * npix * sizeof(int4) + (size_t)B * chunks * sizeof(uint2);
 }
 
+// The launch geometry of the backward, chosen in ONE place: the launcher below and the test hook
+// fr_debug_render_bwd_geom both read it from here.
+namespace {
+struct BwdRenderGeom {
+    int splits, range;  // owner workgroups per face, vertices per owner
+    int shift;          // headroom bits given up by images above 2^20 pixels
+    int chunks;         // 1,024-pixel chunks of the records kernel (workspace variant)
+    size_t lds;         // dynamic LDS of render_backward_kernel
+    bool xcd_map;       // the kernel's block -> (face, owner) map keeps a face's owners on one XCD (batch a multiple of 8)
+};
+BwdRenderGeom render_bwd_geom(int B, int nver, long long npix) {
+    using namespace fr;
+    BwdRenderGeom g{};
+    // the int64 headroom covers 3 * 2^20 terms per vertex at the full 38-bit resolution; larger images give up one bit of
+    // resolution per doubling (the forward renders them through the scan fallback, so the backward must take them too)
+    while ((1ll << (20 + g.shift)) < npix) g.shift++;
+    // owners per face: enough for the LDS budget, and for ~one workgroup per CU on small batches
+    int splits = (nver + BWD_RANGE_MAX - 1) / BWD_RANGE_MAX;
+    const int want = (256 + B - 1) / B;
+    if (splits < want) splits = want;
+    if (splits > nver) splits = nver;
+    g.range = (nver + splits - 1) / splits;
+    g.splits = (nver + g.range - 1) / g.range;
+    g.chunks = (int)((npix + REC_PX - 1) / REC_PX);
+    g.lds = (size_t)g.range * sizeof(unsigned long long) + 2 * (BWD_BLOCK / 64) * sizeof(uint32_t) + 16;
+    g.xcd_map = (B & 7) == 0;
+    return g;
+}
+}  // namespace
+
+// test hook (tests/test_capi_cpu.py, tests/test_render_backward_exact_gpu.py): the geometry the backward launcher would
+// choose, without a GPU.  out = {splits, range, shift, chunks, lds_bytes, xcd_map}; all zero for a shape that launches
+// no kernel or is refused
+extern "C" void fr_debug_render_bwd_geom(int B, int nver, int H, int W, int* out) {
+    for (int i = 0; i < 6; i++) out[i] = 0;
+    const long long npix = (long long)H * W;
+    if (B <= 0 || nver <= 0 || H <= 0 || W <= 0 || npix > 0x7FFFFFFFll) return;
+    const BwdRenderGeom g = render_bwd_geom(B, nver, npix);
+    out[0] = g.splits; out[1] = g.range; out[2] = g.shift; out[3] = g.chunks; out[4] = (int)g.lds; out[5] = g.xcd_map ? 1 : 0;
+}
+
 int fr_launch_render_backward(const float* depth_grad, const float* tri, const float* tri_ind, float* vertex_grad,
                               int B, int nver, int ntri, int H, int W, void* workspace, size_t ws_bytes,
                               hipStream_t stream) {
@@ -1789,32 +1830,22 @@ int fr_launch_render_backward(const float* depth_grad, const float* tri, const f
     if (npix * B == 0 || ntri == 0 || nver == 0)
         return (!bytes || hipMemsetAsync(vertex_grad, 0, bytes, stream) == hipSuccess) ? FR_OK : FR_ERR_LAUNCH;
     if (npix > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
-    // the int64 headroom covers 3 * 2^20 terms per vertex at the full 38-bit resolution; larger images give up one bit of
-    // resolution per doubling (the forward renders them through the scan fallback, so the backward must take them too)
-    int shift = 0;
-    while ((1ll << (20 + shift)) < npix) shift++;
-    // owners per face: enough for the LDS budget, and for ~one workgroup per CU on small batches
-    int splits = (nver + BWD_RANGE_MAX - 1) / BWD_RANGE_MAX;
-    const int want = (256 + B - 1) / B;
-    if (splits < want) splits = want;
-    if (splits > nver) splits = nver;
-    const int range = (nver + splits - 1) / splits;
-    splits = (nver + range - 1) / range;
+    const BwdRenderGeom geo = render_bwd_geom(B, nver, npix);
+    const int splits = geo.splits, chunks = geo.chunks;
     if ((long long)B * splits > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
     BwdRenderArgs a;
     a.depth_grad = depth_grad; a.tri = tri; a.tri_ind = tri_ind; a.vertex_grad = vertex_grad;
-    a.nver = nver; a.ntri = ntri; a.npix = (int)npix; a.splits = splits; a.range = range; a.shift = shift;
+    a.nver = nver; a.ntri = ntri; a.npix = (int)npix; a.splits = splits; a.range = geo.range; a.shift = geo.shift;
     // with a workspace one pre-kernel resolves every pixel to its vertex ids once (instead of once per owner workgroup)
     // and the owners stream 16-byte records
     const bool packed = workspace && ws_bytes >= fr_render_backward_workspace_bytes_impl(B, H, W) &&
                         (((uintptr_t)workspace) & 15) == 0;
     int4* rec = reinterpret_cast<int4*>(workspace);
-    const int chunks = (int)((npix + REC_PX - 1) / REC_PX);
     uint2* partial = reinterpret_cast<uint2*>(rec + (size_t)B * npix);
     a.rec = packed ? rec : nullptr;
     a.partial = packed ? partial : nullptr;
     a.B = B; a.chunks = chunks;
-    const size_t lds = (size_t)range * sizeof(unsigned long long) + 2 * (BWD_BLOCK / 64) * sizeof(uint32_t) + 16;
+    const size_t lds = geo.lds;
     static fr_lds_flags_t lds_ok[2][64];
     if (packed) {
         if ((long long)B * chunks > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;

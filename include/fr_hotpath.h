@@ -147,7 +147,8 @@ int fr_render_depth_backward(const float* depth_grad, const float* tri, const fl
  * batch plus 8 per 1,024 pixels, 16-byte aligned): one pre-kernel resolves every pixel to its triangle's three vertex ids ONCE and writes a
  * record per pixel; the accumulating workgroups (several per face) then stream the records instead of each repeating the
  * scattered id gathers.  Results are bit-identical to fr_render_depth_backward (which is this function with
- * workspace = NULL). */
+ * workspace = NULL).  A workspace smaller than that, or not 16-byte aligned, is not an error here: it is left untouched
+ * and the call runs as fr_render_depth_backward (tests/test_render_backward_exact_gpu.py calls it both ways). */
 size_t fr_render_depth_backward_workspace_bytes(int B, int H, int W);
 
 int fr_render_depth_backward_ws(const float* depth_grad, const float* tri, const float* tri_ind, float* vertex_grad,
@@ -311,6 +312,14 @@ void fr_debug_render_geom(int B, int ntri, int H, int W, int rows_override, int*
  * reference-layout GEMM workgroup, GEMM workgroups, prepass workgroups}.  Used by tests/test_decode_backward_bounds_gpu.py to
  * derive its rounding-error bounds and by tests/test_capi_cpu.py. */
 void fr_debug_decode_bwd_geom(int nbatch, int N, int n_shape, int n_exp, int* out);
+
+/* The render-backward launch geometry (no GPU needed; the launcher reads the same function): out[6] = {owner workgroups
+ * per face, vertices per owner, shift (resolution bits given up above 2^20 pixels), 1,024-pixel record chunks of the
+ * workspace variant, dynamic LDS bytes of an owner workgroup, 1 if the block -> (face, owner) map is the one that keeps a
+ * face's owners on one XCD (batch a multiple of 8) else 0}; all zero for a shape that launches no kernel.  Used by
+ * tests/test_render_backward_exact_gpu.py to assert that a case reaches the geometry it was written for, and by
+ * tests/test_capi_cpu.py. */
+void fr_debug_render_bwd_geom(int B, int nver, int H, int W, int* out);
 
 /* The kernels divide by 3.0f (render_depth_op.cc:217, 223, 361) through a 3-instruction exact sequence: this hook
  * compares it with x / 3.0f on the fp32 bit patterns [first, first + count) and writes the number of differing results

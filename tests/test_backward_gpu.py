@@ -1,6 +1,10 @@
 """GPU parity: fr_render_depth_backward + autograd wiring vs the CPU oracle (render_depth_op.cc:325-368 with
-zero-init and the tri_ind<0 guard).  The HIP kernel scatter-adds with f32 atomics, so the per-vertex sum order
-is not the oracle's row-major order: tolerance = count * ulp of the partial sums (documented in DESIGN.md)."""
+zero-init and the tri_ind<0 guard).  The HIP kernel adds every contribution as an exact 64-bit fixed-point integer (LDS
+integer atomics: order independent) and rounds the per-vertex sum to fp32 once, so its result is bit-reproducible and is
+the rounded real sum up to the grid error n * 2^-39 * max|term| -- it differs from the oracle's row-major fp32 order only
+by that order's own rounding, which is what the tolerances below allow.  Only a face with Inf / NaN gradients takes fp32
+atomics.  The bit-exact statement of the kernel is tests/ref_render_bwd_model.py, and
+tests/test_render_backward_exact_gpu.py holds the kernel to it at every launch geometry."""
 import json
 import os
 

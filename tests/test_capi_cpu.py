@@ -364,3 +364,35 @@ def test_decode_backward_geometry_hook():
         assert geom(64, 53215)[:4] == [7, 476, 4, 4]
     with host.options(FR_BWD_CHUNKS=1, FR_BWD_CB=2):
         assert geom(1, 4270)[:4] == [267, 1, 2, 8]
+
+
+def test_render_backward_geometry_hook():
+    """fr_debug_render_bwd_geom: {owners per face, vertices per owner, shift, record chunks, dynamic LDS bytes, XCD map} from
+    the function the launcher itself reads.  The rows are the launch shapes tests/test_render_backward_exact_gpu.py is
+    written for: owners clamped to the vertex count; 256 owners of 208 at one face; the XCD block map with several owners at
+    a batch of 8; the product batch, whose 106,576 B need the full-LDS opt-in; the other block map at 65 / 70; the largest
+    owner range (131,216 B of LDS) and the short second owner one vertex above it; the shift above 2^20 pixels."""
+    L = pkg("_lib").lib()
+
+    def geom(B, nver, H=200, W=200):
+        out = (ctypes.c_int * 6)()
+        L.fr_debug_render_bwd_geom(B, nver, H, W, out)
+        return list(out)
+
+    assert geom(1, 3) == [3, 1, 0, 40, 152, 0]
+    assert geom(1, 10)[:2] == [10, 1] and geom(1, 1)[:2] == [1, 1]
+    assert geom(1, 53215) == [256, 208, 0, 40, 1808, 0]
+    assert geom(3, 53215)[:2] == [86, 619] and geom(7, 53215)[:2] == [37, 1439]
+    assert geom(8, 53215) == [32, 1663, 0, 40, 13448, 1]
+    assert geom(16, 53215)[:2] == [16, 3326] and geom(16, 53215)[5] == 1
+    assert geom(64, 53215) == [4, 13304, 0, 40, 106576, 1]
+    assert geom(64, 53215)[4] > 64 * 1024                      # above the default dynamic-LDS limit: fr_allow_full_lds
+    assert geom(65, 53215) == [4, 13304, 0, 40, 106576, 0] and geom(70, 53215) == geom(65, 53215)
+    assert geom(256, 16384, 32, 32) == [1, 16384, 0, 1, 131216, 1]
+    assert geom(256, 16385, 32, 32) == [2, 8193, 0, 1, 65688, 1]
+    assert geom(16, 70000)[:2] == [16, 4375]
+    assert [geom(2, 50, 1, n)[3] for n in (1, 1023, 1024, 1025, 8193)] == [1, 1, 1, 2, 9]
+    assert geom(2, 50, 1024, 1024)[2:4] == [0, 1024] and geom(2, 50, 1025, 1024)[2:4] == [1, 1025]
+    assert geom(2, 50, 1025, 2048)[2] == 2 and geom(1, 400, 1100, 1000)[2] == 1
+    assert geom(0, 5) == [0] * 6 and geom(4, 0) == [0] * 6 and geom(4, 5, 0, 9) == [0] * 6
+    assert geom(1, 5, 65536, 65536) == [0] * 6                 # more than 2^31 - 1 pixels: refused by the launcher

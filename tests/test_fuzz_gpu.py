@@ -1,13 +1,14 @@
 """Seeded differential fuzzing of the HIP path against the CPU oracle: scene type, batch, image size, triangle count,
 coordinate scale and special values are all drawn from the seed, so every case is reproducible by its id.  Bars as in
-the targeted tests: forward planes bit-exact; backward bit-reproducible and within the stated bound of the oracle;
-decode bit-exact against the spec of the selected arithmetic."""
+the targeted tests: forward planes bit-exact; backward bit-reproducible, within the stated bound of the oracle and
+bit-equal to its integer model (tests/ref_render_bwd_model.py) on every face without Inf / NaN gradients; decode bit-exact against the spec of the selected arithmetic."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import ref_render_bwd_model as bwd_model
 from conftest import pkg
 from gpu_util import assert_render_equal, net_mod, ops, render_gpu
 
@@ -89,19 +90,58 @@ def test_render_forward_and_backward(oracle, seed):
     rs = np.random.RandomState(seed)
     g = (rs.uniform(-2, 2, (B, H, W, 1)) * (rs.rand(B, H, W, 1) < 0.7)).astype(np.float32)
     dev = torch.device("cuda:0")
-    outs = []
-    for _ in range(2):
-        v = torch.as_tensor(ver, device=dev).requires_grad_(True)
-        d = ops().render_depth(v, torch.as_tensor(tri, device=dev), torch.as_tensor(tex, device=dev),
-                               torch.zeros((B, H, W, 3), device=dev))[0]
-        d.backward(torch.as_tensor(g, device=dev))
-        outs.append(v.grad.cpu().numpy())
-    np.testing.assert_array_equal(outs[0], outs[1])
+
+    def backward_twice(g):
+        outs = []
+        for _ in range(2):
+            v = torch.as_tensor(ver, device=dev).requires_grad_(True)
+            d = ops().render_depth(v, torch.as_tensor(tri, device=dev), torch.as_tensor(tex, device=dev),
+                                   torch.zeros((B, H, W, 3), device=dev))[0]
+            d.backward(torch.as_tensor(g, device=dev))
+            outs.append(v.grad.cpu().numpy())
+        return outs
+
+    def assert_is_the_model(out, g):
+        """bit-equal to the integer model on every fixed-point face; class and sequential-sum bound on the others"""
+        M = bwd_model.model(g, tri, want[3], nver, H, W)
+        fixed = np.flatnonzero(~M.bad)
+        np.testing.assert_array_equal(out.view(np.uint32)[fixed], M.bits[fixed], err_msg="fuzz seed %d" % seed)
+        for b in np.flatnonzero(M.bad):
+            assert not out.view(np.uint32)[b, :2].any()
+            bwd_model.assert_bad_face(out[b, 2], M, b)
+        return M
+
+    out, again = backward_twice(g)
+    np.testing.assert_array_equal(out, again)
     wantg = oracle.render_depth_grad(g, tri, want[3], nver)
     n_terms = 3 * H * W
     tol = n_terms * np.float32(2.0 / 3.0) * np.float32(2.0 ** -23) + 1e-30
-    assert np.max(np.abs(outs[0] - wantg)) <= tol
-    np.testing.assert_array_equal(outs[0][:, :2], 0.0)
+    assert np.max(np.abs(out - wantg)) <= tol
+    np.testing.assert_array_equal(out[:, :2], 0.0)
+    assert not assert_is_the_model(out, g).bad.any()
+    # a second gradient profile drawn from the seed: 12 decades, or the uniform one with a few Inf / NaN / subnormal / zero
+    # entries anywhere (covered or not).  Against the oracle the same n-terms bound, scaled by the face's largest finite
+    # |g| (above: 2), on every value the oracle holds finite; against the model, the bits.
+    if rs.rand() < 0.5:
+        g2 = (rs.standard_normal((B, H, W, 1)) * np.exp(rs.uniform(-14, 14, (B, H, W, 1)))).astype(np.float32)
+    else:
+        g2 = g.copy()
+        flat = g2.reshape(-1)
+        for val in (np.inf, -np.inf, np.nan, 1e-40, -3e-45, 0.0, -0.0, 1.5e-38):
+            flat[rs.randint(0, flat.size, 2)] = val
+    out2, again2 = backward_twice(g2)
+    assert_is_the_model(out2, g2)
+    assert_is_the_model(again2, g2)          # (a face with Inf / NaN has no bits to repeat; every other face has the model's)
+    with np.errstate(all="ignore"):
+        wantg2 = oracle.render_depth_grad(g2, tri, want[3], nver)
+    gmax = np.where(np.isfinite(g2), np.abs(g2), 0).reshape(B, -1).max(axis=1).astype(np.float64)
+    tol2 = (n_terms * (gmax / 3.0) * 2.0 ** -23 + 1e-30)[:, None, None]
+    fin = np.isfinite(wantg2)
+    np.testing.assert_array_equal(np.isnan(out2), np.isnan(wantg2))
+    np.testing.assert_array_equal(out2[~fin & ~np.isnan(wantg2)], wantg2[~fin & ~np.isnan(wantg2)])
+    with np.errstate(invalid="ignore"):
+        assert np.all(np.abs(out2.astype(np.float64) - wantg2)[fin] <= np.broadcast_to(tol2, out2.shape)[fin])
+    np.testing.assert_array_equal(out2[:, :2], 0.0)
 
 
 @pytest.mark.parametrize("seed", range(N_DECODE))
