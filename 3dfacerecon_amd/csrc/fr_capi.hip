@@ -64,7 +64,7 @@ int fr_get_option(const char* name, int* value) {
 #define FR_SRC_HASH "unhashed"
 #endif
 // the build identity: _lib.py refuses a library whose source hash differs from the tree's
-const char* fr_version(void) { return "fr_hotpath 0.3 (gfx950) src=" FR_SRC_HASH; }
+const char* fr_version(void) { return "fr_hotpath 0.4 (gfx950) src=" FR_SRC_HASH; }
 
 const char* fr_strerror(int code) {
     switch (code) {
@@ -375,6 +375,88 @@ int fr_decode_3dmm_backward_packed_mu(const float* grad_vertex_proj, const float
     if (!workspace || ((uintptr_t)workspace & 15)) return FR_ERR_WORKSPACE;
     return fr_launch_decode_backward(grad_vertex_proj, params, nullptr, nullptr, nullptr, R_override, B, N, n_shape, n_exp,
                                      im_size, grad_params, workspace, (hipStream_t)hip_stream, packed_t, mu);
+}
+
+// ---- differentiable decode -> rendering-layer step -----------------------------------------------------------------------
+int fr_decode_rendering_layer_forward(const float* params, const void* packed_basis, const float* R_override, const float* tri,
+                                      const float* texture, const float* im_gray, int B, int N, int n_shape, int n_exp, int ntri,
+                                      int H, int W, int tex_batch, float im_size, float* vertex_handoff, size_t vertex_bytes,
+                                      float* net_input, float* depth_img, float* depth, float* tri_ind, void* workspace,
+                                      size_t ws_bytes, void* hip_stream, int phases) {
+    if ((phases & 15) < 1 || (phases & ~0xFF0F)) return FR_ERR_INVALID_ARG;   // bits 0-3: phases; bits 8-15: strip-height hint
+    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0 || ntri < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
+    if (tex_batch != 1 && tex_batch != B) return FR_ERR_INVALID_ARG;
+    if (B == 0) return FR_OK;
+    const int pitch = fr_decode_render_vertex_pitch(N);
+    if (N > 0 && (!vertex_handoff || vertex_bytes < fr_decode_render_vertex_bytes(B, N) || ((uintptr_t)vertex_handoff & 127)))
+        return FR_ERR_WORKSPACE;
+    const bool layer = (phases & 7) && (size_t)H * W > 0;
+    if ((phases & 8) && N > 0) {
+        if (!params || !packed_basis) return FR_ERR_INVALID_ARG;
+        if (((uintptr_t)packed_basis & 15) != 0) return FR_ERR_INVALID_ARG;
+    }
+    if (layer) {   // the checks of fr_rendering_layer_forward, all of them BEFORE the decode is launched
+        if (!net_input || !depth_img || !depth || !tri_ind || !im_gray) return FR_ERR_INVALID_ARG;
+        if (ntri > 0 && (!tri || (N > 0 && !texture))) return FR_ERR_INVALID_ARG;
+        if (!fr_rendering_layer_supported(B, N, ntri, H, W)) return FR_ERR_UNSUPPORTED;
+        if (ws_bytes < fr_render_depth_workspace_bytes(B, N, ntri, H, W)) return FR_ERR_WORKSPACE;
+    }
+    if ((phases & 8) && N > 0) {
+        const int rc = fr_launch_decode(params, packed_basis, R_override, B, N, n_shape, n_exp, im_size, vertex_handoff, pitch,
+                                        (hipStream_t)hip_stream);
+        if (rc != FR_OK) return rc;
+    }
+    if (!layer) return FR_OK;
+    return fr_launch_rendering_layer(vertex_handoff, tri, texture, im_gray, B, N, ntri, H, W, tex_batch, net_input, depth_img,
+                                     depth, tri_ind, workspace, ws_bytes, (hipStream_t)hip_stream, phases & 7, pitch,
+                                     (phases >> 8) & 0xFF);
+}
+
+// workspace of fr_decode_render_backward: [records + chunk partials of the render backward | z plane [B, pitch] | decode-backward
+// slabs], each part rounded up to 256 bytes
+namespace {
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct DrbLayout { size_t rec, z, dec; };
+DrbLayout drb_layout(int B, int N, int n_shape, int n_exp, int H, int W) {
+    DrbLayout l;
+    l.rec = up256(fr_render_depth_backward_workspace_bytes(B, H, W));
+    l.z = up256((size_t)B * (size_t)fr_decode_render_vertex_pitch(N) * sizeof(float));
+    l.dec = up256(fr_decode_backward_workspace_impl(N, n_shape, n_exp));
+    return l;
+}
+}  // namespace
+
+size_t fr_decode_render_backward_workspace_bytes(int B, int N, int n_shape, int n_exp, int H, int W) {
+    if (B <= 0 || N <= 0 || n_shape < 0 || n_exp < 0 || H < 0 || W < 0) return 0;
+    if (fr_decode_backward_basis_bytes_impl(N, n_shape, n_exp) == 0) return 0;
+    const DrbLayout l = drb_layout(B, N, n_shape, n_exp, H, W);
+    return l.rec + l.z + l.dec;
+}
+
+int fr_decode_render_backward(const float* g_depth, const float* g_depth_img, const float* g_net_input, const float* im_gray,
+                              const float* depth, const float* tri, const float* tri_ind, const float* params, const float* mu,
+                              const void* packed_t, const float* R_override, int B, int N, int n_shape, int n_exp, int ntri,
+                              int H, int W, float im_size, float* grad_params, void* workspace, size_t ws_bytes,
+                              void* hip_stream) {
+    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0 || ntri < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
+    if (fr_decode_backward_basis_bytes(N, n_shape, n_exp) == 0) return FR_ERR_UNSUPPORTED;   // what the fused kernel does not serve
+    if (B == 0) return FR_OK;
+    if (!g_depth && !g_depth_img && !g_net_input) return FR_ERR_INVALID_ARG;
+    if ((g_depth_img || g_net_input) && (!im_gray || !depth)) return FR_ERR_INVALID_ARG;
+    if (!grad_params || !params || !mu || !packed_t || !tri_ind || (ntri > 0 && !tri)) return FR_ERR_INVALID_ARG;
+    if (((uintptr_t)packed_t & 15) != 0 || ((uintptr_t)mu & 15) != 0) return FR_ERR_INVALID_ARG;
+    if ((long long)H * W > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
+    if (!workspace || ((uintptr_t)workspace & 255) || ws_bytes < fr_decode_render_backward_workspace_bytes(B, N, n_shape, n_exp, H, W))
+        return FR_ERR_WORKSPACE;
+    const DrbLayout l = drb_layout(B, N, n_shape, n_exp, H, W);
+    char* ws = reinterpret_cast<char*>(workspace);
+    float* zplane = reinterpret_cast<float*>(ws + l.rec);
+    const int pitch = fr_decode_render_vertex_pitch(N);
+    const FrPixelGrad pg = {g_depth, g_depth_img, g_net_input, im_gray, depth};
+    int rc = fr_launch_render_backward_z(pg, tri, tri_ind, zplane, pitch, B, N, ntri, H, W, ws, l.rec, (hipStream_t)hip_stream);
+    if (rc != FR_OK) return rc;
+    return fr_launch_decode_backward(zplane, params, nullptr, nullptr, nullptr, R_override, B, N, n_shape, n_exp, im_size,
+                                     grad_params, ws + l.rec + l.z, (hipStream_t)hip_stream, packed_t, mu, pitch);
 }
 
 }  // extern "C"

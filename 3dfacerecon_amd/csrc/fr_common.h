@@ -132,10 +132,22 @@ int fr_launch_render_forward_phases(const float* vertex, const float* tri, const
                                     long long vpitch = 0, int rows_hint = 0);
 int fr_launch_rendering_layer(const float* vertex, const float* tri, const float* texture, const float* im_gray, int B,
                               int nver, int ntri, int H, int W, int tex_batch, float* net_in, float* depth_img,
-                              float* depth, float* tri_ind, void* workspace, size_t ws_bytes, hipStream_t stream, int phases = 7);
+                              float* depth, float* tri_ind, void* workspace, size_t ws_bytes, hipStream_t stream, int phases = 7,
+                              long long vpitch = 0, int rows_hint = 0);
+bool fr_rendering_layer_supported(int B, int nver, int ntri, int H, int W);
 int fr_launch_render_backward(const float* depth_grad, const float* tri, const float* tri_ind, float* vertex_grad,
                               int B, int nver, int ntri, int H, int W, void* workspace, size_t ws_bytes,
                               hipStream_t stream);
+// the pixel-gradient planes of fr_decode_render_backward (each gradient may be null; the formula: bwd_records_body in fr_render.hip)
+struct FrPixelGrad {
+    const float* g_depth;      // [B,H,W,1]
+    const float* g_depth_img;  // [B,H,W,1]
+    const float* g_net_input;  // [B,H,W,7], channel 0 read
+    const float* im_gray;      // [B,H,W,1]
+    const float* depth;        // [B,H,W,1]
+};
+int fr_launch_render_backward_z(const FrPixelGrad& pg, const float* tri, const float* tri_ind, float* zplane, int zpitch,
+                                int B, int nver, int ntri, int H, int W, void* workspace, size_t ws_bytes, hipStream_t stream);
 size_t fr_render_backward_workspace_bytes_impl(int B, int H, int W);
 size_t fr_render_workspace_bytes_impl(int B, int ntri, int H, int W);
 size_t fr_packed_basis_bytes(int N, int n_shape, int n_exp);
@@ -158,7 +170,7 @@ size_t fr_decode_backward_workspace_impl(int N, int ns, int ne);
 int fr_launch_decode_backward(const float* grad_vertex_proj, const float* params, const float* vertex_proj,
                               const float* pc_shape, const float* pc_exp, const float* R_override, int B, int N, int ns,
                               int ne, float im_size, float* grad_params, void* workspace, hipStream_t stream,
-                              const void* packed_t = nullptr, const float* mu = nullptr);
+                              const void* packed_t = nullptr, const float* mu = nullptr, int zpitch = 0);
 size_t fr_decode_backward_basis_bytes_impl(int N, int ns, int ne);
 int fr_launch_decode_backward_pack(const float* pc_shape, const float* pc_exp, int N, int ns, int ne, void* packed_t,
                                    hipStream_t stream);

@@ -53,6 +53,8 @@ struct BwdArgs {
                              // vertex groups of 16 in all / per workgroup
     int exp_slot0;           // first coefficient slot of the expression basis in the slabs
     int nslots;              // coefficient slots per partial slab (64 per wave of the GEMM workgroup)
+    int zpitch;              // > 0 (bwd_fused_z_kernel): g is NOT [B,3,N] but the z row alone, face b at g + b * zpitch -- the x and y rows
+                             // are zero by construction (every vertex gradient of this model comes through the depth plane)
     const float* mu;         // [3N] mean shape, or null.  Non-null (fr_decode_3dmm_backward_packed_mu): d f is formed WITHOUT the
                              // forward output -- sum_p (R v_p) . dq = sum_p v_p . dv_p / f with v = mu + S alpha + E beta, i.e.
                              // d f = (sum_p mu_p . dv_p + alpha . d alpha + beta . d beta) / f: the fused kernel reads 0.64 MB of mu
@@ -336,15 +338,21 @@ __global__ __launch_bounds__(256) void bwd_pack_kernel(const float* __restrict__
 // other waits for its fragments) or 4 (four waves, one per SIMD; also what bases of more than 16 blocks take).
 // Either way the packed path covers bases of at most 16 blocks (256 coefficients: the model has 228); larger ones take the
 // reference-layout entry point (fr_decode_backward_basis_bytes answers 0 for them).
-template <int NB, int CB>
-__global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_kernel(BwdArgs a) {
+// ZONLY (bwd_fused_z_kernel, fr_decode_render_backward): the incoming gradient is the pitched z plane of the render backward;
+// the tile is ONE 16-byte load of g_z plus the three mu rows (mu form of d f only) -- four loads per staging thread instead of
+// six, and every counted wait behind a tile counts four.  dv is evaluated with the SAME expression, dq0 = +0.0f and dq1 = -0.0f
+// as constants (what the dense chain reads back from the zeroed x / y rows and negates): bit-identical for every f R,
+// non-finite ones included, at a few VALU operations per vertex.
+template <int NB, int CB, bool ZONLY>
+__device__ __forceinline__ void bwd_fused_body(const BwdArgs& a) {
+    constexpr int TL = ZONLY ? 4 : 6;   // tile loads per staging thread
     __shared__ float Mt[64][13];                                            // f*R (9), t (3), 1/f or 0
     __shared__ __attribute__((aligned(16))) float4 dvL[2][3][4][64];        // [buffer][coordinate][k-step][lane] (mb in .xyzw)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int nd = FR_N_POSE + a.ns + a.ne;
     const int N = a.N;
-    const bool muf = a.mu != nullptr;   // (uniform) d f from mu . dv: the tile's second operand is mu, not vertex_proj
+    const bool muf = ZONLY || a.mu != nullptr;   // (uniform) d f from mu . dv: the tile's second operand is mu, not vertex_proj
     if (tid < 64) {
         float m[13];
 #pragma unroll
@@ -371,7 +379,7 @@ __global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_kernel(BwdArgs 
 #pragma unroll
     for (int i = 0; i < 13; i++) m[i] = Mt[sb_][i];
     const int bc = min(sb_, a.nbatch - 1);   // (dead columns load a live column's tile and discard it)
-    const float* gx = a.g + (size_t)(a.b0 + bc) * 3 * N + 4 * q;
+    const float* gx = ZONLY ? a.g + (size_t)(a.b0 + bc) * a.zpitch + 4 * q : a.g + (size_t)(a.b0 + bc) * 3 * N + 4 * q;
     const float* vx = muf ? a.mu + 4 * q : a.vproj + (size_t)(a.b0 + bc) * 3 * N + 4 * q;
     // MFMA role: this wave's CB 16-coefficient blocks
     const int kq = lane >> 4, jn = lane & 15;
@@ -398,12 +406,22 @@ __global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_kernel(BwdArgs 
         // (the LAST group's vertices may end before its sixteen: its loads are clamped to stay inside the rows; the values
         // of the missing vertices are zeroed by the mask below)
         const long long p0 = min(16 * gc, (long long)max(N - 16, 0));
+        if constexpr (ZONLY) {
+            const float* pg = gx + p0;
+            FRB_LD(tg[2], pg);
 #pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float* pg = gx + (size_t)c * N + p0;
-            const float* pv = vx + (size_t)c * N + p0;
-            FRB_LD(tg[c], pg);
-            FRB_LD(tv[c], pv);
+            for (int c = 0; c < 3; c++) {
+                const float* pv = vx + (size_t)c * N + p0;
+                FRB_LD(tv[c], pv);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float* pg = gx + (size_t)c * N + p0;
+                const float* pv = vx + (size_t)c * N + p0;
+                FRB_LD(tg[c], pg);
+                FRB_LD(tv[c], pv);
+            }
         }
     };
     auto req_basis = [&](int d, int c, long long grp) {
@@ -416,9 +434,13 @@ __global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_kernel(BwdArgs 
         }
     };
     // counted waits: the tile is followed by the 3 CB fragments of its group; a coordinate's CB fragments by 5 CB fragments
-    // (+ 12 tile loads in a staging wave)
+    // (+ in a staging wave the tiles of the next TWO groups, requested in between: 2 TL loads -- 12, or 8 for the z-only tile)
     auto wait_tile = [&]() {
-        if (stage_wave) asm volatile("s_waitcnt vmcnt(%6)" : "+v"(tg[0]), "+v"(tg[1]), "+v"(tg[2]), "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]) : "n"(3 * CB));
+        if constexpr (ZONLY) {
+            if (stage_wave) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(tg[2]), "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]) : "n"(3 * CB));
+        } else {
+            if (stage_wave) asm volatile("s_waitcnt vmcnt(%6)" : "+v"(tg[0]), "+v"(tg[1]), "+v"(tg[2]), "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]) : "n"(3 * CB));
+        }
     };
     // tile -> dv rows of group grp into LDS buffer `buf` + the pose partial sums (tile registers must have arrived)
     auto stage = [&](long long grp, int buf) {
@@ -431,7 +453,8 @@ __global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_kernel(BwdArgs 
             float g0 = 0.f, g1 = 0.f, g2 = 0.f, v0 = 0.f, v1 = 0.f, v2 = 0.f;
             bool ok = blive && (16 * grp + 4 * q + r) < N;
             if (shift == 0) {
-                g0 = tg[0][r]; g1 = tg[1][r]; g2 = tg[2][r]; v0 = tv[0][r]; v1 = tv[1][r]; v2 = tv[2][r];
+                if constexpr (!ZONLY) { g0 = tg[0][r]; g1 = tg[1][r]; }   // (z-only: g_x = g_y = +0, so dq0 = +0 and dq1 = -0)
+                g2 = tg[2][r]; v0 = tv[0][r]; v1 = tv[1][r]; v2 = tv[2][r];
             } else {
                 ok = false;   // (clamped group: taken by the slow path below)
             }
@@ -458,9 +481,13 @@ __global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_kernel(BwdArgs 
                 const bool okx = blive && pvx < N;
                 float vv[3] = {0.f, 0.f, 0.f};
                 if (okx) {
-                    const float* gb = a.g + (size_t)(a.b0 + bc) * 3 * N + pvx;
                     const float* vb = muf ? a.mu + pvx : a.vproj + (size_t)(a.b0 + bc) * 3 * N + pvx;
-                    dq0 = gb[0]; dq1 = -gb[N]; dq2 = gb[2 * (size_t)N];
+                    if constexpr (ZONLY) {
+                        dq0 = 0.f; dq1 = -0.f; dq2 = a.g[(size_t)(a.b0 + bc) * a.zpitch + pvx];
+                    } else {
+                        const float* gb = a.g + (size_t)(a.b0 + bc) * 3 * N + pvx;
+                        dq0 = gb[0]; dq1 = -gb[N]; dq2 = gb[2 * (size_t)N];
+                    }
                     vv[0] = vb[0]; vv[1] = vb[N]; vv[2] = vb[2 * (size_t)N];
                 }
 #pragma unroll
@@ -513,12 +540,13 @@ __global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_kernel(BwdArgs 
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
                     // the CB fragments of (group i, coordinate c), the oldest loads in flight
+                    // (behind them: 5 CB fragments, and in a staging wave the 2 TL loads of two tiles)
                     if constexpr (CB == 4) {
-                        if (stage_wave) asm volatile("s_waitcnt vmcnt(32)" : "+v"(ra[d][c][0]), "+v"(ra[d][c][1]), "+v"(ra[d][c][2]), "+v"(ra[d][c][3]));
+                        if (stage_wave) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(ra[d][c][0]), "+v"(ra[d][c][1]), "+v"(ra[d][c][2]), "+v"(ra[d][c][3]) : "n"(20 + 2 * TL));
                         else asm volatile("s_waitcnt vmcnt(20)" : "+v"(ra[d][c][0]), "+v"(ra[d][c][1]), "+v"(ra[d][c][2]), "+v"(ra[d][c][3]));
                     } else {
                         static_assert(CB == 2 || CB == 4, "coefficient blocks per wave");
-                        if (stage_wave) asm volatile("s_waitcnt vmcnt(22)" : "+v"(ra[d][c][0]), "+v"(ra[d][c][1]));
+                        if (stage_wave) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(ra[d][c][0]), "+v"(ra[d][c][1]) : "n"(10 + 2 * TL));
                         else asm volatile("s_waitcnt vmcnt(10)" : "+v"(ra[d][c][0]), "+v"(ra[d][c][1]));
                     }
                     if (nsb > 0 && i < n) {
@@ -545,7 +573,8 @@ __global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_kernel(BwdArgs 
             for (int c = 0; c < 3; c++)
 #pragma unroll
                 for (int ii = 0; ii < CB; ii++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[dd][c][ii]));
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(tg[0]), "+v"(tg[1]), "+v"(tg[2]), "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]));
+        if constexpr (ZONLY) asm volatile("s_waitcnt vmcnt(0)" : "+v"(tg[2]), "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]));
+        else asm volatile("s_waitcnt vmcnt(0)" : "+v"(tg[0]), "+v"(tg[1]), "+v"(tg[2]), "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]));
     }
     // mu form of d f: this workgroup's share of alpha . d alpha + beta . d beta -- the parameters against the PARTIAL coefficient
     // gradients it has just accumulated (the dot product is linear, so the shares of all workgroups add up to the whole; no
@@ -616,6 +645,16 @@ __global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_kernel(BwdArgs 
         }
 }
 #undef FRB_LD
+template <int NB, int CB>
+__global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_kernel(BwdArgs a) {
+    bwd_fused_body<NB, CB, false>(a);
+}
+// (its own __global__ name, not a third template argument of bwd_fused_kernel: tests/test_capi_cpu.py counts that kernel's
+// instantiations by mangled prefix)
+template <int NB, int CB>
+__global__ __launch_bounds__(CB == 2 ? 512 : 256) void bwd_fused_z_kernel(BwdArgs a) {
+    bwd_fused_body<NB, CB, true>(a);
+}
 
 // ---- fixed-order reduction of the partials ---------------------------------------------------------------------------------
 // One 1024-thread workgroup per 64 consecutive outputs (output i = what*64 + batch: what 0..3 = d t3d / d f, 4.. = the
@@ -796,7 +835,7 @@ int fr_launch_decode_backward_pack(const float* pc_shape, const float* pc_exp, i
 int fr_launch_decode_backward(const float* grad_vertex_proj, const float* params, const float* vertex_proj,
                               const float* pc_shape, const float* pc_exp, const float* R_override, int B, int N, int ns,
                               int ne, float im_size, float* grad_params, void* workspace, hipStream_t stream,
-                              const void* packed_t, const float* mu) {
+                              const void* packed_t, const float* mu, int zpitch) {
     using namespace fr;
     if (B == 0) return FR_OK;
     const int nd = FR_N_POSE + ns + ne;
@@ -822,6 +861,8 @@ int fr_launch_decode_backward(const float* grad_vertex_proj, const float* params
     a.rbt = packed ? g.ngroups : g.rbt;
     a.rb_per_block = packed ? g.groups_per_block : g.rb_per_block;
     a.mu = packed ? mu : nullptr;   // (the mu form of d f exists on the packed path only)
+    a.zpitch = zpitch;
+    if (zpitch > 0 && !(packed && mu)) return FR_ERR_INVALID_ARG;   // (the z-only tile exists in the fused kernel's mu form only)
     a.exp_slot0 = packed ? 16 * g.sbs : bw_ns4(ns);
     a.nslots = packed ? 16 * g.cb_p * g.block_waves_p : 64 * bw_waves(ns, ne);
     for (int b0 = 0; b0 < B; b0 += 64) {
@@ -836,7 +877,11 @@ int fr_launch_decode_backward(const float* grad_vertex_proj, const float* params
                 a.nslots = 16 * cb * g.block_waves_p;
             }
             const dim3 gb(g.block_waves_p * 64);
-#define FR_BWD_LAUNCH1(NBV, CBV) hipLaunchKernelGGL((bwd_fused_kernel<NBV, CBV>), dim3(a.gemm_blocks), gb, 0, stream, a);
+#define FR_BWD_LAUNCH1(NBV, CBV)                                                                                      \
+    {                                                                                                                 \
+        if (zpitch > 0) hipLaunchKernelGGL((bwd_fused_z_kernel<NBV, CBV>), dim3(a.gemm_blocks), gb, 0, stream, a);   \
+        else hipLaunchKernelGGL((bwd_fused_kernel<NBV, CBV>), dim3(a.gemm_blocks), gb, 0, stream, a);                 \
+    }
 #define FR_BWD_LAUNCH(NBV)                                                                                            \
     {                                                                                                                 \
         if (g.cb_p == 2) FR_BWD_LAUNCH1(NBV, 2)                                                                       \

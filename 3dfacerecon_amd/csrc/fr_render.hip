@@ -1297,6 +1297,13 @@ struct BwdRenderArgs {
     int nver, ntri, npix;     // npix = H*W
     int splits, range;        // owner workgroups per face, vertices per owner
     int shift;                // headroom bits given up by images above 2^20 pixels: ceil(log2 npix) - 20, else 0
+    // fr_decode_render_backward: the records pass FORMS the pixel gradient from up to three planes (each may be null) ...
+    const float* g_net;       // [B,H,W,7] gradient of net_input: channel 0 only
+    const float* g_dimg;      // [B,H,W,1] gradient of depth_img
+    const float* im_gray;     // [B,H,W,1]
+    const float* depth;       // [B,H,W,1] forward output
+    // ... and the owners write ONLY the z row, face b at vertex_grad + b * zpitch (0: the dense [B,3,nver] tensor, x / y zeroed)
+    long long zpitch;
 };
 
 // the three vertex ids of pixel value `tv` (a float-stored triangle index, -1 on the background): false when the pixel
@@ -1350,7 +1357,13 @@ __device__ __forceinline__ void bwd_face_max(const BwdRenderArgs& a, int b, uint
 // {p1, p2, p3, g bits} per pixel -- p1 = -1 for pixels that contribute nothing (background, bad ids).  The owners then
 // STREAM the records.  Lane-consecutive pixels: a gather instruction's 64 lanes hold neighbouring triangles.
 constexpr int REC_PX = 1024;  // pixels per records-kernel workgroup (256 threads x 4)
-__global__ __launch_bounds__(256) void bwd_records_kernel(BwdRenderArgs a, int4* rec, uint2* partial, int chunks) {
+// FORM (fr_decode_render_backward): g is not read from depth_grad but formed here, per pixel, in fp32 without contraction --
+//   g = +0;  g += (g_net[..,0] * im_gray) * m1, m1 = (1e-6f <= depth && depth <= 1.0f);  g += g_dimg * m2, m2 = (depth >= 1e-6f);
+//   g += g_depth -- absent planes skipped, the masks MULTIPLIED in as 1.0f / 0.0f (an infinite gradient on a masked pixel is a
+// NaN, as in the torch expression this replaces).  The extra planes are streamed like g and tri_ind: lane-consecutive pixels
+// (the 7-channel plane at a 28-byte stride: seven lines per 64 lanes, each line shared by the lanes that touch it).
+template <bool FORM>
+__device__ __forceinline__ void bwd_records_body(const BwdRenderArgs& a, int4* rec, uint2* partial, int chunks) {
     __shared__ uint32_t red[8];
     const int b = (int)blockIdx.x / chunks, ch = (int)blockIdx.x - b * chunks;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1363,11 +1376,34 @@ __global__ __launch_bounds__(256) void bwd_records_kernel(BwdRenderArgs a, int4*
     constexpr int PU = REC_PX / 256;
     const int i0 = ch * REC_PX + tid;
     float gq[PU], tq[PU];
+    if constexpr (!FORM) {
 #pragma unroll
-    for (int u = 0; u < PU; u++) {
-        const int i = min(i0 + u * 256, a.npix - 1);
-        gq[u] = g[i];
-        tq[u] = ti[i];
+        for (int u = 0; u < PU; u++) {
+            const int i = min(i0 + u * 256, a.npix - 1);
+            gq[u] = g[i];
+            tq[u] = ti[i];
+        }
+    } else {
+        const bool hn = a.g_net != nullptr, hi = a.g_dimg != nullptr, hd = a.depth_grad != nullptr;   // (uniform)
+        float gn[PU], gi[PU], gd[PU], im[PU], dp[PU];
+#pragma unroll
+        for (int u = 0; u < PU; u++) {
+            const size_t i = (size_t)b * a.npix + min(i0 + u * 256, a.npix - 1);
+            tq[u] = a.tri_ind[i];
+            gn[u] = gi[u] = gd[u] = im[u] = dp[u] = 0.f;
+            if (hn) { gn[u] = a.g_net[i * 7]; im[u] = a.im_gray[i]; }
+            if (hi) gi[u] = a.g_dimg[i];
+            if (hn || hi) dp[u] = a.depth[i];
+            if (hd) gd[u] = a.depth_grad[i];
+        }
+#pragma unroll
+        for (int u = 0; u < PU; u++) {
+            float gg = 0.f;
+            if (hn) gg = gg + (gn[u] * im[u]) * ((1e-6f <= dp[u] && dp[u] <= 1.0f) ? 1.0f : 0.0f);
+            if (hi) gg = gg + gi[u] * ((dp[u] >= 1e-6f) ? 1.0f : 0.0f);
+            if (hd) gg = gg + gd[u];
+            gq[u] = gg;
+        }
     }
     int t[PU];
     float f[PU][3];
@@ -1402,6 +1438,12 @@ __global__ __launch_bounds__(256) void bwd_records_kernel(BwdRenderArgs a, int4*
     if (tid == 0)
         partial[(size_t)b * chunks + ch] = make_uint2(max(max(red[0], red[1]), max(red[2], red[3])),
                                                       red[4] | red[5] | red[6] | red[7]);
+}
+__global__ __launch_bounds__(256) void bwd_records_kernel(BwdRenderArgs a, int4* rec, uint2* partial, int chunks) {
+    bwd_records_body<false>(a, rec, partial, chunks);
+}
+__global__ __launch_bounds__(256) void bwd_records_form_kernel(BwdRenderArgs a, int4* rec, uint2* partial, int chunks) {
+    bwd_records_body<true>(a, rec, partial, chunks);
 }
 
 // PACKED (workspace variant): the owners stream the per-pixel records of bwd_records_kernel (the id gathers -- repeated by
@@ -1549,6 +1591,12 @@ __global__ __launch_bounds__(BWD_BLOCK) void render_backward_kernel(BwdRenderArg
         }
     }
     __syncthreads();
+    if (a.zpitch > 0) {   // (uniform) z-only mode: the x / y rows -- zeros -- are neither written here nor read by the consumer
+        float* zrow = a.vertex_grad + (size_t)b * a.zpitch;
+        for (int i = tid; i < v1 - v0; i += BWD_BLOCK)
+            zrow[v0 + i] = bad ? facc[i] : (float)((double)(float)(long long)acc[i] * inv_scale);
+        return;
+    }
     for (int i = tid; i < v1 - v0; i += BWD_BLOCK) {
         gx[v0 + i] = 0.0f;
         gy[v0 + i] = 0.0f;
@@ -1676,9 +1724,19 @@ int fr_launch_render_forward_phases(const float* vertex, const float* tri, const
 
 int fr_launch_rendering_layer(const float* vertex, const float* tri, const float* texture, const float* im_gray, int B,
                               int nver, int ntri, int H, int W, int tex_batch, float* net_in, float* depth_img,
-                              float* depth, float* tri_ind, void* workspace, size_t ws_bytes, hipStream_t stream, int phases) {
+                              float* depth, float* tri_ind, void* workspace, size_t ws_bytes, hipStream_t stream, int phases,
+                              long long vpitch, int rows_hint) {
     return launch_render_impl(vertex, tri, texture, B, nver, ntri, H, W, tex_batch, depth, nullptr, nullptr, tri_ind, im_gray,
-                              net_in, depth_img, workspace, ws_bytes, stream, phases);
+                              net_in, depth_img, workspace, ws_bytes, stream, phases, vpitch, rows_hint);
+}
+
+// true where the fused resolver serves the shape under the knobs in force (what fr_launch_rendering_layer would not answer
+// FR_ERR_UNSUPPORTED for): fr_decode_rendering_layer_forward asks BEFORE it launches its decode
+bool fr_rendering_layer_supported(int B, int nver, int ntri, int H, int W) {
+    if (ntri <= 0 || nver <= 0 || ntri >= (1 << 24)) return false;
+    if ((size_t)W * sizeof(unsigned long long) > kLdsMax) return false;
+    const RenderGeom g = render_geom(B, ntri, H, W);
+    return g.binned_ok && (long long)B * g.strips <= 0x7FFFFFFFll && fr::opt(fr::OPT_RENDER_IMPL) != 1;
 }
 
 // Argument block + geometry of one forward call (everything the kernels read); *binned = the binned rasteriser serves it.
@@ -1821,11 +1879,12 @@ extern "C" void fr_debug_render_bwd_geom(int B, int nver, int H, int W, int* out
     out[0] = g.splits; out[1] = g.range; out[2] = g.shift; out[3] = g.chunks; out[4] = (int)g.lds; out[5] = g.xcd_map ? 1 : 0;
 }
 
-int fr_launch_render_backward(const float* depth_grad, const float* tri, const float* tri_ind, float* vertex_grad,
-                              int B, int nver, int ntri, int H, int W, void* workspace, size_t ws_bytes,
-                              hipStream_t stream) {
+static int launch_render_backward_impl(const FrPixelGrad* pg, const float* depth_grad, const float* tri, const float* tri_ind,
+                                       float* vertex_grad, long long zpitch, int B, int nver, int ntri, int H, int W,
+                                       void* workspace, size_t ws_bytes, hipStream_t stream) {
     using namespace fr;
-    const size_t bytes = (size_t)B * 3 * nver * sizeof(float);
+    // (z-only mode: `vertex_grad` is the [B, zpitch] plane; its pad floats are never written or read)
+    const size_t bytes = zpitch > 0 ? (size_t)B * zpitch * sizeof(float) : (size_t)B * 3 * nver * sizeof(float);
     const long long npix = (long long)H * W;
     if (npix * B == 0 || ntri == 0 || nver == 0)
         return (!bytes || hipMemsetAsync(vertex_grad, 0, bytes, stream) == hipSuccess) ? FR_OK : FR_ERR_LAUNCH;
@@ -1836,10 +1895,14 @@ int fr_launch_render_backward(const float* depth_grad, const float* tri, const f
     BwdRenderArgs a;
     a.depth_grad = depth_grad; a.tri = tri; a.tri_ind = tri_ind; a.vertex_grad = vertex_grad;
     a.nver = nver; a.ntri = ntri; a.npix = (int)npix; a.splits = splits; a.range = geo.range; a.shift = geo.shift;
+    a.g_net = pg ? pg->g_net_input : nullptr; a.g_dimg = pg ? pg->g_depth_img : nullptr;
+    a.im_gray = pg ? pg->im_gray : nullptr; a.depth = pg ? pg->depth : nullptr;
+    a.zpitch = zpitch;
     // with a workspace one pre-kernel resolves every pixel to its vertex ids once (instead of once per owner workgroup)
     // and the owners stream 16-byte records
     const bool packed = workspace && ws_bytes >= fr_render_backward_workspace_bytes_impl(B, H, W) &&
                         (((uintptr_t)workspace) & 15) == 0;
+    if (pg && !packed) return FR_ERR_WORKSPACE;   // (the formed gradient exists in the records only)
     int4* rec = reinterpret_cast<int4*>(workspace);
     uint2* partial = reinterpret_cast<uint2*>(rec + (size_t)B * npix);
     a.rec = packed ? rec : nullptr;
@@ -1849,7 +1912,8 @@ int fr_launch_render_backward(const float* depth_grad, const float* tri, const f
     static fr_lds_flags_t lds_ok[2][64];
     if (packed) {
         if ((long long)B * chunks > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(bwd_records_kernel, dim3((unsigned)(B * chunks)), dim3(256), 0, stream, a, rec, partial, chunks);
+        if (pg) hipLaunchKernelGGL(bwd_records_form_kernel, dim3((unsigned)(B * chunks)), dim3(256), 0, stream, a, rec, partial, chunks);
+        else hipLaunchKernelGGL(bwd_records_kernel, dim3((unsigned)(B * chunks)), dim3(256), 0, stream, a, rec, partial, chunks);
         if (fr_allow_full_lds(reinterpret_cast<const void*>(&render_backward_kernel<true>), lds_ok[1]) != hipSuccess)
             return FR_ERR_LAUNCH;
         hipLaunchKernelGGL(render_backward_kernel<true>, dim3((unsigned)(B * splits)), dim3(BWD_BLOCK), lds, stream, a);
@@ -1859,4 +1923,18 @@ int fr_launch_render_backward(const float* depth_grad, const float* tri, const f
         hipLaunchKernelGGL(render_backward_kernel<false>, dim3((unsigned)(B * splits)), dim3(BWD_BLOCK), lds, stream, a);
     }
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
+
+int fr_launch_render_backward(const float* depth_grad, const float* tri, const float* tri_ind, float* vertex_grad,
+                              int B, int nver, int ntri, int H, int W, void* workspace, size_t ws_bytes,
+                              hipStream_t stream) {
+    return launch_render_backward_impl(nullptr, depth_grad, tri, tri_ind, vertex_grad, 0, B, nver, ntri, H, W, workspace,
+                                       ws_bytes, stream);
+}
+
+// fr_decode_render_backward's first half: pixel gradient formed in the records pass, owners write the pitched z plane only
+int fr_launch_render_backward_z(const FrPixelGrad& pg, const float* tri, const float* tri_ind, float* zplane, int zpitch,
+                                int B, int nver, int ntri, int H, int W, void* workspace, size_t ws_bytes, hipStream_t stream) {
+    return launch_render_backward_impl(&pg, pg.g_depth, tri, tri_ind, zplane, zpitch, B, nver, ntri, H, W, workspace, ws_bytes,
+                                       stream);
 }

@@ -108,12 +108,17 @@ class CoarseNetIter(nn.Module):
 
 
 class CoarseNet(nn.Module):
-    """nIter iterations, each with its own weights (network.py:113-136), around the decode -> render hot path."""
+    """nIter iterations, each with its own weights (network.py:113-136), around the decode -> render hot path.
 
-    def __init__(self, face_net, nIter=4):
+    fused_step=True takes the hot path as ONE call and one autograd node per iteration (FaceRecNet.decode_rendering_layer:
+    the same forward bits; the backward moves only the z row of the vertex gradient and keeps no vertex tensor); the default
+    is the two-step route."""
+
+    def __init__(self, face_net, nIter=4, fused_step=False):
         super().__init__()
         _warn_if_exposed()
         self.face_net = face_net        # nets.network.FaceRecNet (holds the 3DMM constants on the GPU)
+        self.fused_step = bool(fused_step)
         self.iters = nn.ModuleList([CoarseNetIter(face_net.ndim) for _ in range(nIter)])
 
     def forward(self, im_gray, pred_params=None):
@@ -124,14 +129,19 @@ class CoarseNet(nn.Module):
         params = fn.init_pred_params[:B] if pred_params is None else pred_params
         params = params.reshape(B, fn.ndim).to(im_gray.device)
         for it in self.iters:
-            vertices_proj = fn.vertices_transform(params)                       # Input_Rendering_iter%d, :113
-            net_input, _ = fn.coarse_net_input(vertices_proj, im_gray=im_gray)  # :116-122
+            if self.fused_step:
+                net_input, _ = fn.decode_rendering_layer(params, im_gray=im_gray)
+            else:
+                vertices_proj = fn.vertices_transform(params)                       # Input_Rendering_iter%d, :113
+                net_input, _ = fn.coarse_net_input(vertices_proj, im_gray=im_gray)  # :116-122
             params = fn.set_constraints(it(net_input)[:, None, None, :]).reshape(B, fn.ndim)
         return params
 
     def depth(self, im_gray, pred_params):
         """depth_rendering_layer (network.py:300-309) on the final parameters: coarse depth map [B,H,W,1]."""
         fn = self.face_net
+        if self.fused_step:
+            return fn.decode_rendering_layer(pred_params, im_gray=im_gray)[1]
         v = fn.vertices_transform(pred_params)
         return fn.coarse_net_input(v, im_gray=im_gray)[1]
 
@@ -169,22 +179,32 @@ class FaceReconModel(nn.Module):
 
     forward(im_gray) returns {'pred_params' (B,d), 'vertices_proj' (B,3,N), 'coarse_depth_map' (B,H,W,1),
     'pred_depth_map' (B,H,W,1) or None}.  Wrap THIS module in DistributedDataParallel and call the wrapper, so that DDP's
-    forward runs (reducer.prepare_for_backward) and the RCCL all-reduce of the gradients actually happens."""
+    forward runs (reducer.prepare_for_backward) and the RCCL all-reduce of the gradients actually happens.
 
-    def __init__(self, face_net, nIter=4, fine=True):
+    fused_step=True: every CoarseNet iteration and the depth rendering layer go through FaceRecNet.decode_rendering_layer;
+    'vertices_proj' (what the SfS loss reads) then comes from a plain vertices_transform of its own, and only when asked for
+    (forward(..., with_vertices=True), the default)."""
+
+    def __init__(self, face_net, nIter=4, fine=True, fused_step=False):
         super().__init__()
         self.face_net = face_net
-        self.coarse = CoarseNet(face_net, nIter=nIter)
+        self.fused_step = bool(fused_step)
+        self.coarse = CoarseNet(face_net, nIter=nIter, fused_step=fused_step)
         self.fine = FineNet() if fine else None
 
-    def forward(self, im_gray, with_depth=True):
+    def forward(self, im_gray, with_depth=True, with_vertices=True):
         fn = self.face_net
         params = self.coarse(im_gray)
         out = {"pred_params": params, "vertices_proj": None, "coarse_depth_map": None, "pred_depth_map": None}
         if with_depth or self.fine is not None:
-            v = fn.vertices_transform(params)                              # depth_rendering_layer, network.py:300-309
-            out["vertices_proj"] = v
-            out["coarse_depth_map"] = fn.coarse_net_input(v, im_gray=im_gray)[1]
+            if self.fused_step:
+                out["coarse_depth_map"] = fn.decode_rendering_layer(params, im_gray=im_gray)[1]
+                if with_vertices:
+                    out["vertices_proj"] = fn.vertices_transform(params)
+            else:
+                v = fn.vertices_transform(params)                              # depth_rendering_layer, network.py:300-309
+                out["vertices_proj"] = v
+                out["coarse_depth_map"] = fn.coarse_net_input(v, im_gray=im_gray)[1]
             if self.fine is not None:
                 out["pred_depth_map"] = self.fine(im_gray, out["coarse_depth_map"])
         return out

@@ -362,6 +362,36 @@ class FaceRecNet:
             net_in = torch.cat([mask, pncc, normal], dim=3)
         return net_in, depth_img
 
+    def decode_rendering_layer(self, pred_params, im_gray=None, R=None):
+        """vertices_transform -> coarse_net_input in one call and ONE autograd node: (B,1,1,d) or (B,d) parameters ->
+        (net_input [B,H,W,7], depth_img [B,H,W,1]), the same bits as the two-step route.  Forward
+        fr_decode_rendering_layer_forward, backward fr_decode_render_backward (rendering_layer/ops.py::_DecodeRenderingLayer):
+        no dense [B,3,N] vertex tensor exists in either direction and none is kept for the backward.  Where the fused entry
+        points do not serve the call (a shape only the fallback rasteriser covers, a basis of more than 256 coefficients, a
+        mesh of fewer than 16 vertices, the opt-in Q30 decode arithmetic) it IS the two-step route."""
+        h = _host()
+        p = pred_params
+        if p.dim() == 4:
+            p = p.reshape(p.shape[0], p.shape[-1])
+        if p.dim() != 2 or p.shape[1] != self.ndim:
+            raise ValueError("pred_params must be (B,1,1,%d) or (B,%d)" % (self.ndim, self.ndim))
+        p = h.require_gpu_f32(p, "pred_params")
+        B = int(p.shape[0])
+        im_gray = self.im_gray if im_gray is None else im_gray
+        if im_gray is None:
+            im_gray = torch.ones((B, self.im_size, self.im_size, 1), dtype=torch.float32, device=p.device)
+        Rc = None
+        if R is not None:
+            Rc = h.require_gpu_f32(torch.as_tensor(R, dtype=torch.float32, device=p.device), "R")
+            if tuple(Rc.shape) != (B, 3, 3):
+                raise ValueError("R must be (B,3,3)")
+        if self._basis.backward_packed_ok() and not self._basis.use_q30():
+            try:
+                return _ops().decode_rendering_layer(p, Rc, im_gray, self.tri, self.vertex_code, self._basis, self.im_size)
+            except NotImplementedError:
+                pass
+        return self.coarse_net_input(self.vertices_transform(p, R=Rc), im_gray=im_gray)
+
     def compute_abedo_image(self, vertices, triangles, abedos, im_gray=None):
         """Albedo (3,N) -> albedo image + normalised normal map through a second render (network.py:394-417)."""
         ver = vertices.float()

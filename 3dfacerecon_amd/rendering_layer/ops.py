@@ -91,6 +91,7 @@ def clear_workspace_cache():
     """Releases every cached render workspace (their memory returns to torch's caching allocator)."""
     with _WS_LOCK:
         _WS_CACHE.clear()
+        _SCRATCH.clear()
 
 
 def _workspace(dev, nbytes):
@@ -285,6 +286,120 @@ class _RenderingLayerFused(torch.autograd.Function):
         with torch.cuda.device(depth.device):
             _backward_call(h, dg, tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, depth.device)
         return vertex_grad, None, None, None
+
+
+# Per-stream scratch of the decode -> rendering-layer node, kept like the render workspace (least recently used dropped, a
+# fresh buffer under graph capture): the pitched vertex hand-off of the forward and the workspace of the backward.  Launches on
+# one stream are ordered, so consecutive calls share a buffer; nothing in it outlives the call that wrote it.
+_SCRATCH = collections.OrderedDict()
+_SCRATCH_MAX = 8
+
+
+def _scratch(kind, dev, nbytes):
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    key = (kind, dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
+    with _WS_LOCK:
+        buf = _SCRATCH.pop(key, None)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        _SCRATCH[key] = buf
+        while len(_SCRATCH) > _SCRATCH_MAX:
+            _SCRATCH.popitem(last=False)
+    return buf
+
+
+class _DecodeRenderingLayer(torch.autograd.Function):
+    """vertices_transform -> coarse_net_input as ONE autograd node (include/fr_hotpath.h, "differentiable decode ->
+    rendering-layer step"): (params, R, im_gray) -> (net_input [B,H,W,7], depth_img [B,H,W,1]).  Forward:
+    fr_decode_rendering_layer_forward, the vertices in a pitched per-stream scratch buffer that is not kept.  Backward:
+    fr_decode_render_backward -- the pixel gradient is formed inside the render backward's records pass, only the z row of the
+    vertex gradient exists, and the decode backward takes d f from mu: the node saves params, R, tri_ind, depth and im_gray, no
+    [B,3,N]-sized tensor.  Raises NotImplementedError where either entry point answers FR_ERR_UNSUPPORTED."""
+
+    @staticmethod
+    def forward(ctx, params, R, im_gray, tri, texture, basis, im_size):
+        h = _host()
+        L = h.lib()
+        p = h.require_gpu_f32(params, "pred_params")
+        img_c = h.require_gpu_f32(im_gray, "im_gray")
+        tri_c = h.require_gpu_f32(tri, "tri")
+        tex_c = h.require_gpu_f32(texture, "texture")
+        N, ns, ne = basis.nvert, basis.ndim_shape, basis.ndim_exp
+        if p.dim() != 2 or p.shape[1] != 7 + ns + ne:
+            raise ValueError("pred_params must be (B,%d)" % (7 + ns + ne))
+        B = int(p.shape[0])
+        if img_c.dim() != 4 or img_c.shape[0] != B or img_c.shape[-1] != 1:
+            raise ValueError("im_gray must be [B,H,W,1]")
+        if tri_c.dim() != 2 or tri_c.shape[0] != 3:
+            raise ValueError("The tri is not 3 x ntri")
+        if tex_c.dim() not in (2, 3) or tex_c.shape[-2] != 3 or tex_c.shape[-1] != N:
+            raise ValueError("The texture is not Batch x 3 x nver")
+        tex_batch = 1 if tex_c.dim() == 2 else int(tex_c.shape[0])
+        if tex_batch not in (1, B):
+            raise ValueError("The texture's batch is neither 1 nor the image batch")
+        H, W, ntri = int(img_c.shape[1]), int(img_c.shape[2]), int(tri_c.shape[1])
+        dev = p.device
+        if L.fr_decode_render_backward_workspace_bytes(max(B, 1), N, ns, ne, H, W) == 0:
+            raise NotImplementedError("decode -> rendering layer: basis / mesh not served by the fused decode backward")
+        opts = dict(dtype=torch.float32, device=dev)
+        net_in = torch.empty((B, H, W, 7), **opts)
+        depth_img = torch.empty((B, H, W, 1), **opts)
+        depth = torch.empty((B, H, W, 1), **opts)
+        tri_ind = torch.empty((B, H, W, 1), **opts)
+        with torch.cuda.device(dev):
+            ws_bytes = L.fr_render_depth_workspace_bytes(B, N, ntri, H, W)
+            hand_bytes = L.fr_decode_render_vertex_bytes(B, N)
+            ent, cached = _workspace(dev, ws_bytes)
+            with ent.lock:
+                # (the hand-off is taken under the entry's lock: threads that share the stream share both buffers)
+                hand = _scratch("hand", dev, hand_bytes)
+                phases, pending = _render_phases(ent, cached, tri_c, (B, N, ntri, H, W))
+                rc = L.fr_decode_rendering_layer_forward(h.ptr(p), h.ptr(basis.image), h.ptr(R), h.ptr(tri_c), h.ptr(tex_c),
+                                                         h.ptr(img_c), B, N, ns, ne, ntri, H, W, tex_batch, float(im_size),
+                                                         h.ptr(hand), hand_bytes, h.ptr(net_in), h.ptr(depth_img), h.ptr(depth),
+                                                         h.ptr(tri_ind), h.ptr(ent.buf), ws_bytes, h.stream_ptr(dev), 8 | phases)
+                if rc == 0:
+                    _table_packed(ent, pending)
+        if rc == -4:
+            raise NotImplementedError("decode -> rendering layer: shape only covered by the fallback rasteriser")
+        h.check(rc, "fr_decode_rendering_layer_forward")
+        ctx.save_for_backward(p, R if R is not None else p.new_empty(0), tri_ind, depth, img_c)
+        ctx.has_R = R is not None
+        ctx.tri, ctx.basis, ctx.im_size = tri_c, basis, float(im_size)   # (tri: a constant of the model, no gradient)
+        ctx.dims = (B, N, ns, ne, ntri, H, W)
+        ctx.set_materialize_grads(False)
+        return net_in, depth_img
+
+    @staticmethod
+    def backward(ctx, g_net_in, g_depth_img):
+        if g_net_in is None and g_depth_img is None:
+            return (None,) * 7
+        h = _host()
+        L = h.lib()
+        p, R, tri_ind, depth, img = ctx.saved_tensors
+        B, N, ns, ne, ntri, H, W = ctx.dims
+        basis = ctx.basis
+        dev = p.device
+        gn = h.require_gpu_f32(g_net_in, "net_input_grad") if g_net_in is not None else None
+        gd = h.require_gpu_f32(g_depth_img, "depth_img_grad") if g_depth_img is not None else None
+        gp = torch.empty_like(p)
+        with torch.cuda.device(dev):
+            image_t = basis.image_t()
+            nws = L.fr_decode_render_backward_workspace_bytes(B, N, ns, ne, H, W)
+            ws = _scratch("bwd", dev, nws)
+            rc = L.fr_decode_render_backward(None, h.ptr(gd), h.ptr(gn), h.ptr(img), h.ptr(depth), h.ptr(ctx.tri), h.ptr(tri_ind),
+                                             h.ptr(p), h.ptr(basis.mu), h.ptr(image_t), h.ptr(R) if ctx.has_R else None, B, N, ns,
+                                             ne, ntri, H, W, ctx.im_size, h.ptr(gp), h.ptr(ws), nws, h.stream_ptr(dev))
+        h.check(rc, "fr_decode_render_backward")
+        return gp, None, None, None, None, None, None
+
+
+def decode_rendering_layer(params, R, im_gray, tri, texture, basis, im_size):
+    """One-node decode -> rendering layer: (params [B,d], R [B,3,3] or None, im_gray [B,H,W,1]) -> (net_input [B,H,W,7],
+    depth_img [B,H,W,1]); `basis` is the network's PackedBasis.  Raises NotImplementedError where the fused entry points do not
+    serve the shape (the caller composes vertices_transform and rendering_layer_fused instead)."""
+    return _DecodeRenderingLayer.apply(params, R, im_gray, tri, texture, basis, im_size)
 
 
 def rendering_layer_fused(ver, tri, texture, im_gray):

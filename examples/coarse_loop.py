@@ -51,7 +51,7 @@ def build_harness(args, dev, rank, world, local):
     if args.small:  # the tiny mesh is ~30 px wide: centre it and scale it up a little
         face.init_pred_params[..., 6] = 1e-3 * S / 200.0
     # the reference's graph always holds FineNet (build(), network.py:69-101); the forward-only config 3 is CoarseNet + render
-    model = cn.FaceReconModel(face, nIter=args.nIter, fine=args.fine or args.train).to(dev)
+    model = cn.FaceReconModel(face, nIter=args.nIter, fine=args.fine or args.train, fused_step=args.fused_step).to(dev)
     net = model
     if args.train and world > 1:
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local] if dev.type == "cuda" else None)
@@ -104,7 +104,7 @@ def run_test_phase(args, dev, rank, world, local, dist_u):
     face = netm.FaceRecNet(mesh_data=A, batch_size=B, im_size=S, device=dev)
     if args.small:
         face.init_pred_params[..., 6] = 1e-3 * S / 200.0
-    coarse = cn.CoarseNet(face, nIter=args.nIter).to(dev).eval()
+    coarse = cn.CoarseNet(face, nIter=args.nIter, fused_step=args.fused_step).to(dev).eval()
     flights = pipe.BatchesInFlight(face, B, S, S, slots=2)
     g = torch.Generator(device="cpu").manual_seed(100 + rank)
     images = [torch.rand((B, S, S, 1), generator=g).to(dev) for _ in range(4)]   # the "test generator": four resident batches
@@ -199,6 +199,9 @@ def main():
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--val", action="store_true", help="with --train: the reference's per-iteration validation forward")
     ap.add_argument("--fine", action="store_true")
+    ap.add_argument("--fused-step", action="store_true",
+                    help="decode -> rendering layer as one call and one autograd node per CoarseNet iteration "
+                         "(FaceRecNet.decode_rendering_layer); off: the two-step route")
     ap.add_argument("--gather-sfs", action="store_true", help="whole-batch SfS lighting estimate across ranks")
     ap.add_argument("--small", action="store_true", help="tiny synthetic assets (smoke runs)")
     ap.add_argument("--dump-batches", default=None, metavar="FILE.npz",

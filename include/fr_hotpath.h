@@ -301,6 +301,57 @@ int fr_decode_3dmm_backward_packed_mu(const float* grad_vertex_proj, const float
                                       const float* R_override, int B, int N, int n_shape, int n_exp, float im_size,
                                       float* grad_params, void* workspace, size_t ws_bytes, void* hip_stream);
 
+/* ---- differentiable decode -> rendering-layer step (the CoarseNet loop: nets/network.py:140-171 -> :174-201, five times per
+ * training step, nets/coarse_net.py) ---------------------------------------------------------------------------------------
+ * FORWARD.  fr_decode_render_forward with the fused resolver of fr_rendering_layer_forward: same decode and pose arguments, same
+ * pitched vertex hand-off, same render workspace, same `phases` word (8 = decode, 4 = pack the triangle list, 1 = emit, 2 = the
+ * fused resolve, plus FR_PHASES_STRIP_ROWS); it takes im_gray [B,H,W,1] and writes net_input [B,H,W,7], depth_img, depth and
+ * tri_ind exactly as fr_rendering_layer_forward defines them -- bit-identical to fr_decode_3dmm followed by
+ * fr_rendering_layer_forward, without the dense [B,3,N] tensor between them.  The f32 chain only (no Q30 variant).
+ * FR_ERR_UNSUPPORTED wherever fr_rendering_layer_forward answers it (shapes only the fallback rasteriser covers,
+ * FR_RENDER_IMPL = scan, no triangles / vertices), decided before anything is launched. */
+int fr_decode_rendering_layer_forward(const float* params, const void* packed_basis, const float* R_override, const float* tri,
+                                      const float* texture, const float* im_gray, int B, int N, int n_shape, int n_exp, int ntri,
+                                      int H, int W, int tex_batch, float im_size, float* vertex_handoff, size_t vertex_bytes,
+                                      float* net_input, float* depth_img, float* depth, float* tri_ind, void* workspace,
+                                      size_t ws_bytes, void* hip_stream, int phases);
+
+/* BACKWARD.  Pixel gradients -> grad_params [B, 7+n_shape+n_exp] in one call: four launches, no [B,3,N]-sized tensor.
+ * Every vertex gradient of this model comes through the depth plane, so only the z row of d L / d vertex_proj is non-zero
+ * (render_depth_op.cc:359-363): the composed chain writes 2/3 of that tensor as zeros and reads them back.  Here
+ *   1. the records pass of the render backward FORMS the pixel gradient, per pixel, in fp32 without contraction, absent
+ *      planes skipped (not added as zero):
+ *          g = +0
+ *          g_net_input given:  g = g + (g_net_input[..,0] * im_gray) * m1,   m1 = (1e-6f <= depth && depth <= 1.0f) ? 1.0f : 0.0f
+ *          g_depth_img given:  g = g + g_depth_img * m2,                       m2 = (depth >= 1e-6f) ? 1.0f : 0.0f
+ *          g_depth given:      g = g + g_depth
+ *      -- the torch expression of _RenderingLayerFused.backward.  The thresholds are fp32 compares against (float)1e-6 and 1.0f:
+ *      that is what torch does with a Python scalar beside a float32 tensor (the scalar is cast to the tensor's type; checked on
+ *      the values 1e-6f, 1.0f and their 1-ulp neighbours, tests/test_decode_layer_gpu.py).  The masks are multiplied in, so an
+ *      infinite gradient on a masked pixel gives NaN, as there;
+ *   2. the owner kernel of fr_render_depth_backward_ws writes ONLY a pitched z plane [B, pitch], pitch =
+ *      fr_decode_render_vertex_pitch(N): same fixed-point sums, same max|g| predicate over covered pixels, same Inf/NaN path;
+ *   3. a z-only fused decode backward (bwd_fused_z_kernel: one 16-byte load of g_z plus the three mu rows per staging thread
+ *      instead of six loads) and the fixed-order reduction give grad_params = fr_decode_3dmm_backward_packed_mu for
+ *      grad_vertex_proj = (0, 0, z) -- the same expressions with +0 / -0 for the absent rows.
+ * For finite inputs the result is BIT-IDENTICAL to: that torch expression -> fr_render_depth_backward_ws ->
+ * fr_decode_3dmm_backward_packed_mu (same FR_BWD_CHUNKS / FR_BWD_CB dependence, deterministic).
+ *   g_depth / g_depth_img [B,H,W,1], g_net_input [B,H,W,7] (channel 0 read): each may be NULL, all three NULL is
+ *   FR_ERR_INVALID_ARG;  im_gray, depth [B,H,W,1]: required when g_depth_img or g_net_input is given;  tri [3,ntri], tri_ind: as
+ *   fr_render_depth_backward;  params, mu (16-byte aligned), packed_t (fr_decode_backward_pack_basis), R_override (NULL or
+ *   [B,3,3]), im_size: as fr_decode_3dmm_backward_packed_mu.
+ * `workspace`: fr_decode_render_backward_workspace_bytes(B, N, n_shape, n_exp, H, W) bytes, 256-byte aligned, caller-owned: the
+ * per-pixel records and chunk partials, the z plane, the decode backward's slabs.  Too small or misaligned is FR_ERR_WORKSPACE
+ * (no fallback).  The size is 0 -- and the call FR_ERR_UNSUPPORTED -- where fr_decode_backward_basis_bytes is 0.  grad_params is
+ * fully written on every FR_OK; nothing is synchronised or allocated; reentrant under the rules at the top of this file (the
+ * workspace is per call in flight). */
+size_t fr_decode_render_backward_workspace_bytes(int B, int N, int n_shape, int n_exp, int H, int W);
+int fr_decode_render_backward(const float* g_depth, const float* g_depth_img, const float* g_net_input, const float* im_gray,
+                              const float* depth, const float* tri, const float* tri_ind, const float* params, const float* mu,
+                              const void* packed_t, const float* R_override, int B, int N, int n_shape, int n_exp, int ntri,
+                              int H, int W, float im_size, float* grad_params, void* workspace, size_t ws_bytes,
+                              void* hip_stream);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
