@@ -186,6 +186,17 @@ def _bind(L):
     L.fr_decode_render_backward_workspace_bytes.restype = ctypes.c_size_t
     L.fr_decode_render_backward.argtypes = [_vp] * 11 + [_i] * 7 + [ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]
     L.fr_decode_render_backward.restype = _i
+    L.fr_decode_pose_backward_workspace_bytes.argtypes = [_i, _i]
+    L.fr_decode_pose_backward_workspace_bytes.restype = ctypes.c_size_t
+    L.fr_decode_pose_backward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+    L.fr_decode_pose_backward.restype = _i
+    L.fr_decode_render_backward_pose_workspace_bytes.argtypes = [_i] * 6
+    L.fr_decode_render_backward_pose_workspace_bytes.restype = ctypes.c_size_t
+    L.fr_decode_render_backward_pose.argtypes = ([_vp] * 11 + [_i] * 7 + [ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]
+                                                 + [_vp, ctypes.c_size_t, _vp])
+    L.fr_decode_render_backward_pose.restype = _i
+    L.fr_debug_pose_bwd_geom.argtypes = [_i, _i, ctypes.POINTER(ctypes.c_int)]
+    L.fr_debug_pose_bwd_geom.restype = None
     L.fr_render_depth_strip_rows.argtypes = [_i] * 4
     L.fr_render_depth_strip_rows.restype = _i
     L.fr_debug_render_geom.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
@@ -213,7 +224,8 @@ EXPORTS = ["fr_version", "fr_strerror", "fr_render_depth_workspace_bytes", "fr_r
            "fr_decode_backward_basis_bytes", "fr_decode_backward_pack_basis", "fr_decode_3dmm_backward_packed",
            "fr_debug_clock_probe", "fr_rendering_layer_forward_phases", "fr_decode_3dmm_backward_packed_mu",
            "fr_render_depth_strip_rows", "fr_decode_rendering_layer_forward", "fr_decode_render_backward_workspace_bytes",
-           "fr_decode_render_backward"]
+           "fr_decode_render_backward", "fr_decode_pose_backward_workspace_bytes", "fr_decode_pose_backward",
+           "fr_decode_render_backward_pose_workspace_bytes", "fr_decode_render_backward_pose", "fr_debug_pose_bwd_geom"]
 
 
 def lib():

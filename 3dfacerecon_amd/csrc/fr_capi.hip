@@ -459,4 +459,54 @@ int fr_decode_render_backward(const float* g_depth, const float* g_depth_img, co
                                      grad_params, ws + l.rec + l.z, (hipStream_t)hip_stream, packed_t, mu, pitch);
 }
 
+// ---- pose gradients --------------------------------------------------------------------------------------------------------
+size_t fr_decode_pose_backward_workspace_bytes(int B, int N) { return fr_decode_pose_backward_workspace_impl(B, N); }
+
+int fr_decode_pose_backward(const float* grad_vertex_proj, const float* vertex_proj, const float* params,
+                            const float* R_override, int B, int N, int n_shape, int n_exp, float im_size, float* grad_params,
+                            float* grad_R, void* workspace, size_t ws_bytes, void* hip_stream) {
+    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0) return FR_ERR_INVALID_ARG;
+    if (B == 0) return FR_OK;
+    if (!grad_params && !grad_R) return FR_ERR_INVALID_ARG;
+    if (!params || (N > 0 && (!grad_vertex_proj || !vertex_proj))) return FR_ERR_INVALID_ARG;
+    const size_t need = fr_decode_pose_backward_workspace_impl(B, N);
+    if (ws_bytes < need || (need > 0 && (!workspace || ((uintptr_t)workspace & 15)))) return FR_ERR_WORKSPACE;
+    if (need / (9 * sizeof(float)) > 0x7FFFFFFFull) return FR_ERR_UNSUPPORTED;   // (face, chunk) workgroups beyond one grid
+    return fr_launch_decode_pose_backward(grad_vertex_proj, vertex_proj, params, R_override, B, N, n_shape, n_exp, im_size,
+                                          grad_params, grad_R, workspace, (hipStream_t)hip_stream);
+}
+
+// workspace of fr_decode_render_backward_pose: that of fr_decode_render_backward, then the chunk records of the pose moment
+size_t fr_decode_render_backward_pose_workspace_bytes(int B, int N, int n_shape, int n_exp, int H, int W) {
+    const size_t base = fr_decode_render_backward_workspace_bytes(B, N, n_shape, n_exp, H, W);
+    return base == 0 ? 0 : base + up256(fr_decode_pose_backward_workspace_impl(B, N));
+}
+
+int fr_decode_render_backward_pose(const float* g_depth, const float* g_depth_img, const float* g_net_input,
+                                   const float* im_gray, const float* depth, const float* tri, const float* tri_ind,
+                                   const float* params, const float* mu, const void* packed_t, const float* R_override, int B,
+                                   int N, int n_shape, int n_exp, int ntri, int H, int W, float im_size, float* grad_params,
+                                   void* workspace, size_t ws_bytes, void* hip_stream, const float* vertex_handoff,
+                                   size_t vertex_bytes, float* grad_R) {
+    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0 || ntri < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
+    if (fr_decode_backward_basis_bytes(N, n_shape, n_exp) == 0) return FR_ERR_UNSUPPORTED;   // as fr_decode_render_backward
+    if (B == 0) return FR_OK;
+    if ((long long)H * W > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
+    if (!vertex_handoff || vertex_bytes < fr_decode_render_vertex_bytes(B, N) || ((uintptr_t)vertex_handoff & 127))
+        return FR_ERR_WORKSPACE;
+    const size_t base = fr_decode_render_backward_workspace_bytes(B, N, n_shape, n_exp, H, W);
+    if (!workspace || ((uintptr_t)workspace & 255) || ws_bytes < fr_decode_render_backward_pose_workspace_bytes(B, N, n_shape, n_exp, H, W))
+        return FR_ERR_WORKSPACE;
+    // (every remaining check is fr_decode_render_backward's own, made before its first launch)
+    const int rc = fr_decode_render_backward(g_depth, g_depth_img, g_net_input, im_gray, depth, tri, tri_ind, params, mu, packed_t,
+                                             R_override, B, N, n_shape, n_exp, ntri, H, W, im_size, grad_params, workspace, base,
+                                             hip_stream);
+    if (rc != FR_OK) return rc;
+    const DrbLayout l = drb_layout(B, N, n_shape, n_exp, H, W);
+    char* ws = reinterpret_cast<char*>(workspace);
+    return fr_launch_decode_pose_backward(reinterpret_cast<const float*>(ws + l.rec), vertex_handoff, params, R_override, B, N,
+                                          n_shape, n_exp, im_size, grad_params, grad_R, ws + base, (hipStream_t)hip_stream,
+                                          fr_decode_render_vertex_pitch(N));
+}
+
 }  // extern "C"

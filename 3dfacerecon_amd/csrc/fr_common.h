@@ -174,3 +174,8 @@ int fr_launch_decode_backward(const float* grad_vertex_proj, const float* params
 size_t fr_decode_backward_basis_bytes_impl(int N, int ns, int ne);
 int fr_launch_decode_backward_pack(const float* pc_shape, const float* pc_exp, int N, int ns, int ne, void* packed_t,
                                    hipStream_t stream);
+size_t fr_decode_pose_backward_workspace_impl(int B, int N);
+// pitch == 0: g / q are dense [B,3,N]; pitch > 0: g is the pitched z plane [B,pitch], q the pitched hand-off [B,3,pitch]
+int fr_launch_decode_pose_backward(const float* g, const float* q, const float* params, const float* R_override, int B, int N,
+                                   int ns, int ne, float im_size, float* grad_params, float* grad_R, void* workspace,
+                                   hipStream_t stream, int pitch = 0);

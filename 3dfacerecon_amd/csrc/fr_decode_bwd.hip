@@ -5,7 +5,8 @@
 //   d t3d_i = sum_p dq_i                                        (:164-165)
 //   d f     = sum_p (R v) . dq  = sum_p (q - t3d) . dq / f      (f_expand * R, :163-165)
 //   dv      = (f R)^T dq ;  d alpha = pc_shape^T dv ;  d beta = pc_exp^T dv          (:153-159)
-//   d angles = 0: R comes out of tf.py_func (:150), which has no gradient in the reference.
+//   d angles = 0: R comes out of tf.py_func (:150), which has no gradient in the reference.  (The default, and it stays so: the
+//              opt-in pose kernels at the end of this file add d angles and dL/dR for a caller that asks -- fr_decode_pose_backward.)
 //
 // How (reference-layout entry point; the packed entry point runs bwd_fused_kernel + bwd_reduce_kernel: see there): three
 // launches, no float atomics (bit-reproducible):
@@ -712,7 +713,7 @@ __global__ __launch_bounds__(RED_WAVES * 64) void bwd_reduce_kernel(BwdArgs a) {
     float* gp = a.grad_params + (size_t)(a.b0 + b) * nd;
     if (what < 3) {
         gp[3 + what] = tot;
-        gp[what] = 0.0f;  // angles: no gradient through tf.py_func (network.py:150)
+        gp[what] = 0.0f;  // angles: no gradient through tf.py_func (network.py:150) -- the default; bwd_pose_finish_kernel overwrites it on request
     } else if (what == 3) {
         gp[6] = tot;
     } else {
@@ -905,5 +906,239 @@ int fr_launch_decode_backward(const float* grad_vertex_proj, const float* params
         }
         hipLaunchKernelGGL(bwd_reduce_kernel, dim3(4 + 64 * waves), dim3(RED_WAVES * 64), 0, stream, a);
     }
+    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
+
+// ---- pose gradients: dL/dR and the three angles (opt-in; fr_decode_pose_backward, fr_decode_render_backward_pose) ----------------
+// With q - t = f R v and dq = (g_x, -g_y, g_z), formed exactly as above:
+//   pose moment  A[i][k] = sum_p dq_i,p (q_k,p - t_k)          (trace(A) / f is d f)
+//   G = dL/dR    = f sum_p dq_p v_p^T = A R^-T = A cof(R) / det(R)      (cof(R) = R for a rotation; the cofactor form holds for
+//                  any invertible R_override; f == 0 gives A = 0, G = 0: the true value; det(R) == 0 is DEFINED as G = 0)
+//   d angle      = <G, d R / d angle>  with R = R_pitch R_yaw R_roll (network.py:276-290), only when the rotation is evaluated
+//                  in-kernel; with R_override the angles do not enter the forward: exactly 0.
+// Two launches, no float atomics (bit-reproducible):
+//   bwd_pose_moment_kernel  streaming reduction, one workgroup per (face, chunk of PM_CHUNK vertices -- a constant of the code: the
+//                           association of the sums depends on N alone, never on the batch or the part).  Thread t owns the vertex
+//                           quads t, t + 256, ... of its chunk and adds their terms in ascending vertex order from +0; the wave total
+//                           comes from wave_sum_to_lane63, the four waves meet in LDS and are added in wave order; one record of nine
+//                           floats per (face, chunk) goes to the workspace.  DENSE: g and vertex_proj [B,3,N] -- N is odd for the
+//                           model, so rows start at any 4-byte phase: the 16-byte loads are declared 4-byte aligned, and the one quad
+//                           that straddles the row's end is loaded element by element.  ZONLY: g is the pitched z plane of the render
+//                           backward, q the pitched vertex hand-off of the forward (both 128-byte aligned: one aligned 16-byte load
+//                           per operand); rows 0 and 1 of A are +0 -- what the dense chain's sums of (+0) q and (-0) q from +0 give --
+//                           so for finite inputs the record is bit-identical to the dense layout fed (0, 0, z).
+//                           A slot without a vertex adds nothing (skipped, not 0 * x).
+//   bwd_pose_finish_kernel  per face: chunk records summed in chunk order in float64, G and the angle derivatives in float64, ONE
+//                           rounding to fp32; writes grad_R [B,3,3] and columns 0-2 of the face's grad_params row (the angle
+//                           gradients, or zeros under R_override), no other column.
+namespace fr {
+
+constexpr int PM_THREADS = 256;                        // four waves
+constexpr int PM_QPT = 2;                              // vertex quads per thread
+constexpr int PM_CHUNK = PM_THREADS * PM_QPT * 4;      // 2,048 vertices per workgroup
+// longest chain of rounded fp32 additions behind one element of a chunk record: a thread's 4 PM_QPT terms from +0 (the first
+// addition is exact), six DPP steps of the wave sum, three additions across the four waves.  (The chunk records are then summed in float64.)
+constexpr int PM_ADD_DEPTH = (4 * PM_QPT - 1) + 6 + 3;
+
+struct PoseArgs {
+    const float* g;          // DENSE [B,3,N]; ZONLY [B,pitch] (the z row)
+    const float* q;          // DENSE [B,3,N] forward output; ZONLY [B,3,pitch] hand-off
+    const float* params;     // [B,nd]
+    const float* R_override; // [B,9] or null
+    float* part;             // [B][chunks][9] chunk records
+    float* grad_params;      // [B,nd] or null: columns 0-2 written
+    float* grad_R;           // [B,9] or null
+    int B, N, ns, ne, chunks;
+    long long row;           // floats between the x / y / z rows of a face: N (DENSE) or the pitch (ZONLY)
+    float im_size;
+};
+
+template <bool ZONLY>
+__global__ __launch_bounds__(PM_THREADS) void bwd_pose_moment_kernel(PoseArgs a) {
+    __shared__ float part[PM_THREADS / 64][9];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = (int)(blockIdx.x / (unsigned)a.chunks), c = (int)(blockIdx.x % (unsigned)a.chunks);
+    const int nd = FR_N_POSE + a.ns + a.ne;
+    const int N = a.N;
+    const float* pr = a.params + (size_t)b * nd;
+    const float t0 = pr[3], t1 = pr[4], t2 = pr[5];
+    const float* gb = a.g + (size_t)b * (ZONLY ? 1 : 3) * a.row;
+    const float* qb = a.q + (size_t)b * 3 * a.row;
+    constexpr int NG = ZONLY ? 1 : 3;
+    f32x4 gv[PM_QPT][NG], qv[PM_QPT][3];
+    // every load of the thread is requested before anything is added
+#pragma unroll
+    for (int i = 0; i < PM_QPT; i++) {
+        const long long p0 = (long long)c * PM_CHUNK + 4ll * (tid + PM_THREADS * i);
+        // DENSE: the whole quad lies inside the row.  ZONLY: the quad starts inside the row; its end is below the pitch (a multiple of 4)
+        const bool vec = ZONLY ? p0 < N : p0 + 3 < N;
+#pragma unroll
+        for (int r = 0; r < NG; r++) gv[i][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < 3; r++) qv[i][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (vec) {
+            if constexpr (ZONLY) {
+                gv[i][0] = *reinterpret_cast<const f32x4*>(gb + p0);
+#pragma unroll
+                for (int r = 0; r < 3; r++) qv[i][r] = *reinterpret_cast<const f32x4*>(qb + r * a.row + p0);
+            } else {
+#pragma unroll
+                for (int r = 0; r < 3; r++) {
+                    gv[i][r] = *reinterpret_cast<const f32x4u4*>(gb + r * a.row + p0);
+                    qv[i][r] = *reinterpret_cast<const f32x4u4*>(qb + r * a.row + p0);
+                }
+            }
+        } else if (p0 < N) {   // (DENSE only) the quad that straddles the end of the rows
+#pragma unroll
+            for (int e = 0; e < 3; e++)
+                if (p0 + e < N) {
+#pragma unroll
+                    for (int r = 0; r < NG; r++) gv[i][r][e] = gb[r * a.row + p0 + e];
+#pragma unroll
+                    for (int r = 0; r < 3; r++) qv[i][r][e] = qb[r * a.row + p0 + e];
+                }
+        }
+    }
+    float acc[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) acc[k] = 0.f;
+    const float imm1 = a.im_size - 1.0f;
+#pragma unroll
+    for (int i = 0; i < PM_QPT; i++) {
+        const long long p0 = (long long)c * PM_CHUNK + 4ll * (tid + PM_THREADS * i);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            if (p0 + e < N) {
+                // (q - t): q_0 = out_x, q_1 = (im - 1) - out_y, q_2 = out_z -- the expressions of bwd_fused_kernel
+                const float q0 = qv[i][0][e] - t0;
+                const float q1 = (imm1 - qv[i][1][e]) - t1;
+                const float q2 = qv[i][2][e] - t2;
+                if constexpr (!ZONLY) {
+                    const float dq0 = gv[i][0][e], dq1 = -gv[i][1][e];
+                    acc[0] += dq0 * q0; acc[1] += dq0 * q1; acc[2] += dq0 * q2;
+                    acc[3] += dq1 * q0; acc[4] += dq1 * q1; acc[5] += dq1 * q2;
+                }
+                const float dq2 = gv[i][NG - 1][e];
+                acc[6] += dq2 * q0; acc[7] += dq2 * q1; acc[8] += dq2 * q2;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = ZONLY ? 6 : 0; k < 9; k++) {
+        const float s = wave_sum_to_lane63(acc[k]);
+        if (lane == 63) part[wave][k] = s;
+    }
+    __syncthreads();
+    if (tid < 9) {
+        float s = 0.f;   // (ZONLY: rows 0 and 1 are +0)
+        if (!ZONLY || tid >= 6) {
+            s = part[0][tid];
+#pragma unroll
+            for (int w = 1; w < PM_THREADS / 64; w++) s += part[w][tid];
+        }
+        a.part[((size_t)b * a.chunks + c) * 9 + tid] = s;
+    }
+}
+
+__device__ __forceinline__ void pose_mul3(const double* X, const double* Y, double* Z) {
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) Z[3 * i + j] = (X[3 * i] * Y[j] + X[3 * i + 1] * Y[3 + j]) + X[3 * i + 2] * Y[6 + j];
+}
+__device__ __forceinline__ double pose_dot9(const double* X, const double* Y) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) s += X[i] * Y[i];
+    return s;
+}
+
+__global__ __launch_bounds__(64) void bwd_pose_finish_kernel(PoseArgs a) {
+    __shared__ double As[9];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    if (tid < 9) {
+        double s = 0.0;
+        const float* src = a.part + (size_t)b * a.chunks * 9 + tid;
+        for (int c = 0; c < a.chunks; c++) s += (double)src[(size_t)c * 9];
+        As[tid] = s;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const int nd = FR_N_POSE + a.ns + a.ne;
+    BwdArgs ba;   // (bwd_rotation reads these five fields: the fp32 rotation the forward used)
+    ba.params = a.params; ba.R_override = a.R_override; ba.ns = a.ns; ba.ne = a.ne; ba.b0 = 0;
+    float R9[9];
+    bwd_rotation(ba, b, R9);
+    double r[9], A[9], cf[9], G[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) { r[i] = (double)R9[i]; A[i] = As[i]; }
+    cf[0] = r[4] * r[8] - r[5] * r[7]; cf[1] = r[5] * r[6] - r[3] * r[8]; cf[2] = r[3] * r[7] - r[4] * r[6];
+    cf[3] = r[2] * r[7] - r[1] * r[8]; cf[4] = r[0] * r[8] - r[2] * r[6]; cf[5] = r[1] * r[6] - r[0] * r[7];
+    cf[6] = r[1] * r[5] - r[2] * r[4]; cf[7] = r[2] * r[3] - r[0] * r[5]; cf[8] = r[0] * r[4] - r[1] * r[3];
+    const double det = (r[0] * cf[0] + r[1] * cf[1]) + r[2] * cf[2];
+    pose_mul3(A, cf, G);
+#pragma unroll
+    for (int i = 0; i < 9; i++) G[i] = det == 0.0 ? 0.0 : G[i] / det;   // det(R) == 0: G := 0 (include/fr_hotpath.h)
+    if (a.grad_R) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) a.grad_R[(size_t)b * 9 + i] = (float)G[i];
+    }
+    if (a.grad_params) {
+        float* gp = a.grad_params + (size_t)b * nd;
+        double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+        if (!a.R_override && det != 0.0) {
+            const float* pr = a.params + (size_t)b * nd;
+            double sp, cp, sy, cy, st, ct;
+            sincos((double)pr[0], &sp, &cp);
+            sincos((double)pr[1], &sy, &cy);
+            sincos((double)pr[2], &st, &ct);
+            const double Rp[9] = {1, 0, 0, 0, cp, sp, 0, -sp, cp}, dRp[9] = {0, 0, 0, 0, -sp, cp, 0, -cp, -sp};
+            const double Ry[9] = {cy, 0, -sy, 0, 1, 0, sy, 0, cy}, dRy[9] = {-sy, 0, -cy, 0, 0, 0, cy, 0, -sy};
+            const double Rr[9] = {ct, st, 0, -st, ct, 0, 0, 0, 1}, dRr[9] = {-st, ct, 0, -ct, -st, 0, 0, 0, 0};
+            double T[9], D[9];
+            pose_mul3(dRp, Ry, T); pose_mul3(T, Rr, D); d0 = pose_dot9(G, D);
+            pose_mul3(Rp, dRy, T); pose_mul3(T, Rr, D); d1 = pose_dot9(G, D);
+            pose_mul3(Rp, Ry, T); pose_mul3(T, dRr, D); d2 = pose_dot9(G, D);
+        }
+        gp[0] = (float)d0; gp[1] = (float)d1; gp[2] = (float)d2;
+    }
+}
+
+}  // namespace fr
+
+// test hook (include/fr_hotpath.h): the pose-moment launch geometry, a function of N alone
+extern "C" void fr_debug_pose_bwd_geom(int B, int N, int* out) {
+    (void)B;
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    if (N <= 0) return;
+    out[0] = fr::PM_CHUNK; out[1] = (int)(((long long)N + fr::PM_CHUNK - 1) / fr::PM_CHUNK); out[2] = fr::PM_THREADS;
+    out[3] = fr::PM_ADD_DEPTH;
+}
+
+size_t fr_decode_pose_backward_workspace_impl(int B, int N) {
+    if (B <= 0 || N <= 0) return 0;
+    const size_t chunks = (size_t)(((long long)N + fr::PM_CHUNK - 1) / fr::PM_CHUNK);
+    return ((size_t)B * chunks * 9 * sizeof(float) + 15) & ~(size_t)15;
+}
+
+// g / q: dense [B,3,N] tensors (pitch == 0), or the pitched z plane [B,pitch] and the pitched hand-off [B,3,pitch] (pitch > 0)
+int fr_launch_decode_pose_backward(const float* g, const float* q, const float* params, const float* R_override, int B, int N,
+                                   int ns, int ne, float im_size, float* grad_params, float* grad_R, void* workspace,
+                                   hipStream_t stream, int pitch) {
+    using namespace fr;
+    if (B == 0) return FR_OK;
+    PoseArgs a;
+    a.g = g; a.q = q; a.params = params; a.R_override = R_override;
+    a.part = reinterpret_cast<float*>(workspace); a.grad_params = grad_params; a.grad_R = grad_R;
+    a.B = B; a.N = N; a.ns = ns; a.ne = ne; a.im_size = im_size;
+    a.chunks = N > 0 ? (int)(((long long)N + PM_CHUNK - 1) / PM_CHUNK) : 0;
+    a.row = pitch > 0 ? pitch : N;
+    if ((long long)B * a.chunks > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
+    if (a.chunks > 0) {
+        const dim3 grid((unsigned)((long long)B * a.chunks));
+        if (pitch > 0) hipLaunchKernelGGL(bwd_pose_moment_kernel<true>, grid, dim3(PM_THREADS), 0, stream, a);
+        else hipLaunchKernelGGL(bwd_pose_moment_kernel<false>, grid, dim3(PM_THREADS), 0, stream, a);
+    }
+    hipLaunchKernelGGL(bwd_pose_finish_kernel, dim3(B), dim3(64), 0, stream, a);
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }

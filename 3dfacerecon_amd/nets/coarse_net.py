@@ -112,13 +112,16 @@ class CoarseNet(nn.Module):
 
     fused_step=True takes the hot path as ONE call and one autograd node per iteration (FaceRecNet.decode_rendering_layer:
     the same forward bits; the backward moves only the z row of the vertex gradient and keeps no vertex tensor); the default
-    is the two-step route."""
+    is the two-step route.  pose_grad=True (either route) lets the render loop's gradient reach the three pose angles
+    (FaceRecNet.vertices_transform / decode_rendering_layer, pose_grad); the default gives them 0, as the reference does."""
 
-    def __init__(self, face_net, nIter=4, fused_step=False):
+    def __init__(self, face_net, nIter=4, fused_step=False, pose_grad=False):
         super().__init__()
         _warn_if_exposed()
         self.face_net = face_net        # nets.network.FaceRecNet (holds the 3DMM constants on the GPU)
         self.fused_step = bool(fused_step)
+        self.pose_grad = bool(pose_grad)
+        self._pose_kw = {"pose_grad": True} if self.pose_grad else {}   # (the default call is the one every face net already takes)
         self.iters = nn.ModuleList([CoarseNetIter(face_net.ndim) for _ in range(nIter)])
 
     def forward(self, im_gray, pred_params=None):
@@ -130,9 +133,9 @@ class CoarseNet(nn.Module):
         params = params.reshape(B, fn.ndim).to(im_gray.device)
         for it in self.iters:
             if self.fused_step:
-                net_input, _ = fn.decode_rendering_layer(params, im_gray=im_gray)
+                net_input, _ = fn.decode_rendering_layer(params, im_gray=im_gray, **self._pose_kw)
             else:
-                vertices_proj = fn.vertices_transform(params)                       # Input_Rendering_iter%d, :113
+                vertices_proj = fn.vertices_transform(params, **self._pose_kw)   # Input_Rendering_iter%d, :113
                 net_input, _ = fn.coarse_net_input(vertices_proj, im_gray=im_gray)  # :116-122
             params = fn.set_constraints(it(net_input)[:, None, None, :]).reshape(B, fn.ndim)
         return params
@@ -141,8 +144,8 @@ class CoarseNet(nn.Module):
         """depth_rendering_layer (network.py:300-309) on the final parameters: coarse depth map [B,H,W,1]."""
         fn = self.face_net
         if self.fused_step:
-            return fn.decode_rendering_layer(pred_params, im_gray=im_gray)[1]
-        v = fn.vertices_transform(pred_params)
+            return fn.decode_rendering_layer(pred_params, im_gray=im_gray, **self._pose_kw)[1]
+        v = fn.vertices_transform(pred_params, **self._pose_kw)
         return fn.coarse_net_input(v, im_gray=im_gray)[1]
 
 
@@ -183,13 +186,16 @@ class FaceReconModel(nn.Module):
 
     fused_step=True: every CoarseNet iteration and the depth rendering layer go through FaceRecNet.decode_rendering_layer;
     'vertices_proj' (what the SfS loss reads) then comes from a plain vertices_transform of its own, and only when asked for
-    (forward(..., with_vertices=True), the default)."""
+    (forward(..., with_vertices=True), the default).
+    pose_grad=True: every decode of the module also returns the pose-angle gradients (default: 0, as in the reference)."""
 
-    def __init__(self, face_net, nIter=4, fine=True, fused_step=False):
+    def __init__(self, face_net, nIter=4, fine=True, fused_step=False, pose_grad=False):
         super().__init__()
         self.face_net = face_net
         self.fused_step = bool(fused_step)
-        self.coarse = CoarseNet(face_net, nIter=nIter, fused_step=fused_step)
+        self.pose_grad = bool(pose_grad)
+        self._pose_kw = {"pose_grad": True} if self.pose_grad else {}
+        self.coarse = CoarseNet(face_net, nIter=nIter, fused_step=fused_step, pose_grad=pose_grad)
         self.fine = FineNet() if fine else None
 
     def forward(self, im_gray, with_depth=True, with_vertices=True):
@@ -198,11 +204,11 @@ class FaceReconModel(nn.Module):
         out = {"pred_params": params, "vertices_proj": None, "coarse_depth_map": None, "pred_depth_map": None}
         if with_depth or self.fine is not None:
             if self.fused_step:
-                out["coarse_depth_map"] = fn.decode_rendering_layer(params, im_gray=im_gray)[1]
+                out["coarse_depth_map"] = fn.decode_rendering_layer(params, im_gray=im_gray, **self._pose_kw)[1]
                 if with_vertices:
-                    out["vertices_proj"] = fn.vertices_transform(params)
+                    out["vertices_proj"] = fn.vertices_transform(params, **self._pose_kw)
             else:
-                v = fn.vertices_transform(params)                              # depth_rendering_layer, network.py:300-309
+                v = fn.vertices_transform(params, **self._pose_kw)    # depth_rendering_layer, network.py:300-309
                 out["vertices_proj"] = v
                 out["coarse_depth_map"] = fn.coarse_net_input(v, im_gray=im_gray)[1]
             if self.fine is not None:

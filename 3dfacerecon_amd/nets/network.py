@@ -165,10 +165,13 @@ class PackedBasis:
 class _Decode3DMM(torch.autograd.Function):
     """vertices_transform as one autograd node: fr_decode_3dmm forward, fr_decode_3dmm_backward for the gradient TF
     autodiff derives from network.py:140-171 (d alpha, d beta, d t3d, d f; the three angles get zero because the
-    reference's rotation goes through tf.py_func, network.py:150, which has no gradient)."""
+    reference's rotation goes through tf.py_func, network.py:150, which has no gradient).  That is the default and stays so;
+    pose_grad=True adds what the reference drops (fr_decode_pose_backward, enqueued behind the decode backward): the angle
+    columns of the gradient when the rotation is evaluated in-kernel, dL/dR for a caller-computed R (the angle columns then
+    stay 0: the angles did not enter the forward).  It needs the forward's output, so it keeps it (no mu form)."""
 
     @staticmethod
-    def forward(ctx, params, net, R, basis=None, im_size=None):
+    def forward(ctx, params, net, R, basis=None, im_size=None, pose_grad=False):
         B = int(params.shape[0])
         out = torch.empty((B, 3, net.nvert), dtype=torch.float32, device=params.device)
         basis = net._basis if basis is None else basis
@@ -183,7 +186,8 @@ class _Decode3DMM(torch.autograd.Function):
         # faster kernel (same time at 64 faces, 3 us more at 32: profiles/round5_probes/r5d).  Bases / meshes the fused kernel
         # does not serve take the reference-layout entry point, which needs `out`.
         ctx.packed = basis.backward_packed_ok()
-        ctx.from_mu = ctx.packed and bool(getattr(basis, "backward_from_mu", False))
+        ctx.pose_grad = bool(pose_grad)
+        ctx.from_mu = ctx.packed and bool(getattr(basis, "backward_from_mu", False)) and not ctx.pose_grad
         if ctx.from_mu:
             ctx.save_for_backward(params, R if R is not None else params.new_empty(0))
         else:
@@ -219,8 +223,20 @@ class _Decode3DMM(torch.autograd.Function):
                 rc = L.fr_decode_3dmm_backward(h.ptr(g), h.ptr(params), h.ptr(out), h.ptr(basis.pc_shape),
                                                h.ptr(basis.pc_exp), Rp, B, net.nvert, net.ndim_shape, net.ndim_exp,
                                                ctx.im_size, h.ptr(gp), h.ptr(ws), nws, h.stream_ptr(dev))
-        h.check(rc, "fr_decode_3dmm_backward")
-        return gp, None, None, None, None
+            h.check(rc, "fr_decode_3dmm_backward")
+            gR = None
+            if ctx.pose_grad:
+                # completes gp: the angle columns (R evaluated in-kernel) or dL/dR (only when somebody asked for R's gradient)
+                if ctx.has_R and ctx.needs_input_grad[2]:
+                    gR = torch.empty_like(R)
+                if gR is not None or not ctx.has_R:
+                    pws_bytes = L.fr_decode_pose_backward_workspace_bytes(B, net.nvert)
+                    pws = torch.empty((max(pws_bytes, 16),), dtype=torch.uint8, device=dev)
+                    rc = L.fr_decode_pose_backward(h.ptr(g), h.ptr(ctx.saved_tensors[2]), h.ptr(params), Rp, B, net.nvert,
+                                                   net.ndim_shape, net.ndim_exp, ctx.im_size, h.ptr(gp), h.ptr(gR), h.ptr(pws),
+                                                   pws_bytes, h.stream_ptr(dev))
+                    h.check(rc, "fr_decode_pose_backward")
+        return gp, None, gR, None, None, None
 
 
 class FaceRecNet:
@@ -279,11 +295,15 @@ class FaceRecNet:
         self.init_pred_params = self.pred_params.clone()  # eager callers restart every forward from this constant
 
     # ---- 3DMM decode ----------------------------------------------------------------------------------
-    def vertices_transform(self, pred_params, R=None):
+    def vertices_transform(self, pred_params, R=None, pose_grad=False):
         """(B,1,1,d) or (B,d) parameters -> projected vertices (B,3,N)  (network.py:140-171).
 
         R: optional host-computed (B,3,3) rotation (what the reference gets from tf.py_func at :150); by default
-        the rotation is evaluated inside the kernel in float64."""
+        the rotation is evaluated inside the kernel in float64.
+        pose_grad: False (default) -- the three angles get gradient 0 and R none, as in the reference.  True -- the backward
+        also runs fr_decode_pose_backward: with R=None the angle columns of the gradient are filled; with R given its gradient
+        dL/dR is returned (it flows on if R is a tensor that requires grad) and the angle columns stay 0.  The node then keeps
+        the forward's output for the backward (`backward_from_mu` does not apply to such a call)."""
         h = _host()
         p = pred_params
         if p.dim() == 4:
@@ -297,6 +317,8 @@ class FaceRecNet:
             Rc = h.require_gpu_f32(torch.as_tensor(R, dtype=torch.float32, device=p.device), "R")
             if tuple(Rc.shape) != (B, 3, 3):
                 raise ValueError("R must be (B,3,3)")
+        if pose_grad:
+            return _Decode3DMM.apply(p, self, Rc, None, None, True)
         return _Decode3DMM.apply(p, self, Rc)
 
     def geometry_product(self, geometry_params):
@@ -362,13 +384,17 @@ class FaceRecNet:
             net_in = torch.cat([mask, pncc, normal], dim=3)
         return net_in, depth_img
 
-    def decode_rendering_layer(self, pred_params, im_gray=None, R=None):
+    def decode_rendering_layer(self, pred_params, im_gray=None, R=None, pose_grad=False):
         """vertices_transform -> coarse_net_input in one call and ONE autograd node: (B,1,1,d) or (B,d) parameters ->
         (net_input [B,H,W,7], depth_img [B,H,W,1]), the same bits as the two-step route.  Forward
         fr_decode_rendering_layer_forward, backward fr_decode_render_backward (rendering_layer/ops.py::_DecodeRenderingLayer):
         no dense [B,3,N] vertex tensor exists in either direction and none is kept for the backward.  Where the fused entry
         points do not serve the call (a shape only the fallback rasteriser covers, a basis of more than 256 coefficients, a
-        mesh of fewer than 16 vertices, the opt-in Q30 decode arithmetic) it IS the two-step route."""
+        mesh of fewer than 16 vertices, the opt-in Q30 decode arithmetic) it IS the two-step route.
+        pose_grad=True (default False: the angles get 0, R no gradient): the backward is fr_decode_render_backward_pose -- the
+        angle columns are filled (R=None) or dL/dR is returned for R.  The node then KEEPS the forward's pitched vertex hand-off,
+        a [B,3,pitch] buffer of its own (41 MB at 64 faces of the full mesh), instead of the shared per-stream scratch.  The
+        two-step route takes the flag through vertices_transform."""
         h = _host()
         p = pred_params
         if p.dim() == 4:
@@ -387,10 +413,11 @@ class FaceRecNet:
                 raise ValueError("R must be (B,3,3)")
         if self._basis.backward_packed_ok() and not self._basis.use_q30():
             try:
-                return _ops().decode_rendering_layer(p, Rc, im_gray, self.tri, self.vertex_code, self._basis, self.im_size)
+                return _ops().decode_rendering_layer(p, Rc, im_gray, self.tri, self.vertex_code, self._basis, self.im_size,
+                                                     pose_grad=pose_grad)
             except NotImplementedError:
                 pass
-        return self.coarse_net_input(self.vertices_transform(p, R=Rc), im_gray=im_gray)
+        return self.coarse_net_input(self.vertices_transform(p, R=Rc, pose_grad=pose_grad), im_gray=im_gray)
 
     def compute_abedo_image(self, vertices, triangles, abedos, im_gray=None):
         """Albedo (3,N) -> albedo image + normalised normal map through a second render (network.py:394-417)."""

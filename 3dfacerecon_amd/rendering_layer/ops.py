@@ -315,10 +315,13 @@ class _DecodeRenderingLayer(torch.autograd.Function):
     fr_decode_rendering_layer_forward, the vertices in a pitched per-stream scratch buffer that is not kept.  Backward:
     fr_decode_render_backward -- the pixel gradient is formed inside the render backward's records pass, only the z row of the
     vertex gradient exists, and the decode backward takes d f from mu: the node saves params, R, tri_ind, depth and im_gray, no
-    [B,3,N]-sized tensor.  Raises NotImplementedError where either entry point answers FR_ERR_UNSUPPORTED."""
+    [B,3,N]-sized tensor.  Raises NotImplementedError where either entry point answers FR_ERR_UNSUPPORTED.
+    pose_grad=True: the hand-off is a tensor of the node's own and IS kept ([B,3,pitch] floats: 41 MB at 64 faces of the full
+    mesh); the backward is fr_decode_render_backward_pose, which also fills the angle columns (R evaluated in-kernel) or returns
+    dL/dR for a caller-computed R.  The default leaves the angles at 0 and R without a gradient."""
 
     @staticmethod
-    def forward(ctx, params, R, im_gray, tri, texture, basis, im_size):
+    def forward(ctx, params, R, im_gray, tri, texture, basis, im_size, pose_grad=False):
         h = _host()
         L = h.lib()
         p = h.require_gpu_f32(params, "pred_params")
@@ -353,7 +356,8 @@ class _DecodeRenderingLayer(torch.autograd.Function):
             ent, cached = _workspace(dev, ws_bytes)
             with ent.lock:
                 # (the hand-off is taken under the entry's lock: threads that share the stream share both buffers)
-                hand = _scratch("hand", dev, hand_bytes)
+                hand = (torch.empty((max(hand_bytes, 256),), dtype=torch.uint8, device=dev) if pose_grad
+                        else _scratch("hand", dev, hand_bytes))
                 phases, pending = _render_phases(ent, cached, tri_c, (B, N, ntri, H, W))
                 rc = L.fr_decode_rendering_layer_forward(h.ptr(p), h.ptr(basis.image), h.ptr(R), h.ptr(tri_c), h.ptr(tex_c),
                                                          h.ptr(img_c), B, N, ns, ne, ntri, H, W, tex_batch, float(im_size),
@@ -366,6 +370,7 @@ class _DecodeRenderingLayer(torch.autograd.Function):
         h.check(rc, "fr_decode_rendering_layer_forward")
         ctx.save_for_backward(p, R if R is not None else p.new_empty(0), tri_ind, depth, img_c)
         ctx.has_R = R is not None
+        ctx.hand = (hand, hand_bytes) if pose_grad else None   # (an intermediate of this node alone: no other node can reach it)
         ctx.tri, ctx.basis, ctx.im_size = tri_c, basis, float(im_size)   # (tri: a constant of the model, no gradient)
         ctx.dims = (B, N, ns, ne, ntri, H, W)
         ctx.set_materialize_grads(False)
@@ -374,7 +379,7 @@ class _DecodeRenderingLayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_net_in, g_depth_img):
         if g_net_in is None and g_depth_img is None:
-            return (None,) * 7
+            return (None,) * 8
         h = _host()
         L = h.lib()
         p, R, tri_ind, depth, img = ctx.saved_tensors
@@ -386,20 +391,35 @@ class _DecodeRenderingLayer(torch.autograd.Function):
         gp = torch.empty_like(p)
         with torch.cuda.device(dev):
             image_t = basis.image_t()
+            gR = None
+            if ctx.hand is not None:
+                if ctx.has_R and ctx.needs_input_grad[1]:
+                    gR = torch.empty_like(R)
+                nws = L.fr_decode_render_backward_pose_workspace_bytes(B, N, ns, ne, H, W)
+                ws = _scratch("bwd", dev, nws)
+                rc = L.fr_decode_render_backward_pose(None, h.ptr(gd), h.ptr(gn), h.ptr(img), h.ptr(depth), h.ptr(ctx.tri),
+                                                      h.ptr(tri_ind), h.ptr(p), h.ptr(basis.mu), h.ptr(image_t),
+                                                      h.ptr(R) if ctx.has_R else None, B, N, ns, ne, ntri, H, W, ctx.im_size,
+                                                      h.ptr(gp), h.ptr(ws), nws, h.stream_ptr(dev), h.ptr(ctx.hand[0]),
+                                                      ctx.hand[1], h.ptr(gR))
+                h.check(rc, "fr_decode_render_backward_pose")
+                return gp, gR, None, None, None, None, None, None
             nws = L.fr_decode_render_backward_workspace_bytes(B, N, ns, ne, H, W)
             ws = _scratch("bwd", dev, nws)
             rc = L.fr_decode_render_backward(None, h.ptr(gd), h.ptr(gn), h.ptr(img), h.ptr(depth), h.ptr(ctx.tri), h.ptr(tri_ind),
                                              h.ptr(p), h.ptr(basis.mu), h.ptr(image_t), h.ptr(R) if ctx.has_R else None, B, N, ns,
                                              ne, ntri, H, W, ctx.im_size, h.ptr(gp), h.ptr(ws), nws, h.stream_ptr(dev))
         h.check(rc, "fr_decode_render_backward")
-        return gp, None, None, None, None, None, None
+        return gp, None, None, None, None, None, None, None
 
 
-def decode_rendering_layer(params, R, im_gray, tri, texture, basis, im_size):
+def decode_rendering_layer(params, R, im_gray, tri, texture, basis, im_size, pose_grad=False):
     """One-node decode -> rendering layer: (params [B,d], R [B,3,3] or None, im_gray [B,H,W,1]) -> (net_input [B,H,W,7],
     depth_img [B,H,W,1]); `basis` is the network's PackedBasis.  Raises NotImplementedError where the fused entry points do not
-    serve the shape (the caller composes vertices_transform and rendering_layer_fused instead)."""
-    return _DecodeRenderingLayer.apply(params, R, im_gray, tri, texture, basis, im_size)
+    serve the shape (the caller composes vertices_transform and rendering_layer_fused instead).
+    pose_grad=True: the backward also gives the three angles their gradient (R None) or R its own (fr_decode_render_backward_pose);
+    the node then retains the forward's vertex hand-off, one [B,3,pitch] fp32 buffer -- 41 MB at 64 faces of the full mesh."""
+    return _DecodeRenderingLayer.apply(params, R, im_gray, tri, texture, basis, im_size, bool(pose_grad))
 
 
 def rendering_layer_fused(ver, tri, texture, im_gray):

@@ -51,7 +51,8 @@ def build_harness(args, dev, rank, world, local):
     if args.small:  # the tiny mesh is ~30 px wide: centre it and scale it up a little
         face.init_pred_params[..., 6] = 1e-3 * S / 200.0
     # the reference's graph always holds FineNet (build(), network.py:69-101); the forward-only config 3 is CoarseNet + render
-    model = cn.FaceReconModel(face, nIter=args.nIter, fine=args.fine or args.train, fused_step=args.fused_step).to(dev)
+    model = cn.FaceReconModel(face, nIter=args.nIter, fine=args.fine or args.train, fused_step=args.fused_step,
+                              pose_grad=args.pose_grad).to(dev)
     net = model
     if args.train and world > 1:
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local] if dev.type == "cuda" else None)
@@ -202,6 +203,9 @@ def main():
     ap.add_argument("--fused-step", action="store_true",
                     help="decode -> rendering layer as one call and one autograd node per CoarseNet iteration "
                          "(FaceRecNet.decode_rendering_layer); off: the two-step route")
+    ap.add_argument("--pose-grad", action="store_true",
+                    help="let the render loop's gradient reach the three pose angles (fr_decode_pose_backward / "
+                         "fr_decode_render_backward_pose); off: they get 0 from it, as in the reference")
     ap.add_argument("--gather-sfs", action="store_true", help="whole-batch SfS lighting estimate across ranks")
     ap.add_argument("--small", action="store_true", help="tiny synthetic assets (smoke runs)")
     ap.add_argument("--dump-batches", default=None, metavar="FILE.npz",

@@ -251,7 +251,8 @@ int fr_decode_render_forward_q30(const float* params, const void* qimage, const 
  *   mu / pc_shape / pc_exp in the reference layouts (not the packed image);  grad_params [B, 7+n_shape+n_exp].
  * d alpha = pc_shape^T dv, d beta = pc_exp^T dv with dv = (f R)^T dq, dq = (g_x, -g_y, g_z); d t3d = sum_p dq;
  * d f = sum_p (R v_p) . dq evaluated as sum_p (q - t3d) . dq / f, which needs no second pass over the basis; the three
- * angles get 0: in the reference R passes through tf.py_func (network.py:150), which has no gradient.
+ * angles get 0: in the reference R passes through tf.py_func (network.py:150), which has no gradient.  (That is the default and
+ * stays so; fr_decode_pose_backward below adds the angle gradients and dL/dR for a caller that asks for them.)
  * f == 0 (only reachable when set_constraints' sigmoid underflows, raw input < -103): every vertex projects onto t3d, the
  * quotient form is 0/0 and d f is DEFINED as 0 here (the true value sum_p (R v_p) . dq would need the un-projected
  * vertices, i.e. another basis pass); d alpha = d beta = 0 and d t3d are exact in that case.  Stated, tested
@@ -352,6 +353,58 @@ int fr_decode_render_backward(const float* g_depth, const float* g_depth_img, co
                               int H, int W, float im_size, float* grad_params, void* workspace, size_t ws_bytes,
                               void* hip_stream);
 
+/* ---- pose gradients: dL/dR and the three angles (opt-in; SURVEY.md 8f rank 2, "d pose incl. dR/d angles") ------------------
+ * Every entry point above gives the three angles 0 (the reference's rotation passes through tf.py_func, network.py:150) and
+ * nothing for R_override: that stays their definition.  These two calls ADD the missing gradient, from the forward's vertices.
+ * In the notation above -- dq = (g_x, -g_y, g_z); q - t formed as the decode backward forms it, q0 = out_x - tx,
+ * q1 = ((im_size - 1) - out_y) - ty, q2 = out_z - tz; R the fp32 rotation the forward used (evaluated in-kernel, or R_override);
+ * q - t = f R v:
+ *   pose moment  A[i][k] = sum_p dq_i,p (q_k,p - t_k)                     (nine sums per face; trace(A) / f is d f)
+ *   grad_R       G = dL/dR = f sum_p dq_p v_p^T = A R^-T = A cof(R) / det(R)   [B,3,3]
+ *                (cof(R) = R for a rotation; the cofactor form is right for ANY invertible R_override, where A R is not)
+ *   angles       d phi = <G, R_pitch' R_yaw R_roll>, d gamma = <G, R_pitch R_yaw' R_roll>, d theta = <G, R_pitch R_yaw R_roll'>
+ *                (the matrices of network.py:276-290 and their elementwise derivatives), ONLY with R_override == NULL; with
+ *                R_override the angles do not enter the forward and columns 0-2 are written as exactly 0: the caller chains grad_R.
+ * f == 0 gives A = 0 and G = 0, the true value.  det(R) == 0 (a singular R_override) is DEFINED as G = 0 and angle gradients 0
+ * (tests/test_pose_backward_gpu.py).  The moment is a streaming reduction with a fixed association (chunks of 2,048 vertices, a
+ * constant: the bits depend on N alone, not on B or the part), chunk records summed in float64, G and the angle derivatives
+ * formed in float64 and rounded ONCE to fp32; no float atomics: bit-reproducible.  It needs the forward's vertices (there is no
+ * mu form: the cross terms pc_j^T dv_i are never formed).
+ *
+ * fr_decode_pose_backward: enqueue AFTER any of fr_decode_3dmm_backward{,_packed,_packed_mu} on the same stream: it completes
+ * their grad_params.  grad_vertex_proj, vertex_proj [B,3,N] (any N >= 1, rows at any 4-byte phase; no basis is read, so it
+ * also completes the reference-layout entry point for bases above 256 coefficients); grad_params [B, 7+n_shape+n_exp] or NULL:
+ * ONLY columns 0-2 of each row are written; grad_R [B,3,3] or NULL; both NULL is FR_ERR_INVALID_ARG.  `workspace`:
+ * fr_decode_pose_backward_workspace_bytes(B, N) bytes (0 for B <= 0 or N <= 0), 16-byte aligned; too small or misaligned is
+ * FR_ERR_WORKSPACE.  Every check runs before any HIP call; B == 0 is FR_OK; nothing is allocated or synchronised; reentrant
+ * under the rules at the top of this file with a workspace per call in flight.
+ * Measured on an MI355X (tools/pose_grad_probe.py, profiles/decode_pose_backward.json; same process, device events, medians): behind
+ * fr_decode_3dmm_backward_packed this call adds 21.5 us at 64 faces (71.5 -> 92.9) and 16.5 us at 32 (53.7 -> 70.2);
+ * fr_decode_render_backward_pose costs 20.0 us more than fr_decode_render_backward at 64 faces (120.1 -> 140.1) and 16.5 us at 32
+ * (82.2 -> 98.7).  The moment kernel must move 2 x 40.9 MB dense, 13.7 + 41.2 MB z-only at 64 faces (13.0 / 8.7 us at the 6.29 TB/s
+ * measured-copy rate) and takes 14.6 / 10.6 us (rocprofv3 --kernel-trace); the finish kernel, one thread per face, takes 8.7 us:
+ * that and the two launches are the rest of the difference. */
+size_t fr_decode_pose_backward_workspace_bytes(int B, int N);
+int fr_decode_pose_backward(const float* grad_vertex_proj, const float* vertex_proj, const float* params,
+                            const float* R_override, int B, int N, int n_shape, int n_exp, float im_size, float* grad_params,
+                            float* grad_R, void* workspace, size_t ws_bytes, void* hip_stream);
+
+/* fr_decode_render_backward + the z-only pose moment over its own z plane and the forward's hand-off, in ONE call: every
+ * argument of fr_decode_render_backward, then the pitched vertex hand-off the forward wrote (fr_decode_rendering_layer_forward /
+ * fr_decode_render_forward: [B,3,pitch], fr_decode_render_vertex_bytes(B, N) bytes, 128-byte aligned; missing, too small or
+ * misaligned is FR_ERR_WORKSPACE) and grad_R [B,3,3] or NULL.  Columns 3.. of grad_params are bit-identical to
+ * fr_decode_render_backward; columns 0-2 hold the angle gradients (zeros under R_override).  dq0 = +0, dq1 = -0 as in the z-only
+ * decode backward: for finite inputs grad_R and the angle columns are bit-identical to fr_decode_pose_backward fed (0, 0, z).
+ * `workspace`: fr_decode_render_backward_pose_workspace_bytes bytes, 256-byte aligned.  FR_ERR_UNSUPPORTED (and size 0) exactly
+ * where fr_decode_render_backward answers it. */
+size_t fr_decode_render_backward_pose_workspace_bytes(int B, int N, int n_shape, int n_exp, int H, int W);
+int fr_decode_render_backward_pose(const float* g_depth, const float* g_depth_img, const float* g_net_input,
+                                   const float* im_gray, const float* depth, const float* tri, const float* tri_ind,
+                                   const float* params, const float* mu, const void* packed_t, const float* R_override, int B,
+                                   int N, int n_shape, int n_exp, int ntri, int H, int W, float im_size, float* grad_params,
+                                   void* workspace, size_t ws_bytes, void* hip_stream, const float* vertex_handoff,
+                                   size_t vertex_bytes, float* grad_R);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
@@ -363,6 +416,11 @@ void fr_debug_render_geom(int B, int ntri, int H, int W, int rows_override, int*
  * reference-layout GEMM workgroup, GEMM workgroups, prepass workgroups}.  Used by tests/test_decode_backward_bounds_gpu.py to
  * derive its rounding-error bounds and by tests/test_capi_cpu.py. */
 void fr_debug_decode_bwd_geom(int nbatch, int N, int n_shape, int n_exp, int* out);
+
+/* The pose-moment launch geometry (no GPU needed; a function of N alone -- B is accepted and ignored): out[4] = {chunk length in
+ * vertices, chunks per face, threads per workgroup, longest chain of rounded fp32 additions behind one element of a chunk
+ * record}; all zero for N <= 0.  Used by tests/test_pose_backward_gpu.py to derive its bounds. */
+void fr_debug_pose_bwd_geom(int B, int N, int* out);
 
 /* The render-backward launch geometry (no GPU needed; the launcher reads the same function): out[6] = {owner workgroups
  * per face, vertices per owner, shift (resolution bits given up above 2^20 pixels), 1,024-pixel record chunks of the
