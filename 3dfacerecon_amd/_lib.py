@@ -15,7 +15,7 @@ import types
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG_DIR, "csrc")
 LIB_PATH = os.path.join(_PKG_DIR, "libfr_hotpath.so")
-SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip"]
+SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_nbwd.hip"]
 HEADERS = [os.path.join(_CSRC, "fr_common.h"), os.path.join(_CSRC, "fr_decode_shared.h"), os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]  # single-lane LDS atomics stay single instructions
@@ -195,6 +195,12 @@ def _bind(L):
     L.fr_decode_render_backward_pose.argtypes = ([_vp] * 11 + [_i] * 7 + [ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]
                                                  + [_vp, ctypes.c_size_t, _vp])
     L.fr_decode_render_backward_pose.restype = _i
+    L.fr_render_normal_backward_workspace_bytes.argtypes = [_i] * 4
+    L.fr_render_normal_backward_workspace_bytes.restype = ctypes.c_size_t
+    L.fr_render_normal_backward.argtypes = [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
+    L.fr_render_normal_backward.restype = _i
+    L.fr_debug_render_normal_bwd_geom.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
+    L.fr_debug_render_normal_bwd_geom.restype = None
     L.fr_debug_pose_bwd_geom.argtypes = [_i, _i, ctypes.POINTER(ctypes.c_int)]
     L.fr_debug_pose_bwd_geom.restype = None
     L.fr_render_depth_strip_rows.argtypes = [_i] * 4
@@ -225,7 +231,8 @@ EXPORTS = ["fr_version", "fr_strerror", "fr_render_depth_workspace_bytes", "fr_r
            "fr_debug_clock_probe", "fr_rendering_layer_forward_phases", "fr_decode_3dmm_backward_packed_mu",
            "fr_render_depth_strip_rows", "fr_decode_rendering_layer_forward", "fr_decode_render_backward_workspace_bytes",
            "fr_decode_render_backward", "fr_decode_pose_backward_workspace_bytes", "fr_decode_pose_backward",
-           "fr_decode_render_backward_pose_workspace_bytes", "fr_decode_render_backward_pose", "fr_debug_pose_bwd_geom"]
+           "fr_decode_render_backward_pose_workspace_bytes", "fr_decode_render_backward_pose", "fr_debug_pose_bwd_geom",
+           "fr_render_normal_backward_workspace_bytes", "fr_render_normal_backward", "fr_debug_render_normal_bwd_geom"]
 
 
 def lib():

@@ -509,4 +509,28 @@ int fr_decode_render_backward_pose(const float* g_depth, const float* g_depth_im
                                           fr_decode_render_vertex_pitch(N));
 }
 
+// ---- normal-map gradients -----------------------------------------------------------------------------------------------------
+size_t fr_render_normal_backward_workspace_bytes(int B, int nver, int H, int W) {
+    (void)nver;
+    return fr_render_normal_backward_workspace_impl(B, H, W);
+}
+
+int fr_render_normal_backward(const float* normal_grad, int grad_stride, const float* vertex, int vertex_pitch,
+                              const float* tri, const float* tri_ind, float* vertex_grad, int B, int nver, int ntri,
+                              int H, int W, int mode, int accumulate, void* workspace, size_t ws_bytes, void* hip_stream) {
+    if (B < 0 || nver < 0 || ntri < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
+    if ((mode != 0 && mode != 1) || (accumulate != 0 && accumulate != 1)) return FR_ERR_INVALID_ARG;
+    if (grad_stride < 3 || vertex_pitch < nver) return FR_ERR_INVALID_ARG;
+    if (B == 0) return FR_OK;
+    if (nver == 0) return FR_OK;   // an empty vertex_grad: nothing to write
+    if (!vertex_grad) return FR_ERR_INVALID_ARG;
+    const bool work = (size_t)H * W > 0 && ntri > 0;
+    if (work && (!normal_grad || !vertex || !tri || !tri_ind)) return FR_ERR_INVALID_ARG;
+    if (ntri >= (1 << 24)) return FR_ERR_UNSUPPORTED;   // float-stored ids stop being exact
+    if (work && (!workspace || ((uintptr_t)workspace & 15) || ws_bytes < fr_render_normal_backward_workspace_impl(B, H, W)))
+        return FR_ERR_WORKSPACE;
+    return fr_launch_render_normal_backward(normal_grad, grad_stride, vertex, vertex_pitch, tri, tri_ind, vertex_grad, B, nver,
+                                            ntri, H, W, mode, accumulate, workspace, (hipStream_t)hip_stream);
+}
+
 }  // extern "C"

@@ -179,3 +179,7 @@ size_t fr_decode_pose_backward_workspace_impl(int B, int N);
 int fr_launch_decode_pose_backward(const float* g, const float* q, const float* params, const float* R_override, int B, int N,
                                    int ns, int ne, float im_size, float* grad_params, float* grad_R, void* workspace,
                                    hipStream_t stream, int pitch = 0);
+size_t fr_render_normal_backward_workspace_impl(int B, int H, int W);
+int fr_launch_render_normal_backward(const float* normal_grad, int grad_stride, const float* vertex, int vertex_pitch,
+                                     const float* tri, const float* tri_ind, float* vertex_grad, int B, int nver, int ntri,
+                                     int H, int W, int mode, int accumulate, void* workspace, hipStream_t stream);

@@ -113,15 +113,20 @@ class CoarseNet(nn.Module):
     fused_step=True takes the hot path as ONE call and one autograd node per iteration (FaceRecNet.decode_rendering_layer:
     the same forward bits; the backward moves only the z row of the vertex gradient and keeps no vertex tensor); the default
     is the two-step route.  pose_grad=True (either route) lets the render loop's gradient reach the three pose angles
-    (FaceRecNet.vertices_transform / decode_rendering_layer, pose_grad); the default gives them 0, as the reference does."""
+    (FaceRecNet.vertices_transform / decode_rendering_layer, pose_grad); the default gives them 0, as the reference does.
+    normal_grad=True lets the three normal channels of every iteration's input carry their gradient back to x, y and z of the
+    vertices (FaceRecNet.coarse_net_input, normal_grad; with fused_step the step is then the two-step route, whose render node
+    keeps the vertex tensor); the default leaves them constants to autograd, as the reference does."""
 
-    def __init__(self, face_net, nIter=4, fused_step=False, pose_grad=False):
+    def __init__(self, face_net, nIter=4, fused_step=False, pose_grad=False, normal_grad=False):
         super().__init__()
         _warn_if_exposed()
         self.face_net = face_net        # nets.network.FaceRecNet (holds the 3DMM constants on the GPU)
         self.fused_step = bool(fused_step)
         self.pose_grad = bool(pose_grad)
         self._pose_kw = {"pose_grad": True} if self.pose_grad else {}   # (the default call is the one every face net already takes)
+        self.normal_grad = bool(normal_grad)
+        self._normal_kw = {"normal_grad": True} if self.normal_grad else {}
         self.iters = nn.ModuleList([CoarseNetIter(face_net.ndim) for _ in range(nIter)])
 
     def forward(self, im_gray, pred_params=None):
@@ -133,10 +138,10 @@ class CoarseNet(nn.Module):
         params = params.reshape(B, fn.ndim).to(im_gray.device)
         for it in self.iters:
             if self.fused_step:
-                net_input, _ = fn.decode_rendering_layer(params, im_gray=im_gray, **self._pose_kw)
+                net_input, _ = fn.decode_rendering_layer(params, im_gray=im_gray, **self._pose_kw, **self._normal_kw)
             else:
                 vertices_proj = fn.vertices_transform(params, **self._pose_kw)   # Input_Rendering_iter%d, :113
-                net_input, _ = fn.coarse_net_input(vertices_proj, im_gray=im_gray)  # :116-122
+                net_input, _ = fn.coarse_net_input(vertices_proj, im_gray=im_gray, **self._normal_kw)  # :116-122
             params = fn.set_constraints(it(net_input)[:, None, None, :]).reshape(B, fn.ndim)
         return params
 
@@ -187,15 +192,17 @@ class FaceReconModel(nn.Module):
     fused_step=True: every CoarseNet iteration and the depth rendering layer go through FaceRecNet.decode_rendering_layer;
     'vertices_proj' (what the SfS loss reads) then comes from a plain vertices_transform of its own, and only when asked for
     (forward(..., with_vertices=True), the default).
-    pose_grad=True: every decode of the module also returns the pose-angle gradients (default: 0, as in the reference)."""
+    pose_grad=True: every decode of the module also returns the pose-angle gradients (default: 0, as in the reference).
+    normal_grad=True: the CoarseNet iterations' normal channels carry gradients (CoarseNet, normal_grad; default: none)."""
 
-    def __init__(self, face_net, nIter=4, fine=True, fused_step=False, pose_grad=False):
+    def __init__(self, face_net, nIter=4, fine=True, fused_step=False, pose_grad=False, normal_grad=False):
         super().__init__()
         self.face_net = face_net
         self.fused_step = bool(fused_step)
         self.pose_grad = bool(pose_grad)
         self._pose_kw = {"pose_grad": True} if self.pose_grad else {}
-        self.coarse = CoarseNet(face_net, nIter=nIter, fused_step=fused_step, pose_grad=pose_grad)
+        self.normal_grad = bool(normal_grad)
+        self.coarse = CoarseNet(face_net, nIter=nIter, fused_step=fused_step, pose_grad=pose_grad, normal_grad=normal_grad)
         self.fine = FineNet() if fine else None
 
     def forward(self, im_gray, with_depth=True, with_vertices=True):

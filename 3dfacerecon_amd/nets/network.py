@@ -342,8 +342,10 @@ class FaceRecNet:
         return _Decode3DMM.apply(torch.cat([pose, g], 1), self, eye, self._basis_nomu, 1.0)
 
     # ---- rendering layer wrapper --------------------------------------------------------------------------
-    def rendering_layer(self, vertex_proj, triangles, colors, im_gray=None):
-        """(network.py:174-201) -> pncc_batch, normalimg_batch, maskimg_batch, depthimg_batch."""
+    def rendering_layer(self, vertex_proj, triangles, colors, im_gray=None, normal_grad=False):
+        """(network.py:174-201) -> pncc_batch, normalimg_batch, maskimg_batch, depthimg_batch.
+        normal_grad=True: the op's `normal` output has a backward (rendering_layer/ops.py::render_depth), so normalimg_batch
+        carries its gradient to x, y and z of the vertices; the default leaves it a constant to autograd, as the reference."""
         im_gray = self.im_gray if im_gray is None else im_gray
         ver = vertex_proj.float()
         tri = torch.as_tensor(triangles, dtype=torch.float32, device=ver.device)
@@ -352,7 +354,8 @@ class FaceRecNet:
         if im_gray is None:
             im_gray = torch.ones((B, self.im_size, self.im_size, 1), dtype=torch.float32, device=ver.device)
         image = im_gray.expand(-1, -1, -1, 3)
-        depth, tex_img, normal, _ = _ops().render_depth(ver=ver, tri=tri, texture=tex, image=image)
+        kw = {"normal_grad": True} if normal_grad else {}
+        depth, tex_img, normal, _ = _ops().render_depth(ver=ver, tri=tri, texture=tex, image=image, **kw)
         # 1. pncc result
         pncc_batch = torch.clamp(tex_img, 1e-6, 1.0)
         # 2. normal map: flip normals with negative z, normalise by magnitude
@@ -368,9 +371,12 @@ class FaceRecNet:
         depthimg_batch = torch.clamp_min(depth, 1e-6)
         return pncc_batch, normalimg_batch, maskimg_batch, depthimg_batch
 
-    def coarse_net_input(self, vertex_proj, triangles=None, colors=None, im_gray=None):
+    def coarse_net_input(self, vertex_proj, triangles=None, colors=None, im_gray=None, normal_grad=False):
         """The 7-channel CoarseNet input [maskimg | pncc | normal] (network.py:122) and the depth image, produced by
-        the fused kernel pass (falls back to rendering_layer + concat for shapes it does not cover)."""
+        the fused kernel pass (falls back to rendering_layer + concat for shapes it does not cover).
+        normal_grad=True: channels 4-6 carry their gradient to x, y and z of the vertices (fr_render_normal_backward behind the
+        depth backward; the render node keeps the vertex tensor, 41 MB at 64 faces of the full mesh).  Default: none, as the
+        reference -- the vertex gradient is z-only."""
         im_gray = self.im_gray if im_gray is None else im_gray
         ver = vertex_proj.float()
         tri = self.tri if triangles is None else torch.as_tensor(triangles, dtype=torch.float32, device=ver.device)
@@ -378,13 +384,14 @@ class FaceRecNet:
         if im_gray is None:
             im_gray = torch.ones((ver.shape[0], self.im_size, self.im_size, 1), dtype=torch.float32, device=ver.device)
         try:
-            net_in, depth_img, _, _ = _ops().rendering_layer_fused(ver, tri, tex, im_gray)
+            kw = {"normal_grad": True} if normal_grad else {}
+            net_in, depth_img, _, _ = _ops().rendering_layer_fused(ver, tri, tex, im_gray, **kw)
         except NotImplementedError:
-            pncc, normal, mask, depth_img = self.rendering_layer(ver, tri, tex, im_gray=im_gray)
+            pncc, normal, mask, depth_img = self.rendering_layer(ver, tri, tex, im_gray=im_gray, **kw)
             net_in = torch.cat([mask, pncc, normal], dim=3)
         return net_in, depth_img
 
-    def decode_rendering_layer(self, pred_params, im_gray=None, R=None, pose_grad=False):
+    def decode_rendering_layer(self, pred_params, im_gray=None, R=None, pose_grad=False, normal_grad=False):
         """vertices_transform -> coarse_net_input in one call and ONE autograd node: (B,1,1,d) or (B,d) parameters ->
         (net_input [B,H,W,7], depth_img [B,H,W,1]), the same bits as the two-step route.  Forward
         fr_decode_rendering_layer_forward, backward fr_decode_render_backward (rendering_layer/ops.py::_DecodeRenderingLayer):
@@ -394,7 +401,10 @@ class FaceRecNet:
         pose_grad=True (default False: the angles get 0, R no gradient): the backward is fr_decode_render_backward_pose -- the
         angle columns are filled (R=None) or dL/dR is returned for R.  The node then KEEPS the forward's pitched vertex hand-off,
         a [B,3,pitch] buffer of its own (41 MB at 64 faces of the full mesh), instead of the shared per-stream scratch.  The
-        two-step route takes the flag through vertices_transform."""
+        two-step route takes the flag through vertices_transform.
+        normal_grad=True: the call IS the two-step route -- vertices_transform, then coarse_net_input(normal_grad=True).  The
+        one-call backward does not apply: it is z-only by construction (only the z plane of the vertex gradient ever exists in
+        it), and the normal gradient fills x, y and z."""
         h = _host()
         p = pred_params
         if p.dim() == 4:
@@ -411,6 +421,8 @@ class FaceRecNet:
             Rc = h.require_gpu_f32(torch.as_tensor(R, dtype=torch.float32, device=p.device), "R")
             if tuple(Rc.shape) != (B, 3, 3):
                 raise ValueError("R must be (B,3,3)")
+        if normal_grad:
+            return self.coarse_net_input(self.vertices_transform(p, R=Rc, pose_grad=pose_grad), im_gray=im_gray, normal_grad=True)
         if self._basis.backward_packed_ok() and not self._basis.use_q30():
             try:
                 return _ops().decode_rendering_layer(p, Rc, im_gray, self.tri, self.vertex_code, self._basis, self.im_size,
@@ -419,14 +431,17 @@ class FaceRecNet:
                 pass
         return self.coarse_net_input(self.vertices_transform(p, R=Rc, pose_grad=pose_grad), im_gray=im_gray)
 
-    def compute_abedo_image(self, vertices, triangles, abedos, im_gray=None):
-        """Albedo (3,N) -> albedo image + normalised normal map through a second render (network.py:394-417)."""
+    def compute_abedo_image(self, vertices, triangles, abedos, im_gray=None, normal_grad=False):
+        """Albedo (3,N) -> albedo image + normalised normal map through a second render (network.py:394-417).
+        normal_grad=True: the normal map carries its gradient to the vertices (render_depth, normal_grad); default: a constant
+        to autograd, as the reference."""
         ver = vertices.float()
         tri = torch.as_tensor(triangles, dtype=torch.float32, device=ver.device)
         tex = torch.as_tensor(abedos, dtype=torch.float32, device=ver.device)
         B = ver.shape[0]
         image = torch.zeros((B, self.im_size, self.im_size, 3), dtype=torch.float32, device=ver.device)
-        _, tf_abedo, normal, _ = _ops().render_depth(ver=ver, tri=tri, texture=tex, image=image)
+        kw = {"normal_grad": True} if normal_grad else {}
+        _, tf_abedo, normal, _ = _ops().render_depth(ver=ver, tri=tri, texture=tex, image=image, **kw)
         abedos_image = torch.clamp_min(tf_abedo, 1e-6).mean(dim=-1, keepdim=True)  # (B, H, W, 1)
         flip = normal[..., 2:3] < 0
         normal = torch.where(flip, -1.0 * normal, normal)

@@ -14,6 +14,7 @@ module loads the native library and builds it first if the .so is missing (refer
 is no fallback path: no library or no GPU tensor => an exception.
 """
 import collections
+import ctypes
 import importlib.util
 import os
 import sys
@@ -162,11 +163,28 @@ def _backward_call(h, g, tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, dev):
     h.check(rc, "fr_render_depth_backward")
 
 
+def _normal_backward_call(h, g, g_offset, g_stride, ver_c, tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, mode, accumulate,
+                          dev):
+    """fr_render_normal_backward with its workspace (48 bytes per pixel): the gradient read at `g_offset` floats into `g`,
+    `g_stride` floats between pixels; accumulate=1 completes a vertex_grad the depth backward has written on this stream."""
+    L = h.lib()
+    nws = L.fr_render_normal_backward_workspace_bytes(B, nver, H, W)
+    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
+    rc = L.fr_render_normal_backward(ctypes.c_void_p(g.data_ptr() + 4 * g_offset), g_stride, h.ptr(ver_c), nver, h.ptr(tri_c),
+                                     h.ptr(tri_ind), h.ptr(vertex_grad), B, nver, ntri, H, W, mode, accumulate, h.ptr(ws), nws,
+                                     h.stream_ptr(dev))
+    h.check(rc, "fr_render_normal_backward")
+
+
 class _RenderDepth(torch.autograd.Function):
     """RenderDepth / RenderDepthGrad (render_depth_op.cc:535-589) as one autograd node."""
 
     @staticmethod
     def forward(ctx, ver, tri, texture, image):
+        return _RenderDepth._fwd(ctx, ver, tri, texture, image, False)
+
+    @staticmethod
+    def _fwd(ctx, ver, tri, texture, image, keep_ver):   # (keep_ver: _RenderDepthNormal also saves `ver` for the normal backward)
         h = _host()
         _check_forward_shapes(ver, tri, texture, image)
         ver_c = h.require_gpu_f32(ver, "ver")
@@ -202,7 +220,10 @@ class _RenderDepth(torch.autograd.Function):
                                                h.ptr(depth), h.ptr(tex_img), h.ptr(normal), h.ptr(tri_ind), None, 0,
                                                h.stream_ptr(dev))
         h.check(rc, "fr_render_depth_forward")
-        ctx.save_for_backward(tri_c, tri_ind)
+        if keep_ver:
+            ctx.save_for_backward(tri_c, tri_ind, ver_c)
+        else:
+            ctx.save_for_backward(tri_c, tri_ind)
         ctx.dims = (B, nver, ntri, H, W)
         ctx.set_materialize_grads(False)  # an unused depth output (the SfS renders, network.py:423, 454) costs no backward
         return depth, tex_img, normal, tri_ind
@@ -223,12 +244,43 @@ class _RenderDepth(torch.autograd.Function):
         return vertex_grad, None, None, None
 
 
+class _RenderDepthNormal(_RenderDepth):
+    """render_depth(normal_grad=True): the same forward; the node also keeps `ver` ([B,3,nver] fp32: 41 MB at 64 faces of the
+    full mesh) and its backward runs the depth backward, then fr_render_normal_backward (raw mode, accumulate=1) where a
+    gradient of `normal` arrives: all three rows of the vertex gradient are filled."""
+
+    @staticmethod
+    def forward(ctx, ver, tri, texture, image):
+        return _RenderDepth._fwd(ctx, ver, tri, texture, image, True)
+
+    @staticmethod
+    def backward(ctx, depth_grad, texture_image_grad, normal_grad, tri_ind_grad):
+        h = _host()
+        tri_c, tri_ind, ver_c = ctx.saved_tensors
+        B, nver, ntri, H, W = ctx.dims
+        dev = tri_c.device
+        if depth_grad is None and normal_grad is None:
+            return None, None, None, None
+        vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            if depth_grad is not None:
+                _backward_call(h, h.require_gpu_f32(depth_grad, "depth_grad"), tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, dev)
+            if normal_grad is not None:
+                _normal_backward_call(h, h.require_gpu_f32(normal_grad, "normal_grad"), 0, 3, ver_c, tri_c, tri_ind, vertex_grad,
+                                      B, nver, ntri, H, W, 0, 1 if depth_grad is not None else 0, dev)
+        return vertex_grad, None, None, None
+
+
 class _RenderingLayerFused(torch.autograd.Function):
     """render_depth + the post-processing of FaceRecNet.rendering_layer (nets/network.py:185-199) as one kernel pass:
     (ver, tri, texture, im_gray) -> (net_input [B,H,W,7], depth_img [B,H,W,1], depth, tri_ind)."""
 
     @staticmethod
     def forward(ctx, ver, tri, texture, im_gray):
+        return _RenderingLayerFused._fwd(ctx, ver, tri, texture, im_gray, False)
+
+    @staticmethod
+    def _fwd(ctx, ver, tri, texture, im_gray, keep_ver):   # (keep_ver: _RenderingLayerFusedNormal also saves `ver`)
         h = _host()
         image = im_gray
         _check_forward_shapes(ver, tri, texture, image)
@@ -262,7 +314,10 @@ class _RenderingLayerFused(torch.autograd.Function):
         if rc == -4:
             raise NotImplementedError("fused rendering layer: shape only covered by the fallback rasteriser")
         h.check(rc, "fr_rendering_layer_forward")
-        ctx.save_for_backward(tri_c, tri_ind, depth, img_c)
+        if keep_ver:
+            ctx.save_for_backward(tri_c, tri_ind, depth, img_c, ver_c)
+        else:
+            ctx.save_for_backward(tri_c, tri_ind, depth, img_c)
         ctx.dims = (B, nver, ntri, H, W)
         ctx.mark_non_differentiable(tri_ind)
         return net_in, depth_img, depth, tri_ind
@@ -271,8 +326,9 @@ class _RenderingLayerFused(torch.autograd.Function):
     def backward(ctx, g_net_in, g_depth_img, g_depth, g_tri_ind):
         # only the mask channel and the depth image depend on the vertices (through depth, hence vertex z):
         #   mask = clip(depth, 1e-6, 1) * im  ->  g * im where 1e-6 <= depth <= 1;   depth_img = max(depth, 1e-6)
+        # (_RenderingLayerFusedNormal adds the normal channels: all three rows, through the saved vertices)
         h = _host()
-        tri_c, tri_ind, depth, img = ctx.saved_tensors
+        tri_c, tri_ind, depth, img = ctx.saved_tensors[:4]
         B, nver, ntri, H, W = ctx.dims
         dg = torch.zeros_like(depth)
         if g_net_in is not None:
@@ -285,7 +341,22 @@ class _RenderingLayerFused(torch.autograd.Function):
         vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=depth.device)
         with torch.cuda.device(depth.device):
             _backward_call(h, dg, tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, depth.device)
+            if len(ctx.saved_tensors) == 5 and g_net_in is not None:
+                # channels 4-6 of g_net_input are the gradient of the normalised map: post mode, read in place at stride 7
+                gn = h.require_gpu_f32(g_net_in, "net_input_grad")
+                _normal_backward_call(h, gn, 4, 7, ctx.saved_tensors[4], tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, 1, 1,
+                                      depth.device)
         return vertex_grad, None, None, None
+
+
+class _RenderingLayerFusedNormal(_RenderingLayerFused):
+    """rendering_layer_fused(normal_grad=True): the same forward; the node also keeps `ver` ([B,3,nver] fp32: 41 MB at 64 faces
+    of the full mesh) and its backward completes the depth backward's tensor with fr_render_normal_backward (post mode on
+    channels 4-6 of the net_input gradient, accumulate=1)."""
+
+    @staticmethod
+    def forward(ctx, ver, tri, texture, im_gray):
+        return _RenderingLayerFused._fwd(ctx, ver, tri, texture, im_gray, True)
 
 
 # Per-stream scratch of the decode -> rendering-layer node, kept like the render workspace (least recently used dropped, a
@@ -413,28 +484,45 @@ class _DecodeRenderingLayer(torch.autograd.Function):
         return gp, None, None, None, None, None, None, None
 
 
-def decode_rendering_layer(params, R, im_gray, tri, texture, basis, im_size, pose_grad=False):
+def decode_rendering_layer(params, R, im_gray, tri, texture, basis, im_size, pose_grad=False, normal_grad=False):
     """One-node decode -> rendering layer: (params [B,d], R [B,3,3] or None, im_gray [B,H,W,1]) -> (net_input [B,H,W,7],
     depth_img [B,H,W,1]); `basis` is the network's PackedBasis.  Raises NotImplementedError where the fused entry points do not
     serve the shape (the caller composes vertices_transform and rendering_layer_fused instead).
     pose_grad=True: the backward also gives the three angles their gradient (R None) or R its own (fr_decode_render_backward_pose);
-    the node then retains the forward's vertex hand-off, one [B,3,pitch] fp32 buffer -- 41 MB at 64 faces of the full mesh."""
+    the node then retains the forward's vertex hand-off, one [B,3,pitch] fp32 buffer -- 41 MB at 64 faces of the full mesh.
+    normal_grad=True is not served here: the one-call backward is z-only by construction (only the z plane of the vertex gradient
+    exists in it), so it raises NotImplementedError like any other unserved call and the caller takes the two-step route
+    (FaceRecNet.decode_rendering_layer does: vertices_transform, then rendering_layer_fused(normal_grad=True))."""
+    if normal_grad:
+        raise NotImplementedError("decode -> rendering layer: normal gradients need the dense vertex gradient (two-step route)")
     return _DecodeRenderingLayer.apply(params, R, im_gray, tri, texture, basis, im_size, bool(pose_grad))
 
 
-def rendering_layer_fused(ver, tri, texture, im_gray):
+def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     """One-pass rendering layer: returns (net_input [B,H,W,7] = [mask*im | pncc | normal],
-    depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers."""
+    depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers.
+    normal_grad=False (default): as the reference, the normal channels carry no gradient and the vertex gradient is z-only.
+    normal_grad=True: the gradient of channels 4-6 reaches all three coordinates of the winning triangles' vertices
+    (fr_render_normal_backward, post mode, behind the depth backward); same outputs, bit for bit.  The node then keeps the
+    vertex tensor: [B,3,nver] fp32, 41 MB at 64 faces of the full mesh."""
+    if normal_grad:
+        return _RenderingLayerFusedNormal.apply(ver, tri, texture, im_gray)
     return _RenderingLayerFused.apply(ver, tri, texture, im_gray)
 
 
-def render_depth(ver, tri, texture, image, **kwargs):
+def render_depth(ver, tri, texture, image, normal_grad=False, **kwargs):
     """Forward function of RenderDepth (reference ops.py:78-81).
 
     The first output is the rendered depth, the fourth the triangle index each depth pixel corresponds to.
     `image` only donates the batch / height / width (its values are never read, render_depth_op.cc:397-403).
     `**kwargs` is accepted for call compatibility (TF passed `name=`); unknown keys are ignored.
+    normal_grad=False (default): as the reference, only `depth` has a backward (vertex z; the x and y rows are zeros).
+    normal_grad=True: the third output, `normal`, has one too -- its gradient reaches all three coordinates of the winning
+    triangles' vertices (fr_render_normal_backward, raw mode, behind the depth backward; tri_ind held fixed).  Same outputs, bit
+    for bit.  The node then keeps the vertex tensor: [B,3,nver] fp32, 41 MB at 64 faces of the full mesh.
     """
+    if normal_grad:
+        return _RenderDepthNormal.apply(ver, tri, texture, image)
     return _RenderDepth.apply(ver, tri, texture, image)
 
 

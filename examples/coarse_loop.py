@@ -52,7 +52,7 @@ def build_harness(args, dev, rank, world, local):
         face.init_pred_params[..., 6] = 1e-3 * S / 200.0
     # the reference's graph always holds FineNet (build(), network.py:69-101); the forward-only config 3 is CoarseNet + render
     model = cn.FaceReconModel(face, nIter=args.nIter, fine=args.fine or args.train, fused_step=args.fused_step,
-                              pose_grad=args.pose_grad).to(dev)
+                              pose_grad=args.pose_grad, normal_grad=args.normal_grad).to(dev)
     net = model
     if args.train and world > 1:
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local] if dev.type == "cuda" else None)
@@ -206,6 +206,9 @@ def main():
     ap.add_argument("--pose-grad", action="store_true",
                     help="let the render loop's gradient reach the three pose angles (fr_decode_pose_backward / "
                          "fr_decode_render_backward_pose); off: they get 0 from it, as in the reference")
+    ap.add_argument("--normal-grad", action="store_true",
+                    help="let the normal channels of every CoarseNet input carry their gradient to x, y and z of the vertices "
+                         "(fr_render_normal_backward); off: they are constants to autograd, as in the reference")
     ap.add_argument("--gather-sfs", action="store_true", help="whole-batch SfS lighting estimate across ranks")
     ap.add_argument("--small", action="store_true", help="tiny synthetic assets (smoke runs)")
     ap.add_argument("--dump-batches", default=None, metavar="FILE.npz",

@@ -405,6 +405,55 @@ int fr_decode_render_backward_pose(const float* g_depth, const float* g_depth_im
                                    void* workspace, size_t ws_bytes, void* hip_stream, const float* vertex_handoff,
                                    size_t vertex_bytes, float* grad_R);
 
+/* ---- normal-map gradients: the render backward fills x, y and z (opt-in) ------------------------------------------------------
+ * fr_render_depth_backward gives the x and y rows zeros and never reads a gradient of `normal` (render_depth_op.cc:359-363): that
+ * stays its definition.  This call ADDS the gradient of the op's `normal` plane (mode 0, raw) or of the normalised map that
+ * post_normal / FaceRecNet.rendering_layer makes of it (mode 1, post) with respect to the three vertices of each pixel's winning
+ * triangle.  tri_ind is held fixed (no coverage gradient) and the fp32 roundings of the forward are treated as the identity.
+ * Per pixel whose tri_ind names t = (p1, p2, p3) -- 0 <= tri_ind < ntri and all three ids inside [0, nver), else nothing:
+ *   a = fl32(P1 - P2), b = fl32(P1 - P3) (fp32 differences, as the forward); G = normal_grad widened to double; in double, each
+ *   operation rounded on its own:
+ *     da = b x G = (by Gz - bz Gy, bz Gx - bx Gz, bx Gy - by Gx)      db = G x a = (Gy az - Gz ay, Gz ax - Gx az, Gx ay - Gy ax)
+ *     term(p1) = fl32(da + db)   term(p2) = fl32(-da)   term(p3) = fl32(-db)          (nine fp32 terms per pixel)
+ *   mode 1: n = the forward's fp32 normal fl32(a x b); s = (n.z < 0) ? -1 : 1; m = s n; mag32 = (mx mx + my my) + mz mz in fp32
+ *     (post_normal's value: the backward takes the forward's branch); r = sqrt(m.m), d = r + (double)1e-6f;
+ *     mag32 > 1e-6f:  Gm = g'/d - m (g'.m) / (d d r);   else  Gm = g' / (1.0 + (double)1e-6f);   G = s Gm, then as mode 0.
+ *     (the double sqrt / divide sequences are not pinned: a post-mode term may differ from this text by one fp32 ulp)
+ * Each (face, row, vertex) sum of terms is formed as fr_render_depth_backward forms its own: the terms as 64-bit fixed-point
+ * integers on a grid of 2^(e - 39 + shift), e = floor(log2 M), M the face's largest finite |term| over all three rows, shift as
+ * above 2^20 pixels; integer addition in LDS by per-face owner workgroups; one rounding to fp32.  No float atomics, bit-
+ * reproducible, independent of the launch geometry; |result - exact sum| <= 2^-24 |sum| + n 2^(shift - 39) M for n terms.  A face
+ * with a non-finite term takes fp32 LDS atomics: the vertices that receive such a term come out non-finite, the others finite.
+ *   normal_grad: three floats per pixel, grad_stride (>= 3) floats between pixels: 3 for a dense [B,H,W,3] plane, 7 with the
+ *                pointer advanced by 4 for the normal channels of a [B,H,W,7] net_input gradient.
+ *   vertex:      [B,3,vertex_pitch] rows (vertex_pitch >= nver: nver for the dense tensor, fr_decode_render_vertex_pitch(N) for
+ *                the hand-off);  tri [3,ntri], tri_ind [B,H,W,1]: as fr_render_depth_backward.
+ *   vertex_grad: dense [B,3,nver].  accumulate 0: all three rows of every vertex are written.  accumulate 1: each element becomes
+ *                fl32(old + new), one add -- enqueued after fr_render_depth_backward(_ws) on the same stream it completes that
+ *                tensor, and the depth part's bits survive wherever the normal part is zero.
+ *   workspace:   fr_render_normal_backward_workspace_bytes(B, nver, H, W) bytes (48 per pixel + 8 per 1,024-pixel chunk; 0 for
+ *                an empty shape), 16-byte aligned, caller-owned, per call in flight.
+ * Every check runs before any HIP call: a negative size, mode outside {0, 1}, accumulate outside {0, 1}, grad_stride < 3 or
+ * vertex_pitch < nver is FR_ERR_INVALID_ARG; then B == 0 (or nver == 0) is FR_OK; a NULL vertex_grad -- or, where pixels and
+ * triangles exist, a NULL normal_grad / vertex / tri / tri_ind -- is FR_ERR_INVALID_ARG; a workspace that is missing, too small or
+ * misaligned is FR_ERR_WORKSPACE (there is no variant without one).  Nothing is allocated or synchronised; reentrant under the
+ * rules at the top of this file.
+ * Time: tools/normal_grad_probe.py (profiles/render_normal_backward.json) measures this call beside fr_render_depth_backward_ws at 64
+ * and 32 faces of the full mesh at 200 x 200 and the bytes it must move.  MI355X, medians of 6 rounds of 40 calls: raw mode 76.0 /
+ * 44.0 us, post mode at stride 7 with accumulate 92.8 / 51.8 us, fr_render_depth_backward_ws on the same inputs 34.5 / 26.4 us, the
+ * two in a row 140.7 / 75.9 us.  Must move 120 / 60 MB = 19.1 / 9.5 us at the 6.29 TB/s copy rate (0.25 / 0.22 of it in raw mode); the
+ * rest goes to the call's own records and to the id plane that each of a face's 8 owners streams. */
+size_t fr_render_normal_backward_workspace_bytes(int B, int nver, int H, int W);
+int fr_render_normal_backward(const float* normal_grad, int grad_stride, const float* vertex, int vertex_pitch,
+                              const float* tri, const float* tri_ind, float* vertex_grad, int B, int nver, int ntri,
+                              int H, int W, int mode, int accumulate, void* workspace, size_t ws_bytes, void* hip_stream);
+
+/* The normal-backward launch geometry (no GPU needed; the launcher reads the same function): out[6] = {owner workgroups per
+ * face, vertices per owner (three 64-bit accumulators each), shift, 1,024-pixel record chunks, dynamic LDS bytes of an owner
+ * workgroup, 1 if the block -> (face, owner) map keeps a face's owners on one XCD (batch a multiple of 8) else 0}; all zero for a
+ * shape that launches no kernel.  Used by tests/test_normal_backward_cpu.py and tests/test_normal_backward_gpu.py. */
+void fr_debug_render_normal_bwd_geom(int B, int nver, int H, int W, int* out);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
