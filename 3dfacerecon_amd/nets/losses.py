@@ -38,10 +38,30 @@ def laplace_transform(x):
     return y[0] if single else y
 
 
-def _pinv_sym3(A):
+def _pinv_sym3(A, rtol=1e-15):
     """Moore-Penrose inverse of a batch of symmetric 3x3 matrices (the reference calls np.linalg.pinv on Y Y^T through
     tf.py_func, network.py:431: cutoff 1e-15 x the largest singular value, no gradient)."""
-    return torch.linalg.pinv(A.detach(), rtol=1e-15, hermitian=True)
+    return torch.linalg.pinv(A.detach(), rtol=rtol, hermitian=True)
+
+
+def _ops():
+    """rendering_layer/ops.py, loaded by path under the name nets/network.py uses: one module, however this file was imported"""
+    import importlib.util
+    import os
+    import sys
+    mod = sys.modules.get("_fr_hotpath_ops")
+    if mod is None:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rendering_layer", "ops.py")
+        spec = importlib.util.spec_from_file_location("_fr_hotpath_ops", path)
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules["_fr_hotpath_ops"] = mod
+        spec.loader.exec_module(mod)
+    return mod
+
+
+def _world_size():
+    import torch.distributed as dist
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
 def _all_gather_batch(t):
@@ -54,32 +74,53 @@ def _all_gather_batch(t):
     return torch.cat(parts, dim=-1)
 
 
-def spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_image_new, normal_map_new, gather=False):
+def spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_image_new, normal_map_new, gather=False, fused=False,
+                                  rcond=1e-15):
     """The linear-algebra core of get_spherical_harmonics_model (network.py:424-460) on already rendered maps:
     per pixel, lighting l = (Y Y^T)^+ Y (I / (albedo + 1))^T over the batch (Y = [3 x B] normals), then the recovered
-    intensity albedo_new * (l^T Y_new).  All inputs [B,H,W,c]; returns [B,H,W,1]."""
+    intensity albedo_new * (l^T Y_new).  All inputs [B,H,W,c]; returns [B,H,W,1].
+    rcond: the pseudo-inverse's cutoff relative to the largest eigenvalue (the reference's 1e-15).
+    fused=True: the whole expression is one kernel pass (rendering_layer/ops.py::sfs_intensity, fr_sfs_intensity_forward): float64
+    sums in a fixed order, gradients to the two normal maps with the pseudo-inverse held constant -- the same autograd semantics
+    as this torch route, whose pinv is detached.  The albedos and im_gray are constants of that call (they are detached here; in
+    this model neither has a path to a parameter).  gather=True under a world size above 1 stays on the torch route even with
+    fused=True: the per-pixel sums would have to cross ranks, which the kernel does not do."""
+    if fused and not (gather and _world_size() > 1):
+        return _ops().sfs_intensity(abedo_image.detach(), normal_map, im_gray.detach(), abedo_image_new.detach(), normal_map_new,
+                                    rcond=rcond)
     abedo = abedo_image.permute(1, 2, 3, 0)            # (H,W,1,B)
     Yz0 = normal_map.permute(1, 2, 3, 0)               # (H,W,3,B)
     I = im_gray.permute(1, 2, 3, 0)                    # (H,W,1,B)
     rhs = I / (abedo + 1.0)
     Yl, rl = (Yz0, rhs) if not gather else (_all_gather_batch(Yz0), _all_gather_batch(rhs))
-    Yz0_nec_inv = _pinv_sym3(Yl @ Yl.transpose(-1, -2))                                   # (H,W,3,3)
+    Yz0_nec_inv = _pinv_sym3(Yl @ Yl.transpose(-1, -2), rcond)                                  # (H,W,3,3)
     lighting_lse = (Yz0_nec_inv @ Yl) @ rl.transpose(-1, -2)                               # (H,W,3,1)
     Yz = normal_map_new.permute(1, 2, 3, 0)
     intensity = abedo_image_new.permute(1, 2, 3, 0) * (lighting_lse.transpose(-1, -2) @ Yz)  # Eqn (8), (H,W,1,B)
     return intensity.permute(3, 0, 1, 2)
 
 
-def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False):
+def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False, normal_grad=False, fused=False, rcond=1e-15):
     """Recovered intensity (B,H,W,1) of the first-order spherical-harmonics shading model (network.py:420-462): two
-    more render_depth calls (mean albedo, then mean + pc_tex . param_tex) feed spherical_harmonics_intensity."""
+    more render_depth calls (mean albedo, then mean + pc_tex . param_tex) feed spherical_harmonics_intensity.
+    normal_grad=False (default): as the reference, both renders hand autograd constant normal maps, so the term has no gradient
+    with respect to any parameter.  normal_grad=True: both renders carry the normal map's gradient to the vertices
+    (render_depth(normal_grad=True)) and the term moves the geometry.  fused / rcond: as spherical_harmonics_intensity."""
     fn = face_net
     if fn.mu_tex is None or fn.pc_tex is None or fn.param_tex is None:
         raise ValueError("the asset dict has no texture model (mu_tex / pc_tex / param_tex)")
-    abedo_image, normal_map = fn.compute_abedo_image(vertices_proj, fn.tri, fn.mu_tex)   # (B,H,W,1), (B,H,W,3)
+    kw = {"normal_grad": True} if normal_grad else {}
+    abedo_image, normal_map = fn.compute_abedo_image(vertices_proj, fn.tri, fn.mu_tex, **kw)   # (B,H,W,1), (B,H,W,3)
     texture_new = fn.mu_tex + (fn.pc_tex @ fn.param_tex).reshape(3, -1)                    # network.py:446-448
-    abedo_new, normal_new = fn.compute_abedo_image(vertices_proj, fn.tri, texture_new)
-    return spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_new, normal_new, gather=gather)
+    abedo_new, normal_new = fn.compute_abedo_image(vertices_proj, fn.tri, texture_new, **kw)
+    if fused and not normal_grad:
+        # the renders' normal maps are constants to autograd in this mode (their node drops the gradient): say so, and the fused
+        # node runs no backward at all
+        normal_map, normal_new = normal_map.detach(), normal_new.detach()
+    if not (fused or rcond != 1e-15):
+        return spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_new, normal_new, gather=gather)
+    return spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_new, normal_new, gather=gather, fused=fused,
+                                         rcond=rcond)
 
 
 def combine_losses(losses):
@@ -90,8 +131,11 @@ def combine_losses(losses):
 
 
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
-             gather_sfs=False):
-    """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d)."""
+             gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15):
+    """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
+    sfs_normal_grad / sfs_fused / sfs_rcond (defaults: off, off, the reference's 1e-15): the normal_grad / fused / rcond of
+    get_spherical_harmonics_model.  With them off spherical_harmonics_loss is a reported scalar with no gradient, as in the
+    reference; sfs_normal_grad=True lets it reach the vertices through the two SfS renders."""
     fn = face_net
     B = pred_params.shape[0]
     pred = pred_params.reshape(B, fn.ndim)
@@ -102,7 +146,8 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     # rounding of the two products; the difference form needs one pass of the basis instead of two
     g = fn.geometry_product(pred[:, fn.ndim_pose:] - label[:, fn.ndim_pose:])
     losses['geometry_loss'] = (g * g).mean()
-    intensity_recover = get_spherical_harmonics_model(fn, vertices_proj, im_gray, gather=gather_sfs)
+    intensity_recover = get_spherical_harmonics_model(fn, vertices_proj, im_gray, gather=gather_sfs, normal_grad=sfs_normal_grad,
+                                                      fused=sfs_fused, rcond=sfs_rcond)
     losses['spherical_harmonics_loss'] = F.mse_loss(intensity_recover, im_gray)
     losses['fidelity_loss'] = F.mse_loss(pred_depth_map, coarse_depth_map)
     filtered_depth = laplace_transform(pred_depth_map[..., 0])

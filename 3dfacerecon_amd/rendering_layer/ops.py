@@ -498,6 +498,72 @@ def decode_rendering_layer(params, R, im_gray, tri, texture, basis, im_size, pos
     return _DecodeRenderingLayer.apply(params, R, im_gray, tri, texture, basis, im_size, bool(pose_grad))
 
 
+class _SfsIntensity(torch.autograd.Function):
+    """fr_sfs_intensity_forward / _backward (include/fr_hotpath.h, "shape-from-shading term") as one autograd node: the per-pixel
+    lighting solve over the batch and the shading, P held constant in the backward."""
+
+    @staticmethod
+    def forward(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond):
+        h = _host()
+        for t, name in ((abedo, "abedo"), (im_gray, "im_gray"), (abedo_new, "abedo_new")):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise ValueError("sfs_intensity: %s requires grad, but the albedos and im_gray are constants of this model "
+                                 "(detach it)" % name)
+        a_c = h.require_gpu_f32(abedo, "abedo")
+        n_c = h.require_gpu_f32(normal, "normal")
+        i_c = h.require_gpu_f32(im_gray, "im_gray")
+        a2_c = h.require_gpu_f32(abedo_new, "abedo_new")
+        n2_c = n_c if normal_new is normal else h.require_gpu_f32(normal_new, "normal_new")
+        if n_c.dim() != 4 or n_c.shape[3] != 3:
+            raise ValueError("sfs_intensity expects normal [B,H,W,3]")
+        B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+        for t, name, c in ((a_c, "abedo", 1), (i_c, "im_gray", 1), (a2_c, "abedo_new", 1), (n2_c, "normal_new", 3)):
+            if tuple(t.shape) != (B, H, W, c):
+                raise ValueError("sfs_intensity: %s must be [%d,%d,%d,%d] (got %s)" % (name, B, H, W, c, tuple(t.shape)))
+            if t.device != n_c.device:
+                raise ValueError("sfs_intensity: %s is on %s, normal on %s" % (name, t.device, n_c.device))
+        dev = n_c.device
+        L = h.lib()
+        nst = L.fr_sfs_state_bytes(H, W)
+        state = torch.empty((max(nst, 16) // 8,), dtype=torch.float64, device=dev)   # per call: the backward reads it
+        intensity = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = L.fr_sfs_intensity_forward(h.ptr(a_c), h.ptr(n_c), h.ptr(i_c), h.ptr(a2_c), h.ptr(n2_c), B, H, W, float(rcond),
+                                            h.ptr(intensity), h.ptr(state), nst, h.stream_ptr(dev))
+        h.check(rc, "fr_sfs_intensity_forward")
+        ctx.save_for_backward(a_c, i_c, a2_c, n2_c, state)
+        ctx.dims = (B, H, W, nst)
+        return intensity
+
+    @staticmethod
+    def backward(ctx, g):
+        h = _host()
+        a_c, i_c, a2_c, n2_c, state = ctx.saved_tensors
+        B, H, W, nst = ctx.dims
+        dev = a_c.device
+        want_n, want_n2 = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
+        if not (want_n or want_n2):
+            return None, None, None, None, None, None
+        g_c = h.require_gpu_f32(g, "grad_intensity")
+        gn = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n else None
+        gn2 = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n2 else None
+        with torch.cuda.device(dev):
+            rc = h.lib().fr_sfs_intensity_backward(h.ptr(g_c), h.ptr(a_c), h.ptr(i_c), h.ptr(a2_c), h.ptr(n2_c), h.ptr(state), nst,
+                                                   B, H, W, h.ptr(gn), h.ptr(gn2), h.stream_ptr(dev))
+        h.check(rc, "fr_sfs_intensity_backward")
+        return None, gn, None, None, gn2, None
+
+
+def sfs_intensity(abedo, normal, im_gray, abedo_new, normal_new, rcond=1e-15):
+    """The shape-from-shading intensity (nets/network.py:424-460) on rendered maps in ONE kernel pass: per pixel the lighting
+    l = pinv(sum_b n n^T) sum_b n I / (abedo + 1) over the batch, then abedo_new * (l . normal_new) -> [B,H,W,1].  float64 sums in
+    a fixed order (a function of B alone), bit-reproducible; `rcond` is the eigenvalue cutoff of the pseudo-inverse.
+    Gradients go to `normal` and `normal_new` only, with the pseudo-inverse held constant (what a detached pinv gives the torch
+    route); autograd adds the two when one tensor is passed for both.  An albedo or im_gray that requires grad is refused: they are
+    constants of this model.  The node keeps a state tensor of ten float64 planes (3.2 MB at 200 x 200) for its backward."""
+    return _SfsIntensity.apply(abedo, normal, im_gray, abedo_new, normal_new, float(rcond))
+
+
 def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     """One-pass rendering layer: returns (net_input [B,H,W,7] = [mask*im | pncc | normal],
     depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers.

@@ -69,7 +69,8 @@ def build_harness(args, dev, rank, world, local):
     def forward_loss(im, lab):
         out = net(im)
         return out, losses.get_loss(face, out["pred_params"], lab, im, out["vertices_proj"], out["coarse_depth_map"],
-                                    out["pred_depth_map"], gather_sfs=args.gather_sfs)
+                                    out["pred_depth_map"], gather_sfs=args.gather_sfs, sfs_normal_grad=args.sfs_grad,
+                                    sfs_fused=args.sfs_fused, sfs_rcond=args.sfs_rcond)
 
     def step():
         if not args.train:
@@ -210,6 +211,19 @@ def main():
                     help="let the normal channels of every CoarseNet input carry their gradient to x, y and z of the vertices "
                          "(fr_render_normal_backward); off: they are constants to autograd, as in the reference")
     ap.add_argument("--gather-sfs", action="store_true", help="whole-batch SfS lighting estimate across ranks")
+    ap.add_argument("--sfs-grad", action="store_true",
+                    help="let the shape-from-shading term reach the geometry: its two renders carry the normal map's gradient to "
+                         "the vertices (get_loss(sfs_normal_grad=True)); off: the term is a reported scalar with no gradient, as in "
+                         "the reference")
+    ap.add_argument("--sfs-fused", action="store_true",
+                    help="the SfS lighting solve and shading as one kernel pass per direction (fr_sfs_intensity_forward / "
+                         "_backward) instead of the stock-torch permutes, matmuls and batched pinv")
+    ap.add_argument("--sfs-rcond", type=float, default=1e-15,
+                    help="eigenvalue cutoff of the SfS pseudo-inverse, relative to the largest.  With float64 sums a rank-deficient "
+                         "pixel (fewer than three faces cover it, or their normals are parallel) has null eigenvalues near 1e-16 "
+                         "of the largest, so the reference's 1e-15 cuts them unpredictably -- as it does in the reference itself.  "
+                         "A cutoff such as 1e-6 makes the term well defined everywhere and is the sensible choice once the term "
+                         "carries a gradient (--sfs-grad)")
     ap.add_argument("--small", action="store_true", help="tiny synthetic assets (smoke runs)")
     ap.add_argument("--dump-batches", default=None, metavar="FILE.npz",
                     help="--phase test: save every timed batch's parameters, vertices and planes (as its consumer saw them) for an "

@@ -454,6 +454,65 @@ int fr_render_normal_backward(const float* normal_grad, int grad_stride, const f
  * shape that launches no kernel.  Used by tests/test_normal_backward_cpu.py and tests/test_normal_backward_gpu.py. */
 void fr_debug_render_normal_bwd_geom(int B, int nver, int H, int W, int* out);
 
+/* ---- shape-from-shading term: fused lighting solve with a normal backward (opt-in) ---------------------------------------------
+ * Replaces the linear algebra of get_spherical_harmonics_model (nets/network.py:424-460) on already rendered maps: four transposes,
+ * a batched matmul, np.linalg.pinv through tf.py_func on H*W 3x3 matrices (:431), two more matmuls and a transpose back.  One
+ * streaming pass per direction; the backward hands fr_render_normal_backward the gradient of the normalised normal map.
+ *   abedo, im_gray, abedo_new, intensity, grad_intensity  [B,H,W,1];   normal, normal_new, grad_normal, grad_normal_new  [B,H,W,3]
+ *   dense fp32; normal_new may be the same pointer as normal.  Written a_b, I_b, a'_b, n_b, n'_b below (face b, one pixel).
+ * FORWARD, per pixel.  All arithmetic in float64 on the widened fp32 inputs, every operation rounded on its own (no contraction):
+ *   u_b = I_b / (a_b + 1.0)
+ *   M = sum_b n_b n_b^T   (six sums: xx, xy, xz, yy, yz, zz)        r = sum_b n_b u_b   (three sums; the term is n times u)
+ *   P = pinv(M) through the symmetric eigendecomposition M = V diag(lambda) V^T: eigenvalue i is KEPT iff
+ *       lambda_i > rcond * lambda_max  and  lambda_i > 0;   P = sum over the kept i of (v_i v_i^T) * (1 / lambda_i);
+ *       M = 0 gives P = 0 and rank 0.  The eigensolver is cyclic Jacobi with a FIXED count of six sweeps (csrc/fr_sfs_pinv.h, one
+ *       __host__ __device__ function; four reach the float64 floor): no data-dependent loop anywhere.
+ *   l = P r, row by row as (P_i0 r_0 + P_i1 r_1) + P_i2 r_2
+ *   intensity_b = fl32( a'_b * ((l_x n'_bx + l_y n'_by) + l_z n'_bz) )
+ * -- (M^+ Y) rhs^T of network.py:433, associated as M^+ (Y rhs^T).
+ * Association of the sums over b: a function of B ALONE -- not of H, W, the pixel's position or any option.  S = min(4, max(1,
+ * B / 4)) slices (integer division); slice s owns the faces [s C, min(B, (s + 1) C)), C = ceil(B / S), and adds their terms in
+ * ascending b onto +0.0; the slices are then added in ascending s onto slice 0's sum: ((s0 + s1) + s2) + s3.  No float atomics;
+ * bit-reproducible.
+ * Non-finite inputs.  If any of the six sums of M is NaN or Inf, P is six NaNs and the rank is 0; if any of the three sums of r is,
+ * l is three NaNs: every intensity of that pixel is then NaN, and no other pixel changes by a bit.  A NaN or Inf in a'_b or n'_b
+ * alone reaches face b's own intensity through the ordinary IEEE operations above.  Nothing lengthens a loop.
+ * STATE.  state[k H W + p] (doubles, p = the pixel's row-major index): k = 0..5 P as xx, xy, xz, yy, yz, zz; k = 6..8 l; k = 9 the
+ * number of kept eigenvalues.  fr_sfs_state_bytes(H, W) = 10 planes of H * W doubles (0 for an empty image), 16-byte aligned,
+ * caller-owned, one per call in flight; the forward writes all of it, the backward reads it.  The layout is public.
+ * BACKWARD.  P is held constant (the autograd semantics of a detached pinv, and of the reference's tf.py_func).  With g_b = dL / d
+ * intensity_b and w_b = g_b a'_b:
+ *   q = sum_b w_b n'_b   (three sums, the forward's association)         s = P q   (rows as for l)
+ *   grad_normal_b = fl32(u_b * s)   (three components)                   grad_normal_new_b = fl32(w_b * l)
+ * Either output may be NULL (the other is bit-identical to the joint call); both NULL is FR_ERR_INVALID_ARG.  No gradient is formed
+ * for the albedos or im_gray: they are constants of this model.  A caller that passed one tensor as normal and normal_new adds the
+ * two outputs.
+ * Checks, all before any HIP call: a negative size, or an rcond that is negative or not finite, is FR_ERR_INVALID_ARG; then B == 0
+ * or an empty image is FR_OK; then a NULL input or output pointer (the backward: both outputs NULL) is FR_ERR_INVALID_ARG; a state
+ * that is missing, too small or not 16-byte aligned is FR_ERR_WORKSPACE; more than 2^31 - 65 pixels is FR_ERR_UNSUPPORTED.  Nothing
+ * is allocated or synchronised; reentrant under the rules at the top of this file with a state buffer per call in flight.
+ * Kernels (csrc/fr_sfs.hip): a workgroup owns 64 consecutive pixels, one per lane, and S waves; wave s streams its slice's maps (per
+ * face 768 contiguous bytes of a normal plane), the nine partial sums meet in LDS in the order above, wave 0 solves the 3 x 3 once
+ * per pixel and broadcasts l through LDS for the shading pass.  200 x 200 gives 625 workgroups of 4 waves for the chip's 1,024 SIMDs.
+ * Time: tools/sfs_probe.py (profiles/sfs_intensity.json) measures both directions beside the stock-torch route at 64 and 32 faces of
+ * 200 x 200 and the bytes each must move. */
+size_t fr_sfs_state_bytes(int H, int W);
+int fr_sfs_intensity_forward(const float* abedo, const float* normal, const float* im_gray, const float* abedo_new,
+                             const float* normal_new, int B, int H, int W, double rcond, float* intensity, void* state,
+                             size_t state_bytes, void* hip_stream);
+int fr_sfs_intensity_backward(const float* grad_intensity, const float* abedo, const float* im_gray, const float* abedo_new,
+                              const float* normal_new, const void* state, size_t state_bytes, int B, int H, int W,
+                              float* grad_normal, float* grad_normal_new, void* hip_stream);
+
+/* The SfS launch geometry (no GPU needed; the launchers read the same function): out[4] = {pixels per workgroup, batch slices per
+ * pixel (S above), workgroups, dynamic LDS bytes of a forward workgroup}; all zero for an empty shape.  Used by
+ * tests/test_sfs_cpu.py. */
+void fr_debug_sfs_geom(int B, int H, int W, int* out);
+
+/* HOST instantiation of the kernel's pseudo-inverse (no GPU): m6 -> p6, both xx, xy, xz, yy, yz, zz, *rank = kept eigenvalues.
+ * FR_ERR_INVALID_ARG for a NULL pointer or an rcond that is negative or not finite.  Used by tests/test_sfs_cpu.py. */
+int fr_debug_sfs_pinv(const double* m6, double rcond, double* p6, int* rank);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
