@@ -221,6 +221,10 @@ def _bind(L):
     L.fr_debug_render_geom.restype = None
     L.fr_debug_decode_bwd_geom.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
     L.fr_debug_decode_bwd_geom.restype = None
+    L.fr_debug_decode_geom.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
+    L.fr_debug_decode_geom.restype = _i
+    L.fr_debug_decode_walk.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
+    L.fr_debug_decode_walk.restype = _i
     L.fr_debug_render_bwd_geom.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
     L.fr_debug_render_bwd_geom.restype = None
     L.fr_debug_div3_sweep.argtypes = [ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _vp]
@@ -246,7 +250,7 @@ EXPORTS = ["fr_version", "fr_strerror", "fr_render_depth_workspace_bytes", "fr_r
            "fr_decode_render_backward_pose_workspace_bytes", "fr_decode_render_backward_pose", "fr_debug_pose_bwd_geom",
            "fr_render_normal_backward_workspace_bytes", "fr_render_normal_backward", "fr_debug_render_normal_bwd_geom",
            "fr_sfs_state_bytes", "fr_sfs_intensity_forward", "fr_sfs_intensity_backward", "fr_debug_sfs_geom",
-           "fr_debug_sfs_pinv"]
+           "fr_debug_sfs_pinv", "fr_debug_decode_geom", "fr_debug_decode_walk"]
 
 
 def lib():

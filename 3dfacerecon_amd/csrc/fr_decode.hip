@@ -25,8 +25,11 @@ constexpr int KGROUP = 16;      // k values per packed group (4 k-steps of 4)
 __host__ __device__ inline int groups_of(int n) { return (n + KGROUP - 1) / KGROUP; }
 
 // Packed image:  A[tile][g][c][lane] as float4 (4 consecutive k-steps), then mu[tile][c][16].
-//   A[tile][g][c][lane][j] = basis_c[16*tile + (lane&15)][16*g' + 4*j + (lane>>4)]   (0 when out of range)
-// where groups 0..GS-1 come from pc_shape and GS..GS+GE-1 from pc_exp.
+//   A[tile][g][c][lane][j] = basis_c[16*tile + (lane&15)][16*g' + 4*j + (lane>>4)]   (-0.0 when out of range)
+// where groups 0..GS-1 come from pc_shape and GS..GS+GE-1 from pc_exp.  The padding is MINUS zero: a padded k meets a padded
+// parameter of +0 (stage_params), their product -0 is the identity of the chain's addition for EVERY accumulator, one of -0
+// included -- a chain whose products all underflow ends at a zero of its last product's sign, and a +0 x +0 padding step would turn
+// its -0 into +0, which the written definition (include/fr_hotpath.h: chains over the live k only) does not.
 __global__ __launch_bounds__(256) void pack_basis_kernel(const float* __restrict__ mu, const float* __restrict__ pc_shape,
                                                          const float* __restrict__ pc_exp, int N, int ns, int ne,
                                                          float4* __restrict__ A, float* __restrict__ mu_p) {
@@ -42,7 +45,7 @@ __global__ __launch_bounds__(256) void pack_basis_kernel(const float* __restrict
         int g = (int)(r % G);
         long long tile = r / G;
         long long p = tile * TILE_V + (lane & 15);
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        float v[4] = {-0.f, -0.f, -0.f, -0.f};
         if (p < N) {
             size_t row = (size_t)c * N + p;
 #pragma unroll
@@ -216,11 +219,9 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void decode_kernel(DecodeArgs a) {
     const int N = a.N;
     // Work distribution: a tile's column-block halves go to neighbouring waves of one workgroup (they stream the same A
     // fragments at the same time, so the second read is an L1/L2 hit); tiles are dealt as tile_walk describes.
-    const int H2 = a.halves;              // 1 or 2
-    const int slots = DEC_WAVES / H2;     // tiles a workgroup works on at a time
-    const int slot = wave / H2;
-    const int hf = wave - slot * H2;
-    const TileWalk tw = tile_walk(slot, slots, (int)blockIdx.x, (int)gridDim.x);
+    // (a.halves is 1 .. 4; DEC_WAVES / halves tiles are in work at a time, surplus waves get none: wave_work)
+    const WaveWork tw = wave_work(wave, DEC_WAVES, a.halves, (int)blockIdx.x, (int)gridDim.x);
+    const int hf = tw.hf;
     for (int tile = tw.first; tile < tiles; tile += tw.stride) {
         const float4* Ap = a.A + (size_t)tile * G * 3 * 64 + lane;   // group g, coordinate c at Ap[(g*3+c)*64]
         const float* Pll = smem + (size_t)hf * half_floats;  // this half's parameter image; lane offsets in sw[]
@@ -231,10 +232,15 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void decode_kernel(DecodeArgs a) {
         for (int nb = 0; nb < NBW; nb++) s0[nb] = s1[nb] = s2[nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
         // ---- S = pc_shape . alpha : fmaf chain over k from +0.  The A fragments of the next two groups (6 KiB per
-        //      wave, ~96 KiB per CU) are in flight while the current group's MFMAs issue ----
-        float4 c0 = Ap[0], c1 = Ap[64], c2 = Ap[128];
-        const int g1 = G > 1 ? 1 : 0;
-        float4 d0 = Ap[(size_t)(g1 * 3 + 0) * 64], d1 = Ap[(size_t)(g1 * 3 + 1) * 64], d2 = Ap[(size_t)(g1 * 3 + 2) * 64];
+        //      wave, ~96 KiB per CU) are in flight while the current group's MFMAs issue
+        //      (no basis at all, G == 0: the image holds only mu and no fragment may be requested; with G == 1 the second
+        //      prefetch repeats group 0, and the loop below clamps to G - 1: in bounds for every G >= 1) ----
+        float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f), c1 = c0, c2 = c0, d0 = c0, d1 = c0, d2 = c0;
+        if (G > 0) {
+            c0 = Ap[0]; c1 = Ap[64]; c2 = Ap[128];
+            const int g1 = G > 1 ? 1 : 0;
+            d0 = Ap[(size_t)(g1 * 3 + 0) * 64]; d1 = Ap[(size_t)(g1 * 3 + 1) * 64]; d2 = Ap[(size_t)(g1 * 3 + 2) * 64];
+        }
         for (int g = 0; g < GS; g++) {
             const int gn = g + 2 < G ? g + 2 : G - 1;  // the last S groups prefetch the first E groups
             const float4 n0 = Ap[(size_t)(gn * 3 + 0) * 64], n1 = Ap[(size_t)(gn * 3 + 1) * 64],
@@ -362,12 +368,9 @@ void decode_ring_kernel(DecodeArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tiles = tiles_of(a.N);
     const int N = a.N;
-    const int H2 = a.halves;
-    const int slots = DEC_WAVES / H2;
-    const int slot = wave / H2;
-    const int hf = wave - slot * H2;
-    const TileWalk tw = tile_walk(slot, slots, (int)blockIdx.x, (int)gridDim.x);
-    const int tile0 = tw.first, tstride = tw.stride;
+    const WaveWork tw = wave_work(wave, DEC_WAVES, a.halves, (int)blockIdx.x, (int)gridDim.x);
+    const int hf = tw.hf;
+    const int tile0 = tw.first, tstride = tw.stride;   // (a surplus wave: tile0 past every tile, the no-work path below)
     const float* Pll = smem + (size_t)hf * half_floats;
     int sw[4];
     lane_swizzle<NBW>(lane, sw);
@@ -460,8 +463,9 @@ void decode_ring_kernel(DecodeArgs a) {
                     asm volatile("" ::"v"(af), "v"(bq[0]), "v"(bq[3]));  // keeps the fragment and the LDS reads live
                 } else {
                     // k-steps that hold only padding (199 = 12*16 + 7 leaves two of the last shape group's four) are
-                    // skipped: their products are +0 (zero basis x zero parameter) and the chains, started from +0, are
-                    // never -0, so adding them changes nothing -- and the oracle's chains do not contain them
+                    // skipped: their products are -0 (the basis padding) x (+0, the parameter padding) = -0, which changes no
+                    // accumulator -- and the oracle's chains do not contain them.  (The k-steps that mix live and padded k are
+                    // issued; the -0 padding is what keeps an accumulator of -0, the end of a chain of underflowing products.)
                     const int live = (g == GS - 1) ? ks_s : (g == G - 1) ? ks_e : 4;
                     mfma_step<NBW, TR>(af.x, bq[0], c[cc]);
                     if (live > 1) mfma_step<NBW, TR>(af.y, bq[1], c[cc]);
@@ -569,29 +573,121 @@ int fr_device_cu_count() {
 }
 
 template <int NBW, int WAVES>
-static int launch_decode_nbw(const fr::DecodeArgs& a, size_t lds, int cus, size_t tiles, hipStream_t stream) {
+static int launch_decode_nbw(const fr::DecodeArgs& a, size_t lds, int grid, hipStream_t stream) {
     static fr_lds_flags_t lds_ok[64];
     if (fr_allow_full_lds(reinterpret_cast<const void*>(&fr::decode_kernel<NBW, WAVES>), lds_ok) != hipSuccess)
         return FR_ERR_LAUNCH;
-    const int slots = WAVES / a.halves;
-    const int grid = (int)min((long long)cus, (long long)(tiles + slots - 1) / slots);
     hipLaunchKernelGGL((fr::decode_kernel<NBW, WAVES>), dim3(grid), dim3(WAVES * 64), lds, stream, a);
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }
 
 template <int GS, int GE, int R, int NBW, int WAVES, int MB = 64, int WPE = WAVES / 4, bool NT = false, bool PRIO = false,
           bool TR = false>
-static int launch_decode_ring(const fr::DecodeArgs& a, size_t lds, int cus, size_t tiles, hipStream_t stream) {
+static int launch_decode_ring(const fr::DecodeArgs& a, size_t lds, int grid, hipStream_t stream) {
     static fr_lds_flags_t lds_ok[64];
     if (fr_allow_full_lds(reinterpret_cast<const void*>(&fr::decode_ring_kernel<GS, GE, R, NBW, WAVES, MB, WPE, NT, fr::NoProbe, PRIO, TR>),
                           lds_ok) != hipSuccess)
         return FR_ERR_LAUNCH;
-    const int slots = WAVES / a.halves;
-    const int grid = (int)min((long long)cus, (long long)(tiles + slots - 1) / slots);
     hipLaunchKernelGGL((fr::decode_ring_kernel<GS, GE, R, NBW, WAVES, MB, WPE, NT, fr::NoProbe, PRIO, TR>), dim3(grid), dim3(WAVES * 64),
                        lds, stream, a);
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }
+
+// ---- the launch decision, as a pure host function -------------------------------------------------------------------------
+// The nine kernel instantiations the launcher chooses among.  The template arguments of a launch are READ from this table
+// (launch_variant), so what fr_debug_decode_geom reports for a pass is what the pass instantiates.
+namespace {
+enum { DK_GENERIC = 0, DK_RING = 1 };   // decode_kernel | decode_ring_kernel<13, 2, 8, ...>
+struct DecodeVariant {
+    int kernel, nbw, waves, mb, wpe, nt, prio, tr;
+};
+enum {
+    V_RING_WIDE, V_RING_NBW1, V_RING_WAVES8, V_RING_TEMPORAL, V_RING_TR, V_RING_NT, V_GENERIC_1, V_GENERIC_2, V_GENERIC_4,
+    V_COUNT
+};
+constexpr DecodeVariant kDecodeVariants[V_COUNT] = {
+    {DK_RING, 4, 12, 128, 3, 0, 0, 0},   // V_RING_WIDE: 128 columns per pass, 64-column items on 12 waves
+    {DK_RING, 1, 16, 64, 4, 1, 0, 0},    // V_RING_NBW1: 16-column items
+    {DK_RING, 2, 8, 64, 4, 0, 0, 0},     // V_RING_WAVES8: FR_DECODE_WAVES=8
+    {DK_RING, 2, 16, 64, 4, 0, 1, 0},    // V_RING_TEMPORAL: default cache policy for the basis stream, ranked waves
+    {DK_RING, 2, 16, 64, 4, 1, 1, 1},    // V_RING_TR: FR_DECODE_STORE=1, transposed accumulators
+    {DK_RING, 2, 16, 64, 4, 1, 1, 0},    // V_RING_NT: non-temporal basis stream, ranked waves
+    {DK_GENERIC, 1, 16, 64, 4, 0, 0, 0},
+    {DK_GENERIC, 2, 16, 64, 4, 0, 0, 0},
+    {DK_GENERIC, 4, 12, 64, 3, 0, 0, 0},
+};
+
+struct DecodePass {
+    int variant;
+    int b0, cols, next;   // first column, live columns, first column of the following pass
+    int halves;           // column-block groups per tile (DecodeArgs::halves)
+    size_t lds;           // dynamic LDS bytes
+    int grid;             // workgroups
+};
+
+// One pass of fr_launch_decode starting at column b0, under the current knobs, on a part of `cus` compute units.
+// FR_ERR_UNSUPPORTED when the basis does not fit the LDS image of a 64-column pass.
+int decode_plan_pass(int B, int b0, int N, int n_shape, int n_exp, int cus, DecodePass* p) {
+    using namespace fr;
+    const size_t tiles = (size_t)tiles_of(N);
+    const size_t G = (size_t)groups_of(n_shape) + groups_of(n_exp);
+    const size_t lds = G * KGROUP * 16 * sizeof(float4) + 64 * 12 * sizeof(float) + 64 * 3 * 2 * sizeof(double);
+    if (lds > 160 * 1024) return FR_ERR_UNSUPPORTED;
+    const bool loop_env = opt(OPT_DECODE_IMPL) == 1;
+    const bool wide_off = opt(OPT_DECODE_WIDE) == 0;
+    const int nbw_env = opt(OPT_DECODE_NBW), waves_env = opt(OPT_DECODE_WAVES);
+    const int nt_opt = opt(OPT_DECODE_NT);
+    const bool ring_shape = !loop_env && groups_of(n_shape) == 13 && groups_of(n_exp) == 2;
+    // 128 columns per pass (64-column items on 12 waves) when more than 64 remain: the basis is streamed once per 128
+    // faces instead of once per 64 (102 vs 110 us at B = 128; FR_DECODE_WIDE=0 turns it off)
+    const size_t lds_wide = G * KGROUP * 32 * sizeof(float4) + 128 * 12 * sizeof(float) + 128 * 3 * 2 * sizeof(double);
+    p->b0 = b0;
+    if (ring_shape && !wide_off && B - b0 > MAXB && lds_wide <= 160 * 1024) {
+        p->variant = V_RING_WIDE;
+        p->halves = 2;  // two 64-column items per tile (32-column items on 16 waves measured the same)
+        p->lds = lds_wide;
+        p->cols = min(B - b0, 2 * MAXB);
+        p->next = b0 + 2 * MAXB;
+    } else {
+        const int nbt = (min(B - b0, MAXB) + 15) / 16;  // 16-column blocks in this pass (1..4)
+        int nbw = nbt == 1 ? 1 : 2;                     // column blocks per work item
+        if (nbw_env == 4 && nbt > 2) nbw = 4;
+        if (nbw_env == 1) nbw = 1;                      // quarter-tile items: 13,304 at B = 64 (12.99 per SIMD)
+        p->halves = (nbt + nbw - 1) / nbw;              // (3 for FR_DECODE_NBW=1 at 33-48 columns: the sixteenth wave idles)
+        p->lds = lds;
+        p->cols = min(B - b0, MAXB);
+        p->next = b0 + MAXB;
+        // the model's own basis shape (199 + 29 coefficients = 13 + 2 groups) takes the fully unrolled ring schedule
+        const bool ring = ring_shape && nbw <= 2;
+        if (ring && nbw == 1) p->variant = V_RING_NBW1;
+        else if (ring && waves_env == 8) p->variant = V_RING_WAVES8;
+        else if (ring && (nt_opt == 0 || (nt_opt < 0 && B - b0 < MAXB)))
+            // default cache policy for the basis stream of a pass below 64 faces: its working set (153 MB of basis + 3.7 MB of
+            // vertices, records and planes per face) leaves the basis a share of the 256 MiB Infinity Cache worth having --
+            // one batch at a time +4.1 % at 32 faces and +2.0 % at 48, two in flight +3.1 % at 48, nothing either way at 16
+            // (profiles/round6_probes/r6a); at 64 faces the non-temporal hint below wins (r2f, r5m)
+            p->variant = V_RING_TEMPORAL;
+        else if (ring && opt(OPT_DECODE_STORE) == 1) p->variant = V_RING_TR;  // A/B knob: transposed accumulators
+        else if (ring)
+            // the basis stream carries the non-temporal hint: it is read once per launch, and keeping its 153 MB out of
+            // the way leaves the L2 / Infinity Cache to the vertices and hit records the render kernels re-read (measured
+            // in the pipeline: decode +2 us, emit -1.5 us, resolve -5 us per 64-face step)
+            p->variant = V_RING_NT;
+        else p->variant = nbw == 1 ? V_GENERIC_1 : nbw == 2 ? V_GENERIC_2 : V_GENERIC_4;
+    }
+    const int slots = kDecodeVariants[p->variant].waves / p->halves;
+    p->grid = (int)min((long long)cus, (long long)(tiles + slots - 1) / slots);
+    return FR_OK;
+}
+
+template <int V>
+int launch_variant(const fr::DecodeArgs& a, size_t lds, int grid, hipStream_t stream) {
+    constexpr DecodeVariant v = kDecodeVariants[V];
+    if constexpr (v.kernel == DK_RING)
+        return launch_decode_ring<13, 2, 8, v.nbw, v.waves, v.mb, v.wpe, v.nt != 0, v.prio != 0, v.tr != 0>(a, lds, grid, stream);
+    else return launch_decode_nbw<v.nbw, v.waves>(a, lds, grid, stream);
+}
+}  // namespace
 
 int fr_launch_decode(const float* params, const void* packed, const float* R_override, int B, int N, int n_shape,
                      int n_exp, float im_size, float* vertex_proj, int pitch, hipStream_t stream) {
@@ -599,8 +695,6 @@ int fr_launch_decode(const float* params, const void* packed, const float* R_ove
     if (B == 0 || N == 0) return FR_OK;
     size_t tiles = (size_t)tiles_of(N);
     size_t G = (size_t)groups_of(n_shape) + groups_of(n_exp);
-    size_t lds = G * KGROUP * 16 * sizeof(float4) + 64 * 12 * sizeof(float) + 64 * 3 * 2 * sizeof(double);
-    if (lds > 160 * 1024) return FR_ERR_UNSUPPORTED;
     DecodeArgs a;
     a.params = params;
     a.A = reinterpret_cast<const float4*>(packed);
@@ -611,52 +705,57 @@ int fr_launch_decode(const float* params, const void* packed, const float* R_ove
     a.im_size = im_size;
     a.pitch = pitch;
     const int cus = fr_device_cu_count();
-    const bool loop_env = opt(OPT_DECODE_IMPL) == 1;
-    const bool wide_off = opt(OPT_DECODE_WIDE) == 0;
-    const int nbw_env = opt(OPT_DECODE_NBW), waves_env = opt(OPT_DECODE_WAVES);
-    const int nt_opt = opt(OPT_DECODE_NT);
-    const bool ring_shape = !loop_env && groups_of(n_shape) == 13 && groups_of(n_exp) == 2;
-    // 128 columns per pass (64-column items on 12 waves) when more than 64 remain: the basis is streamed once per 128
-    // faces instead of once per 64 (102 vs 110 us at B = 128; FR_DECODE_WIDE=0 turns it off)
-    const size_t lds_wide = G * KGROUP * 32 * sizeof(float4) + 128 * 12 * sizeof(float) + 128 * 3 * 2 * sizeof(double);
     for (int b0 = 0; b0 < B;) {
-        a.b0 = b0;
-        if (ring_shape && !wide_off && B - b0 > MAXB && lds_wide <= 160 * 1024) {
-            a.halves = 2;  // two 64-column items per tile (32-column items on 16 waves measured the same)
-            int rc = launch_decode_ring<13, 2, 8, 4, 12, 128>(a, lds_wide, cus, tiles, stream);
-            if (rc != FR_OK) return rc;
-            b0 += 2 * MAXB;
-            continue;
-        }
-        const int nbt = (min(B - b0, MAXB) + 15) / 16;  // 16-column blocks in this pass (1..4)
-        int nbw = nbt == 1 ? 1 : 2;                     // column blocks per work item
-        if (nbw_env == 4 && nbt > 2) nbw = 4;
-        if (nbw_env == 1) nbw = 1;                      // quarter-tile items: 13,304 at B = 64 (12.99 per SIMD)
-        a.halves = (nbt + nbw - 1) / nbw;
-        // the model's own basis shape (199 + 29 coefficients = 13 + 2 groups) takes the fully unrolled ring schedule
-        const bool ring = ring_shape && nbw <= 2;
-        int rc;
-        if (ring && nbw == 1) rc = launch_decode_ring<13, 2, 8, 1, 16, 64, 4, true>(a, lds, cus, tiles, stream);
-        else if (ring && waves_env == 8) rc = launch_decode_ring<13, 2, 8, 2, 8, 64, 4>(a, lds, cus, tiles, stream);
-        else if (ring && (nt_opt == 0 || (nt_opt < 0 && B - b0 < MAXB)))
-            // default cache policy for the basis stream of a pass below 64 faces: its working set (153 MB of basis + 3.7 MB of
-            // vertices, records and planes per face) leaves the basis a share of the 256 MiB Infinity Cache worth having --
-            // one batch at a time +4.1 % at 32 faces and +2.0 % at 48, two in flight +3.1 % at 48, nothing either way at 16
-            // (profiles/round6_probes/r6a); at 64 faces the non-temporal hint below wins (r2f, r5m)
-            rc = launch_decode_ring<13, 2, 8, 2, 16, 64, 4, false, true>(a, lds, cus, tiles, stream);
-        else if (ring && opt(OPT_DECODE_STORE) == 1)
-            rc = launch_decode_ring<13, 2, 8, 2, 16, 64, 4, true, true, true>(a, lds, cus, tiles, stream);  // A/B knob: transposed accumulators
-        else if (ring)
-            // the basis stream carries the non-temporal hint: it is read once per launch, and keeping its 153 MB out of
-            // the way leaves the L2 / Infinity Cache to the vertices and hit records the render kernels re-read (measured
-            // in the pipeline: decode +2 us, emit -1.5 us, resolve -5 us per 64-face step)
-            rc = launch_decode_ring<13, 2, 8, 2, 16, 64, 4, true, true>(a, lds, cus, tiles, stream);
-        else
-            rc = nbw == 1   ? launch_decode_nbw<1, 16>(a, lds, cus, tiles, stream)
-                 : nbw == 2 ? launch_decode_nbw<2, 16>(a, lds, cus, tiles, stream)
-                            : launch_decode_nbw<4, 12>(a, lds, cus, tiles, stream);
+        DecodePass p;
+        int rc = decode_plan_pass(B, b0, N, n_shape, n_exp, cus, &p);
         if (rc != FR_OK) return rc;
-        b0 += MAXB;
+        a.b0 = b0;
+        a.halves = p.halves;
+        switch (p.variant) {
+            case V_RING_WIDE: rc = launch_variant<V_RING_WIDE>(a, p.lds, p.grid, stream); break;
+            case V_RING_NBW1: rc = launch_variant<V_RING_NBW1>(a, p.lds, p.grid, stream); break;
+            case V_RING_WAVES8: rc = launch_variant<V_RING_WAVES8>(a, p.lds, p.grid, stream); break;
+            case V_RING_TEMPORAL: rc = launch_variant<V_RING_TEMPORAL>(a, p.lds, p.grid, stream); break;
+            case V_RING_TR: rc = launch_variant<V_RING_TR>(a, p.lds, p.grid, stream); break;
+            case V_RING_NT: rc = launch_variant<V_RING_NT>(a, p.lds, p.grid, stream); break;
+            case V_GENERIC_1: rc = launch_variant<V_GENERIC_1>(a, p.lds, p.grid, stream); break;
+            case V_GENERIC_2: rc = launch_variant<V_GENERIC_2>(a, p.lds, p.grid, stream); break;
+            default: rc = launch_variant<V_GENERIC_4>(a, p.lds, p.grid, stream); break;
+        }
+        if (rc != FR_OK) return rc;
+        b0 = p.next;
     }
+    return FR_OK;
+}
+
+// test hooks (include/fr_hotpath.h): the launch decision and the tile walk, without a GPU
+extern "C" int fr_debug_decode_geom(int B, int N, int n_shape, int n_exp, int cus, int* out) {
+    if (!out) return FR_ERR_INVALID_ARG;
+    out[0] = 0;
+    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0 || cus < 1) return FR_ERR_INVALID_ARG;
+    if (B == 0 || N == 0) return FR_OK;
+    int n = 0;
+    for (int b0 = 0; b0 < B;) {
+        DecodePass p;
+        const int rc = decode_plan_pass(B, b0, N, n_shape, n_exp, cus, &p);
+        if (rc != FR_OK) return rc;
+        const DecodeVariant& v = kDecodeVariants[p.variant];
+        int* o = out + 1 + 12 * n++;
+        o[0] = p.b0; o[1] = p.cols; o[2] = v.kernel; o[3] = v.nbw; o[4] = v.waves; o[5] = v.mb; o[6] = p.halves;
+        o[7] = v.nt; o[8] = v.prio; o[9] = v.tr; o[10] = (int)p.lds; o[11] = p.grid;
+        b0 = p.next;
+    }
+    out[0] = n;
+    return FR_OK;
+}
+
+extern "C" int fr_debug_decode_walk(int tiles, int waves, int halves, int grid, int* visits) {
+    if (tiles < 0 || waves < 1 || halves < 1 || halves > waves || grid < 1 || (!visits && tiles > 0)) return FR_ERR_INVALID_ARG;
+    for (long long i = 0; i < (long long)tiles * halves; i++) visits[i] = 0;
+    for (int b = 0; b < grid; b++)
+        for (int wave = 0; wave < waves; wave++) {
+            const fr::WaveWork w = fr::wave_work(wave, waves, halves, b, grid);
+            for (long long tile = w.first; tile < tiles; tile += w.stride) visits[tile * halves + w.hf]++;
+        }
     return FR_OK;
 }

@@ -56,15 +56,39 @@ __device__ __forceinline__ void rotation_from_sincos(double sp, double cp, doubl
 struct TileWalk {
     int first, stride;
 };
-__device__ __forceinline__ TileWalk tile_walk(int slot, int slots, int b, int grid) {
+__host__ __device__ __forceinline__ TileWalk tile_walk(int slot, int slots, int b, int grid) {
     const int pb = (grid & 7) == 0 ? (b & 7) * (grid >> 3) + (b >> 3) : b;
     TileWalk w;
-    if (slots & 1) {  // odd slot count (not used by the launchers): plain round-robin over tiles
+    if (slots & 1) {  // odd slot count (FR_DECODE_NBW=1 with 33-48 columns: 16 waves / 3 = 5 slots): plain round-robin over tiles
         w.first = slot * grid + pb;
         w.stride = slots * grid;
     } else {
         w.first = 2 * ((slot >> 1) * grid + pb) + (slot & 1);
         w.stride = slots * grid;  // = 2 * (slots / 2) * grid
+    }
+    return w;
+}
+
+// What one wave of a decode workgroup works on: the items (tile, hf) for tile = first, first + stride, ... < tiles.  `waves`
+// need not be a multiple of `halves` (16 waves, 3 halves): the waves beyond slots * halves are SURPLUS and take no work
+// (first past every tile) -- handed to tile_walk with slot = slots they would repeat slot 0's second tile.  The kernels and
+// the host-side fr_debug_decode_walk both read the distribution from here.
+constexpr int NO_TILE = 0x7fffffff;
+struct WaveWork {
+    int hf, first, stride;
+};
+__host__ __device__ __forceinline__ WaveWork wave_work(int wave, int waves, int halves, int b, int grid) {
+    const int slots = waves / halves;
+    const int slot = wave / halves;
+    WaveWork w;
+    w.hf = wave - slot * halves;
+    if (slot >= slots) {
+        w.first = NO_TILE;
+        w.stride = 1;
+    } else {
+        const TileWalk tw = tile_walk(slot, slots, b, grid);
+        w.first = tw.first;
+        w.stride = tw.stride;
     }
     return w;
 }

@@ -176,7 +176,12 @@ int fr_decode_pack_basis(const float* mu, const float* pc_shape, const float* pc
  * Numerical definition: the reference evaluates S = pc_shape.alpha and E = pc_exp.beta with two fp32
  * tf.matmuls whose summation order is unspecified (network.py:153-156).  fr_decode_3dmm's written definition:
  *   S, E = k-ordered fmaf chains from +0, v = (mu + S) + E  (the f32-input MFMA; the reference's own arithmetic type),
- * restated on the CPU in oracle/fr_oracle.c; the kernel is held to it bit for bit. */
+ * restated on the CPU in oracle/fr_oracle.c; the kernel is held to it bit for bit, at every schedule the launcher can choose
+ * (FR_DECODE_*, every batch boundary, every grid size) and over all of fp32: subnormal parameters, products and sums are kept
+ * (never flushed), a chain may overflow to Inf, a non-finite parameter or pose scalar gives what IEEE arithmetic gives (NaN
+ * compares equal to NaN of any sign / payload), and the SIGN of a zero is part of the result -- a chain whose products all
+ * underflow ends at -0 when its last product is negative, which is why the packed image pads the basis with -0.0
+ * (tests/test_decode_forward_edges_gpu.py).  With n_shape = n_exp = 0 the result is the pose applied to mu. */
 int fr_decode_3dmm(const float* params, const void* packed_basis, const float* R_override, int B, int N,
                    int n_shape, int n_exp, float im_size, float* vertex_proj, void* hip_stream);
 
@@ -524,6 +529,24 @@ void fr_debug_render_geom(int B, int ntri, int H, int W, int rows_override, int*
  * reference-layout GEMM workgroup, GEMM workgroups, prepass workgroups}.  Used by tests/test_decode_backward_bounds_gpu.py to
  * derive its rounding-error bounds and by tests/test_capi_cpu.py. */
 void fr_debug_decode_bwd_geom(int nbatch, int N, int n_shape, int n_exp, int* out);
+
+/* The decode-forward launch decision under the current FR_DECODE_* knobs on a part of `cus` compute units (no GPU needed; the
+ * launcher of fr_decode_3dmm calls the same function, with the device's CU count, and takes its kernel template arguments from
+ * the table this reports from): out[0] = passes, then 12 ints per pass = {first column, live columns, kernel (0 = generic
+ * decode_kernel, 1 = ring schedule of the 13 + 2 group shape), NBW (16-column blocks per work item), waves per workgroup, MB
+ * (columns the pass's LDS image holds: 64 or 128), halves (items per tile), NT (non-temporal basis stream), PRIO (ranked waves),
+ * TR (transposed accumulators), dynamic LDS bytes, workgroups}.  `out` must hold 1 + 12 * ceil(B / 64) ints.  Returns FR_OK
+ * (out[0] = 0 for B = 0 or N = 0), FR_ERR_INVALID_ARG (a negative size, cus < 1, NULL), or FR_ERR_UNSUPPORTED exactly where
+ * fr_decode_3dmm does (a basis whose 64-column LDS image exceeds 160 KiB).  Used by tests/test_decode_geom_cpu.py and by
+ * tests/test_decode_forward_edges_gpu.py to pick shapes that reach a geometry. */
+int fr_debug_decode_geom(int B, int N, int n_shape, int n_exp, int cus, int* out);
+
+/* The decode kernels' work distribution, evaluated on the host through the function the kernels call (wave_work / tile_walk of
+ * csrc/fr_decode_shared.h): visits[tile * halves + half] = how many waves of a launch of `grid` workgroups of `waves` waves take
+ * the item (tile, half), for tile < tiles.  Every entry is 1 for every geometry fr_debug_decode_geom can return: waves / halves
+ * tiles are in work per workgroup, and when halves does not divide waves (FR_DECODE_NBW=1 with 33-48 columns: 3 halves on 16
+ * waves) the surplus waves take no work.  FR_ERR_INVALID_ARG for tiles < 0, halves < 1, halves > waves or grid < 1. */
+int fr_debug_decode_walk(int tiles, int waves, int halves, int grid, int* visits);
 
 /* The pose-moment launch geometry (no GPU needed; a function of N alone -- B is accepted and ignored): out[4] = {chunk length in
  * vertices, chunks per face, threads per workgroup, longest chain of rounded fp32 additions behind one element of a chunk

@@ -36,3 +36,17 @@ def assert_render_equal(got, want, what=""):
             bad = np.argwhere((g != w) & ~(np.isnan(g) & np.isnan(w)))
             raise AssertionError("%s %s: %d mismatches, first at %s: got %r want %r" %
                                  (what, n, len(bad), bad[0], g[tuple(bad[0])], w[tuple(bad[0])]))
+
+
+def assert_bits_equal(got, want, what=""):
+    """fp32 arrays equal by BIT PATTERN -- -0.0 is not +0.0, which `==` and np.testing.assert_array_equal call equal -- except
+    that a NaN equals a NaN whatever its sign / payload (the IEEE default NaN differs by platform: assert_render_equal)."""
+    got = np.ascontiguousarray(got, np.float32)
+    want = np.ascontiguousarray(want, np.float32)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = (got.view(np.uint32) != want.view(np.uint32)) & ~(np.isnan(got) & np.isnan(want))
+    if bad.any():
+        idx = np.argwhere(bad)
+        i = tuple(idx[0])
+        raise AssertionError("%s: %d of %d elements differ in their bits, first at %s: got %r (0x%08x) want %r (0x%08x)" % (
+            what, len(idx), got.size, i, got[i], got.view(np.uint32)[i], want[i], want.view(np.uint32)[i]))

@@ -125,7 +125,7 @@ def test_full_size_batch64(oracle, full_assets, synth):
 
 
 @pytest.mark.parametrize("knobs", [{"FR_DECODE_NT": 0}, {"FR_DECODE_NT": 1}, {"FR_DECODE_NBW": 1}, {"FR_DECODE_WAVES": 8}, {"FR_DECODE_IMPL": 1},
-                                   {"FR_DECODE_WIDE": 0}])
+                                   {"FR_DECODE_WIDE": 0}, {"FR_DECODE_STORE": 1}, {"FR_DECODE_NBW": 4}])
 def test_launcher_knobs_do_not_change_a_bit(oracle, synth, knobs):
     """The decode launcher's A/B knobs (fr_set_option; the environment is read once per process) select other schedules of
     the same arithmetic: the model's basis shape at B = 70 (one 128-column pass, or 64 + 6 with FR_DECODE_WIDE=0) stays
