@@ -15,7 +15,8 @@ import types
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG_DIR, "csrc")
 LIB_PATH = os.path.join(_PKG_DIR, "libfr_hotpath.so")
-SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_nbwd.hip", "fr_sfs.hip"]
+SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_nbwd.hip", "fr_render_tbwd.hip",
+           "fr_sfs.hip"]
 HEADERS = [os.path.join(_CSRC, "fr_common.h"), os.path.join(_CSRC, "fr_decode_shared.h"), os.path.join(_CSRC, "fr_sfs_pinv.h"),
            os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -202,6 +203,14 @@ def _bind(L):
     L.fr_render_normal_backward.restype = _i
     L.fr_debug_render_normal_bwd_geom.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
     L.fr_debug_render_normal_bwd_geom.restype = None
+    L.fr_render_texture_backward_workspace_bytes.argtypes = [_i] * 5
+    L.fr_render_texture_backward_workspace_bytes.restype = ctypes.c_size_t
+    L.fr_render_texture_backward.argtypes = [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
+    L.fr_render_texture_backward.restype = _i
+    L.fr_debug_render_texture_bwd_geom.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
+    L.fr_debug_render_texture_bwd_geom.restype = None
+    L.fr_sfs_intensity_backward_tex.argtypes = [_vp] * 6 + [ctypes.c_size_t, _i, _i, _i, _vp, _vp, _vp, _vp]
+    L.fr_sfs_intensity_backward_tex.restype = _i
     L.fr_sfs_state_bytes.argtypes = [_i, _i]
     L.fr_sfs_state_bytes.restype = ctypes.c_size_t
     L.fr_sfs_intensity_forward.argtypes = [_vp] * 5 + [_i, _i, _i, ctypes.c_double, _vp, _vp, ctypes.c_size_t, _vp]
@@ -250,7 +259,9 @@ EXPORTS = ["fr_version", "fr_strerror", "fr_render_depth_workspace_bytes", "fr_r
            "fr_decode_render_backward_pose_workspace_bytes", "fr_decode_render_backward_pose", "fr_debug_pose_bwd_geom",
            "fr_render_normal_backward_workspace_bytes", "fr_render_normal_backward", "fr_debug_render_normal_bwd_geom",
            "fr_sfs_state_bytes", "fr_sfs_intensity_forward", "fr_sfs_intensity_backward", "fr_debug_sfs_geom",
-           "fr_debug_sfs_pinv", "fr_debug_decode_geom", "fr_debug_decode_walk"]
+           "fr_debug_sfs_pinv", "fr_debug_decode_geom", "fr_debug_decode_walk",
+           "fr_render_texture_backward_workspace_bytes", "fr_render_texture_backward", "fr_debug_render_texture_bwd_geom",
+           "fr_sfs_intensity_backward_tex"]
 
 
 def lib():

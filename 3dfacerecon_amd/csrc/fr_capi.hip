@@ -533,4 +533,29 @@ int fr_render_normal_backward(const float* normal_grad, int grad_stride, const f
                                             ntri, H, W, mode, accumulate, workspace, (hipStream_t)hip_stream);
 }
 
+// ---- texture gradients ----------------------------------------------------------------------------------------------------------
+size_t fr_render_texture_backward_workspace_bytes(int B, int nver, int H, int W, int tex_batch) {
+    if (B > 0 && tex_batch != 1 && tex_batch != B) return 0;
+    return fr_render_texture_backward_workspace_impl(B, nver, H, W, tex_batch);
+}
+
+int fr_render_texture_backward(const float* tex_grad, int grad_stride, const float* tri, const float* tri_ind,
+                               float* texture_grad, int B, int nver, int ntri, int H, int W, int tex_batch, int accumulate,
+                               void* workspace, size_t ws_bytes, void* hip_stream) {
+    if (B < 0 || nver < 0 || ntri < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
+    if (B > 0 && tex_batch != 1 && tex_batch != B) return FR_ERR_INVALID_ARG;
+    if ((accumulate != 0 && accumulate != 1) || grad_stride < 3) return FR_ERR_INVALID_ARG;
+    if (B == 0 || nver == 0) return FR_OK;   // an empty batch or an empty texture_grad: nothing to write
+    if (!texture_grad) return FR_ERR_INVALID_ARG;
+    const bool work = (size_t)H * W > 0 && ntri > 0;
+    if (work && (!tex_grad || !tri || !tri_ind)) return FR_ERR_INVALID_ARG;
+    if (ntri >= (1 << 24)) return FR_ERR_UNSUPPORTED;   // float-stored ids stop being exact
+    if ((long long)H * W > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;   // (a shape no workspace serves: answered before the workspace)
+    if (work && (!workspace || ((uintptr_t)workspace & 15) ||
+                 ws_bytes < fr_render_texture_backward_workspace_impl(B, nver, H, W, tex_batch)))
+        return FR_ERR_WORKSPACE;
+    return fr_launch_render_texture_backward(tex_grad, grad_stride, tri, tri_ind, texture_grad, B, nver, ntri, H, W, tex_batch,
+                                             accumulate, workspace, (hipStream_t)hip_stream);
+}
+
 }  // extern "C"

@@ -45,6 +45,21 @@ __device__ __forceinline__ unsigned long long bg_key() {
     return ((unsigned long long)f32_ord(bg_depth()) << 32) | 0xFFFFFFFFull;
 }
 
+// x / 3.0f, correctly rounded like the division the reference performs (render_depth_op.cc:217, 223): for |x| in
+// [2^-100, 2^100] the quotient comes from q0 = x*(1/3), r = fma(-3, q0, x) (exact), q = fma(r, 1/3, q0) -- three
+// instructions instead of the ~12 of the IEEE division sequence (bit-identical to x / 3.0f on every finite x of that
+// range: tests/test_render_gpu.py sweeps all 2^32 bit patterns); anything else takes the division.
+__device__ __forceinline__ float div3(float x) {
+    const float ax = __builtin_fabsf(x);
+    if (ax >= 7.888609052e-31f && ax <= 1.267650600e30f) {
+        const float y = 0.3333333432674407958984375f;
+        const float q0 = x * y;
+        const float r = __builtin_fmaf(-3.0f, q0, x);
+        return __builtin_fmaf(r, y, q0);
+    }
+    return x / 3.0f;
+}
+
 // Barycentric inside test, op flavour (u+v < 1), fp64, operation order of render_depth_op.cc:90-121.
 struct TriSetup {
     double x1, y1;
@@ -183,3 +198,7 @@ size_t fr_render_normal_backward_workspace_impl(int B, int H, int W);
 int fr_launch_render_normal_backward(const float* normal_grad, int grad_stride, const float* vertex, int vertex_pitch,
                                      const float* tri, const float* tri_ind, float* vertex_grad, int B, int nver, int ntri,
                                      int H, int W, int mode, int accumulate, void* workspace, hipStream_t stream);
+size_t fr_render_texture_backward_workspace_impl(int B, int nver, int H, int W, int tex_batch);
+int fr_launch_render_texture_backward(const float* tex_grad, int grad_stride, const float* tri, const float* tri_ind,
+                                      float* texture_grad, int B, int nver, int ntri, int H, int W, int tex_batch, int accumulate,
+                                      void* workspace, hipStream_t stream);

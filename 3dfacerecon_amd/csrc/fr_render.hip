@@ -508,21 +508,6 @@ __global__ __launch_bounds__(256) void pack_tri_kernel(const float* __restrict__
 __device__ __forceinline__ float ld_boff(const float* __restrict__ base, int boff) {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (size_t)(uint32_t)boff);
 }
-// x / 3.0f, correctly rounded like the division the reference performs (render_depth_op.cc:217, 223): for |x| in
-// [2^-100, 2^100] the quotient comes from q0 = x*(1/3), r = fma(-3, q0, x) (exact), q = fma(r, 1/3, q0) -- three
-// instructions instead of the ~12 of the IEEE division sequence (bit-identical to x / 3.0f on every finite x of that
-// range: tests/test_render_gpu.py sweeps all 2^32 bit patterns); anything else takes the division.
-__device__ __forceinline__ float div3(float x) {
-    const float ax = __builtin_fabsf(x);
-    if (ax >= 7.888609052e-31f && ax <= 1.267650600e30f) {
-        const float y = 0.3333333432674407958984375f;
-        const float q0 = x * y;
-        const float r = __builtin_fmaf(-3.0f, q0, x);
-        return __builtin_fmaf(r, y, q0);
-    }
-    return x / 3.0f;
-}
-
 // Inclusive prefix sum over the 64 lanes of a wave in six v_add_u32_dpp (Hillis-Steele inside each row of 16 lanes, then the
 // row totals passed on with row_bcast:15 / row_bcast:31) -- the __shfl_up form is six DEPENDENT trips through the LDS
 // crossbar (ds_bpermute), several hundred cycles on the critical path of every workgroup of both kernels.

@@ -39,6 +39,7 @@ struct SfsArgs {
     float* intensity;         // [B,npix]     (forward)
     float* gn;                // [B,npix,3]   (backward, may be null)
     float* gnn;               // [B,npix,3]   (backward, may be null)
+    float* gan;               // [B,npix]     (backward, may be null): the gradient of abedo_new
     double* state;            // [10,npix]
     double rcond;
     int B, npix, S, chunk;
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(SFS_PX* FR_SFS_SLICES_MAX) void sfs_backward_kernel
     }
     if (!active) return;
     double lx = 0.0, ly = 0.0, lz = 0.0;
-    if (a.gnn) {
+    if (a.gnn || a.gan) {
         const double* l = a.state + 6 * npix + p;
         lx = l[0]; ly = l[npix]; lz = l[2 * npix];
     }
@@ -169,6 +170,11 @@ __global__ __launch_bounds__(SFS_PX* FR_SFS_SLICES_MAX) void sfs_backward_kernel
             const double ga = (double)a.g[i] * (double)a.abedo_new[i];
             float* o = a.gnn + i * 3;
             o[0] = (float)(ga * lx); o[1] = (float)(ga * ly); o[2] = (float)(ga * lz);
+        }
+        if (a.gan) {   // d intensity / d abedo_new: the forward's own d = l . n'
+            const float* n = a.normal_new + i * 3;
+            const double d = (lx * (double)n[0] + ly * (double)n[1]) + lz * (double)n[2];
+            a.gan[i] = (float)((double)a.g[i] * d);
         }
     }
 }
@@ -240,13 +246,13 @@ int fr_sfs_intensity_forward(const float* abedo, const float* normal, const floa
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }
 
-int fr_sfs_intensity_backward(const float* grad_intensity, const float* abedo, const float* im_gray, const float* abedo_new,
-                              const float* normal_new, const void* state, size_t state_bytes, int B, int H, int W,
-                              float* grad_normal, float* grad_normal_new, void* hip_stream) {
+int fr_sfs_intensity_backward_tex(const float* grad_intensity, const float* abedo, const float* im_gray, const float* abedo_new,
+                                  const float* normal_new, const void* state, size_t state_bytes, int B, int H, int W,
+                                  float* grad_normal, float* grad_normal_new, float* grad_abedo_new, void* hip_stream) {
     using namespace fr;
     if (B < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
     if (sfs_shape_empty(B, H, W)) return FR_OK;
-    if (!grad_normal && !grad_normal_new) return FR_ERR_INVALID_ARG;
+    if (!grad_normal && !grad_normal_new && !grad_abedo_new) return FR_ERR_INVALID_ARG;
     if (!grad_intensity || !abedo || !im_gray || !abedo_new || !normal_new) return FR_ERR_INVALID_ARG;
     if (!state || ((uintptr_t)state & 15) || state_bytes < fr_sfs_state_bytes(H, W)) return FR_ERR_WORKSPACE;
     const long long npix = (long long)H * W;
@@ -254,12 +260,19 @@ int fr_sfs_intensity_backward(const float* grad_intensity, const float* abedo, c
     const SfsGeom geo = sfs_geom(B, npix);
     SfsArgs a{};
     a.g = grad_intensity; a.abedo = abedo; a.im_gray = im_gray; a.abedo_new = abedo_new; a.normal_new = normal_new;
-    a.gn = grad_normal; a.gnn = grad_normal_new;
+    a.gn = grad_normal; a.gnn = grad_normal_new; a.gan = grad_abedo_new;
     a.state = const_cast<double*>(reinterpret_cast<const double*>(state));
     a.B = B; a.npix = (int)npix; a.S = geo.slices; a.chunk = geo.chunk;
     hipLaunchKernelGGL(sfs_backward_kernel, dim3((unsigned)geo.blocks), dim3(SFS_PX * geo.slices), geo.lds_bwd,
                        (hipStream_t)hip_stream, a);
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
+
+int fr_sfs_intensity_backward(const float* grad_intensity, const float* abedo, const float* im_gray, const float* abedo_new,
+                              const float* normal_new, const void* state, size_t state_bytes, int B, int H, int W,
+                              float* grad_normal, float* grad_normal_new, void* hip_stream) {
+    return fr_sfs_intensity_backward_tex(grad_intensity, abedo, im_gray, abedo_new, normal_new, state, state_bytes, B, H, W,
+                                         grad_normal, grad_normal_new, nullptr, hip_stream);
 }
 
 }  // extern "C"

@@ -193,9 +193,12 @@ class FaceReconModel(nn.Module):
     'vertices_proj' (what the SfS loss reads) then comes from a plain vertices_transform of its own, and only when asked for
     (forward(..., with_vertices=True), the default).
     pose_grad=True: every decode of the module also returns the pose-angle gradients (default: 0, as in the reference).
-    normal_grad=True: the CoarseNet iterations' normal channels carry gradients (CoarseNet, normal_grad; default: none)."""
+    normal_grad=True: the CoarseNet iterations' normal channels carry gradients (CoarseNet, normal_grad; default: none).
+    learn_tex=True: the albedo coefficients face_net.param_tex become an nn.Parameter of this module (an optimiser and DDP see
+    it) and face_net.param_tex points at it; get_loss(sfs_tex_grad=True) gives it a gradient.  Default: a constant tensor, as the
+    reference's frozen param_tex (network.py:447-448)."""
 
-    def __init__(self, face_net, nIter=4, fine=True, fused_step=False, pose_grad=False, normal_grad=False):
+    def __init__(self, face_net, nIter=4, fine=True, fused_step=False, pose_grad=False, normal_grad=False, learn_tex=False):
         super().__init__()
         self.face_net = face_net
         self.fused_step = bool(fused_step)
@@ -204,6 +207,13 @@ class FaceReconModel(nn.Module):
         self.normal_grad = bool(normal_grad)
         self.coarse = CoarseNet(face_net, nIter=nIter, fused_step=fused_step, pose_grad=pose_grad, normal_grad=normal_grad)
         self.fine = FineNet() if fine else None
+        self.learn_tex = bool(learn_tex)
+        if self.learn_tex:
+            if face_net.param_tex is None:
+                raise ValueError("learn_tex: the asset dict has no texture model (mu_tex / pc_tex / param_tex)")
+            # (already on face_net's device; .to() rewrites a parameter's data in place, so the object face_net holds stays this one)
+            self.param_tex = nn.Parameter(face_net.param_tex.detach().clone())
+            face_net.param_tex = self.param_tex
 
     def forward(self, im_gray, with_depth=True, with_vertices=True):
         fn = self.face_net

@@ -75,7 +75,7 @@ def _all_gather_batch(t):
 
 
 def spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_image_new, normal_map_new, gather=False, fused=False,
-                                  rcond=1e-15):
+                                  rcond=1e-15, tex_grad=False):
     """The linear-algebra core of get_spherical_harmonics_model (network.py:424-460) on already rendered maps:
     per pixel, lighting l = (Y Y^T)^+ Y (I / (albedo + 1))^T over the batch (Y = [3 x B] normals), then the recovered
     intensity albedo_new * (l^T Y_new).  All inputs [B,H,W,c]; returns [B,H,W,1].
@@ -84,7 +84,12 @@ def spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_image_
     sums in a fixed order, gradients to the two normal maps with the pseudo-inverse held constant -- the same autograd semantics
     as this torch route, whose pinv is detached.  The albedos and im_gray are constants of that call (they are detached here; in
     this model neither has a path to a parameter).  gather=True under a world size above 1 stays on the torch route even with
-    fused=True: the per-pixel sums would have to cross ranks, which the kernel does not do."""
+    fused=True: the per-pixel sums would have to cross ranks, which the kernel does not do.
+    tex_grad=True: on the fused route abedo_image_new is no longer detached and receives its gradient, the lighting held constant
+    (sfs_intensity(abedo_grad=True)); the torch route differentiates abedo_image_new anyway, so the flag changes nothing there."""
+    if fused and tex_grad and not (gather and _world_size() > 1):
+        return _ops().sfs_intensity(abedo_image.detach(), normal_map, im_gray.detach(), abedo_image_new, normal_map_new,
+                                    rcond=rcond, abedo_grad=True)
     if fused and not (gather and _world_size() > 1):
         return _ops().sfs_intensity(abedo_image.detach(), normal_map, im_gray.detach(), abedo_image_new.detach(), normal_map_new,
                                     rcond=rcond)
@@ -100,27 +105,33 @@ def spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_image_
     return intensity.permute(3, 0, 1, 2)
 
 
-def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False, normal_grad=False, fused=False, rcond=1e-15):
+def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False, normal_grad=False, fused=False, rcond=1e-15,
+                                  tex_grad=False):
     """Recovered intensity (B,H,W,1) of the first-order spherical-harmonics shading model (network.py:420-462): two
     more render_depth calls (mean albedo, then mean + pc_tex . param_tex) feed spherical_harmonics_intensity.
     normal_grad=False (default): as the reference, both renders hand autograd constant normal maps, so the term has no gradient
     with respect to any parameter.  normal_grad=True: both renders carry the normal map's gradient to the vertices
-    (render_depth(normal_grad=True)) and the term moves the geometry.  fused / rcond: as spherical_harmonics_intensity."""
+    (render_depth(normal_grad=True)) and the term moves the geometry.  fused / rcond: as spherical_harmonics_intensity.
+    tex_grad=True: the second render, the one of texture_new, carries the albedo image's gradient to the texture
+    (render_depth(texture_grad=True)), hence to face_net.param_tex where that requires grad; the render of the mean texture
+    stays a constant."""
     fn = face_net
     if fn.mu_tex is None or fn.pc_tex is None or fn.param_tex is None:
         raise ValueError("the asset dict has no texture model (mu_tex / pc_tex / param_tex)")
     kw = {"normal_grad": True} if normal_grad else {}
     abedo_image, normal_map = fn.compute_abedo_image(vertices_proj, fn.tri, fn.mu_tex, **kw)   # (B,H,W,1), (B,H,W,3)
     texture_new = fn.mu_tex + (fn.pc_tex @ fn.param_tex).reshape(3, -1)                    # network.py:446-448
-    abedo_new, normal_new = fn.compute_abedo_image(vertices_proj, fn.tri, texture_new, **kw)
+    kw_new = dict(kw, texture_grad=True) if tex_grad else kw
+    abedo_new, normal_new = fn.compute_abedo_image(vertices_proj, fn.tri, texture_new, **kw_new)
     if fused and not normal_grad:
         # the renders' normal maps are constants to autograd in this mode (their node drops the gradient): say so, and the fused
         # node runs no backward at all
         normal_map, normal_new = normal_map.detach(), normal_new.detach()
     if not (fused or rcond != 1e-15):
         return spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_new, normal_new, gather=gather)
+    kw_tex = {"tex_grad": True} if tex_grad else {}
     return spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_new, normal_new, gather=gather, fused=fused,
-                                         rcond=rcond)
+                                         rcond=rcond, **kw_tex)
 
 
 def combine_losses(losses):
@@ -131,11 +142,13 @@ def combine_losses(losses):
 
 
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
-             gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15):
+             gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
     sfs_normal_grad / sfs_fused / sfs_rcond (defaults: off, off, the reference's 1e-15): the normal_grad / fused / rcond of
     get_spherical_harmonics_model.  With them off spherical_harmonics_loss is a reported scalar with no gradient, as in the
-    reference; sfs_normal_grad=True lets it reach the vertices through the two SfS renders."""
+    reference; sfs_normal_grad=True lets it reach the vertices through the two SfS renders.
+    sfs_tex_grad=True (default off): the term also reaches the albedo coefficients face_net.param_tex, where that tensor requires
+    grad (FaceReconModel(learn_tex=True)), through the render of texture_new."""
     fn = face_net
     B = pred_params.shape[0]
     pred = pred_params.reshape(B, fn.ndim)
@@ -146,8 +159,9 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     # rounding of the two products; the difference form needs one pass of the basis instead of two
     g = fn.geometry_product(pred[:, fn.ndim_pose:] - label[:, fn.ndim_pose:])
     losses['geometry_loss'] = (g * g).mean()
+    kw_tex = {"tex_grad": True} if sfs_tex_grad else {}
     intensity_recover = get_spherical_harmonics_model(fn, vertices_proj, im_gray, gather=gather_sfs, normal_grad=sfs_normal_grad,
-                                                      fused=sfs_fused, rcond=sfs_rcond)
+                                                      fused=sfs_fused, rcond=sfs_rcond, **kw_tex)
     losses['spherical_harmonics_loss'] = F.mse_loss(intensity_recover, im_gray)
     losses['fidelity_loss'] = F.mse_loss(pred_depth_map, coarse_depth_map)
     filtered_depth = laplace_transform(pred_depth_map[..., 0])

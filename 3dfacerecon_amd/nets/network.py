@@ -431,16 +431,19 @@ class FaceRecNet:
                 pass
         return self.coarse_net_input(self.vertices_transform(p, R=Rc, pose_grad=pose_grad), im_gray=im_gray)
 
-    def compute_abedo_image(self, vertices, triangles, abedos, im_gray=None, normal_grad=False):
+    def compute_abedo_image(self, vertices, triangles, abedos, im_gray=None, normal_grad=False, texture_grad=False):
         """Albedo (3,N) -> albedo image + normalised normal map through a second render (network.py:394-417).
         normal_grad=True: the normal map carries its gradient to the vertices (render_depth, normal_grad); default: a constant
-        to autograd, as the reference."""
+        to autograd, as the reference.
+        texture_grad=True: the albedo image carries its gradient to `abedos` (render_depth, texture_grad); default: none."""
         ver = vertices.float()
         tri = torch.as_tensor(triangles, dtype=torch.float32, device=ver.device)
         tex = torch.as_tensor(abedos, dtype=torch.float32, device=ver.device)
         B = ver.shape[0]
         image = torch.zeros((B, self.im_size, self.im_size, 3), dtype=torch.float32, device=ver.device)
         kw = {"normal_grad": True} if normal_grad else {}
+        if texture_grad:
+            kw["texture_grad"] = True
         _, tf_abedo, normal, _ = _ops().render_depth(ver=ver, tri=tri, texture=tex, image=image, **kw)
         abedos_image = torch.clamp_min(tf_abedo, 1e-6).mean(dim=-1, keepdim=True)  # (B, H, W, 1)
         flip = normal[..., 2:3] < 0

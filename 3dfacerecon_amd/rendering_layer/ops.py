@@ -7,6 +7,7 @@ Same names and argument meaning as the reference module (rendering_layer/ops.py:
     render_depth(ver, tri, texture, image, **kwargs)
                                    -> (depth [B,H,W,1], texture_image [B,H,W,3], normal [B,H,W,3], tri_ind [B,H,W,1])
     gradient                       flows to `ver` only (d depth / d vertex z); tri, texture, image get None
+                                   (opt-in: normal_grad=True, texture_grad=True -- see render_depth)
 
 Tensors are torch.Tensors on an MI355X instead of tf.Tensors; the op is a torch.autograd.Function calling the
 C ABI of include/fr_hotpath.h through ctypes on torch's current HIP stream.  Like the reference, importing the
@@ -271,6 +272,67 @@ class _RenderDepthNormal(_RenderDepth):
         return vertex_grad, None, None, None
 
 
+def _texture_backward_call(h, g, g_offset, g_stride, tri_c, tri_ind, texture_grad, B, nver, ntri, H, W, tex_batch, accumulate, dev):
+    """fr_render_texture_backward with its workspace (24 bytes per pixel, plus the slabs of a shared texture): the gradient read
+    at `g_offset` floats into `g`, `g_stride` floats between pixels; texture_grad is dense [tex_batch,3,nver]."""
+    L = h.lib()
+    nws = L.fr_render_texture_backward_workspace_bytes(B, nver, H, W, tex_batch)
+    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
+    rc = L.fr_render_texture_backward(ctypes.c_void_p(g.data_ptr() + 4 * g_offset), g_stride, h.ptr(tri_c), h.ptr(tri_ind),
+                                      h.ptr(texture_grad), B, nver, ntri, H, W, tex_batch, accumulate, h.ptr(ws), nws,
+                                      h.stream_ptr(dev))
+    h.check(rc, "fr_render_texture_backward")
+
+
+def _texture_grad_of(ctx, texture_image_grad):
+    """The `texture` gradient of a render_depth node built with texture_grad=True, in the input's own shape ([3,N], [1,3,N] or
+    [B,3,N]); None -- and no launch -- when nothing downstream used tex_img or the texture needs no gradient."""
+    if texture_image_grad is None or not ctx.needs_input_grad[2]:
+        return None
+    h = _host()
+    tri_c, tri_ind = ctx.saved_tensors[:2]
+    B, nver, ntri, H, W = ctx.dims
+    dev = tri_c.device
+    shape = ctx.tex_shape
+    tex_batch = 1 if len(shape) == 2 else int(shape[0])
+    texture_grad = torch.empty((tex_batch, 3, nver), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _texture_backward_call(h, h.require_gpu_f32(texture_image_grad, "texture_image_grad"), 0, 3, tri_c, tri_ind, texture_grad,
+                               B, nver, ntri, H, W, tex_batch, 0, dev)
+    return texture_grad.reshape(shape)
+
+
+class _RenderDepthTex(_RenderDepth):
+    """render_depth(texture_grad=True): the same forward and the same saved tensors (the texture's shape is all the node adds);
+    a gradient arriving at `tex_img` reaches `texture` through fr_render_texture_backward.  The vertex gradient is
+    _RenderDepth's, launched only where `depth` was used."""
+
+    @staticmethod
+    def forward(ctx, ver, tri, texture, image):
+        ctx.tex_shape = tuple(texture.shape)
+        return _RenderDepth._fwd(ctx, ver, tri, texture, image, False)
+
+    @staticmethod
+    def backward(ctx, depth_grad, texture_image_grad, normal_grad, tri_ind_grad):
+        vertex_grad = _RenderDepth.backward(ctx, depth_grad, None, None, None)[0]
+        return vertex_grad, None, _texture_grad_of(ctx, texture_image_grad), None
+
+
+class _RenderDepthNormalTex(_RenderDepthNormal):
+    """render_depth(normal_grad=True, texture_grad=True): _RenderDepthNormal's vertex gradient and _RenderDepthTex's texture
+    gradient from one node."""
+
+    @staticmethod
+    def forward(ctx, ver, tri, texture, image):
+        ctx.tex_shape = tuple(texture.shape)
+        return _RenderDepth._fwd(ctx, ver, tri, texture, image, True)
+
+    @staticmethod
+    def backward(ctx, depth_grad, texture_image_grad, normal_grad, tri_ind_grad):
+        vertex_grad = _RenderDepthNormal.backward(ctx, depth_grad, None, normal_grad, None)[0]
+        return vertex_grad, None, _texture_grad_of(ctx, texture_image_grad), None
+
+
 class _RenderingLayerFused(torch.autograd.Function):
     """render_depth + the post-processing of FaceRecNet.rendering_layer (nets/network.py:185-199) as one kernel pass:
     (ver, tri, texture, im_gray) -> (net_input [B,H,W,7], depth_img [B,H,W,1], depth, tri_ind)."""
@@ -504,8 +566,13 @@ class _SfsIntensity(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond):
+        return _SfsIntensity._fwd(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond, False)
+
+    @staticmethod
+    def _fwd(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond, abedo_grad):   # (abedo_grad: _SfsIntensityTex)
         h = _host()
-        for t, name in ((abedo, "abedo"), (im_gray, "im_gray"), (abedo_new, "abedo_new")):
+        ctx.abedo_grad = bool(abedo_grad)
+        for t, name in ((abedo, "abedo"), (im_gray, "im_gray")) + (() if abedo_grad else ((abedo_new, "abedo_new"),)):
             if isinstance(t, torch.Tensor) and t.requires_grad:
                 raise ValueError("sfs_intensity: %s requires grad, but the albedos and im_gray are constants of this model "
                                  "(detach it)" % name)
@@ -542,25 +609,45 @@ class _SfsIntensity(torch.autograd.Function):
         B, H, W, nst = ctx.dims
         dev = a_c.device
         want_n, want_n2 = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
-        if not (want_n or want_n2):
+        want_a2 = ctx.abedo_grad and ctx.needs_input_grad[3]
+        if not (want_n or want_n2 or want_a2):
             return None, None, None, None, None, None
         g_c = h.require_gpu_f32(g, "grad_intensity")
         gn = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n else None
         gn2 = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n2 else None
+        ga2 = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev) if want_a2 else None
         with torch.cuda.device(dev):
-            rc = h.lib().fr_sfs_intensity_backward(h.ptr(g_c), h.ptr(a_c), h.ptr(i_c), h.ptr(a2_c), h.ptr(n2_c), h.ptr(state), nst,
-                                                   B, H, W, h.ptr(gn), h.ptr(gn2), h.stream_ptr(dev))
+            if want_a2:
+                rc = h.lib().fr_sfs_intensity_backward_tex(h.ptr(g_c), h.ptr(a_c), h.ptr(i_c), h.ptr(a2_c), h.ptr(n2_c),
+                                                           h.ptr(state), nst, B, H, W, h.ptr(gn), h.ptr(gn2), h.ptr(ga2),
+                                                           h.stream_ptr(dev))
+            else:
+                rc = h.lib().fr_sfs_intensity_backward(h.ptr(g_c), h.ptr(a_c), h.ptr(i_c), h.ptr(a2_c), h.ptr(n2_c), h.ptr(state),
+                                                       nst, B, H, W, h.ptr(gn), h.ptr(gn2), h.stream_ptr(dev))
         h.check(rc, "fr_sfs_intensity_backward")
-        return None, gn, None, None, gn2, None
+        return None, gn, None, ga2, gn2, None
 
 
-def sfs_intensity(abedo, normal, im_gray, abedo_new, normal_new, rcond=1e-15):
+class _SfsIntensityTex(_SfsIntensity):
+    """sfs_intensity(abedo_grad=True): the same forward; `abedo_new` may require grad and the backward also returns
+    grad_abedo_new (fr_sfs_intensity_backward_tex).  `abedo` and `im_gray` stay constants."""
+
+    @staticmethod
+    def forward(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond):
+        return _SfsIntensity._fwd(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond, True)
+
+
+def sfs_intensity(abedo, normal, im_gray, abedo_new, normal_new, rcond=1e-15, abedo_grad=False):
     """The shape-from-shading intensity (nets/network.py:424-460) on rendered maps in ONE kernel pass: per pixel the lighting
     l = pinv(sum_b n n^T) sum_b n I / (abedo + 1) over the batch, then abedo_new * (l . normal_new) -> [B,H,W,1].  float64 sums in
     a fixed order (a function of B alone), bit-reproducible; `rcond` is the eigenvalue cutoff of the pseudo-inverse.
     Gradients go to `normal` and `normal_new` only, with the pseudo-inverse held constant (what a detached pinv gives the torch
     route); autograd adds the two when one tensor is passed for both.  An albedo or im_gray that requires grad is refused: they are
-    constants of this model.  The node keeps a state tensor of ten float64 planes (3.2 MB at 200 x 200) for its backward."""
+    constants of this model.  The node keeps a state tensor of ten float64 planes (3.2 MB at 200 x 200) for its backward.
+    abedo_grad=True: `abedo_new` may require grad and receives g * (l . normal_new), the lighting held as the state holds it
+    (fr_sfs_intensity_backward_tex); `abedo` and `im_gray` are still refused.  Same intensity, bit for bit."""
+    if abedo_grad:
+        return _SfsIntensityTex.apply(abedo, normal, im_gray, abedo_new, normal_new, float(rcond))
     return _SfsIntensity.apply(abedo, normal, im_gray, abedo_new, normal_new, float(rcond))
 
 
@@ -576,7 +663,7 @@ def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     return _RenderingLayerFused.apply(ver, tri, texture, im_gray)
 
 
-def render_depth(ver, tri, texture, image, normal_grad=False, **kwargs):
+def render_depth(ver, tri, texture, image, normal_grad=False, texture_grad=False, **kwargs):
     """Forward function of RenderDepth (reference ops.py:78-81).
 
     The first output is the rendered depth, the fourth the triangle index each depth pixel corresponds to.
@@ -586,7 +673,13 @@ def render_depth(ver, tri, texture, image, normal_grad=False, **kwargs):
     normal_grad=True: the third output, `normal`, has one too -- its gradient reaches all three coordinates of the winning
     triangles' vertices (fr_render_normal_backward, raw mode, behind the depth backward; tri_ind held fixed).  Same outputs, bit
     for bit.  The node then keeps the vertex tensor: [B,3,nver] fp32, 41 MB at 64 faces of the full mesh.
+    texture_grad=False (default): as the reference, `texture` gets no gradient.  texture_grad=True: a gradient arriving at the
+    second output, `tex_img`, reaches `texture` in the input's own shape ([3,N], [1,3,N] or [B,3,N]) -- the adjoint of the
+    lookup (t[p1] + t[p2] + t[p3]) / 3 (fr_render_texture_backward; tri_ind held fixed).  Same outputs, bit for bit; the node
+    saves no tensor beyond what it keeps anyway, and no backward is launched for an output nobody used.  Combines with normal_grad.
     """
+    if texture_grad:
+        return (_RenderDepthNormalTex if normal_grad else _RenderDepthTex).apply(ver, tri, texture, image)
     if normal_grad:
         return _RenderDepthNormal.apply(ver, tri, texture, image)
     return _RenderDepth.apply(ver, tri, texture, image)

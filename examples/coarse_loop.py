@@ -52,7 +52,8 @@ def build_harness(args, dev, rank, world, local):
         face.init_pred_params[..., 6] = 1e-3 * S / 200.0
     # the reference's graph always holds FineNet (build(), network.py:69-101); the forward-only config 3 is CoarseNet + render
     model = cn.FaceReconModel(face, nIter=args.nIter, fine=args.fine or args.train, fused_step=args.fused_step,
-                              pose_grad=args.pose_grad, normal_grad=args.normal_grad).to(dev)
+                              pose_grad=args.pose_grad, normal_grad=args.normal_grad,
+                              **({"learn_tex": True} if args.sfs_tex_grad else {})).to(dev)
     net = model
     if args.train and world > 1:
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local] if dev.type == "cuda" else None)
@@ -70,7 +71,8 @@ def build_harness(args, dev, rank, world, local):
         out = net(im)
         return out, losses.get_loss(face, out["pred_params"], lab, im, out["vertices_proj"], out["coarse_depth_map"],
                                     out["pred_depth_map"], gather_sfs=args.gather_sfs, sfs_normal_grad=args.sfs_grad,
-                                    sfs_fused=args.sfs_fused, sfs_rcond=args.sfs_rcond)
+                                    sfs_fused=args.sfs_fused, sfs_rcond=args.sfs_rcond,
+                                    **({"sfs_tex_grad": True} if args.sfs_tex_grad else {}))
 
     def step():
         if not args.train:
@@ -187,7 +189,7 @@ def ddp_bucket_bytes(model, net):
     return int(sum(p.numel() * p.element_size() for p in model.parameters() if p.requires_grad))
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, choices=sorted(CONFIG_PRESETS), default=None,
                     help="BASELINE.json config preset (3, 4 or 5): sets batch / im-size / train / val / fine; on fewer GPUs "
@@ -218,6 +220,10 @@ def main():
     ap.add_argument("--sfs-fused", action="store_true",
                     help="the SfS lighting solve and shading as one kernel pass per direction (fr_sfs_intensity_forward / "
                          "_backward) instead of the stock-torch permutes, matmuls and batched pinv")
+    ap.add_argument("--sfs-tex-grad", action="store_true",
+                    help="let the shape-from-shading term fit the albedo coefficients: param_tex becomes a parameter of the model "
+                         "(FaceReconModel(learn_tex=True)) and the render of the new texture carries the albedo image's gradient to it "
+                         "(get_loss(sfs_tex_grad=True), fr_render_texture_backward); off: param_tex is a constant, as in the reference")
     ap.add_argument("--sfs-rcond", type=float, default=1e-15,
                     help="eigenvalue cutoff of the SfS pseudo-inverse, relative to the largest.  With float64 sums a rank-deficient "
                          "pixel (fewer than three faces cover it, or their normals are parallel) has null eigenvalues near 1e-16 "
@@ -231,7 +237,11 @@ def main():
     ap.add_argument("--phase", choices=("train", "test"), default="train",
                     help="trainval.py's phase switch (:223-225).  test = the forward-only evaluation loop over independent batches "
                          "with the depth rendering in flight (run_test_phase); train = everything else this script does")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     # (ONE line on stdout: RCCL prints a version banner to fd 1 when its first communicator comes up -- from here on fd 1 is
     # stderr and the JSON line goes to the saved real stdout)
     sys.stdout.flush()

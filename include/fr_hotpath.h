@@ -459,6 +459,70 @@ int fr_render_normal_backward(const float* normal_grad, int grad_stride, const f
  * shape that launches no kernel.  Used by tests/test_normal_backward_cpu.py and tests/test_normal_backward_gpu.py. */
 void fr_debug_render_normal_bwd_geom(int B, int nver, int H, int W, int* out);
 
+/* ---- texture gradients: tex_img backward down to the texture (opt-in) ----------------------------------------------------------
+ * fr_render_depth_backward never reads a gradient of `tex_img`: the reference's op has none, and its "LSE for alpha" block
+ * (nets/network.py:436-445) gives up on "inversely transforming the diff into (3N, 1, B) space".  That inverse transform is the
+ * adjoint of the rasteriser's texture lookup, and this call is it.  tri_ind is held fixed; every default stays the reference's.
+ * The forward gives a pixel tritex_c = (t_c[p1] + t_c[p2] + t_c[p3]) / 3.0f in fp32.
+ * Which pixels contribute.  A pixel is COUNTED when 0 <= (int)tri_ind < ntri (the x86 conversion of the other backwards: NaN and
+ * out-of-range floats become INT_MIN).  A counted pixel CONTRIBUTES when all three ids (int)tri[k,t] lie in [0, nver).  A
+ * contributing pixel has three terms term_c = fl32(g_c / 3.0f), c = 0..2, by the forward's own division sequence; every one of the
+ * triangle's three vertices receives term_c in row c (a triangle that names one vertex three times gives it three terms).
+ * Scale and sum, per scope.  A SCOPE is one face when tex_batch == B, the whole batch when tex_batch == 1 (B == 1: the same thing).
+ *   m     = the largest finite |term| among the scope's contributing pixels, all three channels, as fp32 bits;  e = (m >> 23) - 127
+ *   shift = the smallest s >= 0 with 2^(20+s) >= the scope's pixel count (H*W, or B*H*W for the shared texture)
+ *   q     = rint(term * 2^(39 - shift - e)) as int64 (the product is exact in double; ties to even)
+ *   S     = sum of q per (scope, row, vertex): integer addition, any order;   r = fp32(S), one rounding
+ *   out   = fp32(double(r) * 2^(e - 39 + shift))
+ * |q| < 2^(40 - shift) and an element receives at most 3 * 2^(20+shift) terms, so |S| < 2^62.  An element that receives no term is
+ * +0.  accumulate 1 makes each element fl32(old + out), one add.  |out - exact sum| <= 2^-24 |sum| + n 2^(shift - 39) M for n terms,
+ * M = the scope's largest |term| (plus one rounding to the subnormal grid where out is subnormal).
+ * No float atomics on the finite path; bit-reproducible; independent of the launch geometry; with tex_batch == 1 independent of how
+ * the faces are grouped (and of their order in the batch).
+ * Non-finite terms.  A scope with a non-finite term does not have predictable bits.  An element that receives such a term comes out
+ * non-finite: NaN if a NaN arrives or Infs of both signs arrive, otherwise the Inf.  Every other element of the scope is finite and
+ * within 2^-23 A of the float64 sum of its terms, A = sum |term| over that element (float64 LDS atomics, one rounding to fp32).
+ *   tex_grad:     three floats per pixel, grad_stride (>= 3) floats between pixels: 3 for a dense [B,H,W,3] plane, 7 with the
+ *                 pointer advanced by 1 for channels 1-3 of a [B,H,W,7] net_input gradient.
+ *   tri [3,ntri], tri_ind [B,H,W,1]: as fr_render_depth_backward.
+ *   texture_grad: dense [tex_batch,3,nver]; tex_batch is 1 (the texture shared by the batch) or B.
+ *   workspace:    fr_render_texture_backward_workspace_bytes(B, nver, H, W, tex_batch) bytes: 24 per pixel + 8 per 1,024-pixel
+ *                 chunk (rounded up to 16), and for a shared texture of more than one face 24 nver per face slice; 0 for an empty
+ *                 shape or a tex_batch that is neither 1 nor B.  16-byte aligned, caller-owned, per call in flight.
+ * Every check runs before any HIP call: a negative size, tex_batch outside {1, B} (for B > 0), accumulate outside {0, 1} or
+ * grad_stride < 3 is FR_ERR_INVALID_ARG; then B == 0 or nver == 0 is FR_OK; then a NULL texture_grad -- or, where pixels and
+ * triangles exist, a NULL tex_grad / tri / tri_ind -- is FR_ERR_INVALID_ARG; more than 2^31 - 1 pixels per face (or 2^24 triangles
+ * and more) is FR_ERR_UNSUPPORTED; where pixels and triangles exist a workspace that is missing, too small or not 16-byte aligned
+ * is FR_ERR_WORKSPACE.  H*W == 0 or ntri == 0 writes zeros (accumulate: leaves the tensor as it is).  Nothing is allocated or
+ * synchronised; the call can be captured in a graph; reentrant under the rules at the top of this file, one workspace per call in
+ * flight.
+ * Kernels (csrc/fr_render_tbwd.hip; the scheme of fr_render_normal_backward): a records pass (triangle -> ids once, a 16-byte
+ * {p1,p2,p3,term0} plane and an 8-byte {term1,term2} plane, {max, non-finite} per chunk), then owner workgroups with three 64-bit
+ * LDS accumulators per owned vertex that stream the id plane.  tex_batch == B: one owner per (face, vertex range) rounds and writes.
+ * tex_batch == 1: owners are (face slice, vertex range), each stores its raw int64 slab [3][range] in the workspace with plain
+ * stores and a finish kernel adds a vertex's slabs and rounds once.  Sized before it was built: at 64 faces of the
+ * full mesh 32 slices of 2 faces x 8 ranges keep one workgroup per CU; their slabs are 32 x 1.28 MB written and read once, against
+ * 61 MB of records -- the alternative, 64-bit integer global atomics into one [3][nver] array, has no published rate on this chip
+ * and was not built.
+ * Time: tools/texture_grad_probe.py (profiles/render_texture_backward.json) measures this call in both modes beside
+ * fr_render_depth_backward_ws at 64 and 32 faces of the full mesh at 200 x 200 and the bytes it must move.  MI355X, medians of 6 rounds of 40 calls: tex_batch == B 59.6 / 33.9 us,
+ * tex_batch == 1 62.6 / 45.1 us (32 / 32 face slices x 8 ranges), fr_render_depth_backward_ws on the same inputs 34.5 / 26.0 us.  Must move 91 / 46 MB
+ * (per face) and 51 / 26 MB (shared) = 14.5 / 7.3 and 8.1 / 4.1 us at the 6.29 TB/s copy rate (0.24 / 0.21 and 0.13 / 0.09 of it); the rest goes to
+ * the call's own records, the id plane every owner streams and, for the shared texture, 82 / 82 MB of slabs.  The SfS
+ * backward writing grad_normal_new takes 10.8 / 6.2 us without and 17.1 / 9.6 us with the albedo output. */
+size_t fr_render_texture_backward_workspace_bytes(int B, int nver, int H, int W, int tex_batch);
+int fr_render_texture_backward(const float* tex_grad, int grad_stride, const float* tri, const float* tri_ind,
+                               float* texture_grad, int B, int nver, int ntri, int H, int W, int tex_batch, int accumulate,
+                               void* workspace, size_t ws_bytes, void* hip_stream);
+
+/* The texture-backward launch geometry (no GPU needed; the launcher reads the same function): out[7] = {owner workgroups per face
+ * (tex_batch == B) or per face slice (shared texture), vertices per owner (three 64-bit accumulators each), shift, 1,024-pixel
+ * record chunks per face, dynamic LDS bytes of an owner workgroup, 1 if the block -> (face or slice, owner) map keeps a group's
+ * owners on one XCD (a group count that is a multiple of 8) else 0, face slices of the shared texture (0 where each face is its own
+ * scope, B == 1 included: no cross-face reduction, no finish kernel)}; all zero for a shape that launches no kernel or is refused.
+ * Used by tests/test_texture_backward_cpu.py and tests/test_texture_backward_gpu.py. */
+void fr_debug_render_texture_bwd_geom(int B, int nver, int H, int W, int tex_batch, int* out);
+
 /* ---- shape-from-shading term: fused lighting solve with a normal backward (opt-in) ---------------------------------------------
  * Replaces the linear algebra of get_spherical_harmonics_model (nets/network.py:424-460) on already rendered maps: four transposes,
  * a batched matmul, np.linalg.pinv through tf.py_func on H*W 3x3 matrices (:431), two more matmuls and a transpose back.  One
@@ -490,8 +554,13 @@ void fr_debug_render_normal_bwd_geom(int B, int nver, int H, int W, int* out);
  *   q = sum_b w_b n'_b   (three sums, the forward's association)         s = P q   (rows as for l)
  *   grad_normal_b = fl32(u_b * s)   (three components)                   grad_normal_new_b = fl32(w_b * l)
  * Either output may be NULL (the other is bit-identical to the joint call); both NULL is FR_ERR_INVALID_ARG.  No gradient is formed
- * for the albedos or im_gray: they are constants of this model.  A caller that passed one tensor as normal and normal_new adds the
+ * for abedo or im_gray: they are constants of this model.  A caller that passed one tensor as normal and normal_new adds the
  * two outputs.
+ * fr_sfs_intensity_backward_tex (opt-in: the albedo coefficients as a fitted quantity) is the same call with one more output,
+ *   grad_abedo_new_b = fl32( (double)g_b * d_b ),   d_b = (l_x n'_bx + l_y n'_by) + l_z n'_bz   -- the forward's own d,
+ * float64 with l from state planes 6-8, each operation rounded on its own; [B,H,W,1].  Any of the three outputs may be NULL (the
+ * others are bit-identical to fr_sfs_intensity_backward's); all three NULL is FR_ERR_INVALID_ARG.  fr_sfs_intensity_backward IS
+ * this call with a NULL grad_abedo_new.  abedo (the render of the mean texture) and im_gray stay constants.
  * Checks, all before any HIP call: a negative size, or an rcond that is negative or not finite, is FR_ERR_INVALID_ARG; then B == 0
  * or an empty image is FR_OK; then a NULL input or output pointer (the backward: both outputs NULL) is FR_ERR_INVALID_ARG; a state
  * that is missing, too small or not 16-byte aligned is FR_ERR_WORKSPACE; more than 2^31 - 65 pixels is FR_ERR_UNSUPPORTED.  Nothing
@@ -508,6 +577,9 @@ int fr_sfs_intensity_forward(const float* abedo, const float* normal, const floa
 int fr_sfs_intensity_backward(const float* grad_intensity, const float* abedo, const float* im_gray, const float* abedo_new,
                               const float* normal_new, const void* state, size_t state_bytes, int B, int H, int W,
                               float* grad_normal, float* grad_normal_new, void* hip_stream);
+int fr_sfs_intensity_backward_tex(const float* grad_intensity, const float* abedo, const float* im_gray, const float* abedo_new,
+                                  const float* normal_new, const void* state, size_t state_bytes, int B, int H, int W,
+                                  float* grad_normal, float* grad_normal_new, float* grad_abedo_new, void* hip_stream);
 
 /* The SfS launch geometry (no GPU needed; the launchers read the same function): out[4] = {pixels per workgroup, batch slices per
  * pixel (S above), workgroups, dynamic LDS bytes of a forward workgroup}; all zero for an empty shape.  Used by
