@@ -211,6 +211,20 @@ def _bind(L):
     L.fr_debug_render_texture_bwd_geom.restype = None
     L.fr_sfs_intensity_backward_tex.argtypes = [_vp] * 6 + [ctypes.c_size_t, _i, _i, _i, _vp, _vp, _vp, _vp]
     L.fr_sfs_intensity_backward_tex.restype = _i
+    L.fr_sfs_moments_bytes.argtypes = [_i, _i]
+    L.fr_sfs_moments_bytes.restype = ctypes.c_size_t
+    L.fr_sfs_moments.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
+    L.fr_sfs_moments.restype = _i
+    L.fr_sfs_solve_shade.argtypes = [_vp, _i, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, ctypes.c_size_t, _vp]
+    L.fr_sfs_solve_shade.restype = _i
+    L.fr_sfs_q_bytes.argtypes = [_i, _i]
+    L.fr_sfs_q_bytes.restype = ctypes.c_size_t
+    L.fr_sfs_backward_q.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
+    L.fr_sfs_backward_q.restype = _i
+    L.fr_sfs_backward_apply.argtypes = [_vp] * 6 + [ctypes.c_size_t, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]
+    L.fr_sfs_backward_apply.restype = _i
+    L.fr_debug_sfs_split_geom.argtypes = [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]
+    L.fr_debug_sfs_split_geom.restype = None
     L.fr_sfs_state_bytes.argtypes = [_i, _i]
     L.fr_sfs_state_bytes.restype = ctypes.c_size_t
     L.fr_sfs_intensity_forward.argtypes = [_vp] * 5 + [_i, _i, _i, ctypes.c_double, _vp, _vp, ctypes.c_size_t, _vp]
@@ -261,7 +275,9 @@ EXPORTS = ["fr_version", "fr_strerror", "fr_render_depth_workspace_bytes", "fr_r
            "fr_sfs_state_bytes", "fr_sfs_intensity_forward", "fr_sfs_intensity_backward", "fr_debug_sfs_geom",
            "fr_debug_sfs_pinv", "fr_debug_decode_geom", "fr_debug_decode_walk",
            "fr_render_texture_backward_workspace_bytes", "fr_render_texture_backward", "fr_debug_render_texture_bwd_geom",
-           "fr_sfs_intensity_backward_tex"]
+           "fr_sfs_intensity_backward_tex",
+           "fr_sfs_moments_bytes", "fr_sfs_moments", "fr_sfs_solve_shade", "fr_sfs_q_bytes", "fr_sfs_backward_q",
+           "fr_sfs_backward_apply", "fr_debug_sfs_split_geom"]
 
 
 def lib():

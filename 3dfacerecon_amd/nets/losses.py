@@ -14,8 +14,13 @@ computes its share and DDP averages the gradients.  The exception is the SfS lig
 per-pixel least squares over the whole batch (network.py:430-434: (Y Y^T)^+ Y (I/(albedo+1))^T with Y = [3 x B] normals
 of that pixel), so under batch sharding each rank's lighting is estimated from its own B/world faces -- a different
 (noisier) estimator, not a bug; `get_spherical_harmonics_model(..., gather=True)` all-gathers the per-pixel normal,
-intensity and albedo planes first and reproduces the single-process estimate (one all-gather of 5 floats per pixel per
-face, no gradient through the gathered remote shards, like the reference's py_func pinv has none).
+intensity and albedo planes first and reproduces the single-process estimate (one all-gather of 4 floats per pixel per
+face, no gradient through the gathered remote shards, like the reference's py_func pinv has none).  That route stays on
+stock torch, every rank repeats the pinv and the matmuls over all faces, and rank i never receives the part of rank j's
+loss that passes through the shared lighting into rank i's normals.  `fused_gather=True` (with gather and fused; opt-in)
+exchanges the per-pixel SUMS instead -- nine float64 planes per rank forward, three backward -- around the fused kernels
+(rendering_layer/ops.py::sfs_intensity_sharded): the same whole-batch estimate on every rank, bit for bit, and a
+DDP-averaged gradient equal to the single-process one.
 """
 import torch
 import torch.nn.functional as F
@@ -75,7 +80,7 @@ def _all_gather_batch(t):
 
 
 def spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_image_new, normal_map_new, gather=False, fused=False,
-                                  rcond=1e-15, tex_grad=False):
+                                  rcond=1e-15, tex_grad=False, fused_gather=False):
     """The linear-algebra core of get_spherical_harmonics_model (network.py:424-460) on already rendered maps:
     per pixel, lighting l = (Y Y^T)^+ Y (I / (albedo + 1))^T over the batch (Y = [3 x B] normals), then the recovered
     intensity albedo_new * (l^T Y_new).  All inputs [B,H,W,c]; returns [B,H,W,1].
@@ -84,9 +89,20 @@ def spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_image_
     sums in a fixed order, gradients to the two normal maps with the pseudo-inverse held constant -- the same autograd semantics
     as this torch route, whose pinv is detached.  The albedos and im_gray are constants of that call (they are detached here; in
     this model neither has a path to a parameter).  gather=True under a world size above 1 stays on the torch route even with
-    fused=True: the per-pixel sums would have to cross ranks, which the kernel does not do.
+    fused=True: the per-pixel sums would have to cross ranks, which that kernel does not do (fused_gather below does).
     tex_grad=True: on the fused route abedo_image_new is no longer detached and receives its gradient, the lighting held constant
-    (sfs_intensity(abedo_grad=True)); the torch route differentiates abedo_image_new anyway, so the flag changes nothing there."""
+    (sfs_intensity(abedo_grad=True)); the torch route differentiates abedo_image_new anyway, so the flag changes nothing there.
+    fused_gather=True (requires gather and fused, else ValueError): the whole-batch estimate on the fused kernels at any world
+    size (sfs_intensity_sharded): the ranks all-gather nine float64 planes of per-pixel sums in the forward and three in the
+    backward instead of their maps, and the backward uses the total q, so the DDP-averaged gradient is the single-process
+    gradient (the torch gather route keeps only the local shard differentiable).  Every rank must make the same call and run the
+    backward (it holds a collective); with no process group it equals fused=True bit for bit.  Works with tex_grad."""
+    if fused_gather:
+        if not (gather and fused):
+            raise ValueError("fused_gather=True needs gather=True and fused=True")
+        return _ops().sfs_intensity_sharded(abedo_image.detach(), normal_map, im_gray.detach(),
+                                            abedo_image_new if tex_grad else abedo_image_new.detach(), normal_map_new,
+                                            rcond=rcond, abedo_grad=bool(tex_grad))
     if fused and tex_grad and not (gather and _world_size() > 1):
         return _ops().sfs_intensity(abedo_image.detach(), normal_map, im_gray.detach(), abedo_image_new, normal_map_new,
                                     rcond=rcond, abedo_grad=True)
@@ -106,7 +122,7 @@ def spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_image_
 
 
 def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False, normal_grad=False, fused=False, rcond=1e-15,
-                                  tex_grad=False):
+                                  tex_grad=False, fused_gather=False):
     """Recovered intensity (B,H,W,1) of the first-order spherical-harmonics shading model (network.py:420-462): two
     more render_depth calls (mean albedo, then mean + pc_tex . param_tex) feed spherical_harmonics_intensity.
     normal_grad=False (default): as the reference, both renders hand autograd constant normal maps, so the term has no gradient
@@ -114,8 +130,12 @@ def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False
     (render_depth(normal_grad=True)) and the term moves the geometry.  fused / rcond: as spherical_harmonics_intensity.
     tex_grad=True: the second render, the one of texture_new, carries the albedo image's gradient to the texture
     (render_depth(texture_grad=True)), hence to face_net.param_tex where that requires grad; the render of the mean texture
-    stays a constant."""
+    stays a constant.
+    fused_gather=True (requires gather and fused, else ValueError): as spherical_harmonics_intensity; works with normal_grad and
+    tex_grad."""
     fn = face_net
+    if fused_gather and not (gather and fused):
+        raise ValueError("fused_gather=True needs gather=True and fused=True")
     if fn.mu_tex is None or fn.pc_tex is None or fn.param_tex is None:
         raise ValueError("the asset dict has no texture model (mu_tex / pc_tex / param_tex)")
     kw = {"normal_grad": True} if normal_grad else {}
@@ -130,6 +150,8 @@ def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False
     if not (fused or rcond != 1e-15):
         return spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_new, normal_new, gather=gather)
     kw_tex = {"tex_grad": True} if tex_grad else {}
+    if fused_gather:
+        kw_tex["fused_gather"] = True
     return spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_new, normal_new, gather=gather, fused=fused,
                                          rcond=rcond, **kw_tex)
 
@@ -142,13 +164,16 @@ def combine_losses(losses):
 
 
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
-             gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False):
+             gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False,
+             sfs_fused_gather=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
     sfs_normal_grad / sfs_fused / sfs_rcond (defaults: off, off, the reference's 1e-15): the normal_grad / fused / rcond of
     get_spherical_harmonics_model.  With them off spherical_harmonics_loss is a reported scalar with no gradient, as in the
     reference; sfs_normal_grad=True lets it reach the vertices through the two SfS renders.
     sfs_tex_grad=True (default off): the term also reaches the albedo coefficients face_net.param_tex, where that tensor requires
-    grad (FaceReconModel(learn_tex=True)), through the render of texture_new."""
+    grad (FaceReconModel(learn_tex=True)), through the render of texture_new.
+    sfs_fused_gather=True (default off; needs gather_sfs and sfs_fused, else ValueError): the whole-batch lighting estimate on
+    the fused kernels under any world size, the ranks exchanging per-pixel sums (get_spherical_harmonics_model(fused_gather=True))."""
     fn = face_net
     B = pred_params.shape[0]
     pred = pred_params.reshape(B, fn.ndim)
@@ -160,6 +185,8 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     g = fn.geometry_product(pred[:, fn.ndim_pose:] - label[:, fn.ndim_pose:])
     losses['geometry_loss'] = (g * g).mean()
     kw_tex = {"tex_grad": True} if sfs_tex_grad else {}
+    if sfs_fused_gather:
+        kw_tex["fused_gather"] = True
     intensity_recover = get_spherical_harmonics_model(fn, vertices_proj, im_gray, gather=gather_sfs, normal_grad=sfs_normal_grad,
                                                       fused=sfs_fused, rcond=sfs_rcond, **kw_tex)
     losses['spherical_harmonics_loss'] = F.mse_loss(intensity_recover, im_gray)

@@ -651,6 +651,130 @@ def sfs_intensity(abedo, normal, im_gray, abedo_new, normal_new, rcond=1e-15, ab
     return _SfsIntensity.apply(abedo, normal, im_gray, abedo_new, normal_new, float(rcond))
 
 
+def _dist():
+    """utils/dist.py, loaded by path like _host() (the module holds no state of its own: the process group is torch's)."""
+    name = "_fr_hotpath_dist"
+    mod = sys.modules.get(name)
+    if mod is None:
+        spec = importlib.util.spec_from_file_location(name, os.path.join(_PKG_DIR, "utils", "dist.py"))
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[name] = mod
+        spec.loader.exec_module(mod)
+    return mod
+
+
+def _sfs_exchange(exchange, local, planes, H, W):
+    """local [planes,H,W] float64 -> the stacked parts [nparts,planes,H,W], contiguous on local's device"""
+    parts = (exchange if exchange is not None else _dist().all_gather_stack)(local)
+    if (not isinstance(parts, torch.Tensor) or parts.dtype != torch.float64 or parts.dim() != 4 or parts.shape[0] < 1
+            or tuple(parts.shape[1:]) != (planes, H, W) or parts.device != local.device):
+        raise ValueError("sfs_intensity_sharded: exchange must return a float64 tensor [nparts,%d,%d,%d] on %s (got %s)"
+                         % (planes, H, W, local.device, getattr(parts, "shape", type(parts))))
+    return parts.detach().contiguous()
+
+
+class _SfsIntensitySharded(torch.autograd.Function):
+    """fr_sfs_moments -> exchange -> fr_sfs_solve_shade, and fr_sfs_backward_q -> exchange -> fr_sfs_backward_apply (include/
+    fr_hotpath.h, "shape-from-shading term across ranks") as one autograd node."""
+
+    @staticmethod
+    def forward(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond, abedo_grad, exchange):
+        h = _host()
+        ctx.abedo_grad = bool(abedo_grad)
+        ctx.exchange = exchange
+        for t, name in ((abedo, "abedo"), (im_gray, "im_gray")) + (() if abedo_grad else ((abedo_new, "abedo_new"),)):
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                raise ValueError("sfs_intensity_sharded: %s requires grad, but the albedos and im_gray are constants of this model "
+                                 "(detach it)" % name)
+        a_c = h.require_gpu_f32(abedo, "abedo")
+        n_c = h.require_gpu_f32(normal, "normal")
+        i_c = h.require_gpu_f32(im_gray, "im_gray")
+        a2_c = h.require_gpu_f32(abedo_new, "abedo_new")
+        n2_c = n_c if normal_new is normal else h.require_gpu_f32(normal_new, "normal_new")
+        if n_c.dim() != 4 or n_c.shape[3] != 3:
+            raise ValueError("sfs_intensity_sharded expects normal [B,H,W,3]")
+        B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+        for t, name, c in ((a_c, "abedo", 1), (i_c, "im_gray", 1), (a2_c, "abedo_new", 1), (n2_c, "normal_new", 3)):
+            if tuple(t.shape) != (B, H, W, c):
+                raise ValueError("sfs_intensity_sharded: %s must be [%d,%d,%d,%d] (got %s)" % (name, B, H, W, c, tuple(t.shape)))
+            if t.device != n_c.device:
+                raise ValueError("sfs_intensity_sharded: %s is on %s, normal on %s" % (name, t.device, n_c.device))
+        dev = n_c.device
+        L = h.lib()
+        nst = L.fr_sfs_state_bytes(H, W)
+        state = torch.empty((max(nst, 16) // 8,), dtype=torch.float64, device=dev)   # per call: the backward reads it
+        intensity = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev)
+        ctx.dims = (B, H, W, nst)
+        ctx.save_for_backward(a_c, i_c, a2_c, n2_c, state)
+        if H * W == 0:   # (the same on every rank: nobody calls the exchange)
+            return intensity
+        mine = torch.empty((9, H, W), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            rc = L.fr_sfs_moments(h.ptr(a_c), h.ptr(n_c), h.ptr(i_c), B, H, W, h.ptr(mine), mine.numel() * 8, h.stream_ptr(dev))
+        h.check(rc, "fr_sfs_moments")
+        parts = _sfs_exchange(exchange, mine, 9, H, W)
+        with torch.cuda.device(dev):
+            rc = L.fr_sfs_solve_shade(h.ptr(parts), int(parts.shape[0]), h.ptr(a2_c), h.ptr(n2_c), B, H, W, float(rcond),
+                                      h.ptr(intensity), h.ptr(state), nst, h.stream_ptr(dev))
+        h.check(rc, "fr_sfs_solve_shade")
+        return intensity
+
+    @staticmethod
+    def backward(ctx, g):
+        h = _host()
+        a_c, i_c, a2_c, n2_c, state = ctx.saved_tensors
+        B, H, W, nst = ctx.dims
+        dev = a_c.device
+        want_n, want_n2 = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
+        want_a2 = ctx.abedo_grad and ctx.needs_input_grad[3]
+        none = (None,) * 8
+        if not (want_n or want_n2 or want_a2):
+            return none
+        g_c = h.require_gpu_f32(g, "grad_intensity")
+        gn = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n else None
+        gn2 = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n2 else None
+        ga2 = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev) if want_a2 else None
+        if H * W == 0:
+            return None, gn, None, ga2, gn2, None, None, None
+        L = h.lib()
+        parts = None
+        if want_n:   # the one collective of the backward: issued by every rank or by none (same graph on every rank)
+            mine = torch.empty((3, H, W), dtype=torch.float64, device=dev)
+            with torch.cuda.device(dev):
+                rc = L.fr_sfs_backward_q(h.ptr(g_c), h.ptr(a2_c), h.ptr(n2_c), B, H, W, h.ptr(mine), mine.numel() * 8,
+                                         h.stream_ptr(dev))
+            h.check(rc, "fr_sfs_backward_q")
+            parts = _sfs_exchange(ctx.exchange, mine, 3, H, W)
+        with torch.cuda.device(dev):
+            rc = L.fr_sfs_backward_apply(h.ptr(g_c), h.ptr(a_c), h.ptr(i_c), h.ptr(a2_c), h.ptr(n2_c), h.ptr(state), nst,
+                                         h.ptr(parts), int(parts.shape[0]) if parts is not None else 1, B, H, W, h.ptr(gn),
+                                         h.ptr(gn2), h.ptr(ga2), h.stream_ptr(dev))
+        h.check(rc, "fr_sfs_backward_apply")
+        return None, gn, None, ga2, gn2, None, None, None
+
+
+def sfs_intensity_sharded(abedo, normal, im_gray, abedo_new, normal_new, rcond=1e-15, abedo_grad=False, exchange=None):
+    """sfs_intensity with the batch spread over several ranks: this rank passes its OWN faces' maps ([B,H,W,c]; B may differ from
+    rank to rank and may be 0, H and W may not) and receives its own faces' intensity, computed with the lighting of ALL ranks'
+    faces.  The ranks exchange sums, not maps: nine float64 planes per rank in the forward (M and r), three in the backward (q);
+    the totals are formed in rank order, so every rank holds the same lighting, bit for bit, and the result does not depend on
+    which rank computes it (fr_sfs_moments / fr_sfs_solve_shade / fr_sfs_backward_q / fr_sfs_backward_apply).
+    exchange(local [k,H,W] float64) -> [nparts,k,H,W] float64 on the same device, the ranks' planes stacked in rank order;
+    default: utils/dist.py all_gather_stack on the default process group.  It is called ONCE in the forward (k = 9) and once in the
+    backward (k = 3), the latter only when `normal` needs a gradient.  With no process group and no `exchange` the node equals
+    sfs_intensity bit for bit.  Same argument checks and refusals as sfs_intensity; abedo_grad as there.
+    Gradient semantics.  The backward uses the TOTAL q = sum over ranks r of q_r: rank i returns u_b * (P sum_r q_r) for its own
+    faces b, i.e. also the part of every OTHER rank's loss that passes through the shared lighting into rank i's normals.  With
+    each rank's loss the mean over its own faces and DDP's averaging of the ranks' gradients, that is the single-process gradient
+    of the mean loss over all ranks' faces (the gather=True torch route drops the cross-rank part).  grad_normal_new and
+    grad_abedo_new are local.  P is held constant, as in sfs_intensity.
+    Every rank must build the same graph: the backward issues a collective when, and only when, `normal` needs a gradient, so
+    `normal` must require grad on all ranks or on none, and every rank must run the backward.  With a real collective behind
+    `exchange` the node cannot be captured into a HIP graph (the collective and, under gloo, its host staging are not capturable
+    work of this stream)."""
+    return _SfsIntensitySharded.apply(abedo, normal, im_gray, abedo_new, normal_new, float(rcond), bool(abedo_grad), exchange)
+
+
 def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     """One-pass rendering layer: returns (net_input [B,H,W,7] = [mask*im | pncc | normal],
     depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers.

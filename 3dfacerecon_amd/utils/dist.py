@@ -79,6 +79,21 @@ def gather_over_ranks(value, device="cpu"):
     return [float(x.item()) for x in out]
 
 
+def all_gather_stack(t, group=None):
+    """Every rank's `t` (same shape and dtype on all ranks) stacked in rank order -> [world, *t.shape], on t's device: ONE
+    all-gather into ONE tensor (the layout the split SfS entry points read: include/fr_hotpath.h, "part layout").  Under gloo the
+    tensor is staged through the host, as _collective_device does for the reductions above.  Without a process group: t[None].
+    A collective: every rank of the group must call it, in the same order.  No gradient passes through it."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return t.detach()[None]
+    world = dist.get_world_size(group)
+    cdev = torch.device("cpu") if dist.get_backend(group) == "gloo" else t.device
+    src = t.detach().contiguous().to(cdev)
+    out = torch.empty((world,) + tuple(src.shape), dtype=src.dtype, device=cdev)
+    dist.all_gather_into_tensor(out.view(-1), src.view(-1), group=group)   # (flat: the concatenation form every backend takes)
+    return out.to(t.device)
+
+
 def device_identity(device="cpu"):
     """What THIS rank computes on: host, device name and a device id that is unique per physical GPU on the node (the PCI
     bus id; the uuid when torch exposes it).  A CPU rank (the gloo tests) reports its process id."""

@@ -72,7 +72,8 @@ def build_harness(args, dev, rank, world, local):
         return out, losses.get_loss(face, out["pred_params"], lab, im, out["vertices_proj"], out["coarse_depth_map"],
                                     out["pred_depth_map"], gather_sfs=args.gather_sfs, sfs_normal_grad=args.sfs_grad,
                                     sfs_fused=args.sfs_fused, sfs_rcond=args.sfs_rcond,
-                                    **({"sfs_tex_grad": True} if args.sfs_tex_grad else {}))
+                                    **({"sfs_tex_grad": True} if args.sfs_tex_grad else {}),
+                                    **({"sfs_fused_gather": True} if args.sfs_fused_gather else {}))
 
     def step():
         if not args.train:
@@ -220,6 +221,11 @@ def build_parser():
     ap.add_argument("--sfs-fused", action="store_true",
                     help="the SfS lighting solve and shading as one kernel pass per direction (fr_sfs_intensity_forward / "
                          "_backward) instead of the stock-torch permutes, matmuls and batched pinv")
+    ap.add_argument("--sfs-fused-gather", action="store_true",
+                    help="with --gather-sfs and --sfs-fused: the whole-batch lighting estimate on the fused kernels under several "
+                         "ranks -- the ranks all-gather nine float64 planes of per-pixel sums forward and three backward instead of "
+                         "their maps, and the DDP-averaged gradient equals the single-process one (get_loss(sfs_fused_gather=True)); "
+                         "off: --gather-sfs under several ranks stays on the stock-torch route")
     ap.add_argument("--sfs-tex-grad", action="store_true",
                     help="let the shape-from-shading term fit the albedo coefficients: param_tex becomes a parameter of the model "
                          "(FaceReconModel(learn_tex=True)) and the render of the new texture carries the albedo image's gradient to it "

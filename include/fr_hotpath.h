@@ -590,6 +590,68 @@ void fr_debug_sfs_geom(int B, int H, int W, int* out);
  * FR_ERR_INVALID_ARG for a NULL pointer or an rcond that is negative or not finite.  Used by tests/test_sfs_cpu.py. */
 int fr_debug_sfs_pinv(const double* m6, double rcond, double* p6, int* rank);
 
+/* ---- shape-from-shading term across ranks: the same solve with the batch spread over several callers (opt-in) -------------------
+ * The lighting solve couples the faces of a batch only through sums that are additive over faces: M and r in the forward (nine
+ * sums), q in the backward (three).  These entry points cut the two passes above at that point, so that each of several callers
+ * (data-parallel ranks, each with its own B faces of one H x W image grid) streams its own maps once, exchanges 9 + 3 float64 planes
+ * per direction instead of its maps, and finishes with the totals.  The exchange itself is the caller's (an all-gather into one
+ * tensor: utils/dist.py, all_gather_stack); nothing here communicates.  Inputs, outputs, u_b, w_b and the state are those of the
+ * section above; the one-call entry points do not change.
+ * PART.  A part is one caller's nine (or three) sums over its own B faces, formed exactly as the one-call kernel forms them for a
+ * batch of that size: S = sfs_slices(B) slices, each adding its faces' terms in ascending b onto +0.0, then the slices added in
+ * ascending s onto slice 0's sum.  fr_sfs_moments writes the part [9][H*W] doubles: Mxx, Mxy, Mxz, Myy, Myz, Mzz, rx, ry, rz;
+ * fr_sfs_backward_q writes [3][H*W]: qx, qy, qz.  fr_sfs_moments_bytes(H, W) = 9 planes, fr_sfs_q_bytes(H, W) = 3 planes of H * W
+ * doubles (0 for an empty image); the buffers are caller-owned and 16-byte aligned.
+ * PART LAYOUT.  moment_parts is [nparts][9][H*W] doubles and q_parts is [nparts][3][H*W] doubles, both contiguous: what an
+ * all-gather of the parts into one tensor produces.  Every caller passes the same stacked buffer, in the same order.
+ * TOTALS.  total = ((part0 + part1) + part2) + ...  in ascending part index, per plane and pixel, float64, starting FROM part0 (not
+ * from zero).  The bits are a function of the parts and their order, and of nothing else -- not of B, H, W or the caller.
+ * Everything after the totals is the text of the section above: fr_sfs_pinv3 on the total M, the rows of l, the poison rule for
+ * non-finite sums (applied to the totals), the ten state planes, intensity_b = fl32(a'_b (l . n'_b)) for the caller's own faces,
+ * s = P q with the total q, and the three gradient outputs of fr_sfs_intensity_backward_tex for the caller's own faces.  Every
+ * caller therefore holds the same state, bit for bit.
+ * nparts == 1 is bit-identical to the one-call entry points: fr_sfs_moments then fr_sfs_solve_shade gives the state and intensity
+ * of fr_sfs_intensity_forward; fr_sfs_backward_q then fr_sfs_backward_apply gives the outputs of fr_sfs_intensity_backward_tex.
+ * GRADIENT ACROSS CALLERS.  grad_normal_b = fl32(u_b * (P sum_r q_r)) for the caller's own faces: the part of EVERY caller's loss
+ * that passes through the shared lighting into this caller's normals.  With each caller's loss the mean over its own faces and the
+ * callers' gradients averaged (data-parallel training), that is the single-process gradient of the mean loss over all faces.
+ * grad_normal_new and grad_abedo_new are local.  P is held constant, as above.
+ * EMPTY SHARDS.  A caller may own no faces.  With B == 0 and a non-empty image fr_sfs_moments and fr_sfs_backward_q write planes of
+ * +0.0 (the caller still takes part in the exchange; the face pointers may then be NULL); fr_sfs_solve_shade and
+ * fr_sfs_backward_apply with B == 0 are FR_OK and write nothing, the state included.  An empty image is FR_OK everywhere.
+ * q_parts may be NULL exactly when grad_normal is NULL (it is not read then); all three outputs NULL is FR_ERR_INVALID_ARG.
+ * Checks, all before any HIP call, in this order: a negative size is FR_ERR_INVALID_ARG; an rcond that is negative or not finite
+ * is FR_ERR_INVALID_ARG; nparts < 1 or nparts > 4096 is FR_ERR_INVALID_ARG; then the empty cases above are FR_OK; then a NULL
+ * input, parts or output pointer is FR_ERR_INVALID_ARG; a moments, q or state buffer that is missing, too small or not 16-byte
+ * aligned is FR_ERR_WORKSPACE; more than 2^31 - 65 pixels is FR_ERR_UNSUPPORTED.  The stacked parts carry no size: the caller
+ * vouches for nparts * 9 (or 3) planes.  Nothing is allocated or synchronised; reentrant with buffers per call in flight.
+ * Kernels (csrc/fr_sfs.hip), built from the device functions of the one-call kernels: sfs_moments_kernel and sfs_backward_q_kernel
+ * are their streaming halves (a workgroup owns 64 consecutive pixels, S waves stream contiguous shares of the faces, the partial
+ * sums meet in LDS, wave 0 stores the planes); sfs_solve_shade_kernel: wave 0 adds the parts, solves once per pixel and broadcasts
+ * l through LDS, every wave shades its faces; sfs_backward_apply_kernel: every wave adds the q parts for itself (24 doubles per
+ * pixel at 8 parts, from the workgroup's own L1 lines; no LDS, no barrier).  No atomics.
+ * Bytes and time: per direction the split route moves the one-call route's maps plus 72 B per pixel and part written and read
+ * (forward) or 24 B (backward), plus one launch; tools/sfs_probe.py --sharded measures it beside the one-call kernels
+ * (profiles/sfs_sharded.json; the figures and their reading: DESIGN.md 4.4f). */
+size_t fr_sfs_moments_bytes(int H, int W);
+int fr_sfs_moments(const float* abedo, const float* normal, const float* im_gray, int B, int H, int W, void* moments,
+                   size_t moments_bytes, void* hip_stream);
+int fr_sfs_solve_shade(const void* moment_parts, int nparts, const float* abedo_new, const float* normal_new, int B, int H, int W,
+                       double rcond, float* intensity, void* state, size_t state_bytes, void* hip_stream);
+size_t fr_sfs_q_bytes(int H, int W);
+int fr_sfs_backward_q(const float* grad_intensity, const float* abedo_new, const float* normal_new, int B, int H, int W, void* q,
+                      size_t q_bytes, void* hip_stream);
+int fr_sfs_backward_apply(const float* grad_intensity, const float* abedo, const float* im_gray, const float* abedo_new,
+                          const float* normal_new, const void* state, size_t state_bytes, const void* q_parts, int nparts, int B,
+                          int H, int W, float* grad_normal, float* grad_normal_new, float* grad_abedo_new, void* hip_stream);
+
+/* The split route's launch geometry (no GPU needed; the four launchers read the same function): out[6] = {pixels per workgroup,
+ * batch slices per pixel (S = sfs_slices(B); 1 for B == 0, which still launches the two part kernels), workgroups, dynamic LDS
+ * bytes of the moments kernel (9 S 64 doubles), of the solve-and-shade kernel (3 x 64 doubles), of the q kernel (3 S 64 doubles)};
+ * the apply kernel uses no LDS.  All zero for a negative B, an empty image or one the launchers refuse.  Used by
+ * tests/test_sfs_sharded_cpu.py. */
+void fr_debug_sfs_split_geom(int B, int H, int W, int* out);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0

@@ -18,7 +18,18 @@ route on the well-conditioned pixels (recorded, not asserted; the tests hold the
 --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -DFR_SFS_SLICES_MAX=8 -o PATH fr_sfs.hip): its forward and
 backward are timed in the same rounds -- how the batch-slice count of the launch geometry was chosen.
 --trace: a few calls of each route and nothing else, for a `rocprofv3 --kernel-trace --stats` run of its own.
---out FILE: where the JSON goes besides stdout (default profiles/sfs_intensity.json)."""
+--out FILE: where the JSON goes besides stdout (default profiles/sfs_intensity.json).
+
+--sharded: instead of the above, the SPLIT route (fr_sfs_moments + fr_sfs_solve_shade, fr_sfs_backward_q + fr_sfs_backward_apply:
+one rank's share of a whole-batch solve across ranks) beside the one-call kernels, raw C ABI, same rounds, same process:
+  'one_fwd' / 'one_bwd'              = fr_sfs_intensity_forward / fr_sfs_intensity_backward (both normal outputs)
+  'split_fwd_p1' / 'split_bwd_p1'    = the two split calls of a direction with ONE part (this rank alone)
+  'split_fwd_p8' / 'split_bwd_p8'    = the same with eight parts: this rank's planes written into slot 0 of the stacked buffer, the
+                                       other seven slots synthetic remote parts (the sums of the same maps); no collective runs
+with the bytes each leg must move: the one-call figure + (1 + nparts) x 72 B per pixel forward (the part written, the stack read),
++ (1 + nparts) x 24 B backward, and what a rank would RECEIVE in the exchange (not timed here: no second GPU).  A library given
+with --alt-lib (the parent commit's fr_sfs.hip, say) has its one-call kernels timed in the same rounds, and whether its bits equal
+this build's is recorded.  Default --out profiles/sfs_sharded.json."""
 import argparse
 import ctypes
 import importlib
@@ -41,8 +52,11 @@ ap.add_argument("--faces", type=int, nargs="+", default=[64, 32])
 ap.add_argument("--rcond", type=float, default=1e-6)
 ap.add_argument("--alt-lib", action="append", default=[], metavar="NAME=PATH")
 ap.add_argument("--trace", action="store_true")
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sfs_intensity.json"))
+ap.add_argument("--sharded", action="store_true")
+ap.add_argument("--out", default=None)
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "sfs_sharded.json" if args.sharded else "sfs_intensity.json")
 
 if not torch.cuda.is_available():
     raise SystemExit("sfs_probe: needs an MI355X (a measurement path does not fall back)")
@@ -122,6 +136,79 @@ for B in args.faces:
         return lambda: lib.fr_sfs_intensity_backward(h.ptr(g), h.ptr(alb), h.ptr(im), h.ptr(alb2), h.ptr(nmap2), h.ptr(state), nst,
                                                      B, H, W, h.ptr(gn), h.ptr(gn2), st)
 
+    if args.sharded:
+        NP = 8
+        npix = H * W
+        nm, nq = L.fr_sfs_moments_bytes(H, W), L.fr_sfs_q_bytes(H, W)
+        mstack = torch.empty((NP, 9, H, W), dtype=torch.float64, device=dev)   # slot 0: this rank; 1-7: synthetic remote parts
+        qstack = torch.empty((NP, 3, H, W), dtype=torch.float64, device=dev)
+        state2, inten2 = torch.empty_like(state), torch.empty_like(inten)
+        gn_s, gn2_s = torch.empty_like(gn), torch.empty_like(gn2)
+
+        def split_fwd(nparts):
+            def run():
+                rc = L.fr_sfs_moments(h.ptr(alb), h.ptr(nmap), h.ptr(im), B, H, W, h.ptr(mstack), nm, st)
+                return rc or L.fr_sfs_solve_shade(h.ptr(mstack), nparts, h.ptr(alb2), h.ptr(nmap2), B, H, W, args.rcond,
+                                                  h.ptr(inten2), h.ptr(state2), nst, st)
+            return run
+
+        def split_bwd(nparts):
+            def run():
+                rc = L.fr_sfs_backward_q(h.ptr(g), h.ptr(alb2), h.ptr(nmap2), B, H, W, h.ptr(qstack), nq, st)
+                return rc or L.fr_sfs_backward_apply(h.ptr(g), h.ptr(alb), h.ptr(im), h.ptr(alb2), h.ptr(nmap2), h.ptr(state), nst,
+                                                     h.ptr(qstack), nparts, B, H, W, h.ptr(gn_s), h.ptr(gn2_s), None, st)
+            return run
+        assert c_fwd(L)() == 0 and c_bwd(L)() == 0 and split_fwd(1)() == 0 and split_bwd(1)() == 0
+        torch.cuda.synchronize()
+
+        def same(a, b):
+            return bool((a.reshape(-1).view(torch.int32) == b.reshape(-1).view(torch.int32)).all())
+        bits = {"split_p1_equals_one_call": same(inten2, inten) and same(state2, state) and same(gn_s, gn) and same(gn2_s, gn2)}
+        for name, lib in ALT.items():   # the other library's one-call kernels on the same inputs: the same bits?
+            keep = [t.clone() for t in (inten, state, gn, gn2)]
+            assert c_fwd(lib)() == 0 and c_bwd(lib)() == 0
+            torch.cuda.synchronize()
+            bits["one_call_equals_" + name] = all(same(a, b) for a, b in zip(keep, (inten, state, gn, gn2)))
+        mstack[1:] = mstack[0]
+        qstack[1:] = qstack[0]
+        routes = {"one_fwd": c_fwd(L), "split_fwd_p1": split_fwd(1), "split_fwd_p8": split_fwd(NP),
+                  "one_bwd": c_bwd(L), "split_bwd_p1": split_bwd(1), "split_bwd_p8": split_bwd(NP)}
+        for name, lib in ALT.items():
+            routes["%s_one_fwd" % name] = c_fwd(lib)
+            routes["%s_one_bwd" % name] = c_bwd(lib)
+        for fn in routes.values():
+            for _ in range(3):
+                assert fn() == 0
+        torch.cuda.synchronize()
+        if args.trace:
+            continue
+        res = {k: [] for k in routes}
+        for rnd in range(args.rounds):
+            for k, fn in routes.items():
+                res[k].append(timed(fn, args.calls))
+        assert c_fwd(L)() == 0   # (the state the backward legs read: left as the one-call forward writes it)
+        rec = {k: summary(v) for k, v in res.items()}
+        must_f = B * npix * 40 + npix * 80
+        must_b = B * npix * 52 + npix * 72
+        rec["bytes"] = {"one_fwd": must_f, "one_bwd": must_b}
+        for n in (1, NP):
+            rec["bytes"]["split_fwd_p%d" % n] = must_f + (1 + n) * npix * 72
+            rec["bytes"]["split_bwd_p%d" % n] = must_b + (1 + n) * npix * 24
+            rec["bytes"]["exchange_received_fwd_p%d" % n] = (n - 1) * npix * 72
+            rec["bytes"]["exchange_received_bwd_p%d" % n] = (n - 1) * npix * 24
+        rec["bytes"]["map_gather_received_p%d" % NP] = (NP - 1) * B * npix * 16   # the gather=True torch route: 4 floats per (face, pixel)
+        rec["time_at_copy_rate_us"] = {k: round(v / COPY_RATE * 1e6, 2) for k, v in rec["bytes"].items() if not k.startswith(("exch", "map"))}
+        for k in ("fwd", "bwd"):
+            for n in (1, NP):
+                rec["split_%s_p%d_minus_one_call_us" % (k, n)] = round(rec["split_%s_p%d" % (k, n)]["median"] - rec["one_" + k]["median"], 2)
+        g6 = (ctypes.c_int * 6)()
+        L.fr_debug_sfs_split_geom(B, H, W, g6)
+        rec["geometry"] = dict(zip(("pixels_per_workgroup", "batch_slices", "workgroups", "lds_moments", "lds_solve_shade", "lds_q"), g6))
+        rec["bits"] = bits
+        out["B=%d" % B] = rec
+        print("B=%d" % B, json.dumps(rec), flush=True)
+        continue
+
     def torch_fwd():
         with torch.no_grad():
             return losses.spherical_harmonics_intensity(alb, nmap, im, alb2, nmap2, rcond=args.rcond)
@@ -181,7 +268,21 @@ for B in args.faces:
     out["B=%d" % B] = rec
     print("B=%d" % B, json.dumps(rec), flush=True)
 
-if not args.trace:
+if args.sharded and not args.trace:
+    doc = {"what": "us per leg, device events around %d repetitions per figure, %d alternating rounds, one process, raw C ABI; maps from "
+                   "render_depth of the full-size synthetic mesh at 200 x 200, rcond %g; one_* = the one-call kernels, split_*_pN = the "
+                   "two split calls of that direction with N parts (N = 8: this rank's part + seven synthetic remote parts already in "
+                   "the stacked buffer; no collective is timed); bytes = what each leg must move, exchange_received_* = what a rank "
+                   "would receive in the all-gather, map_gather_received = the same for the gather=True torch route; "
+                   "<name>_one_* = the one-call kernels of the library given as --alt-lib <name>=..." % (args.calls, args.rounds, args.rcond),
+           "copy_rate_bytes_per_s": COPY_RATE, "device": torch.cuda.get_device_name(0), "lib": L.fr_version().decode(),
+           "results": out}
+    print(json.dumps(doc))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+elif not args.trace:
     doc = {"what": "us per call, device events around %d fused / %d torch calls per figure, %d alternating rounds, one process; maps "
                    "from render_depth of the full-size synthetic mesh at 200 x 200, rcond %g; torch_* = the stock-torch "
                    "spherical_harmonics_intensity, fused_fwd / fused_bwd = fr_sfs_intensity_forward / _backward through the raw C ABI, "
