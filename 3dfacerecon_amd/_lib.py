@@ -15,10 +15,10 @@ import types
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG_DIR, "csrc")
 LIB_PATH = os.path.join(_PKG_DIR, "libfr_hotpath.so")
-SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_nbwd.hip", "fr_render_tbwd.hip",
-           "fr_sfs.hip"]
+SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_bwd.hip", "fr_render_nbwd.hip",
+           "fr_render_tbwd.hip", "fr_sfs.hip"]
 HEADERS = [os.path.join(_CSRC, "fr_common.h"), os.path.join(_CSRC, "fr_decode_shared.h"), os.path.join(_CSRC, "fr_sfs_pinv.h"),
-           os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
+           os.path.join(_CSRC, "fr_owner_scatter.h"), os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]  # single-lane LDS atomics stay single instructions
 

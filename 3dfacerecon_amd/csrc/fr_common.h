@@ -153,7 +153,7 @@ bool fr_rendering_layer_supported(int B, int nver, int ntri, int H, int W);
 int fr_launch_render_backward(const float* depth_grad, const float* tri, const float* tri_ind, float* vertex_grad,
                               int B, int nver, int ntri, int H, int W, void* workspace, size_t ws_bytes,
                               hipStream_t stream);
-// the pixel-gradient planes of fr_decode_render_backward (each gradient may be null; the formula: bwd_records_body in fr_render.hip)
+// the pixel-gradient planes of fr_decode_render_backward (each gradient may be null; the formula: bwd_records_body in fr_render_bwd.hip)
 struct FrPixelGrad {
     const float* g_depth;      // [B,H,W,1]
     const float* g_depth_img;  // [B,H,W,1]

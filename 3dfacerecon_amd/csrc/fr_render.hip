@@ -1,8 +1,8 @@
-// render_depth forward / backward for gfx950 (MI355X).
+// render_depth forward for gfx950 (MI355X); the backward is fr_render_bwd.hip.
 //
 // What it computes: the CPU functor of the reference, rendering_layer/ops_src/render_depth_op.cc:132-322
-// (forward) and :325-368 (backward) -- NOT the reference's CUDA kernels (render_depth_op.cu.cc:176-237 race
-// on the z-test and are not the numerical spec).
+// -- NOT the reference's CUDA kernels (render_depth_op.cu.cc:176-237 race on the z-test and are not the
+// numerical spec).
 //
 // How (MI355X-first, nothing like the reference's three-kernel + 705 MB fp64 scratch pipeline).  At BFM density
 // triangles are sub-pixel (about half have no pixel centre in their bbox, the rest test ~1 pixel), so the work is
@@ -1254,342 +1254,6 @@ __global__ __launch_bounds__(BLOCK) void resolve_write_kernel(RenderArgs a) {
     resolve_body<BLOCK, FUSED, PR>(a, xcd_remap(blockIdx.x, gridDim.x), keys, pr);
 }
 
-// ---- backward: zeros + scatter-add of g/3 to the z row (render_depth_op.cc:345-363) -------------------------
-// The reference is a serial loop (one fixed summation order); float atomics would make the per-vertex order depend on
-// the schedule.  Here the sum is made ORDER-INDEPENDENT instead: every contribution c = (g * 1.0f) / 3.0f (fp32, as
-// :361 computes it) is converted EXACTLY to a 64-bit fixed-point integer (c * 2^k is exact in double; one llrint), the
-// integers are added with LDS integer atomics (associative => bit-reproducible whatever the order), and the total is
-// rounded to fp32 once.  k is chosen per face from max|g| so that the largest term has at least 38 significant bits below
-// the int64 headroom the H*W*3 possible terms need: every term is represented to 2^-39 of the face's largest term, i.e.
-// the result is the exactly rounded real sum up to  n_terms * 2^-39 * max|c|  -- at least as close to the real-number sum
-// as the reference's sequential fp32 order (whose error grows with the partial sums), and identical run to run.
-// One workgroup owns one (face, vertex range) pair: it scans ALL the face's pixels (L2-resident planes) and keeps only
-// the contributions that land in its range, so no two workgroups ever add to the same vertex and nothing needs zeroing:
-// the owner writes its range of all three rows (x and y rows: zeros, render_depth_op.cc:359-363).
-// A face whose gradients contain Inf / NaN cannot be scaled: it takes fp32 LDS atomics (the class of the result --
-// NaN / +-Inf -- does not depend on the order).
-constexpr int BWD_BLOCK = 1024;
-constexpr int BWD_RANGE_MAX = 16 * 1024;  // vertices per owner workgroup (8 B each: 128 KiB of LDS)
-
-struct BwdRenderArgs {
-    const float* depth_grad;  // [B,H,W,1]
-    const int4* rec;          // [B,H,W] per-pixel records {p1,p2,p3,g bits} (bwd_records_kernel), or null: float ids
-    const uint2* partial;     // [B,chunks] {largest |g| bits, Inf/NaN flag} of each 1,024-pixel chunk
-    int B, chunks;
-    const float* tri;         // [3,ntri]
-    const float* tri_ind;     // [B,H,W,1]
-    float* vertex_grad;       // [B,3,nver]
-    int nver, ntri, npix;     // npix = H*W
-    int splits, range;        // owner workgroups per face, vertices per owner
-    int shift;                // headroom bits given up by images above 2^20 pixels: ceil(log2 npix) - 20, else 0
-    // fr_decode_render_backward: the records pass FORMS the pixel gradient from up to three planes (each may be null) ...
-    const float* g_net;       // [B,H,W,7] gradient of net_input: channel 0 only
-    const float* g_dimg;      // [B,H,W,1] gradient of depth_img
-    const float* im_gray;     // [B,H,W,1]
-    const float* depth;       // [B,H,W,1] forward output
-    // ... and the owners write ONLY the z row, face b at vertex_grad + b * zpitch (0: the dense [B,3,nver] tensor, x / y zeroed)
-    long long zpitch;
-};
-
-// the three vertex ids of pixel value `tv` (a float-stored triangle index, -1 on the background): false when the pixel
-// contributes nothing (deviation 2: tri_ind < 0; deviation 3: an id outside [0,nver))
-__device__ __forceinline__ int bwd_tri_of(float tv, int ntri) {
-    const int t = f2i_x86(tv);
-    return (t >= 0 && t < ntri) ? t : -1;
-}
-
-// Per-face scan: largest |g| over the covered pixels + an Inf/NaN flag, by one 1,024-thread
-// workgroup, no atomics (nothing to zero).  Used by the plain (no-workspace) variant.
-__device__ __forceinline__ void bwd_face_max(const BwdRenderArgs& a, int b, uint32_t* red /*[2 * BWD_BLOCK / 64]*/, uint2* out) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int npix = a.npix;
-    const float* __restrict__ g = a.depth_grad + (size_t)b * npix;
-    const float* __restrict__ ti = a.tri_ind + (size_t)b * npix;
-    uint32_t m = 0, bad = 0;
-    constexpr int PU = 8;  // pixels per lane per trip, all loads issued before the first use
-    for (int i0 = tid; i0 < npix; i0 += PU * BWD_BLOCK) {
-        float gq[PU], tq[PU];
-#pragma unroll
-        for (int u = 0; u < PU; u++) {
-            const int i = min(i0 + u * BWD_BLOCK, npix - 1);
-            gq[u] = g[i];
-            tq[u] = ti[i];
-        }
-#pragma unroll
-        for (int u = 0; u < PU; u++) {
-            if (i0 + u * BWD_BLOCK < npix && bwd_tri_of(tq[u], a.ntri) >= 0) {
-                const uint32_t v = __float_as_uint(gq[u]) & 0x7FFFFFFFu;
-                if (v >= 0x7F800000u) bad = 1; else m = max(m, v);
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        m = max(m, (uint32_t)__shfl_xor((int)m, d));
-        bad |= (uint32_t)__shfl_xor((int)bad, d);
-    }
-    if (lane == 0) { red[wave] = m; red[BWD_BLOCK / 64 + wave] = bad; }
-    __syncthreads();
-    if (tid == 0) {
-        m = 0; bad = 0;
-        for (int w = 0; w < BWD_BLOCK / 64; w++) { m = max(m, red[w]); bad |= red[BWD_BLOCK / 64 + w]; }
-        *out = make_uint2(m, bad);
-    }
-}
-
-// Pre-kernel of the workspace variant: ONE pass over all pixels of the batch resolves each pixel's triangle to its three
-// vertex ids (the scattered gathers, done once instead of once per owner workgroup) and writes a 16-byte record
-// {p1, p2, p3, g bits} per pixel -- p1 = -1 for pixels that contribute nothing (background, bad ids).  The owners then
-// STREAM the records.  Lane-consecutive pixels: a gather instruction's 64 lanes hold neighbouring triangles.
-constexpr int REC_PX = 1024;  // pixels per records-kernel workgroup (256 threads x 4)
-// FORM (fr_decode_render_backward): g is not read from depth_grad but formed here, per pixel, in fp32 without contraction --
-//   g = +0;  g += (g_net[..,0] * im_gray) * m1, m1 = (1e-6f <= depth && depth <= 1.0f);  g += g_dimg * m2, m2 = (depth >= 1e-6f);
-//   g += g_depth -- absent planes skipped, the masks MULTIPLIED in as 1.0f / 0.0f (an infinite gradient on a masked pixel is a
-// NaN, as in the torch expression this replaces).  The extra planes are streamed like g and tri_ind: lane-consecutive pixels
-// (the 7-channel plane at a 28-byte stride: seven lines per 64 lanes, each line shared by the lanes that touch it).
-template <bool FORM>
-__device__ __forceinline__ void bwd_records_body(const BwdRenderArgs& a, int4* rec, uint2* partial, int chunks) {
-    __shared__ uint32_t red[8];
-    const int b = (int)blockIdx.x / chunks, ch = (int)blockIdx.x - b * chunks;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* __restrict__ tri0 = a.tri;
-    const float* __restrict__ tri1 = a.tri + a.ntri;
-    const float* __restrict__ tri2 = a.tri + 2 * (size_t)a.ntri;
-    const float* __restrict__ g = a.depth_grad + (size_t)b * a.npix;
-    const float* __restrict__ ti = a.tri_ind + (size_t)b * a.npix;
-    int4* __restrict__ out = rec + (size_t)b * a.npix;
-    constexpr int PU = REC_PX / 256;
-    const int i0 = ch * REC_PX + tid;
-    float gq[PU], tq[PU];
-    if constexpr (!FORM) {
-#pragma unroll
-        for (int u = 0; u < PU; u++) {
-            const int i = min(i0 + u * 256, a.npix - 1);
-            gq[u] = g[i];
-            tq[u] = ti[i];
-        }
-    } else {
-        const bool hn = a.g_net != nullptr, hi = a.g_dimg != nullptr, hd = a.depth_grad != nullptr;   // (uniform)
-        float gn[PU], gi[PU], gd[PU], im[PU], dp[PU];
-#pragma unroll
-        for (int u = 0; u < PU; u++) {
-            const size_t i = (size_t)b * a.npix + min(i0 + u * 256, a.npix - 1);
-            tq[u] = a.tri_ind[i];
-            gn[u] = gi[u] = gd[u] = im[u] = dp[u] = 0.f;
-            if (hn) { gn[u] = a.g_net[i * 7]; im[u] = a.im_gray[i]; }
-            if (hi) gi[u] = a.g_dimg[i];
-            if (hn || hi) dp[u] = a.depth[i];
-            if (hd) gd[u] = a.depth_grad[i];
-        }
-#pragma unroll
-        for (int u = 0; u < PU; u++) {
-            float gg = 0.f;
-            if (hn) gg = gg + (gn[u] * im[u]) * ((1e-6f <= dp[u] && dp[u] <= 1.0f) ? 1.0f : 0.0f);
-            if (hi) gg = gg + gi[u] * ((dp[u] >= 1e-6f) ? 1.0f : 0.0f);
-            if (hd) gg = gg + gd[u];
-            gq[u] = gg;
-        }
-    }
-    int t[PU];
-    float f[PU][3];
-#pragma unroll
-    for (int u = 0; u < PU; u++) {
-        t[u] = bwd_tri_of(tq[u], a.ntri);
-        const int tt = max(t[u], 0);
-        f[u][0] = tri0[tt]; f[u][1] = tri1[tt]; f[u][2] = tri2[tt];
-    }
-    uint32_t m = 0, bad = 0;
-#pragma unroll
-    for (int u = 0; u < PU; u++) {
-        const int i = i0 + u * 256;
-        if (i < a.npix) {
-            const int p1 = f2i_x86(f[u][0]), p2 = f2i_x86(f[u][1]), p3 = f2i_x86(f[u][2]);
-            const bool ok = t[u] >= 0 && (unsigned)p1 < (unsigned)a.nver && (unsigned)p2 < (unsigned)a.nver &&
-                            (unsigned)p3 < (unsigned)a.nver;
-            out[i] = make_int4(ok ? p1 : -1, p2, p3, (int)__float_as_uint(gq[u]));
-            if (t[u] >= 0) {  // the face's largest |g| over the covered pixels (the predicate of bwd_face_max), in parts
-                const uint32_t v = __float_as_uint(gq[u]) & 0x7FFFFFFFu;
-                if (v >= 0x7F800000u) bad = 1; else m = max(m, v);
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        m = max(m, (uint32_t)__shfl_xor((int)m, d));
-        bad |= (uint32_t)__shfl_xor((int)bad, d);
-    }
-    if (lane == 0) { red[wave] = m; red[4 + wave] = bad; }
-    __syncthreads();
-    if (tid == 0)
-        partial[(size_t)b * chunks + ch] = make_uint2(max(max(red[0], red[1]), max(red[2], red[3])),
-                                                      red[4] | red[5] | red[6] | red[7]);
-}
-__global__ __launch_bounds__(256) void bwd_records_kernel(BwdRenderArgs a, int4* rec, uint2* partial, int chunks) {
-    bwd_records_body<false>(a, rec, partial, chunks);
-}
-__global__ __launch_bounds__(256) void bwd_records_form_kernel(BwdRenderArgs a, int4* rec, uint2* partial, int chunks) {
-    bwd_records_body<true>(a, rec, partial, chunks);
-}
-
-// PACKED (workspace variant): the owners stream the per-pixel records of bwd_records_kernel (the id gathers -- repeated by
-// every owner of the face, they are what the plain variant spends its time on -- were done once); otherwise float ids
-// gathered in-kernel.
-template <bool PACKED>
-__global__ __launch_bounds__(BWD_BLOCK) void render_backward_kernel(BwdRenderArgs a) {
-    // all LDS is dynamic (the launcher raises the dynamic limit to the CU's full 160 KiB, which leaves no room for
-    // static objects): [range] accumulators, then two small per-wave reduction arrays
-    extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];  // [range]
-    uint32_t* red = reinterpret_cast<uint32_t*>(acc + a.range);               // [2 * BWD_BLOCK / 64]
-    const int tid = threadIdx.x;
-    // block -> (face, owner): blocks that share blockIdx % 8 share an XCD / L2; when the batch is a multiple of 8 the
-    // owners of a face are given ids of one residue class, so the face's planes / records are fetched into ONE L2 and
-    // re-read there, instead of once per owner
-    int b, sp;
-    if ((a.B & 7) == 0) {
-        const int xcd = (int)blockIdx.x & 7, q = (int)blockIdx.x >> 3;
-        b = (q / a.splits) * 8 + xcd;
-        sp = q % a.splits;
-    } else {
-        b = (int)blockIdx.x / a.splits;
-        sp = (int)blockIdx.x - b * a.splits;
-    }
-    const int v0 = sp * a.range;
-    const int v1 = min(a.nver, v0 + a.range);
-    const int npix = a.npix, ntri = a.ntri, nver = a.nver;
-    const float* __restrict__ g = a.depth_grad + (size_t)b * npix;
-    const float* __restrict__ ti = a.tri_ind + (size_t)b * npix;
-    const float* __restrict__ tri0 = a.tri;
-    const float* __restrict__ tri1 = a.tri + ntri;
-    const float* __restrict__ tri2 = a.tri + 2 * (size_t)ntri;
-    for (int i = tid; i < v1 - v0; i += BWD_BLOCK) acc[i] = 0ull;
-
-    // the face's largest |g| over the covered pixels (max is order independent); c = g/3 is at most two binades below,
-    // which the scale accounts for -- so the scan needs no division
-    uint32_t m, bad;
-    const int4* __restrict__ rec = PACKED ? a.rec + (size_t)b * npix : nullptr;
-    if constexpr (PACKED) {
-        // the records kernel left the face's largest |g| in parts: one per 1,024-pixel chunk
-        m = 0; bad = 0;
-        for (int c = tid; c < a.chunks; c += BWD_BLOCK) {
-            const uint2 pm = a.partial[(size_t)b * a.chunks + c];
-            m = max(m, pm.x); bad |= pm.y;
-        }
-        const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            m = max(m, (uint32_t)__shfl_xor((int)m, d));
-            bad |= (uint32_t)__shfl_xor((int)bad, d);
-        }
-        if (lane == 0) { red[wave] = m; red[BWD_BLOCK / 64 + wave] = bad; }
-        __syncthreads();
-        m = 0; bad = 0;
-#pragma unroll
-        for (int w = 0; w < BWD_BLOCK / 64; w++) { m = max(m, red[w]); bad |= red[BWD_BLOCK / 64 + w]; }
-    } else {
-        uint2* slot = reinterpret_cast<uint2*>(red + 2 * (BWD_BLOCK / 64));
-        bwd_face_max(a, b, red, slot);
-        __syncthreads();
-        m = slot->x; bad = slot->y;
-    }
-    float* gx = a.vertex_grad + (size_t)b * 3 * nver;
-    float* gy = gx + nver;
-    float* gz = gy + nver;
-    // scale 2^k from e = floor(log2 max|g|): the largest term c = g/3 lands in [2^38, 2^40); up to 2^21 terms (3 per
-    // pixel) stay below 2^62
-    const int e = (int)(m >> 23) - 127;  // floor(log2 max|g|) for a normal float; -127 for subnormals / zero
-    const double scale = ldexp(1.0, 40 - a.shift - e);
-    const double inv_scale = ldexp(1.0, e - 40 + a.shift);
-    float* facc = reinterpret_cast<float*>(acc);  // Inf / NaN gradients: fp32 LDS atomics in the same buffer
-    if (bad) {
-        __syncthreads();
-        for (int i = tid; i < v1 - v0; i += BWD_BLOCK) facc[i] = 0.0f;
-    }
-    __syncthreads();
-    // one contribution: c = (g * 1.0f) / 3.0f to the three vertices of triangle t that this workgroup owns
-    auto add = [&](float gv, int p1, int p2, int p3, bool ids_ok) {
-        if (!ids_ok) return;
-        // ownership first: every owner of the face sees every pixel, but only ~1 / splits of them land in its range --
-        // the division and the fixed-point conversion are done for those only
-        const bool in1 = p1 >= v0 && p1 < v1, in2 = p2 >= v0 && p2 < v1, in3 = p3 >= v0 && p3 < v1;
-        if (!(in1 || in2 || in3)) return;
-        const float c = gv * 1.0f / 3.0f;
-        if (bad) {
-            if (in1) atomicAdd(&facc[p1 - v0], c);
-            if (in2) atomicAdd(&facc[p2 - v0], c);
-            if (in3) atomicAdd(&facc[p3 - v0], c);
-        } else {
-            const unsigned long long q = (unsigned long long)__double2ll_rn((double)c * scale);  // exact product, one rounding
-            if (q == 0ull) return;
-            if (in1) atomicAdd(&acc[p1 - v0], q);
-            if (in2) atomicAdd(&acc[p2 - v0], q);
-            if (in3) atomicAdd(&acc[p3 - v0], q);
-        }
-    };
-    if ((m != 0 || bad) && PACKED) {
-        // the owners stream the face's records: no gathers, no dependent loads
-        constexpr int QU = 8;
-        for (int i0 = tid; i0 < npix; i0 += QU * BWD_BLOCK) {
-            int4 rq[QU];
-#pragma unroll
-            for (int u = 0; u < QU; u++) rq[u] = rec[min(i0 + u * BWD_BLOCK, npix - 1)];
-#pragma unroll
-            for (int u = 0; u < QU; u++)
-                if (i0 + u * BWD_BLOCK < npix) add(__uint_as_float((uint32_t)rq[u].w), rq[u].x, rq[u].y, rq[u].z, rq[u].x >= 0);
-        }
-    }
-    if ((m != 0 || bad) && !PACKED) {
-        // The scan.  Lane l of a trip's u-th slice takes pixel i0 + u * BLOCK: the 64 lanes of a gather instruction hold
-        // 64 CONSECUTIVE pixels -> neighbouring triangles -> a few cache lines of the id table per instruction (four
-        // pixels per lane, the obvious 16-byte-load mapping, puts every lane of a gather on its own line and runs the
-        // texture addresser at one lane per cycle).  Software pipelined: the (g, tri_ind) values of the NEXT trip are
-        // requested before the id gathers of the current one are consumed.
-        constexpr int QU = 8;
-        float gv[QU], tv[QU];
-#pragma unroll
-        for (int u = 0; u < QU; u++) {
-            const int i = tid + u * BWD_BLOCK;
-            gv[u] = 0.f; tv[u] = -1.f;
-            if (i < npix) { gv[u] = g[i]; tv[u] = ti[i]; }
-        }
-        for (int i0 = tid; i0 < npix; i0 += QU * BWD_BLOCK) {
-            int t[QU], id[QU][3];
-            bool ok[QU];
-            float gc[QU];
-#pragma unroll
-            for (int u = 0; u < QU; u++) {
-                t[u] = bwd_tri_of(tv[u], ntri);
-                gc[u] = gv[u];
-                const int tt = max(t[u], 0);
-                id[u][0] = f2i_x86(tri0[tt]); id[u][1] = f2i_x86(tri1[tt]); id[u][2] = f2i_x86(tri2[tt]);
-                ok[u] = (unsigned)id[u][0] < (unsigned)nver && (unsigned)id[u][1] < (unsigned)nver &&
-                        (unsigned)id[u][2] < (unsigned)nver;
-            }
-#pragma unroll
-            for (int u = 0; u < QU; u++) {
-                const int in = i0 + (QU + u) * BWD_BLOCK;
-                tv[u] = -1.f;
-                if (in < npix) { gv[u] = g[in]; tv[u] = ti[in]; }
-            }
-#pragma unroll
-            for (int u = 0; u < QU; u++)
-                if (t[u] >= 0) add(gc[u], id[u][0], id[u][1], id[u][2], ok[u]);
-        }
-    }
-    __syncthreads();
-    if (a.zpitch > 0) {   // (uniform) z-only mode: the x / y rows -- zeros -- are neither written here nor read by the consumer
-        float* zrow = a.vertex_grad + (size_t)b * a.zpitch;
-        for (int i = tid; i < v1 - v0; i += BWD_BLOCK)
-            zrow[v0 + i] = bad ? facc[i] : (float)((double)(float)(long long)acc[i] * inv_scale);
-        return;
-    }
-    for (int i = tid; i < v1 - v0; i += BWD_BLOCK) {
-        gx[v0 + i] = 0.0f;
-        gy[v0 + i] = 0.0f;
-        // fixed point: one rounding to 24 bits (int64 -> fp32), then an exact power-of-two scaling in double
-        gz[v0 + i] = bad ? facc[i] : (float)((double)(float)(long long)acc[i] * inv_scale);
-    }
-}
-
 }  // namespace fr
 
 namespace {
@@ -1814,112 +1478,4 @@ static int launch_render_impl(const float* vertex, const float* tri, const float
         rc = fused ? launch_resolve<256, true>(a, nbins, g.lds, stream) : launch_resolve<256, false>(a, nbins, g.lds, stream);
     if (rc != FR_OK) return rc;
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
-}
-
-// workspace of the ws variant: one 16-byte record per pixel of the batch + one {max, flag} pair per 1,024-pixel chunk
-size_t fr_render_backward_workspace_bytes_impl(int B, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t npix = (size_t)H * W, chunks = (npix + fr::REC_PX - 1) / fr::REC_PX;
-    return (size_t)B * npix * sizeof(int4) + (size_t)B * chunks * sizeof(uint2);
-}
-
-// The launch geometry of the backward, chosen in ONE place: the launcher below and the test hook
-// fr_debug_render_bwd_geom both read it from here.
-namespace {
-struct BwdRenderGeom {
-    int splits, range;  // owner workgroups per face, vertices per owner
-    int shift;          // headroom bits given up by images above 2^20 pixels
-    int chunks;         // 1,024-pixel chunks of the records kernel (workspace variant)
-    size_t lds;         // dynamic LDS of render_backward_kernel
-    bool xcd_map;       // the kernel's block -> (face, owner) map keeps a face's owners on one XCD (batch a multiple of 8)
-};
-BwdRenderGeom render_bwd_geom(int B, int nver, long long npix) {
-    using namespace fr;
-    BwdRenderGeom g{};
-    // the int64 headroom covers 3 * 2^20 terms per vertex at the full 38-bit resolution; larger images give up one bit of
-    // resolution per doubling (the forward renders them through the scan fallback, so the backward must take them too)
-    while ((1ll << (20 + g.shift)) < npix) g.shift++;
-    // owners per face: enough for the LDS budget, and for ~one workgroup per CU on small batches
-    int splits = (nver + BWD_RANGE_MAX - 1) / BWD_RANGE_MAX;
-    const int want = (256 + B - 1) / B;
-    if (splits < want) splits = want;
-    if (splits > nver) splits = nver;
-    g.range = (nver + splits - 1) / splits;
-    g.splits = (nver + g.range - 1) / g.range;
-    g.chunks = (int)((npix + REC_PX - 1) / REC_PX);
-    g.lds = (size_t)g.range * sizeof(unsigned long long) + 2 * (BWD_BLOCK / 64) * sizeof(uint32_t) + 16;
-    g.xcd_map = (B & 7) == 0;
-    return g;
-}
-}  // namespace
-
-// test hook (tests/test_capi_cpu.py, tests/test_render_backward_exact_gpu.py): the geometry the backward launcher would
-// choose, without a GPU.  out = {splits, range, shift, chunks, lds_bytes, xcd_map}; all zero for a shape that launches
-// no kernel or is refused
-extern "C" void fr_debug_render_bwd_geom(int B, int nver, int H, int W, int* out) {
-    for (int i = 0; i < 6; i++) out[i] = 0;
-    const long long npix = (long long)H * W;
-    if (B <= 0 || nver <= 0 || H <= 0 || W <= 0 || npix > 0x7FFFFFFFll) return;
-    const BwdRenderGeom g = render_bwd_geom(B, nver, npix);
-    out[0] = g.splits; out[1] = g.range; out[2] = g.shift; out[3] = g.chunks; out[4] = (int)g.lds; out[5] = g.xcd_map ? 1 : 0;
-}
-
-static int launch_render_backward_impl(const FrPixelGrad* pg, const float* depth_grad, const float* tri, const float* tri_ind,
-                                       float* vertex_grad, long long zpitch, int B, int nver, int ntri, int H, int W,
-                                       void* workspace, size_t ws_bytes, hipStream_t stream) {
-    using namespace fr;
-    // (z-only mode: `vertex_grad` is the [B, zpitch] plane; its pad floats are never written or read)
-    const size_t bytes = zpitch > 0 ? (size_t)B * zpitch * sizeof(float) : (size_t)B * 3 * nver * sizeof(float);
-    const long long npix = (long long)H * W;
-    if (npix * B == 0 || ntri == 0 || nver == 0)
-        return (!bytes || hipMemsetAsync(vertex_grad, 0, bytes, stream) == hipSuccess) ? FR_OK : FR_ERR_LAUNCH;
-    if (npix > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
-    const BwdRenderGeom geo = render_bwd_geom(B, nver, npix);
-    const int splits = geo.splits, chunks = geo.chunks;
-    if ((long long)B * splits > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
-    BwdRenderArgs a;
-    a.depth_grad = depth_grad; a.tri = tri; a.tri_ind = tri_ind; a.vertex_grad = vertex_grad;
-    a.nver = nver; a.ntri = ntri; a.npix = (int)npix; a.splits = splits; a.range = geo.range; a.shift = geo.shift;
-    a.g_net = pg ? pg->g_net_input : nullptr; a.g_dimg = pg ? pg->g_depth_img : nullptr;
-    a.im_gray = pg ? pg->im_gray : nullptr; a.depth = pg ? pg->depth : nullptr;
-    a.zpitch = zpitch;
-    // with a workspace one pre-kernel resolves every pixel to its vertex ids once (instead of once per owner workgroup)
-    // and the owners stream 16-byte records
-    const bool packed = workspace && ws_bytes >= fr_render_backward_workspace_bytes_impl(B, H, W) &&
-                        (((uintptr_t)workspace) & 15) == 0;
-    if (pg && !packed) return FR_ERR_WORKSPACE;   // (the formed gradient exists in the records only)
-    int4* rec = reinterpret_cast<int4*>(workspace);
-    uint2* partial = reinterpret_cast<uint2*>(rec + (size_t)B * npix);
-    a.rec = packed ? rec : nullptr;
-    a.partial = packed ? partial : nullptr;
-    a.B = B; a.chunks = chunks;
-    const size_t lds = geo.lds;
-    static fr_lds_flags_t lds_ok[2][64];
-    if (packed) {
-        if ((long long)B * chunks > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
-        if (pg) hipLaunchKernelGGL(bwd_records_form_kernel, dim3((unsigned)(B * chunks)), dim3(256), 0, stream, a, rec, partial, chunks);
-        else hipLaunchKernelGGL(bwd_records_kernel, dim3((unsigned)(B * chunks)), dim3(256), 0, stream, a, rec, partial, chunks);
-        if (fr_allow_full_lds(reinterpret_cast<const void*>(&render_backward_kernel<true>), lds_ok[1]) != hipSuccess)
-            return FR_ERR_LAUNCH;
-        hipLaunchKernelGGL(render_backward_kernel<true>, dim3((unsigned)(B * splits)), dim3(BWD_BLOCK), lds, stream, a);
-    } else {
-        if (fr_allow_full_lds(reinterpret_cast<const void*>(&render_backward_kernel<false>), lds_ok[0]) != hipSuccess)
-            return FR_ERR_LAUNCH;
-        hipLaunchKernelGGL(render_backward_kernel<false>, dim3((unsigned)(B * splits)), dim3(BWD_BLOCK), lds, stream, a);
-    }
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
-}
-
-int fr_launch_render_backward(const float* depth_grad, const float* tri, const float* tri_ind, float* vertex_grad,
-                              int B, int nver, int ntri, int H, int W, void* workspace, size_t ws_bytes,
-                              hipStream_t stream) {
-    return launch_render_backward_impl(nullptr, depth_grad, tri, tri_ind, vertex_grad, 0, B, nver, ntri, H, W, workspace,
-                                       ws_bytes, stream);
-}
-
-// fr_decode_render_backward's first half: pixel gradient formed in the records pass, owners write the pitched z plane only
-int fr_launch_render_backward_z(const FrPixelGrad& pg, const float* tri, const float* tri_ind, float* zplane, int zpitch,
-                                int B, int nver, int ntri, int H, int W, void* workspace, size_t ws_bytes, hipStream_t stream) {
-    return launch_render_backward_impl(&pg, pg.g_depth, tri, tri_ind, zplane, zpitch, B, nver, ntri, H, W, workspace, ws_bytes,
-                                       stream);
 }

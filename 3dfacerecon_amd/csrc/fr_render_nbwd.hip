@@ -3,7 +3,7 @@
 // winning triangle's vertices.  The reference has no such gradient (render_depth_op.cc:359-363 writes zeros into the x / y
 // rows and never reads normal_grad); fr_render_depth_backward keeps that definition, this call ADDS the missing part.
 //
-// Two kernels, the scheme of render_backward_kernel (fr_render.hip) with nine terms per pixel instead of one:
+// Two kernels, the owner-scatter scheme of fr_owner_scatter.h with nine terms per pixel:
 //   nbwd_records_kernel   one pass over the batch's pixels: triangle -> three vertex ids -> nine vertex coordinates
 //                         (the only gathers of the call, done once), the pixel's nine fp32 terms formed in double, written
 //                         as three 16-byte planes {p1 p2 p3 t1x | t1y t1z t2x t2y | t2z t3x t3y t3z}; the largest |term|
@@ -12,13 +12,14 @@
 //                         of the pixels that land in its range only, and adds the terms as 64-bit fixed-point integers to
 //                         three LDS accumulators per owned vertex (integer addition: exact, any order).  No two workgroups
 //                         write the same element, nothing needs zeroing, no float atomics on the finite path.
-#include "fr_common.h"
+#include "fr_owner_scatter.h"
 
 namespace fr {
 
-constexpr int NB_BLOCK = 1024;
+constexpr int NB_BLOCK = OWNER_BLOCK;
 constexpr int NB_RANGE_MAX = 6656;  // vertices per owner: 3 accumulators x 8 B each = 156 KiB of the CU's 160 KiB of LDS
-constexpr int NB_REC_PX = 1024;     // pixels per records-kernel workgroup (256 threads x 4)
+constexpr int NB_TOP = 39;          // the face's largest finite |term| lands in [2^39, 2^40); an element receives at most three terms
+                                    // per pixel (a triangle naming one vertex three times), 3 * 2^20 of them stay below 2^62
 
 struct NbwdArgs {
     const float* ngrad;     // three floats per pixel, `gstride` floats between pixels
@@ -71,7 +72,7 @@ __device__ __forceinline__ void nbwd_terms(const float (&P)[3][3] /*[vertex][xyz
 __global__ __launch_bounds__(256) void nbwd_records_kernel(NbwdArgs a) {
     __shared__ uint32_t red[8];
     const int b = (int)blockIdx.x / a.chunks, ch = (int)blockIdx.x - b * a.chunks;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int npix = a.npix, ntri = a.ntri, nver = a.nver;
     const float* __restrict__ tri0 = a.tri;
     const float* __restrict__ tri1 = a.tri + ntri;
@@ -82,8 +83,8 @@ __global__ __launch_bounds__(256) void nbwd_records_kernel(NbwdArgs a) {
     int4* __restrict__ r0 = a.rec + (size_t)b * 3 * npix;
     int4* __restrict__ r1 = r0 + npix;
     int4* __restrict__ r2 = r1 + npix;
-    constexpr int PU = NB_REC_PX / 256;
-    const int i0 = ch * NB_REC_PX + tid;   // lane-consecutive pixels: a gather instruction's 64 lanes hold neighbouring triangles
+    constexpr int PU = REC_PX / 256;
+    const int i0 = ch * REC_PX + tid;   // lane-consecutive pixels: a gather instruction's 64 lanes hold neighbouring triangles
     float tq[PU], g[PU][3];
 #pragma unroll
     for (int u = 0; u < PU; u++) {
@@ -95,14 +96,7 @@ __global__ __launch_bounds__(256) void nbwd_records_kernel(NbwdArgs a) {
     int id[PU][3];
     bool ok[PU];
 #pragma unroll
-    for (int u = 0; u < PU; u++) {
-        const int t = f2i_x86(tq[u]);
-        const bool covered = t >= 0 && t < ntri && i0 + u * 256 < npix;
-        const int tt = covered ? t : 0;
-        id[u][0] = f2i_x86(tri0[tt]); id[u][1] = f2i_x86(tri1[tt]); id[u][2] = f2i_x86(tri2[tt]);
-        ok[u] = covered && (unsigned)id[u][0] < (unsigned)nver && (unsigned)id[u][1] < (unsigned)nver &&
-                (unsigned)id[u][2] < (unsigned)nver;
-    }
+    for (int u = 0; u < PU; u++) ok[u] = pixel_tri_ids(tq[u], tri0, tri1, tri2, ntri, nver, id[u]).ok && i0 + u * 256 < npix;
     float P[PU][3][3];
 #pragma unroll
     for (int u = 0; u < PU; u++)
@@ -124,67 +118,29 @@ __global__ __launch_bounds__(256) void nbwd_records_kernel(NbwdArgs a) {
         float t[9];
         nbwd_terms(P[u], g[u], a.mode, t);
 #pragma unroll
-        for (int j = 0; j < 9; j++) {
-            const uint32_t v = __float_as_uint(t[j]) & 0x7FFFFFFFu;
-            if (v >= 0x7F800000u) bad = 1; else m = max(m, v);
-        }
+        for (int j = 0; j < 9; j++) track_term(__float_as_uint(t[j]), m, bad);   // over the OK pixels
         r0[i] = make_int4(id[u][0], id[u][1], id[u][2], (int)__float_as_uint(t[0]));
         r1[i] = make_int4((int)__float_as_uint(t[1]), (int)__float_as_uint(t[2]), (int)__float_as_uint(t[3]), (int)__float_as_uint(t[4]));
         r2[i] = make_int4((int)__float_as_uint(t[5]), (int)__float_as_uint(t[6]), (int)__float_as_uint(t[7]), (int)__float_as_uint(t[8]));
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        m = max(m, (uint32_t)__shfl_xor((int)m, d));
-        bad |= (uint32_t)__shfl_xor((int)bad, d);
-    }
-    if (lane == 0) { red[wave] = m; red[4 + wave] = bad; }
-    __syncthreads();
-    if (tid == 0)
-        a.partial[(size_t)b * a.chunks + ch] = make_uint2(max(max(red[0], red[1]), max(red[2], red[3])),
-                                                          red[4] | red[5] | red[6] | red[7]);
+    chunk_publish(m, bad, red, &a.partial[(size_t)b * a.chunks + ch]);
 }
 
 __global__ __launch_bounds__(NB_BLOCK) void nbwd_owner_kernel(NbwdArgs a) {
     // all LDS is dynamic (the launcher raises the limit to the CU's 160 KiB): [3][range] accumulators, then the reduction array
     extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];  // [3 * range]
     uint32_t* red = reinterpret_cast<uint32_t*>(acc + 3 * (size_t)a.range);  // [2 * NB_BLOCK / 64]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // block -> (face, owner) as in render_backward_kernel: with a batch that is a multiple of 8 the owners of a face share
-    // blockIdx % 8, hence an XCD and its L2, where the face's records are fetched once and re-read by the other owners
+    const int tid = threadIdx.x;
     int b, sp;
-    if ((a.B & 7) == 0) {
-        const int xcd = (int)blockIdx.x & 7, q = (int)blockIdx.x >> 3;
-        b = (q / a.splits) * 8 + xcd;
-        sp = q % a.splits;
-    } else {
-        b = (int)blockIdx.x / a.splits;
-        sp = (int)blockIdx.x - b * a.splits;
-    }
+    owner_block_map(a.B, a.splits, &b, &sp);
     const int range = a.range, npix = a.npix, nver = a.nver;
     const int v0 = sp * range;
     const int v1 = min(nver, v0 + range);
     const int n = v1 - v0;
     for (int i = tid; i < 3 * range; i += NB_BLOCK) acc[i] = 0ull;
-    uint32_t m = 0, bad = 0;
-    for (int c = tid; c < a.chunks; c += NB_BLOCK) {
-        const uint2 pm = a.partial[(size_t)b * a.chunks + c];
-        m = max(m, pm.x); bad |= pm.y;
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        m = max(m, (uint32_t)__shfl_xor((int)m, d));
-        bad |= (uint32_t)__shfl_xor((int)bad, d);
-    }
-    if (lane == 0) { red[wave] = m; red[NB_BLOCK / 64 + wave] = bad; }
-    __syncthreads();
-    m = 0; bad = 0;
-#pragma unroll
-    for (int w = 0; w < NB_BLOCK / 64; w++) { m = max(m, red[w]); bad |= red[NB_BLOCK / 64 + w]; }
-    // scale 2^k from e = floor(log2 M), M the face's largest finite |term|: M lands in [2^39, 2^40); an element receives at
-    // most three terms per pixel (a triangle naming one vertex three times), 3 * 2^20 of them stay below 2^62
-    const int e = (int)(m >> 23) - 127;
-    const double scale = ldexp(1.0, 39 - a.shift - e);
-    const double inv_scale = ldexp(1.0, e - 39 + a.shift);
+    const uint2 mb = scope_max<NB_BLOCK>(a.partial + (size_t)b * a.chunks, a.chunks, red);
+    const uint32_t m = mb.x, bad = mb.y;
+    const FixedScale<NB_TOP> fx(m, a.shift);
     float* facc = reinterpret_cast<float*>(acc);   // a face with an Inf / NaN term: fp32 LDS atomics, [3][range] floats
     if (bad) {
         __syncthreads();
@@ -200,36 +156,20 @@ __global__ __launch_bounds__(NB_BLOCK) void nbwd_owner_kernel(NbwdArgs a) {
             atomicAdd(&facc[range + local], ty);
             atomicAdd(&facc[2 * range + local], tz);
         } else {
-            // the term has 24 significant bits and the scale is a power of two: the product is exact, one rounding to the grid
-            const unsigned long long qx = (unsigned long long)__double2ll_rn((double)tx * scale);
-            const unsigned long long qy = (unsigned long long)__double2ll_rn((double)ty * scale);
-            const unsigned long long qz = (unsigned long long)__double2ll_rn((double)tz * scale);
-            if (qx) atomicAdd(&acc[local], qx);
-            if (qy) atomicAdd(&acc[range + local], qy);
-            if (qz) atomicAdd(&acc[2 * range + local], qz);
+            const unsigned long long qx = fx.to_fixed(tx), qy = fx.to_fixed(ty), qz = fx.to_fixed(tz);
+            fixed_add(&acc[local], qx);
+            fixed_add(&acc[range + local], qy);
+            fixed_add(&acc[2 * range + local], qz);
         }
     };
     if (m != 0 || bad) {
-        constexpr int QU = 8;
-        for (int i0 = tid; i0 < npix; i0 += QU * NB_BLOCK) {
-            int4 q0[QU];
-#pragma unroll
-            for (int u = 0; u < QU; u++) q0[u] = r0[min(i0 + u * NB_BLOCK, npix - 1)];
-#pragma unroll
-            for (int u = 0; u < QU; u++) {
-                const int i = i0 + u * NB_BLOCK;
-                const int p1 = q0[u].x, p2 = q0[u].y, p3 = q0[u].z;
-                if (i >= npix || p1 < 0) continue;
-                // ownership first: every owner sees every pixel, ~1 / splits of them land in its range -- the term planes are
-                // fetched for those only
-                const bool in1 = p1 >= v0 && p1 < v1, in2 = p2 >= v0 && p2 < v1, in3 = p3 >= v0 && p3 < v1;
-                if (!(in1 || in2 || in3)) continue;
-                const int4 q1 = r1[i], q2 = r2[i];
-                if (in1) add3(p1 - v0, __int_as_float(q0[u].w), __int_as_float(q1.x), __int_as_float(q1.y));
-                if (in2) add3(p2 - v0, __int_as_float(q1.z), __int_as_float(q1.w), __int_as_float(q2.x));
-                if (in3) add3(p3 - v0, __int_as_float(q2.y), __int_as_float(q2.z), __int_as_float(q2.w));
-            }
-        }
+        // the two term planes are fetched for the pixels that land in this range only
+        owner_stream<NB_BLOCK>(r0, npix, v0, v1, [&](int i, const int4& q0, bool in1, bool in2, bool in3) {
+            const int4 q1 = r1[i], q2 = r2[i];
+            if (in1) add3(q0.x - v0, __int_as_float(q0.w), __int_as_float(q1.x), __int_as_float(q1.y));
+            if (in2) add3(q0.y - v0, __int_as_float(q1.z), __int_as_float(q1.w), __int_as_float(q2.x));
+            if (in3) add3(q0.z - v0, __int_as_float(q2.y), __int_as_float(q2.z), __int_as_float(q2.w));
+        });
     }
     __syncthreads();
     float* out = a.vertex_grad + (size_t)b * 3 * nver;
@@ -237,8 +177,7 @@ __global__ __launch_bounds__(NB_BLOCK) void nbwd_owner_kernel(NbwdArgs a) {
     for (int c = 0; c < 3; c++) {
         float* row = out + (size_t)c * nver + v0;
         for (int i = tid; i < n; i += NB_BLOCK) {
-            // fixed point: one rounding to 24 bits (int64 -> fp32), then an exact power-of-two scaling in double
-            const float v = bad ? facc[c * range + i] : (float)((double)(float)(long long)acc[c * range + i] * inv_scale);
+            const float v = bad ? facc[c * range + i] : fx.round(acc[c * range + i]);
             row[i] = a.accumulate ? row[i] + v : v;
         }
     }
@@ -246,34 +185,15 @@ __global__ __launch_bounds__(NB_BLOCK) void nbwd_owner_kernel(NbwdArgs a) {
 
 }  // namespace fr
 
-// The launch geometry, chosen in ONE place: the launcher and the test hook both read it from here.
-namespace {
-struct NbwdGeom {
-    int splits, range, shift, chunks;
-    size_t lds;
-    bool xcd_map;
-};
-NbwdGeom nbwd_geom(int B, int nver, long long npix) {
-    using namespace fr;
-    NbwdGeom g{};
-    while ((1ll << (20 + g.shift)) < npix) g.shift++;
-    // owners per face: enough for the LDS budget, and for ~one workgroup per CU on small batches
-    int splits = (nver + NB_RANGE_MAX - 1) / NB_RANGE_MAX;
-    const int want = (256 + B - 1) / B;
-    if (splits < want) splits = want;
-    if (splits > nver) splits = nver;
-    g.range = (nver + splits - 1) / splits;
-    g.splits = (nver + g.range - 1) / g.range;
-    g.chunks = (int)((npix + NB_REC_PX - 1) / NB_REC_PX);
-    g.lds = 3 * (size_t)g.range * sizeof(unsigned long long) + 2 * (NB_BLOCK / 64) * sizeof(uint32_t) + 16;
-    g.xcd_map = (B & 7) == 0;
-    return g;
+// The launch geometry, chosen in ONE place: the launcher and the test hook both read it from here.  (The splits are clamped to
+// one vertex per owner.)
+static fr::OwnerGeom nbwd_geom(int B, int nver, long long npix) {
+    return fr::owner_geom(B, nver, npix, npix, fr::NB_RANGE_MAX, 1, 3);
 }
-}  // namespace
 
 size_t fr_render_normal_backward_workspace_impl(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t npix = (size_t)H * W, chunks = (npix + fr::NB_REC_PX - 1) / fr::NB_REC_PX;
+    const size_t npix = (size_t)H * W, chunks = (npix + fr::REC_PX - 1) / fr::REC_PX;
     return (size_t)B * npix * 3 * sizeof(int4) + (size_t)B * chunks * sizeof(uint2);
 }
 
@@ -283,8 +203,7 @@ extern "C" void fr_debug_render_normal_bwd_geom(int B, int nver, int H, int W, i
     for (int i = 0; i < 6; i++) out[i] = 0;
     const long long npix = (long long)H * W;
     if (B <= 0 || nver <= 0 || H <= 0 || W <= 0 || npix > 0x7FFFFFFFll) return;
-    const NbwdGeom g = nbwd_geom(B, nver, npix);
-    out[0] = g.splits; out[1] = g.range; out[2] = g.shift; out[3] = g.chunks; out[4] = (int)g.lds; out[5] = g.xcd_map ? 1 : 0;
+    fr::owner_geom_report(nbwd_geom(B, nver, npix), B, out);
 }
 
 int fr_launch_render_normal_backward(const float* normal_grad, int grad_stride, const float* vertex, int vertex_pitch,
@@ -292,12 +211,9 @@ int fr_launch_render_normal_backward(const float* normal_grad, int grad_stride, 
                                      int H, int W, int mode, int accumulate, void* workspace, hipStream_t stream) {
     using namespace fr;
     const long long npix = (long long)H * W;
-    if (npix == 0 || ntri == 0) {   // no term exists: zeros, or the tensor as it is
-        if (accumulate) return FR_OK;
-        return hipMemsetAsync(vertex_grad, 0, (size_t)B * 3 * nver * sizeof(float), stream) == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
-    }
+    if (npix == 0 || ntri == 0) return owner_no_terms(vertex_grad, (size_t)B * 3 * nver * sizeof(float), accumulate, stream);
     if (npix > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
-    const NbwdGeom geo = nbwd_geom(B, nver, npix);
+    const OwnerGeom geo = nbwd_geom(B, nver, npix);
     if ((long long)B * geo.splits > 0x7FFFFFFFll || (long long)B * geo.chunks > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
     NbwdArgs a;
     a.ngrad = normal_grad; a.gstride = grad_stride; a.vertex = vertex; a.vpitch = vertex_pitch;

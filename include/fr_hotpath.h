@@ -496,7 +496,7 @@ void fr_debug_render_normal_bwd_geom(int B, int nver, int H, int W, int* out);
  * is FR_ERR_WORKSPACE.  H*W == 0 or ntri == 0 writes zeros (accumulate: leaves the tensor as it is).  Nothing is allocated or
  * synchronised; the call can be captured in a graph; reentrant under the rules at the top of this file, one workspace per call in
  * flight.
- * Kernels (csrc/fr_render_tbwd.hip; the scheme of fr_render_normal_backward): a records pass (triangle -> ids once, a 16-byte
+ * Kernels (csrc/fr_render_tbwd.hip on the shared scheme of csrc/fr_owner_scatter.h): a records pass (triangle -> ids once, a 16-byte
  * {p1,p2,p3,term0} plane and an 8-byte {term1,term2} plane, {max, non-finite} per chunk), then owner workgroups with three 64-bit
  * LDS accumulators per owned vertex that stream the id plane.  tex_batch == B: one owner per (face, vertex range) rounds and writes.
  * tex_batch == 1: owners are (face slice, vertex range), each stores its raw int64 slab [3][range] in the workspace with plain

@@ -1,7 +1,7 @@
 """The render backward's integer model in numpy: what fr_render_depth_backward(_ws) must return, BIT FOR BIT.
 
-Written from the text of include/fr_hotpath.h ("render_depth backward") and the comment above BWD_BLOCK in
-csrc/fr_render.hip; it shares no code with the oracle or the product.  Per face:
+Written from the text of include/fr_hotpath.h ("render_depth backward") and the header comments of
+csrc/fr_render_bwd.hip and csrc/fr_owner_scatter.h; it shares no code with the oracle or the product.  Per face:
 
   counted pixels   0 <= (int)tri_ind < ntri                 (x86 conversion: truncation, NaN / out of int32 -> INT_MIN)
   m                largest finite |g| over the counted pixels (as fp32 bits);  bad = an Inf / NaN among them

@@ -1,4 +1,4 @@
-"""GPU: fr_render_normal_backward (nbwd_records_kernel, nbwd_owner_kernel) held to its float64 model with exact sums
+"""GPU: fr_render_normal_backward (nbwd_records_kernel, nbwd_owner_kernel; csrc/fr_render_nbwd.hip) held to its float64 model with exact sums
 (tests/ref_normal_backward.py, pinned on the CPU by tests/test_normal_backward_cpu.py), and the opt-in `normal_grad` flag of the
 Python surface.
 

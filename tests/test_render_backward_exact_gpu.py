@@ -1,4 +1,4 @@
-"""GPU: the render backward (render_backward_kernel<PACKED>, bwd_records_kernel; fr_render_depth_backward and
+"""GPU: the render backward (render_backward_kernel<PACKED>, bwd_records_kernel in csrc/fr_render_bwd.hip; fr_render_depth_backward and
 fr_render_depth_backward_ws) held to its integer model (tests/ref_render_bwd_model.py, pinned on the CPU by
 tests/test_render_bwd_model_cpu.py) BIT FOR BIT, at every launch geometry the launcher chooses from and at the values
 where a fixed-point scatter goes wrong.

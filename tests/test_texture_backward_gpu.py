@@ -1,4 +1,4 @@
-"""GPU: fr_render_texture_backward (tbwd_records_kernel, tbwd_owner_kernel, tbwd_finish_kernel) held BIT FOR BIT to its integer
+"""GPU: fr_render_texture_backward (tbwd_records_kernel, tbwd_owner_kernel, tbwd_finish_kernel; csrc/fr_render_tbwd.hip) held BIT FOR BIT to its integer
 model (tests/ref_texture_backward.py, pinned on the CPU by tests/test_texture_backward_cpu.py), fr_sfs_intensity_backward_tex to
 numpy float64 on the state the GPU wrote, and the opt-in texture flags of the Python surface.
 
