@@ -246,6 +246,8 @@ def _bind(L):
     L.fr_debug_decode_bwd_geom.restype = None
     L.fr_debug_decode_geom.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
     L.fr_debug_decode_geom.restype = _i
+    L.fr_debug_decode_q_geom.argtypes = [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
+    L.fr_debug_decode_q_geom.restype = _i
     L.fr_debug_decode_walk.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
     L.fr_debug_decode_walk.restype = _i
     L.fr_debug_render_bwd_geom.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
@@ -273,7 +275,7 @@ EXPORTS = ["fr_version", "fr_strerror", "fr_render_depth_workspace_bytes", "fr_r
            "fr_decode_render_backward_pose_workspace_bytes", "fr_decode_render_backward_pose", "fr_debug_pose_bwd_geom",
            "fr_render_normal_backward_workspace_bytes", "fr_render_normal_backward", "fr_debug_render_normal_bwd_geom",
            "fr_sfs_state_bytes", "fr_sfs_intensity_forward", "fr_sfs_intensity_backward", "fr_debug_sfs_geom",
-           "fr_debug_sfs_pinv", "fr_debug_decode_geom", "fr_debug_decode_walk",
+           "fr_debug_sfs_pinv", "fr_debug_decode_geom", "fr_debug_decode_walk", "fr_debug_decode_q_geom",
            "fr_render_texture_backward_workspace_bytes", "fr_render_texture_backward", "fr_debug_render_texture_bwd_geom",
            "fr_sfs_intensity_backward_tex",
            "fr_sfs_moments_bytes", "fr_sfs_moments", "fr_sfs_solve_shade", "fr_sfs_q_bytes", "fr_sfs_backward_q",

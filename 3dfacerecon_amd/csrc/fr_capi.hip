@@ -18,7 +18,7 @@ const OptDesc kOpts[fr::OPT_COUNT] = {
     {"FR_EMIT_FILTER", 3, nullptr}, {"FR_RENDER_IMPL", 0, "scan"}, {"FR_RESOLVE_BLOCK", 0, nullptr},
     {"FR_RENDER_ROWS", 0, nullptr}, {"FR_DECODE_STORE", 0, nullptr},
     {"FR_BWD_CHUNKS", 256, nullptr}, {"FR_BWD_CB", 0, nullptr}, {"FR_EMIT_ORDER", -1, nullptr},
-    {"FR_Q30_SCHED", 0, nullptr},
+    {"FR_Q30_SCHED", 0, nullptr}, {"FR_DECODE_CUS", 0, nullptr},
 };
 std::atomic<int> g_opt[fr::OPT_COUNT];
 std::once_flag g_opt_once;

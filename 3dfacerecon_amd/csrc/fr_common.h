@@ -132,6 +132,8 @@ enum Opt {
     OPT_EMIT_ORDER,     // FR_EMIT_ORDER     lane order of a segment's triangles: -1 scored per segment (default), 0 identity, 1 even / odd passes
     OPT_Q30_SCHED,      // FR_Q30_SCHED      Q30 streaming schedule: 0 = 8 waves x whole tiles, 16-deep ring (default) | 1 = 16 waves, 32-column
                         //                   halves on neighbouring waves, 8-deep ring
+    OPT_DECODE_CUS,     // FR_DECODE_CUS     test knob: 0 = the decode forward launchers (f32 and Q30) plan for the device's compute units
+                        //                   (default), n > 0 = for min(n, device) -- fewer, longer tile walks; no result bit depends on it
     OPT_COUNT
 };
 int opt(Opt o);
@@ -181,6 +183,7 @@ int fr_launch_decode_q(const float* params, const void* qimage, const float* R_o
 bool fr_decode_q_levels_ok(int levels);
 size_t fr_decode_q_workspace_bytes_impl(int n_shape, int n_exp);
 int fr_device_cu_count();
+int fr_decode_plan_cus();   // fr_device_cu_count() under FR_DECODE_CUS: what fr_launch_decode / fr_launch_decode_q plan for
 size_t fr_decode_backward_workspace_impl(int N, int ns, int ne);
 int fr_launch_decode_backward(const float* grad_vertex_proj, const float* params, const float* vertex_proj,
                               const float* pc_shape, const float* pc_exp, const float* R_override, int B, int N, int ns,

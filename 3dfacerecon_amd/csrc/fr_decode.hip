@@ -572,6 +572,12 @@ int fr_device_cu_count() {
     return n;
 }
 
+// the CU count the decode launchers plan for: the device's, or FR_DECODE_CUS (a test knob) where that is smaller
+int fr_decode_plan_cus() {
+    const int dev = fr_device_cu_count(), cap = fr::opt(fr::OPT_DECODE_CUS);
+    return cap > 0 ? min(cap, dev) : dev;
+}
+
 template <int NBW, int WAVES>
 static int launch_decode_nbw(const fr::DecodeArgs& a, size_t lds, int grid, hipStream_t stream) {
     static fr_lds_flags_t lds_ok[64];
@@ -704,7 +710,7 @@ int fr_launch_decode(const float* params, const void* packed, const float* R_ove
     a.B = B; a.N = N; a.ns = n_shape; a.ne = n_exp;
     a.im_size = im_size;
     a.pitch = pitch;
-    const int cus = fr_device_cu_count();
+    const int cus = fr_decode_plan_cus();
     for (int b0 = 0; b0 < B;) {
         DecodePass p;
         int rc = decode_plan_pass(B, b0, N, n_shape, n_exp, cus, &p);

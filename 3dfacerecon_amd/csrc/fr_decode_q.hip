@@ -596,30 +596,28 @@ int fr_launch_pack_q(const float* mu, const float* pc_shape, const float* pc_exp
 bool fr_decode_q_supported(int n_shape, int n_exp) { return n_shape + n_exp <= 512; }
 
 template <int NBW, int LV>
-static int launch_q_generic(const fr::DecodeQArgs& a, size_t lds, int cus, hipStream_t stream) {
+static int launch_q_generic(const fr::DecodeQArgs& a, size_t lds, int grid, hipStream_t stream) {
     static fr_lds_flags_t lds_ok[64];
     if (fr_allow_full_lds(reinterpret_cast<const void*>(&fr::decode_q_kernel<NBW, 8, LV>), lds_ok) != hipSuccess)
         return FR_ERR_LAUNCH;
-    const int tiles = fr::tiles_of(a.d.N);
-    const int grid = (int)min((long long)cus, (long long)(tiles + 7) / 8);
     hipLaunchKernelGGL((fr::decode_q_kernel<NBW, 8, LV>), dim3(grid), dim3(512), lds, stream, a);
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }
 
 template <int R, int NBW, int WAVES, int WPE, int LV, int H2>
-static int launch_q_ring(const fr::DecodeQArgs& a, int cus, hipStream_t stream) {
+static int launch_q_ring(const fr::DecodeQArgs& a, size_t lds, int grid, hipStream_t stream) {
     static fr_lds_flags_t lds_ok[64];
     const void* k = reinterpret_cast<const void*>(&fr::decode_q_ring_kernel<R, NBW, WAVES, WPE, true, LV, H2>);
     if (fr_allow_full_lds(k, lds_ok) != hipSuccess) return FR_ERR_LAUNCH;
-    const size_t lds = fr::q_stage_bytes(fr::QR_S) + (size_t)WAVES * 256 + (size_t)WAVES * 2 * NBW * 1024;
-    const int tiles = fr::tiles_of(a.d.N);
-    const int slots = WAVES / H2;
-    const int grid = (int)min((long long)cus, (long long)(tiles + slots - 1) / slots);
     hipLaunchKernelGGL((fr::decode_q_ring_kernel<R, NBW, WAVES, WPE, true, LV, H2>), dim3(grid), dim3(WAVES * 64), lds, stream, a);
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }
 
-// One pass (<= 64 columns, nbt live 16-column blocks) of the model's basis shape through the streaming schedule.
+// ---- the launch decision, as a pure host function -------------------------------------------------------------------------
+// The kernel instantiations the launcher chooses among (times the three level counts).  The template arguments of a launch are
+// READ from this table (launch_q_variant), so what fr_debug_decode_q_geom reports for a pass is what the pass instantiates.
+//
+// One pass (<= 64 columns, nbt live 16-column blocks) of the model's basis shape goes through the streaming schedule:
 //   sched 0 (default): 8 waves per CU, a wave owns a tile's nbt column blocks (every basis byte is requested once on the chip),
 //                      16-deep fragment ring, behind the staging launch (q_stage_kernel)
 //   sched 1: 16 waves per CU at <= 128 registers (12 at <= 168 with all seven levels), 8-deep ring, a full pass cut into two
@@ -632,27 +630,94 @@ static int launch_q_ring(const fr::DecodeQArgs& a, int cus, hipStream_t stream) 
 // every CU to the other stream's emit workgroups: +9 us in flight; write-through (sc0 sc1) stores of the vertex rows: 0, non-
 // temporal ones: +4 us (the emit kernel's event bracket is ~2 us longer behind this kernel than behind the f32 one under every
 // store policy, while rocprofv3 shows the same 40.5 us emit kernel: the difference sits in the kernel boundary).
-template <int LV>
-static int launch_q_pass(const fr::DecodeQArgs& a, int nbt, int sched, int cus, hipStream_t stream) {
-    if (sched != 1 || nbt <= 2)
-        return nbt == 1 ? launch_q_ring<16, 1, 8, 2, LV, 1>(a, cus, stream)
-               : nbt == 2 ? launch_q_ring<16, 2, 8, 2, LV, 1>(a, cus, stream)
-                          : launch_q_ring<16, 4, 8, 2, LV, 1>(a, cus, stream);
-    // (all seven levels: 56 accumulators + the ring do not fit 128 registers -- twelve waves at <= 168)
-    if constexpr (LV == 7) return launch_q_ring<8, 2, 12, 3, LV, 2>(a, cus, stream);
-    else return launch_q_ring<8, 2, 16, 4, LV, 2>(a, cus, stream);
-}
-template <int LV>
-static int launch_q_generic_pass(fr::DecodeQArgs& a, int nbt, size_t lds, int cus, hipStream_t stream) {
-    // (three or four column blocks: two passes of two -- one wave holding four blocks' accumulators spills)
-    int rc = nbt == 1 ? launch_q_generic<1, LV>(a, lds, cus, stream) : launch_q_generic<2, LV>(a, lds, cus, stream);
-    if (rc == FR_OK && nbt > 2) {
-        a.cb0 = 2;
-        rc = launch_q_generic<2, LV>(a, lds, cus, stream);
-        a.cb0 = 0;
+namespace {
+enum { QK_GENERIC = 0, QK_RING = 1 };   // decode_q_kernel | decode_q_ring_kernel
+struct DecodeQVariant {
+    int kernel, nbw, waves, wpe, h2, ring;   // (ring = fragment ring depth, 0 for the generic kernel)
+};
+enum { QV_RING_1, QV_RING_2, QV_RING_4, QV_RING_H12, QV_RING_H16, QV_GENERIC_1, QV_GENERIC_2, QV_COUNT };
+constexpr DecodeQVariant kDecodeQVariants[QV_COUNT] = {
+    {QK_RING, 1, 8, 2, 1, 16},      // QV_RING_1 / _2 / _4: a wave owns a tile's 1 / 2 / 3-4 live column blocks
+    {QK_RING, 2, 8, 2, 1, 16},
+    {QK_RING, 4, 8, 2, 1, 16},
+    {QK_RING, 2, 12, 3, 2, 8},      // QV_RING_H12: FR_Q30_SCHED=1, all seven levels (56 accumulators + the ring do not fit 128
+                                    //              registers -- twelve waves at <= 168)
+    {QK_RING, 2, 16, 4, 2, 8},      // QV_RING_H16: FR_Q30_SCHED=1, five or four levels
+    {QK_GENERIC, 1, 8, 2, 1, 0},
+    {QK_GENERIC, 2, 8, 2, 1, 0},    // (three or four column blocks: two launches of two -- one wave holding four blocks'
+                                    //  accumulators spills)
+};
+
+struct DecodeQPass {
+    int variant;
+    int b0, cols;    // first column, live columns
+    int launches;    // decode launches of the pass (2: a generic pass of 3-4 column blocks, the second with cb0 = 2)
+    size_t lds;      // dynamic LDS bytes
+    int grid;        // workgroups
+};
+
+// One pass of fr_launch_decode_q starting at column b0, under the current knobs, on a part of `cus` compute units.
+int decode_q_plan_pass(int B, int b0, int N, int n_shape, int n_exp, int levels, int cus, DecodeQPass* p) {
+    using namespace fr;
+    if (!fr_decode_q_levels_ok(levels)) return FR_ERR_INVALID_ARG;
+    if (!fr_decode_q_supported(n_shape, n_exp)) return FR_ERR_UNSUPPORTED;
+    const QShape qs = q_shape(n_shape, n_exp);
+    if (q_stage_bytes(qs.S) > 160 * 1024) return FR_ERR_UNSUPPORTED;
+    const bool loop_env = opt(OPT_DECODE_IMPL) == 1;
+    const int sched = opt(OPT_Q30_SCHED);
+    const int nbt = (min(B - b0, MAXB) + 15) / 16;   // live 16-column blocks (1..4)
+    p->b0 = b0;
+    p->cols = min(B - b0, MAXB);
+    p->launches = 1;
+    if (!loop_env && qs.KB == QR_KB) {   // the model's basis shape: streaming schedule
+        if (sched != 1 || nbt <= 2) p->variant = nbt == 1 ? QV_RING_1 : nbt == 2 ? QV_RING_2 : QV_RING_4;
+        else p->variant = levels == 7 ? QV_RING_H12 : QV_RING_H16;
+    } else {
+        p->variant = nbt == 1 ? QV_GENERIC_1 : QV_GENERIC_2;
+        if (nbt > 2) p->launches = 2;
     }
-    return rc;
+    const DecodeQVariant& v = kDecodeQVariants[p->variant];
+    p->lds = q_stage_bytes(qs.S);
+    if (v.kernel == QK_RING)   // + the waves' payload slots and their parked x / y rows
+        p->lds = q_stage_bytes(QR_S) + (size_t)v.waves * 256 + (size_t)v.waves * 2 * v.nbw * 1024;
+    const int tiles = tiles_of(N);
+    const int slots = v.waves / v.h2;
+    p->grid = (int)min((long long)cus, (long long)(tiles + slots - 1) / slots);
+    return FR_OK;
 }
+
+template <int V, int LV>
+int launch_q_variant(fr::DecodeQArgs& a, const DecodeQPass& p, hipStream_t stream) {
+    constexpr DecodeQVariant v = kDecodeQVariants[V];
+    if constexpr (v.kernel == QK_RING) {
+        return launch_q_ring<v.ring, v.nbw, v.waves, v.wpe, LV, v.h2>(a, p.lds, p.grid, stream);
+    } else {
+        int rc = launch_q_generic<v.nbw, LV>(a, p.lds, p.grid, stream);
+        if (rc == FR_OK && p.launches == 2) {
+            a.cb0 = 2;
+            rc = launch_q_generic<v.nbw, LV>(a, p.lds, p.grid, stream);
+            a.cb0 = 0;
+        }
+        return rc;
+    }
+}
+template <int LV>
+int launch_q_pass(fr::DecodeQArgs& a, const DecodeQPass& p, hipStream_t stream) {
+    switch (p.variant) {
+        case QV_RING_1: return launch_q_variant<QV_RING_1, LV>(a, p, stream);
+        case QV_RING_2: return launch_q_variant<QV_RING_2, LV>(a, p, stream);
+        case QV_RING_4: return launch_q_variant<QV_RING_4, LV>(a, p, stream);
+        case QV_RING_H12:
+            if constexpr (LV == 7) return launch_q_variant<QV_RING_H12, LV>(a, p, stream);
+            else return FR_ERR_LAUNCH;   // (never planned: the twelve-wave variant is the seven-level one)
+        case QV_RING_H16:
+            if constexpr (LV != 7) return launch_q_variant<QV_RING_H16, LV>(a, p, stream);
+            else return FR_ERR_LAUNCH;
+        case QV_GENERIC_1: return launch_q_variant<QV_GENERIC_1, LV>(a, p, stream);
+        default: return launch_q_variant<QV_GENERIC_2, LV>(a, p, stream);
+    }
+}
+}  // namespace
 
 bool fr_decode_q_levels_ok(int levels) { return levels == 7 || levels == 5 || levels == 4; }
 
@@ -675,30 +740,42 @@ int fr_launch_decode_q(const float* params, const void* qimage, const float* R_o
     a.d.halves = 1;
     a.d.im_size = im_size;
     a.d.pitch = pitch;
-    const size_t lds = q_stage_bytes(a.qs.S);
-    if (lds > 160 * 1024) return FR_ERR_UNSUPPORTED;
-    if (!workspace || ws_bytes < lds || ((uintptr_t)workspace & 15)) return FR_ERR_WORKSPACE;
+    const size_t ws_need = q_stage_bytes(a.qs.S);
+    if (ws_need > 160 * 1024) return FR_ERR_UNSUPPORTED;
+    if (!workspace || ws_bytes < ws_need || ((uintptr_t)workspace & 15)) return FR_ERR_WORKSPACE;
     char* stage = reinterpret_cast<char*>(workspace);
     a.stage = stage;
     a.cb0 = 0;
-    const int cus = fr_device_cu_count();
-    const bool loop_env = opt(OPT_DECODE_IMPL) == 1;
-    const int sched = opt(OPT_Q30_SCHED);
+    const int cus = fr_decode_plan_cus();
     for (int b0 = 0; b0 < B; b0 += MAXB) {
+        DecodeQPass p;
+        int rc = decode_q_plan_pass(B, b0, N, n_shape, n_exp, levels, cus, &p);
+        if (rc != FR_OK) return rc;
         a.d.b0 = b0;
-        const int nbt = (min(B - b0, MAXB) + 15) / 16;
-        const bool ring = !loop_env && a.qs.KB == QR_KB;
         hipLaunchKernelGGL(q_stage_kernel, dim3(MAXB), dim3(128), 0, stream, a, stage);
-        int rc;
-        if (ring)   // the model's basis shape: streaming schedule
-            rc = levels == 7 ? launch_q_pass<7>(a, nbt, sched, cus, stream)
-                 : levels == 5 ? launch_q_pass<5>(a, nbt, sched, cus, stream)
-                               : launch_q_pass<4>(a, nbt, sched, cus, stream);
-        else
-            rc = levels == 7 ? launch_q_generic_pass<7>(a, nbt, lds, cus, stream)
-                 : levels == 5 ? launch_q_generic_pass<5>(a, nbt, lds, cus, stream)
-                               : launch_q_generic_pass<4>(a, nbt, lds, cus, stream);
+        rc = levels == 7 ? launch_q_pass<7>(a, p, stream) : levels == 5 ? launch_q_pass<5>(a, p, stream) : launch_q_pass<4>(a, p, stream);
         if (rc != FR_OK) return rc;
     }
+    return FR_OK;
+}
+
+// test hook (include/fr_hotpath.h): the launch decision, without a GPU
+extern "C" int fr_debug_decode_q_geom(int B, int N, int n_shape, int n_exp, int levels, int cus, int* out) {
+    if (!out) return FR_ERR_INVALID_ARG;
+    out[0] = 0;
+    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0 || cus < 1 || !fr_decode_q_levels_ok(levels)) return FR_ERR_INVALID_ARG;
+    if (!fr_decode_q_supported(n_shape, n_exp)) return FR_ERR_UNSUPPORTED;
+    if (B == 0 || N == 0) return FR_OK;
+    int n = 0;
+    for (int b0 = 0; b0 < B; b0 += fr::MAXB) {
+        DecodeQPass p;
+        const int rc = decode_q_plan_pass(B, b0, N, n_shape, n_exp, levels, cus, &p);
+        if (rc != FR_OK) return rc;
+        const DecodeQVariant& v = kDecodeQVariants[p.variant];
+        int* o = out + 1 + 10 * n++;
+        o[0] = p.b0; o[1] = p.cols; o[2] = v.kernel; o[3] = v.nbw; o[4] = v.waves; o[5] = v.h2; o[6] = v.ring;
+        o[7] = p.launches; o[8] = (int)p.lds; o[9] = p.grid;
+    }
+    out[0] = n;
     return FR_OK;
 }

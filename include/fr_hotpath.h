@@ -63,14 +63,17 @@ const char* fr_strerror(int code);
  *   records in registers | 0 = two-pass resolver)   FR_EMIT_FILTER (bits 0-1, default 3)   FR_RENDER_IMPL (0 | 1 = "scan": strip-scan fallback)
  *   FR_RESOLVE_BLOCK (0 = auto | 256 | 512 | 1024)   FR_RENDER_ROWS (0 = auto | rows per screen strip)
  *   FR_DECODE_STORE (0 | 1 = transposed accumulators, one dword per lane per store: measured +1.1 us, A/B only)
+ *   FR_DECODE_CUS (test knob: 0 = default, the decode forward launchers fr_decode_3dmm / fr_decode_3dmm_q30* plan for the device's
+ *   compute units | n > 0 = for min(n, device): fewer workgroups, so a small mesh walks several rounds of tiles per wave; it
+ *   changes no result bit and, at its default, no launch)
  *   FR_BWD_CHUNKS (row chunks of the packed decode-backward GEMM: 256 = default | 1 .. 512; changes the association of the
  *   partial sums, i.e. the gradient's last bits)
  *   FR_BWD_CB (16-coefficient blocks per wave of the fused decode backward: 0 = by batch | 2 | 4; changes no result bit except
  *   d f of fr_decode_3dmm_backward_packed_mu, whose per-workgroup partial it re-associates)
  *   FR_EMIT_ORDER (lane order of a segment's triangles in the emit kernel, fixed by the pack phase: -1 = scored per segment
  *   (default) | 0 = list order | 1 = even triangles, then odd ones; read when the triangle list is packed)
- * Apart from those two, none of them changes a result bit (tests/test_render_gpu.py, tests/test_decode_gpu.py hold every setting to
- * the oracle; tests/test_decode_backward_bounds_gpu.py the two backward knobs).
+ * Apart from FR_BWD_CHUNKS and FR_BWD_CB, none of them changes a result bit (tests/test_render_gpu.py, tests/test_decode_gpu.py
+ * hold every setting to the oracle; tests/test_decode_backward_bounds_gpu.py the two backward knobs).
  * Returns FR_OK or FR_ERR_INVALID_ARG (unknown name). */
 int fr_set_option(const char* name, int value);
 int fr_get_option(const char* name, int* value);
@@ -226,7 +229,10 @@ int fr_decode_render_forward(const float* params, const void* packed_basis, cons
  *   products of weight >= 2^-32 of full scale (what is dropped is below 2^-38 of a term's scale: the same fp32 result in
  *   > 99.98 % of the cases), 4 = the ten products of weight >= 2^-24 (dropped: below 2^-30; mean error 0.29 ulp against 0.26
  *   for the exact product and 0.34 - 0.5 for the f32 chain).  Integer arithmetic: order-independent, restated bit for bit in
- *   oracle/fr_oracle.c ("Q30 decode", the same `levels`).  A non-finite parameter makes the face's vertices NaN.
+ *   oracle/fr_oracle.c ("Q30 decode", the same `levels`).  A non-finite parameter makes the face's vertices NaN, a non-finite
+ *   basis entry its own vertex's.  The blend is rounded ONCE, from mu + I 2^e with I an integer: a zero blend is the exact +0, so
+ *   a mu of -0.0 under all-zero coefficients gives +0.0 (the f32 chain's rule for the sign of a zero does not apply), and a sum
+ *   below half the smallest subnormal gives a zero of the sum's sign (tests/test_decode_q30_edges_gpu.py).
  * It has its own basis image (fr_decode_q30_image_bytes, 256-byte aligned; 0 = shape not covered: n_shape + n_exp > 512,
  * for which fr_decode_q30_pack / fr_decode_3dmm_q30 return FR_ERR_UNSUPPORTED; the image does not depend on `levels`) and
  * needs a caller-owned staging workspace (fr_decode_q30_workspace_bytes: 68 KiB for the model's shape, 16-byte aligned) that
@@ -674,6 +680,18 @@ void fr_debug_decode_bwd_geom(int nbatch, int N, int n_shape, int n_exp, int* ou
  * fr_decode_3dmm does (a basis whose 64-column LDS image exceeds 160 KiB).  Used by tests/test_decode_geom_cpu.py and by
  * tests/test_decode_forward_edges_gpu.py to pick shapes that reach a geometry. */
 int fr_debug_decode_geom(int B, int N, int n_shape, int n_exp, int cus, int* out);
+
+/* The same for the Q30 decode (fr_decode_3dmm_q30_lv and the decode phase of fr_decode_render_forward_q30) under the current
+ * FR_DECODE_IMPL / FR_Q30_SCHED: its launcher calls the same function, with the device's CU count (under FR_DECODE_CUS), and
+ * takes its kernel template arguments from the table this reports from.  out[0] = passes (one per 64 columns), then 10 ints per
+ * pass = {first column, live columns, kernel (0 = generic decode_q_kernel, 1 = ring schedule of the 15-group shape), NBW
+ * (16-column blocks per wave), waves per workgroup, H2 (waves that share a tile: 2 = its two 32-column halves on neighbouring
+ * waves), ring depth in fragments (0: generic), decode launches of the pass (2 for a generic pass of 3-4 column blocks; the
+ * staging launch is not counted), dynamic LDS bytes, workgroups}; a wave owns whole tiles, waves / H2 of them in work per
+ * workgroup.  `out` must hold 1 + 10 * ceil(B / 64) ints.  Returns FR_OK (out[0] = 0 for B = 0 or N = 0), FR_ERR_INVALID_ARG
+ * (a negative size, cus < 1, levels not 7 / 5 / 4, NULL) or FR_ERR_UNSUPPORTED (n_shape + n_exp > 512).  Used by
+ * tests/test_decode_geom_cpu.py and by tests/test_decode_q30_edges_gpu.py to pick shapes that reach a geometry. */
+int fr_debug_decode_q_geom(int B, int N, int n_shape, int n_exp, int levels, int cus, int* out);
 
 /* The decode kernels' work distribution, evaluated on the host through the function the kernels call (wave_work / tile_walk of
  * csrc/fr_decode_shared.h): visits[tile * halves + half] = how many waves of a launch of `grid` workgroups of `waves` waves take

@@ -147,6 +147,22 @@ def test_options_read_the_environment_once_and_never_on_the_launch_path(monkeypa
     assert [h[0] for h in hits] == ["fr_capi.hip"], hits
 
 
+def test_decode_cus_option_round_trips():
+    """FR_DECODE_CUS (test knob: the CU count the decode forward launchers plan for) is in the option table, 0 by default"""
+    host = pkg("_lib")
+    L = host.lib()
+    v = ctypes.c_int(-5)
+    assert L.fr_get_option(b"FR_DECODE_CUS", ctypes.byref(v)) == 0 and v.value == int(os.environ.get("FR_DECODE_CUS") or 0)
+    before = v.value
+    for n in (1, 3, 8, 300, 0):
+        assert L.fr_set_option(b"FR_DECODE_CUS", n) == 0
+        assert L.fr_get_option(b"FR_DECODE_CUS", ctypes.byref(v)) == 0 and v.value == n
+    with host.options(FR_DECODE_CUS=2):
+        assert host.get_option("FR_DECODE_CUS") == 2
+    assert host.get_option("FR_DECODE_CUS") == 0
+    assert L.fr_set_option(b"FR_DECODE_CUS", before) == 0
+
+
 def test_binary_only_deployment_loads_without_sources(tmp_path, monkeypatch):
     """A copied .so without csrc/, include/ or the .srchash sidecar: the identity is read from the hash embedded in the
     binary, nothing tries to open a source file, and with sources present a sidecar-less library is not declared stale."""

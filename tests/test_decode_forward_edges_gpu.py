@@ -3,8 +3,9 @@ k-ordered fmaf chains from +0) at every schedule the launcher can pick and at th
 
 Everything is compared with oracle.decode_3dmm by BIT PATTERN (gpu_util.assert_bits_equal: -0.0 is not +0.0; a NaN equals any
 NaN).  The rotation is supplied by the host unless a test is about the in-kernel one.  Shapes are chosen by asking the launcher's
-own decision function (fr_debug_decode_geom, with the device's CU count) which (N, B) reach a geometry, never by re-deriving its
-rules.  Outputs are pre-filled with a finite sentinel, so an element the kernel does not write is a mismatch too."""
+own decision function (fr_debug_decode_geom, with the CU count the launcher plans for: the device's, or FR_DECODE_CUS where a cell
+caps it so that a small mesh walks several rounds of tiles) which (N, B) reach a geometry, never by re-deriving its rules.
+Outputs are pre-filled with a finite sentinel, so an element the kernel does not write is a mismatch too."""
 import ctypes
 
 import numpy as np
@@ -156,17 +157,42 @@ def _n_for_grid(B, ns, ne, cus, want_grid, which, pick):
     return min(lo + pick, hi)
 
 
+CAPS = (1, 2, 3, 8)      # FR_DECODE_CUS: the launcher plans for so many compute units (8: tile_walk's `(grid & 7) == 0` permutation)
+
+
+def walk_rounds(p, N):
+    """(rounds of tiles a wave slot of pass p walks, tiles in the last round, tiles a full round holds)"""
+    tiles = (N + 15) // 16
+    per = (p["waves"] // p["halves"]) * p["grid"]
+    return -(-tiles // per), tiles - (-(-tiles // per) - 1) * per, per
+
+
+def _n_for_rounds(B, ns, ne, cap_cus):
+    """the smallest N from 700, no multiple of 16, at which the first pass of a B-face decode planned for cap_cus compute units runs
+    on that many workgroups whose wave slots walk at least three rounds of tiles, the last one ragged, under the current knobs"""
+    for N in range(700, NMAX + 1):
+        p = geom(B, N, ns, ne, cap_cus)[0]
+        r = walk_rounds(p, N)
+        if N % 16 and p["grid"] == cap_cus and r[0] >= 3 and r[1] < r[2]:
+            return N
+    raise AssertionError((B, ns, ne, cap_cus))
+
+
 def matrix_points(ns, ne, cus):
-    """[(N, B)] of one (schedule, family) cell, under the current knobs: every batch boundary of the launcher at small meshes of
+    """[(N, B, cap)] of one (schedule, family) cell, under the current knobs: every batch boundary of the launcher at small meshes of
     every raggedness, then every grid size of GRIDS at 64 faces (the pass every 64-column variant serves), and a few grids at 20
-    faces (one item per tile) and at 129 (a 128-column pass and a pass of one face)"""
-    pts = list(zip(N_EDGES, B_EDGES))
+    faces (one item per tile) and at 129 (a 128-column pass and a pass of one face) -- all of them one round of tiles, cap = 0: the
+    launcher plans for the device -- and then, at 64 faces, the multi-round cells: FR_DECODE_CUS = cap of CAPS at an N that makes
+    every wave slot walk three rounds or more (the ring wrapping from one item's last fragments into the next item's first)"""
+    pts = [(N, B, 0) for N, B in zip(N_EDGES, B_EDGES)]
     for i, g in enumerate(GRIDS):
-        pts.append((_n_for_grid(64, ns, ne, cus, g, 0, (0, 2, 3, 14, 15, 7)[i]), 64))
-    pts.append((_n_for_grid(20, ns, ne, cus, 7, 0, 5), 20))
-    pts.append((_n_for_grid(20, ns, ne, cus, 16, 0, 15), 20))
-    pts.append((_n_for_grid(129, ns, ne, cus, 2, 0, 3), 129))
-    pts.append((_n_for_grid(129, ns, ne, cus, 9, 0, 0), 129))
+        pts.append((_n_for_grid(64, ns, ne, cus, g, 0, (0, 2, 3, 14, 15, 7)[i]), 64, 0))
+    pts.append((_n_for_grid(20, ns, ne, cus, 7, 0, 5), 20, 0))
+    pts.append((_n_for_grid(20, ns, ne, cus, 16, 0, 15), 20, 0))
+    pts.append((_n_for_grid(129, ns, ne, cus, 2, 0, 3), 129, 0))
+    pts.append((_n_for_grid(129, ns, ne, cus, 9, 0, 0), 129, 0))
+    for cap in CAPS:
+        pts.append((_n_for_rounds(64, ns, ne, min(cap, cus)), 64, cap))
     return pts
 
 
@@ -177,20 +203,37 @@ def test_schedule_geometry_matrix(oracle, knobs, ns, ne):
     assert cus >= 16, "the grid cases are written for a part of at least 16 compute units"
     with _h().options(**knobs):
         pts = matrix_points(ns, ne, cus)
-        geoms = [geom(B, N, ns, ne, cus) for N, B in pts]
+        geoms = [geom(B, N, ns, ne, min(cap, cus) if cap else cus) for N, B, cap in pts]
         # the cell reaches what it was written for
         grids = {p["grid"] for g in geoms for p in g}
         assert grids >= set(GRIDS), (sorted(grids), pts)
-        assert {N % 16 for N, _ in pts} >= {0, 1, 3, 4, 15} and any(N < 16 for N, _ in pts)
-        assert {((N + 15) // 16) & 1 for N, _ in pts} == {0, 1}
-        assert {B for _, B in pts} >= set(B_EDGES)
-        print("\n%s %d+%d:" % (_sid(knobs), ns, ne), "; ".join(
-            "N=%d B=%d -> %s" % (N, B, " | ".join("%s nbw%d w%d mb%d h%d nt%d prio%d tr%d grid%d" % (
-                ("generic", "ring")[p["kernel"]], p["nbw"], p["waves"], p["mb"], p["halves"], p["nt"], p["prio"], p["tr"], p["grid"])
-                for p in g)) for (N, B), g in zip(pts, geoms)))
-        for N, B in pts:
+        assert {N % 16 for N, _, _ in pts} >= {0, 1, 3, 4, 15} and any(N < 16 for N, _, _ in pts)
+        assert {((N + 15) // 16) & 1 for N, _, _ in pts} == {0, 1}
+        assert {B for _, B, _ in pts} >= set(B_EDGES)
+        assert {cap for _, _, cap in pts} == {0} | set(CAPS)
+        for (N, B, cap), g in zip(pts, geoms):
+            r = walk_rounds(g[0], N)
+            if cap:     # more tiles than one round of the capped grid holds: three rounds or more, the last one ragged
+                slots = g[0]["waves"] // g[0]["halves"]
+                assert -(-((N + 15) // 16) // slots) > g[0]["grid"] == min(cap, cus) and r[0] >= 3 and r[1] < r[2], (N, B, cap, g)
+            else:
+                assert r[0] == 1, (N, B, g)
+        # the block of this cell in profiles/decode_forward_schedule_matrix.txt: per variant its grids, the rounds walked under a cap
+        agg = {}
+        for (N, B, cap), g in zip(pts, geoms):
+            for i, p in enumerate(g):
+                a = agg.setdefault("%s nbw%d w%d mb%d h%d nt%d prio%d tr%d" % (
+                    ("generic", "ring")[p["kernel"]], p["nbw"], p["waves"], p["mb"], p["halves"], p["nt"], p["prio"], p["tr"]), (set(), set()))
+                a[0].add(p["grid"])
+                if cap and i == 0:
+                    a[1].add(walk_rounds(p, N)[0])
+        print("\n%s %d+%d\n" % (_sid(knobs), ns, ne) + "\n".join(
+            "    %s grids %s%s" % (k, sorted(a[0]), " rounds %s" % sorted(a[1]) if a[1] else "") for k, a in agg.items()))
+        for N, B, cap in pts:
             g, P, R, want = case(oracle, ns, ne, N, B)
-            assert_bits_equal(g.decode(P, R), want, "%s %d+%d N=%d B=%d" % (_sid(knobs), ns, ne, N, B))
+            with _h().options(FR_DECODE_CUS=cap):
+                got = g.decode(P, R)
+            assert_bits_equal(got, want, "%s %d+%d N=%d B=%d cus=%d" % (_sid(knobs), ns, ne, N, B, cap))
 
 
 # ---- basis shapes ---------------------------------------------------------------------------------------------------------------

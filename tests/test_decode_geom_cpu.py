@@ -3,7 +3,8 @@ distribution (fr_debug_decode_walk: the wave_work / tile_walk the kernels call, 
 
   * every geometry the launcher can choose -- all FR_DECODE_* knobs, the ring shape and generic shapes, B = 1 .. 200, the model's
     N and small ones, parts of 1 .. 256 compute units -- deals every work item (tile, half) to EXACTLY one wave;
-  * the documented boundaries of the decision (the comments of decode_plan_pass in csrc/fr_decode.hip) are what it returns."""
+  * the documented boundaries of the decision (the comments of decode_plan_pass in csrc/fr_decode.hip) are what it returns;
+  * the same for the Q30 decode (fr_debug_decode_q_geom: the function fr_launch_decode_q calls) and its slot shapes."""
 import ctypes
 
 import numpy as np
@@ -209,3 +210,119 @@ def test_unsupported_and_invalid():
     assert L.fr_debug_decode_geom(4, 100, 5, -3, 256, out) == -1
     assert L.fr_debug_decode_geom(4, 100, 5, 3, 0, out) == -1
     assert L.fr_debug_decode_geom(4, 100, 5, 3, 256, None) == -1
+
+
+# ---- the Q30 decode's launch decision (fr_debug_decode_q_geom: the function fr_launch_decode_q itself calls) ----------------------
+Q_INTS = 10
+Q_FIELDS = ("b0", "cols", "kernel", "nbw", "waves", "h2", "ring", "launches", "lds", "grid")
+Q_SLOT_SHAPES = ((8, 1), (16, 2), (12, 2))          # (waves, waves that share a tile) of the ring kernel's instantiations
+Q_GRIDS = (1, 2, 3, 7, 8, 16, 256)
+Q_STAGE = 4 * 16384 + 64 * 12 * 4 + 64 * 4          # staged parameter image of a 4-k-step shape
+
+
+def qgeom(B, N, ns, ne, levels, cus=256):
+    out = (ctypes.c_int * (1 + Q_INTS * ((B + 63) // 64 + 1)))()
+    rc = _h().lib().fr_debug_decode_q_geom(B, N, ns, ne, levels, cus, out)
+    assert rc == 0, rc
+    return [dict(zip(Q_FIELDS, out[1 + Q_INTS * i:1 + Q_INTS * (i + 1)])) for i in range(out[0])]
+
+
+def test_walk_is_exact_for_the_q30_slot_shapes():
+    """every tile is taken by exactly one slot (and by each of the waves that share it) at the grids a capped part gives and at the
+    full part, at tile counts around each multiple of slots x grid: a full last round, one tile short of it, one tile into the next"""
+    for waves, h2 in Q_SLOT_SHAPES:
+        slots = waves // h2
+        for grid in Q_GRIDS:
+            per_round = slots * grid
+            for tiles in sorted({max(m * per_round + d, 0) for m in range(0, 4) for d in (-1, 0, 1)} | {1, slots - 1, slots, slots + 1}):
+                v = walk(tiles, waves, h2, grid)
+                assert v.shape == (tiles, h2) and (v == 1).all(), (waves, h2, grid, tiles)
+
+
+def test_q30_geom_is_consistent_at_every_batch_and_knob():
+    host = _h()
+    seen = set()
+    for knobs in ({}, {"FR_Q30_SCHED": 1}, {"FR_DECODE_IMPL": 1}, {"FR_DECODE_IMPL": 1, "FR_Q30_SCHED": 1}):
+        with host.options(**knobs):
+            for ns, ne in ((199, 29), (225, 0), (211, 29), (0, 230), (200, 24), (212, 29), (33, 16), (0, 0), (512, 0)):
+                KB = max((ns + ne + 15) // 16, 1)
+                S = (KB + 3) // 4
+                for lv in (7, 5, 4):
+                    for N in (N_MODEL, 700, 15):
+                        tiles = (N + 15) // 16
+                        for cus in (1, 8, 256):
+                            for B in list(range(1, 131, 3)) + [16, 17, 32, 33, 48, 49, 64, 65, 128, 129, 192, 193]:
+                                g = qgeom(B, N, ns, ne, lv, cus)
+                                assert [p["b0"] for p in g] == list(range(0, B, 64))
+                                for p in g:
+                                    what = (knobs, ns, ne, lv, N, cus, B, p)
+                                    nbt = (p["cols"] + 15) // 16
+                                    ring = KB == 15 and not knobs.get("FR_DECODE_IMPL")
+                                    assert p["cols"] == min(B - p["b0"], 64) and p["kernel"] == int(ring), what
+                                    # the pass's column blocks are covered: by one wave, by the two waves of a pair, or by two launches
+                                    assert p["nbw"] * p["h2"] * p["launches"] * 16 >= p["cols"], what
+                                    slots = p["waves"] // p["h2"]
+                                    assert p["grid"] == min(cus, -(-tiles // slots)), what
+                                    if ring:
+                                        halves = knobs.get("FR_Q30_SCHED") == 1 and nbt >= 3
+                                        assert p["h2"] == (2 if halves else 1) and p["launches"] == 1, what
+                                        assert p["nbw"] == (2 if halves else {1: 1, 2: 2, 3: 4, 4: 4}[nbt]), what
+                                        assert p["waves"] == ((12 if lv == 7 else 16) if halves else 8), what
+                                        assert p["ring"] == (8 if halves else 16), what
+                                        assert p["lds"] == Q_STAGE + p["waves"] * 256 + p["waves"] * 2 * p["nbw"] * 1024, what
+                                    else:
+                                        assert (p["nbw"], p["launches"]) == {1: (1, 1), 2: (2, 1), 3: (2, 2), 4: (2, 2)}[nbt], what
+                                        assert p["waves"] == 8 and p["h2"] == 1 and p["ring"] == 0, what
+                                        assert p["lds"] == S * 16384 + 64 * 12 * 4 + 64 * 4, what
+                                    assert p["lds"] <= 160 * 1024, what
+                                    seen.add((p["kernel"], p["nbw"], p["waves"], p["h2"], p["launches"]))
+    assert seen == {(1, 1, 8, 1, 1), (1, 2, 8, 1, 1), (1, 4, 8, 1, 1), (1, 2, 12, 2, 1), (1, 2, 16, 2, 1),
+                    (0, 1, 8, 1, 1), (0, 2, 8, 1, 1), (0, 2, 8, 1, 2)}, seen
+    # every reported (waves, h2) is a slot shape whose walk the test above holds exact
+    assert {(w, h) for _, _, w, h, _ in seen} == set(Q_SLOT_SHAPES)
+
+
+def test_q30_geom_documented_boundaries():
+    """the model's shape and N on 256 compute units: a wave first takes a second tile where ceil(tiles / slots) passes the grid"""
+    host = _h()
+    assert host.get_option("FR_Q30_SCHED") == 0 and host.get_option("FR_DECODE_IMPL") == 0 and host.get_option("FR_DECODE_CUS") == 0
+    (p,) = qgeom(64, N_MODEL, 199, 29, 4)
+    _is(p, b0=0, cols=64, kernel=RING, nbw=4, waves=8, h2=1, ring=16, launches=1, grid=256)
+    (p,) = qgeom(64, 256 * 8 * 16, 199, 29, 7)        # 2,048 tiles: exactly one per wave
+    assert p["grid"] == 256
+    (p,) = qgeom(64, 256 * 8 * 16 - 16, 199, 29, 7)   # one tile fewer: still 256 workgroups (the last one short of a wave)
+    assert p["grid"] == 256
+    (p,) = qgeom(64, 255 * 8 * 16, 199, 29, 7)
+    assert p["grid"] == 255
+    with host.options(FR_Q30_SCHED=1):
+        (p,) = qgeom(64, N_MODEL, 199, 29, 7)
+        _is(p, kernel=RING, nbw=2, waves=12, h2=2, ring=8, grid=256)
+        (p,) = qgeom(64, N_MODEL, 199, 29, 5)
+        _is(p, kernel=RING, nbw=2, waves=16, h2=2, ring=8, grid=256)
+        (p,) = qgeom(32, N_MODEL, 199, 29, 7)         # two live blocks: the whole-tile schedule
+        _is(p, kernel=RING, nbw=2, waves=8, h2=1, ring=16)
+        p, q = qgeom(97, N_MODEL, 199, 29, 4)         # 33 columns in the second pass: a half-dead pair
+        _is(q, b0=64, cols=33, nbw=2, waves=16, h2=2)
+    for ns, ne, kernel in ((225, 0, RING), (211, 29, RING), (0, 230, RING), (240, 0, RING), (200, 24, GENERIC), (212, 29, GENERIC)):
+        (p,) = qgeom(20, 1000, ns, ne, 7)
+        assert p["kernel"] == kernel, (ns, ne, p)
+    with host.options(FR_DECODE_IMPL=1):
+        (p,) = qgeom(64, N_MODEL, 199, 29, 7)
+        _is(p, kernel=GENERIC, nbw=2, waves=8, h2=1, ring=0, launches=2, lds=Q_STAGE, grid=256)
+
+
+def test_q30_geom_unsupported_and_invalid():
+    L = _h().lib()
+    out = (ctypes.c_int * 64)()
+    assert L.fr_debug_decode_q_geom(4, 100, 512, 0, 7, 256, out) == 0 and out[0] == 1 and out[1 + 8] == 8 * 16384 + 3328
+    assert L.fr_debug_decode_q_geom(4, 100, 513, 0, 7, 256, out) == -4 and out[0] == 0
+    assert L.fr_debug_decode_q_geom(4, 100, 500, 13, 4, 256, out) == -4
+    assert L.fr_debug_decode_q_geom(0, 100, 5, 3, 7, 256, out) == 0 and out[0] == 0
+    assert L.fr_debug_decode_q_geom(4, 0, 5, 3, 7, 256, out) == 0 and out[0] == 0
+    for lv in (0, 1, 3, 6, 8, -7):
+        assert L.fr_debug_decode_q_geom(4, 100, 5, 3, lv, 256, out) == -1
+    assert L.fr_debug_decode_q_geom(-1, 100, 5, 3, 7, 256, out) == -1
+    assert L.fr_debug_decode_q_geom(4, -1, 5, 3, 7, 256, out) == -1
+    assert L.fr_debug_decode_q_geom(4, 100, 5, -3, 7, 256, out) == -1
+    assert L.fr_debug_decode_q_geom(4, 100, 5, 3, 7, 0, out) == -1
+    assert L.fr_debug_decode_q_geom(4, 100, 5, 3, 7, 256, None) == -1

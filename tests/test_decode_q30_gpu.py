@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import pkg
-from gpu_util import net_mod
+from gpu_util import assert_bits_equal, net_mod
 
 pytestmark = pytest.mark.gpu
 
@@ -26,11 +26,21 @@ def q30_mode(request):
     h.set_decode_arith(prev, prev_lv)
 
 
+SENTINEL = 12345.678
+
+
 def _decode_gpu(net, P, R=None):
+    """the operator surface's result -- which allocates its own output -- after the same launch through the basis object into an
+    output PRE-FILLED with a finite sentinel has given the same bits: an element the kernel does not write cannot pass"""
     p = torch.as_tensor(P, device="cuda:0")
-    out = net.vertices_transform(p, R=None if R is None else torch.as_tensor(R, device="cuda:0"))
+    r = None if R is None else torch.as_tensor(R, device="cuda:0")
+    out = net.vertices_transform(p, R=r)
+    pre = torch.full(tuple(out.shape), SENTINEL, dtype=torch.float32, device="cuda:0")
+    net._basis.decode(p.contiguous(), None if r is None else r.contiguous(), p.shape[0], net.im_size, pre)
     torch.cuda.synchronize()
-    return out.cpu().numpy()
+    got = out.cpu().numpy()
+    assert_bits_equal(pre.cpu().numpy(), got, "pre-filled output against the operator's")
+    return got
 
 
 def _rand_params(rs, B, ns, ne, im):
@@ -76,10 +86,10 @@ def test_vs_q30_spec_bit_exact(q30_mode, oracle, synth, gu, gv, ns, ne, B):
     R = oracle.rotation_matrix_batch(P[:, :3])
     want = oracle.decode_3dmm_q30(P, A["mu"], A["pc_shape"], A["pc_exp"], 200.0, R=R, levels=q30_mode.levels)
     got = _decode_gpu(net, P, R)
-    np.testing.assert_array_equal(got, want)
+    assert_bits_equal(got, want, "default schedule")
     for sched in (1,):   # the two-halves schedule: the same bits
         with q30_mode.options(FR_Q30_SCHED=sched):
-            np.testing.assert_array_equal(_decode_gpu(net, P, R), want, err_msg="FR_Q30_SCHED=%d" % sched)
+            assert_bits_equal(_decode_gpu(net, P, R), want, "FR_Q30_SCHED=%d" % sched)
     # against the reference's arithmetic type (f32 chain spec): both are within a few ulp of the float64 evaluation
     chain = oracle.decode_3dmm(P, A["mu"], A["pc_shape"], A["pc_exp"], 200.0, R=R)
     truth = oracle.decode_3dmm_f64(P, A["mu"], A["pc_shape"], A["pc_exp"], 200.0)
@@ -110,9 +120,9 @@ def test_special_values(q30_mode, oracle, synth):
     got = _decode_gpu(net, P, R)
     want = oracle.decode_3dmm_q30(P, A["mu"], A["pc_shape"], A["pc_exp"], 200.0, R=R, levels=q30_mode.levels)
     np.testing.assert_array_equal(np.isnan(got), np.isnan(want))
-    np.testing.assert_array_equal(got[~np.isnan(want)], want[~np.isnan(want)])
+    assert_bits_equal(got, want, "special values")
     with q30_mode.options(FR_Q30_SCHED=1):
-        np.testing.assert_array_equal(_decode_gpu(net, P, R), got)
+        assert_bits_equal(_decode_gpu(net, P, R), got, "FR_Q30_SCHED=1")
     assert np.isnan(got[1]).all() and np.isnan(got[2]).all() and not np.isnan(got[[0, 3, 4, 5, 6, 7, 8]]).any()
 
 
@@ -136,7 +146,7 @@ def test_special_basis(q30_mode, oracle, synth):
     got = _decode_gpu(net, P, R)
     want = oracle.decode_3dmm_q30(P, A["mu"], A["pc_shape"], A["pc_exp"], 200.0, R=R, levels=q30_mode.levels)
     np.testing.assert_array_equal(np.isnan(got), np.isnan(want))
-    np.testing.assert_array_equal(got[~np.isnan(want)], want[~np.isnan(want)])
+    assert_bits_equal(got, want, "special basis")
     N = 48
     assert np.isnan(got[:, :, 7 % N]).all() and np.isnan(got[:, :, 9 % N]).all() and np.isnan(want).mean() < 0.1
 
@@ -151,15 +161,15 @@ def test_full_size_batch64(q30_mode, oracle, full_assets, synth):
     got = _decode_gpu(net, P, R)
     for b in (0, 63):
         want = oracle.decode_3dmm_q30(P[b:b + 1], A["mu"], A["pc_shape"], A["pc_exp"], 200.0, R=R[b:b + 1], levels=q30_mode.levels)
-        np.testing.assert_array_equal(got[b:b + 1], want)
+        assert_bits_equal(got[b:b + 1], want, "face %d" % b)
     for sched in (1,):
         with q30_mode.options(FR_Q30_SCHED=sched):
-            np.testing.assert_array_equal(_decode_gpu(net, P, R), got, err_msg="FR_Q30_SCHED=%d" % sched)
+            assert_bits_equal(_decode_gpu(net, P, R), got, "FR_Q30_SCHED=%d" % sched)
     # deterministic; a face's result does not depend on what else is in the batch (its scale is its own)
-    np.testing.assert_array_equal(_decode_gpu(net, P, R), got)
+    assert_bits_equal(_decode_gpu(net, P, R), got, "second run")
     perm = np.random.RandomState(1).permutation(64)
-    np.testing.assert_array_equal(_decode_gpu(net, P[perm], R[perm]), got[perm])
-    np.testing.assert_array_equal(_decode_gpu(net, P[5:22], R[5:22]), got[5:22])
+    assert_bits_equal(_decode_gpu(net, P[perm], R[perm]), got[perm], "permuted batch")
+    assert_bits_equal(_decode_gpu(net, P[5:22], R[5:22]), got[5:22], "faces 5 .. 21 alone")
     # accuracy of the blend itself: identity pose, so x and z ARE v = mu + S + E
     P2 = P[:4].copy()
     P2[:, 3:6] = 0
