@@ -16,7 +16,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG_DIR, "csrc")
 LIB_PATH = os.path.join(_PKG_DIR, "libfr_hotpath.so")
 SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_bwd.hip", "fr_render_nbwd.hip",
-           "fr_render_tbwd.hip", "fr_sfs.hip"]
+           "fr_render_tbwd.hip", "fr_sfs.hip", "fr_depth_normals.hip"]
 HEADERS = [os.path.join(_CSRC, "fr_common.h"), os.path.join(_CSRC, "fr_decode_shared.h"), os.path.join(_CSRC, "fr_sfs_pinv.h"),
            os.path.join(_CSRC, "fr_owner_scatter.h"), os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -225,6 +225,12 @@ def _bind(L):
     L.fr_sfs_backward_apply.restype = _i
     L.fr_debug_sfs_split_geom.argtypes = [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]
     L.fr_debug_sfs_split_geom.restype = None
+    L.fr_depth_normals_forward.argtypes = [_vp, _vp, _i, _i, _i, _vp, _vp]
+    L.fr_depth_normals_forward.restype = _i
+    L.fr_depth_normals_backward.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]
+    L.fr_depth_normals_backward.restype = _i
+    L.fr_debug_depth_normals_geom.argtypes = [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]
+    L.fr_debug_depth_normals_geom.restype = None
     L.fr_sfs_state_bytes.argtypes = [_i, _i]
     L.fr_sfs_state_bytes.restype = ctypes.c_size_t
     L.fr_sfs_intensity_forward.argtypes = [_vp] * 5 + [_i, _i, _i, ctypes.c_double, _vp, _vp, ctypes.c_size_t, _vp]
@@ -279,7 +285,8 @@ EXPORTS = ["fr_version", "fr_strerror", "fr_render_depth_workspace_bytes", "fr_r
            "fr_render_texture_backward_workspace_bytes", "fr_render_texture_backward", "fr_debug_render_texture_bwd_geom",
            "fr_sfs_intensity_backward_tex",
            "fr_sfs_moments_bytes", "fr_sfs_moments", "fr_sfs_solve_shade", "fr_sfs_q_bytes", "fr_sfs_backward_q",
-           "fr_sfs_backward_apply", "fr_debug_sfs_split_geom"]
+           "fr_sfs_backward_apply", "fr_debug_sfs_split_geom",
+           "fr_depth_normals_forward", "fr_depth_normals_backward", "fr_debug_depth_normals_geom"]
 
 
 def lib():

@@ -122,7 +122,7 @@ def spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_image_
 
 
 def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False, normal_grad=False, fused=False, rcond=1e-15,
-                                  tex_grad=False, fused_gather=False):
+                                  tex_grad=False, fused_gather=False, fine_depth=None):
     """Recovered intensity (B,H,W,1) of the first-order spherical-harmonics shading model (network.py:420-462): two
     more render_depth calls (mean albedo, then mean + pc_tex . param_tex) feed spherical_harmonics_intensity.
     normal_grad=False (default): as the reference, both renders hand autograd constant normal maps, so the term has no gradient
@@ -132,7 +132,12 @@ def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False
     (render_depth(texture_grad=True)), hence to face_net.param_tex where that requires grad; the render of the mean texture
     stays a constant.
     fused_gather=True (requires gather and fused, else ValueError): as spherical_harmonics_intensity; works with normal_grad and
-    tex_grad."""
+    tex_grad.
+    fine_depth ([B,H,W,1], default None): the predicted fine depth map.  When given, the shaded normals are ITS normals on the pixel
+    grid -- depth_normals(fine_depth, mask = tri_ind of the second render) -- instead of the second render's normal map, which is
+    the coarse mesh's a second time (the reference's own complaint, network.py:451-453); the term then constrains the fine depth
+    and its gradient reaches fine_depth.  The lighting still comes from the first render and abedo_new from the second.  Works with
+    every flag above (the gradient of the shaded normals is local to the rank)."""
     fn = face_net
     if fused_gather and not (gather and fused):
         raise ValueError("fused_gather=True needs gather=True and fused=True")
@@ -142,11 +147,17 @@ def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False
     abedo_image, normal_map = fn.compute_abedo_image(vertices_proj, fn.tri, fn.mu_tex, **kw)   # (B,H,W,1), (B,H,W,3)
     texture_new = fn.mu_tex + (fn.pc_tex @ fn.param_tex).reshape(3, -1)                    # network.py:446-448
     kw_new = dict(kw, texture_grad=True) if tex_grad else kw
-    abedo_new, normal_new = fn.compute_abedo_image(vertices_proj, fn.tri, texture_new, **kw_new)
+    if fine_depth is None:
+        abedo_new, normal_new = fn.compute_abedo_image(vertices_proj, fn.tri, texture_new, **kw_new)
+    else:
+        abedo_new, _, tri_ind_new = fn.compute_abedo_image(vertices_proj, fn.tri, texture_new, with_tri_ind=True, **kw_new)
+        normal_new = _ops().depth_normals(fine_depth, mask=tri_ind_new.detach())
     if fused and not normal_grad:
         # the renders' normal maps are constants to autograd in this mode (their node drops the gradient): say so, and the fused
-        # node runs no backward at all
-        normal_map, normal_new = normal_map.detach(), normal_new.detach()
+        # node runs no backward at all -- unless the shaded normals are the fine depth map's, which are not constants
+        normal_map = normal_map.detach()
+        if fine_depth is None:
+            normal_new = normal_new.detach()
     if not (fused or rcond != 1e-15):
         return spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_new, normal_new, gather=gather)
     kw_tex = {"tex_grad": True} if tex_grad else {}
@@ -165,7 +176,7 @@ def combine_losses(losses):
 
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
              gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False,
-             sfs_fused_gather=False):
+             sfs_fused_gather=False, sfs_fine=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
     sfs_normal_grad / sfs_fused / sfs_rcond (defaults: off, off, the reference's 1e-15): the normal_grad / fused / rcond of
     get_spherical_harmonics_model.  With them off spherical_harmonics_loss is a reported scalar with no gradient, as in the
@@ -173,7 +184,10 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     sfs_tex_grad=True (default off): the term also reaches the albedo coefficients face_net.param_tex, where that tensor requires
     grad (FaceReconModel(learn_tex=True)), through the render of texture_new.
     sfs_fused_gather=True (default off; needs gather_sfs and sfs_fused, else ValueError): the whole-batch lighting estimate on
-    the fused kernels under any world size, the ranks exchanging per-pixel sums (get_spherical_harmonics_model(fused_gather=True))."""
+    the fused kernels under any world size, the ranks exchanging per-pixel sums (get_spherical_harmonics_model(fused_gather=True)).
+    sfs_fine=True (default off): the term shades the normals of pred_depth_map instead of the coarse mesh's a second time
+    (get_spherical_harmonics_model(fine_depth=pred_depth_map)), so spherical_harmonics_loss has a gradient with respect to
+    pred_depth_map on either route; ValueError when pred_depth_map is None."""
     fn = face_net
     B = pred_params.shape[0]
     pred = pred_params.reshape(B, fn.ndim)
@@ -187,6 +201,10 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     kw_tex = {"tex_grad": True} if sfs_tex_grad else {}
     if sfs_fused_gather:
         kw_tex["fused_gather"] = True
+    if sfs_fine:
+        if pred_depth_map is None:
+            raise ValueError("sfs_fine=True needs pred_depth_map (the fine depth map whose normals the term shades)")
+        kw_tex["fine_depth"] = pred_depth_map
     intensity_recover = get_spherical_harmonics_model(fn, vertices_proj, im_gray, gather=gather_sfs, normal_grad=sfs_normal_grad,
                                                       fused=sfs_fused, rcond=sfs_rcond, **kw_tex)
     losses['spherical_harmonics_loss'] = F.mse_loss(intensity_recover, im_gray)

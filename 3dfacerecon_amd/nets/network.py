@@ -431,11 +431,13 @@ class FaceRecNet:
                 pass
         return self.coarse_net_input(self.vertices_transform(p, R=Rc, pose_grad=pose_grad), im_gray=im_gray)
 
-    def compute_abedo_image(self, vertices, triangles, abedos, im_gray=None, normal_grad=False, texture_grad=False):
+    def compute_abedo_image(self, vertices, triangles, abedos, im_gray=None, normal_grad=False, texture_grad=False,
+                            with_tri_ind=False):
         """Albedo (3,N) -> albedo image + normalised normal map through a second render (network.py:394-417).
         normal_grad=True: the normal map carries its gradient to the vertices (render_depth, normal_grad); default: a constant
         to autograd, as the reference.
-        texture_grad=True: the albedo image carries its gradient to `abedos` (render_depth, texture_grad); default: none."""
+        texture_grad=True: the albedo image carries its gradient to `abedos` (render_depth, texture_grad); default: none.
+        with_tri_ind=True: also returns the render's tri_ind [B,H,W,1] (-1 = background) as a third value; default: two values."""
         ver = vertices.float()
         tri = torch.as_tensor(triangles, dtype=torch.float32, device=ver.device)
         tex = torch.as_tensor(abedos, dtype=torch.float32, device=ver.device)
@@ -444,13 +446,15 @@ class FaceRecNet:
         kw = {"normal_grad": True} if normal_grad else {}
         if texture_grad:
             kw["texture_grad"] = True
-        _, tf_abedo, normal, _ = _ops().render_depth(ver=ver, tri=tri, texture=tex, image=image, **kw)
+        _, tf_abedo, normal, tri_ind = _ops().render_depth(ver=ver, tri=tri, texture=tex, image=image, **kw)
         abedos_image = torch.clamp_min(tf_abedo, 1e-6).mean(dim=-1, keepdim=True)  # (B, H, W, 1)
         flip = normal[..., 2:3] < 0
         normal = torch.where(flip, -1.0 * normal, normal)
         mag = (normal * normal).sum(-1)
         mag = torch.where(mag > 1e-6, mag, torch.ones_like(mag))
         normal_map = normal / (torch.sqrt(mag) + 1e-6)[..., None]
+        if with_tri_ind:
+            return abedos_image, normal_map, tri_ind
         return abedos_image, normal_map
 
     def depth_rendering_layer(self):

@@ -775,6 +775,65 @@ def sfs_intensity_sharded(abedo, normal, im_gray, abedo_new, normal_new, rcond=1
     return _SfsIntensitySharded.apply(abedo, normal, im_gray, abedo_new, normal_new, float(rcond), bool(abedo_grad), exchange)
 
 
+class _DepthNormals(torch.autograd.Function):
+    """fr_depth_normals_forward / _backward (include/fr_hotpath.h, "depth-map normals") as one autograd node."""
+
+    @staticmethod
+    def forward(ctx, depth, mask):
+        h = _host()
+        if isinstance(mask, torch.Tensor) and mask.requires_grad:
+            raise ValueError("depth_normals: mask requires grad, but the mask is a constant of this operator (detach it)")
+        d_c = h.require_gpu_f32(depth, "depth")
+        if d_c.dim() == 4 and d_c.shape[3] == 1:
+            B, H, W = int(d_c.shape[0]), int(d_c.shape[1]), int(d_c.shape[2])
+        elif d_c.dim() == 3:
+            B, H, W = (int(v) for v in d_c.shape)
+        else:
+            raise ValueError("depth_normals expects depth [B,H,W,1] or [B,H,W] (got %s)" % (tuple(d_c.shape),))
+        m_c = None
+        if mask is not None:
+            m_c = h.require_gpu_f32(mask, "mask")
+            if tuple(m_c.shape) not in ((B, H, W, 1), (B, H, W)):
+                raise ValueError("depth_normals: mask must be [%d,%d,%d,1] or [%d,%d,%d] (got %s)"
+                                 % (B, H, W, B, H, W, tuple(m_c.shape)))
+            if m_c.device != d_c.device:
+                raise ValueError("depth_normals: mask is on %s, depth on %s" % (m_c.device, d_c.device))
+        dev = d_c.device
+        normal = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = h.lib().fr_depth_normals_forward(h.ptr(d_c), h.ptr(m_c), B, H, W, h.ptr(normal), h.stream_ptr(dev))
+        h.check(rc, "fr_depth_normals_forward")
+        ctx.save_for_backward(d_c, m_c)
+        ctx.dims = (B, H, W)
+        ctx.depth_shape = tuple(depth.shape)
+        return normal
+
+    @staticmethod
+    def backward(ctx, g):
+        h = _host()
+        d_c, m_c = ctx.saved_tensors
+        B, H, W = ctx.dims
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        dev = d_c.device
+        g_c = h.require_gpu_f32(g, "grad_normal")
+        gd = torch.empty(ctx.depth_shape, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = h.lib().fr_depth_normals_backward(h.ptr(g_c), h.ptr(d_c), h.ptr(m_c), B, H, W, h.ptr(gd), h.stream_ptr(dev))
+        h.check(rc, "fr_depth_normals_backward")
+        return gd, None
+
+
+def depth_normals(depth, mask=None):
+    """The normal map [B,H,W,3] of a depth map [B,H,W,1] (or [B,H,W]) on the pixel grid, in the renderer's conventions: per valid
+    pixel (-dz/dx, -dz/dy, 1) normalised, x = column, y = row, n_z > 0; central differences inside the mask, one-sided ones at its
+    edges, a zero slope where a pixel has no valid neighbour on an axis; (0, 0, 0) at invalid pixels (fr_depth_normals_forward:
+    float64 arithmetic, one kernel pass).  `mask` ([B,H,W,1] or [B,H,W], e.g. a render's tri_ind): a pixel is valid iff mask >= 0
+    (NaN is invalid); None: every pixel is.  The gradient goes to `depth`, in depth's own shape (fr_depth_normals_backward: a
+    gather, bit-reproducible); `mask` gets None, and a mask that requires grad is refused.  The node saves `depth` and `mask`."""
+    return _DepthNormals.apply(depth, mask)
+
+
 def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     """One-pass rendering layer: returns (net_input [B,H,W,7] = [mask*im | pncc | normal],
     depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers.

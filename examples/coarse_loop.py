@@ -73,7 +73,8 @@ def build_harness(args, dev, rank, world, local):
                                     out["pred_depth_map"], gather_sfs=args.gather_sfs, sfs_normal_grad=args.sfs_grad,
                                     sfs_fused=args.sfs_fused, sfs_rcond=args.sfs_rcond,
                                     **({"sfs_tex_grad": True} if args.sfs_tex_grad else {}),
-                                    **({"sfs_fused_gather": True} if args.sfs_fused_gather else {}))
+                                    **({"sfs_fused_gather": True} if args.sfs_fused_gather else {}),
+                                    **({"sfs_fine": True} if args.sfs_fine else {}))
 
     def step():
         if not args.train:
@@ -230,6 +231,10 @@ def build_parser():
                     help="let the shape-from-shading term fit the albedo coefficients: param_tex becomes a parameter of the model "
                          "(FaceReconModel(learn_tex=True)) and the render of the new texture carries the albedo image's gradient to it "
                          "(get_loss(sfs_tex_grad=True), fr_render_texture_backward); off: param_tex is a constant, as in the reference")
+    ap.add_argument("--sfs-fine", action="store_true",
+                    help="the SfS term shades the normals of the predicted FINE depth map (depth_normals: fr_depth_normals_forward / "
+                         "_backward, masked by the render's tri_ind) instead of the coarse mesh's a second time, so the term's gradient "
+                         "reaches pred_depth_map (get_loss(sfs_fine=True)); needs --fine; off: as the reference")
     ap.add_argument("--sfs-rcond", type=float, default=1e-15,
                     help="eigenvalue cutoff of the SfS pseudo-inverse, relative to the largest.  With float64 sums a rank-deficient "
                          "pixel (fewer than three faces cover it, or their normals are parallel) has null eigenvalues near 1e-16 "

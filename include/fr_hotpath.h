@@ -658,6 +658,63 @@ int fr_sfs_backward_apply(const float* grad_intensity, const float* abedo, const
  * tests/test_sfs_sharded_cpu.py. */
 void fr_debug_sfs_split_geom(int B, int H, int W, int* out);
 
+/* ---- depth-map normals: the normal map of a depth map on the pixel grid, with a backward (opt-in) --------------------------------
+ * The reference's shape-from-shading term shades the COARSE mesh's normals twice and says so (nets/network.py:451-453: "how to
+ * inversely convert predicted fine depth into new vertices, in order to get new normals ??").  No conversion is needed: the fine
+ * depth map lives on the pixel grid and so do its normals.  These entry points turn a depth map into a normal map in the renderer's
+ * conventions, masked to the face and exact at the mask's edges, and carry a normal-map gradient back to the depth map; the
+ * backward's input is what fr_sfs_intensity_backward hands out as grad_normal_new.
+ *   depth, mask, grad_depth  [B,H,W,1];   normal, grad_normal  [B,H,W,3];   dense fp32.  Pixel (r, c) is row-major with x = column,
+ *   y = row: the rasteriser's q = y * W + x.
+ * MASK.  mask may be NULL: every pixel of the image is then valid.  Otherwise pixel p is valid iff mask[p] >= 0.0f -- the tri_ind
+ * convention (background is -1; a NaN is invalid).  Positions outside the image are invalid.
+ * FORWARD, per pixel.  All arithmetic in float64 on the widened fp32 inputs, every operation rounded on its own (no contraction).
+ * An invalid p gives normal = (+0, +0, +0).  For a valid p = (r, c), with L = valid(r, c - 1), R = valid(r, c + 1) and z_L, z_R, z_p
+ * the depths there:
+ *   dx = (z_R - z_L) * 0.5   L and R (central)          dx = z_R - z_p   R only          dx = z_p - z_L   L only          dx = 0.0   neither
+ *   dy likewise from the rows r - 1 (lo) and r + 1 (hi)
+ *   s = sqrt((dx * dx + dy * dy) + 1.0)
+ *   normal = ( fl32(-dx / s), fl32(-dy / s), fl32(1.0 / s) )
+ * The sign is the renderer's: the larger depth wins the z-test, so the surface faces +z and its normal is (-dz/dx, -dz/dy, 1)
+ * normalised, n_z > 0 -- compute_abedo_image's normalised map is the triangle normal flipped to z >= 0 (on a tessellated plane the
+ * two agree to the render's own +1e-6 and fp32 roundings: tests/test_depth_normals_cpu.py).  An invalid pixel's depth is never
+ * read, and a valid pixel's own depth enters a one-sided difference only.  A non-finite depth reaches only the pixels whose stencil
+ * reads it, through the ordinary IEEE operations above; no other pixel changes by a bit.
+ * BACKWARD.  g = grad_normal[p] widened; dx, dy, s recomputed as in the forward; n = (-dx / s, -dy / s, 1.0 / s) in float64, NOT
+ * rounded to fp32.  Per valid pixel
+ *   d = (g_x n_x + g_y n_y) + g_z n_z          e_x(p) = -((g_x - n_x d) / s)          e_y(p) = -((g_y - n_y d) / s)
+ * (dL / d dx and dL / d dy).  The coefficients of dx on the depths it reads are the forward's: +-0.5 for a central difference, +-1
+ * for a one-sided one, and on the pixel's own depth -1 ("R only"), +1 ("L only"), 0 otherwise.  For a valid p
+ *   grad_depth[p] = fl32( ((((own_x + own_y) + from_left) + from_right) + from_up) + from_down )
+ *   own_x      = -e_x(p) "R only", e_x(p) "L only", else +0.0;   own_y alike with e_y and the rows
+ *   from_left  = c * e_x(left neighbour),  c = 0.5 if that neighbour's difference is central, 1 if one-sided (p is its R)
+ *   from_right = -(c * e_x(right neighbour)),  c likewise (p is its L);   from_up, from_down: the same with e_y of (r - 1, c), (r + 1, c)
+ * A term whose neighbour is invalid, and an own term whose coefficient is 0, is +0.0 -- never 0 times a value.  An invalid p gets
+ * exactly +0.  A gather: no atomics, no workspace; each output is a function of its pixel's 13-point neighbourhood (mask, depth,
+ * grad_normal) and of nothing else -- not of B, H, W, the pixel's position or the launch geometry.  Bit-reproducible.  No gradient
+ * is formed for the mask.
+ * Checks, all before any HIP call, in this order: a negative size is FR_ERR_INVALID_ARG; then B == 0 or an empty image is FR_OK;
+ * then a NULL depth, output or grad_normal is FR_ERR_INVALID_ARG; more than 2^31 - 65 pixels per face is FR_ERR_UNSUPPORTED (as is
+ * a grid the runtime does not take: more than 65,535 faces or 65,535 tile rows).  Nothing is allocated or synchronised; reentrant
+ * under the rules at the top of this file.
+ * Kernels (csrc/fr_depth_normals.hip): a workgroup owns a 32 x 16 pixel tile of one face, one lane per pixel; a wave covers two
+ * 32-pixel row segments (2 x 384 contiguous bytes of a normal plane).  The forward reads its five-point stencil from global memory
+ * (the workgroup's own L1 lines) and uses no LDS.  The backward STAGES e_x, e_y in LDS instead of recomputing them in their readers:
+ * every lane evaluates its own pixel once, 96 lanes the halo (two columns for e_x, two rows for e_y), one barrier, then the gather
+ * -- 1.19 evaluations per output instead of 5, 8,960 bytes of LDS.  200 x 200 x 64 faces is 5,824 workgroups of 8 waves.
+ * Bytes and time: at 64 faces of 200 x 200 the forward must move 51 MB (depth 10 + mask 10 read, normal 31 written), the backward
+ * 61 MB (31 + 10 + 10 read, 10 written); tools/depth_normals_probe.py (profiles/depth_normals.json) measures both beside the same
+ * operator composed from stock torch ops. */
+int fr_depth_normals_forward(const float* depth, const float* mask, int B, int H, int W, float* normal, void* hip_stream);
+int fr_depth_normals_backward(const float* grad_normal, const float* depth, const float* mask, int B, int H, int W,
+                              float* grad_depth, void* hip_stream);
+
+/* The depth-normals launch geometry (no GPU needed; the launchers read the same function): out[6] = {tile width, tile height,
+ * threads per workgroup, tiles across, tiles down, static LDS bytes of a backward workgroup}; the grid is tiles across x tiles
+ * down x B.  All zero for an empty shape or one the launchers refuse.  Used by tests/ref_depth_normals.py to place its shapes on
+ * the tile's edges and by tests/test_depth_normals_cpu.py. */
+void fr_debug_depth_normals_geom(int B, int H, int W, int* out);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
