@@ -29,9 +29,6 @@ _ERR_NAMES = {-1: "invalid argument", -2: "workspace / packed buffer too small",
 _lock = threading.Lock()
 _lib = None
 
-_vp = ctypes.c_void_p
-_i = ctypes.c_int
-
 
 def _hipcc():
     for cand in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", "hipcc"):
@@ -111,182 +108,95 @@ def compile(force=False, verbose=False):
     return LIB_PATH
 
 
-def _bind(L):
-    L.fr_version.restype = ctypes.c_char_p
-    L.fr_strerror.argtypes = [_i]
-    L.fr_strerror.restype = ctypes.c_char_p
-    L.fr_render_depth_workspace_bytes.argtypes = [_i] * 5
-    L.fr_render_depth_workspace_bytes.restype = ctypes.c_size_t
-    L.fr_render_depth_forward.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                                          ctypes.c_size_t, _vp]
-    L.fr_render_depth_forward.restype = _i
-    L.fr_render_depth_forward_phases.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                                                 ctypes.c_size_t, _vp, _i]
-    L.fr_render_depth_forward_phases.restype = _i
-    L.fr_rendering_layer_forward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                                             ctypes.c_size_t, _vp]
-    L.fr_rendering_layer_forward.restype = _i
-    L.fr_rendering_layer_forward_phases.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                                                    ctypes.c_size_t, _vp, _i]
-    L.fr_rendering_layer_forward_phases.restype = _i
-    L.fr_render_depth_backward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]
-    L.fr_render_depth_backward.restype = _i
-    L.fr_render_depth_backward_workspace_bytes.argtypes = [_i, _i, _i]
-    L.fr_render_depth_backward_workspace_bytes.restype = ctypes.c_size_t
-    L.fr_render_depth_backward_ws.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
-    L.fr_render_depth_backward_ws.restype = _i
-    L.fr_decode_packed_basis_bytes.argtypes = [_i, _i, _i]
-    L.fr_decode_packed_basis_bytes.restype = ctypes.c_size_t
-    L.fr_decode_pack_basis.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
-    L.fr_decode_pack_basis.restype = _i
-    L.fr_decode_3dmm.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp]
-    L.fr_decode_3dmm.restype = _i
-    L.fr_decode_q30_image_bytes.argtypes = [_i, _i, _i]
-    L.fr_decode_q30_image_bytes.restype = ctypes.c_size_t
-    L.fr_decode_q30_pack.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
-    L.fr_decode_q30_pack.restype = _i
-    L.fr_decode_q30_workspace_bytes.argtypes = [_i, _i]
-    L.fr_decode_q30_workspace_bytes.restype = ctypes.c_size_t
-    L.fr_decode_3dmm_q30.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]
-    L.fr_decode_3dmm_q30.restype = _i
-    L.fr_decode_3dmm_q30_lv.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _i, _vp, _vp, ctypes.c_size_t, _vp]
-    L.fr_decode_3dmm_q30_lv.restype = _i
-    L.fr_decode_render_forward_q30.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, _i, _vp,
-                                               ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
-                                               _vp, _i]
-    L.fr_decode_render_forward_q30.restype = _i
-    L.fr_decode_render_vertex_pitch.argtypes = [_i]
-    L.fr_decode_render_vertex_pitch.restype = _i
-    L.fr_decode_render_vertex_bytes.argtypes = [_i, _i]
-    L.fr_decode_render_vertex_bytes.restype = ctypes.c_size_t
-    L.fr_decode_render_forward.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, _vp,
-                                           ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, _i]
-    L.fr_decode_render_forward.restype = _i
-    L.fr_set_option.argtypes = [ctypes.c_char_p, _i]
-    L.fr_set_option.restype = _i
-    L.fr_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
-    L.fr_get_option.restype = _i
-    L.fr_decode_backward_workspace_bytes.argtypes = [_i, _i, _i, _i]
-    L.fr_decode_backward_workspace_bytes.restype = ctypes.c_size_t
-    L.fr_decode_3dmm_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp,
-                                          ctypes.c_size_t, _vp]
-    L.fr_decode_3dmm_backward.restype = _i
-    L.fr_decode_backward_basis_bytes.argtypes = [_i, _i, _i]
-    L.fr_decode_backward_basis_bytes.restype = ctypes.c_size_t
-    L.fr_decode_backward_pack_basis.argtypes = [_vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
-    L.fr_decode_backward_pack_basis.restype = _i
-    L.fr_decode_3dmm_backward_packed.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp,
-                                                 ctypes.c_size_t, _vp]
-    L.fr_decode_3dmm_backward_packed.restype = _i
-    L.fr_decode_3dmm_backward_packed_mu.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp,
-                                                    ctypes.c_size_t, _vp]
-    L.fr_decode_3dmm_backward_packed_mu.restype = _i
-    L.fr_decode_rendering_layer_forward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float,
-                                                    _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, _i]
-    L.fr_decode_rendering_layer_forward.restype = _i
-    L.fr_decode_render_backward_workspace_bytes.argtypes = [_i] * 6
-    L.fr_decode_render_backward_workspace_bytes.restype = ctypes.c_size_t
-    L.fr_decode_render_backward.argtypes = [_vp] * 11 + [_i] * 7 + [ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]
-    L.fr_decode_render_backward.restype = _i
-    L.fr_decode_pose_backward_workspace_bytes.argtypes = [_i, _i]
-    L.fr_decode_pose_backward_workspace_bytes.restype = ctypes.c_size_t
-    L.fr_decode_pose_backward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp]
-    L.fr_decode_pose_backward.restype = _i
-    L.fr_decode_render_backward_pose_workspace_bytes.argtypes = [_i] * 6
-    L.fr_decode_render_backward_pose_workspace_bytes.restype = ctypes.c_size_t
-    L.fr_decode_render_backward_pose.argtypes = ([_vp] * 11 + [_i] * 7 + [ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]
-                                                 + [_vp, ctypes.c_size_t, _vp])
-    L.fr_decode_render_backward_pose.restype = _i
-    L.fr_render_normal_backward_workspace_bytes.argtypes = [_i] * 4
-    L.fr_render_normal_backward_workspace_bytes.restype = ctypes.c_size_t
-    L.fr_render_normal_backward.argtypes = [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
-    L.fr_render_normal_backward.restype = _i
-    L.fr_debug_render_normal_bwd_geom.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_render_normal_bwd_geom.restype = None
-    L.fr_render_texture_backward_workspace_bytes.argtypes = [_i] * 5
-    L.fr_render_texture_backward_workspace_bytes.restype = ctypes.c_size_t
-    L.fr_render_texture_backward.argtypes = [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
-    L.fr_render_texture_backward.restype = _i
-    L.fr_debug_render_texture_bwd_geom.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_render_texture_bwd_geom.restype = None
-    L.fr_sfs_intensity_backward_tex.argtypes = [_vp] * 6 + [ctypes.c_size_t, _i, _i, _i, _vp, _vp, _vp, _vp]
-    L.fr_sfs_intensity_backward_tex.restype = _i
-    L.fr_sfs_moments_bytes.argtypes = [_i, _i]
-    L.fr_sfs_moments_bytes.restype = ctypes.c_size_t
-    L.fr_sfs_moments.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
-    L.fr_sfs_moments.restype = _i
-    L.fr_sfs_solve_shade.argtypes = [_vp, _i, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, ctypes.c_size_t, _vp]
-    L.fr_sfs_solve_shade.restype = _i
-    L.fr_sfs_q_bytes.argtypes = [_i, _i]
-    L.fr_sfs_q_bytes.restype = ctypes.c_size_t
-    L.fr_sfs_backward_q.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]
-    L.fr_sfs_backward_q.restype = _i
-    L.fr_sfs_backward_apply.argtypes = [_vp] * 6 + [ctypes.c_size_t, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]
-    L.fr_sfs_backward_apply.restype = _i
-    L.fr_debug_sfs_split_geom.argtypes = [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_sfs_split_geom.restype = None
-    L.fr_depth_normals_forward.argtypes = [_vp, _vp, _i, _i, _i, _vp, _vp]
-    L.fr_depth_normals_forward.restype = _i
-    L.fr_depth_normals_backward.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]
-    L.fr_depth_normals_backward.restype = _i
-    L.fr_debug_depth_normals_geom.argtypes = [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_depth_normals_geom.restype = None
-    L.fr_sfs_state_bytes.argtypes = [_i, _i]
-    L.fr_sfs_state_bytes.restype = ctypes.c_size_t
-    L.fr_sfs_intensity_forward.argtypes = [_vp] * 5 + [_i, _i, _i, ctypes.c_double, _vp, _vp, ctypes.c_size_t, _vp]
-    L.fr_sfs_intensity_forward.restype = _i
-    L.fr_sfs_intensity_backward.argtypes = [_vp] * 6 + [ctypes.c_size_t, _i, _i, _i, _vp, _vp, _vp]
-    L.fr_sfs_intensity_backward.restype = _i
-    L.fr_debug_sfs_geom.argtypes = [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_sfs_geom.restype = None
-    L.fr_debug_sfs_pinv.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.POINTER(ctypes.c_double),
-                                    ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_sfs_pinv.restype = _i
-    L.fr_debug_pose_bwd_geom.argtypes = [_i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_pose_bwd_geom.restype = None
-    L.fr_render_depth_strip_rows.argtypes = [_i] * 4
-    L.fr_render_depth_strip_rows.restype = _i
-    L.fr_debug_render_geom.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_render_geom.restype = None
-    L.fr_debug_decode_bwd_geom.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_decode_bwd_geom.restype = None
-    L.fr_debug_decode_geom.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_decode_geom.restype = _i
-    L.fr_debug_decode_q_geom.argtypes = [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_decode_q_geom.restype = _i
-    L.fr_debug_decode_walk.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_decode_walk.restype = _i
-    L.fr_debug_render_bwd_geom.argtypes = [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    L.fr_debug_render_bwd_geom.restype = None
-    L.fr_debug_div3_sweep.argtypes = [ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _vp]
-    L.fr_debug_div3_sweep.restype = _i
-    L.fr_debug_clock_probe.argtypes = [_vp, _i, _i, _vp]
-    L.fr_debug_clock_probe.restype = _i
-    return L
+# The C ABI of include/fr_hotpath.h, one row per entry point: "return:arguments", one letter per type as Python sees it.
+# The library is bound from this table alone (a binary-only deployment has no header to read);
+# tests/test_capi_signatures_cpu.py holds every row to the header's prototype, position by position.
+_CTYPE = {"p": ctypes.c_void_p, "i": ctypes.c_int, "z": ctypes.c_size_t, "u": ctypes.c_ulonglong, "f": ctypes.c_float,
+          "d": ctypes.c_double, "s": ctypes.c_char_p, "I": ctypes.POINTER(ctypes.c_int), "D": ctypes.POINTER(ctypes.c_double),
+          "v": None}
+SIGNATURES = {
+    "fr_version":                                     "s:",
+    "fr_strerror":                                    "s:i",
+    "fr_set_option":                                  "i:si",
+    "fr_get_option":                                  "i:sI",
+    "fr_render_depth_workspace_bytes":                "z:iiiii",
+    "fr_render_depth_forward":                        "i:pppiiiiiiipppppzp",
+    "fr_render_depth_forward_phases":                 "i:pppiiiiiiipppppzpi",
+    "fr_rendering_layer_forward":                     "i:ppppiiiiiipppppzp",
+    "fr_rendering_layer_forward_phases":              "i:ppppiiiiiipppppzpi",
+    "fr_render_depth_backward":                       "i:ppppiiiiip",
+    "fr_render_depth_backward_workspace_bytes":       "z:iii",
+    "fr_render_depth_backward_ws":                    "i:ppppiiiiipzp",
+    "fr_decode_packed_basis_bytes":                   "z:iii",
+    "fr_decode_pack_basis":                           "i:pppiiipzp",
+    "fr_decode_3dmm":                                 "i:pppiiiifpp",
+    "fr_render_depth_strip_rows":                     "i:iiii",
+    "fr_decode_render_vertex_pitch":                  "i:i",
+    "fr_decode_render_vertex_bytes":                  "z:ii",
+    "fr_decode_render_forward":                       "i:pppppiiiiiiiifpzpppppzpi",
+    "fr_decode_q30_image_bytes":                      "z:iii",
+    "fr_decode_q30_pack":                             "i:pppiiipzp",
+    "fr_decode_q30_workspace_bytes":                  "z:ii",
+    "fr_decode_3dmm_q30":                             "i:pppiiiifppzp",
+    "fr_decode_3dmm_q30_lv":                          "i:pppiiiifippzp",
+    "fr_decode_render_forward_q30":                   "i:pppppiiiiiiiifipzpppppzpzpi",
+    "fr_decode_backward_workspace_bytes":             "z:iiii",
+    "fr_decode_3dmm_backward":                        "i:ppppppiiiifppzp",
+    "fr_decode_backward_basis_bytes":                 "z:iii",
+    "fr_decode_backward_pack_basis":                  "i:ppiiipzp",
+    "fr_decode_3dmm_backward_packed":                 "i:pppppiiiifppzp",
+    "fr_decode_3dmm_backward_packed_mu":              "i:pppppiiiifppzp",
+    "fr_decode_rendering_layer_forward":              "i:ppppppiiiiiiiifpzpppppzpi",
+    "fr_decode_render_backward_workspace_bytes":      "z:iiiiii",
+    "fr_decode_render_backward":                      "i:pppppppppppiiiiiiifppzp",
+    "fr_decode_pose_backward_workspace_bytes":        "z:ii",
+    "fr_decode_pose_backward":                        "i:ppppiiiifpppzp",
+    "fr_decode_render_backward_pose_workspace_bytes": "z:iiiiii",
+    "fr_decode_render_backward_pose":                 "i:pppppppppppiiiiiiifppzppzp",
+    "fr_render_normal_backward_workspace_bytes":      "z:iiii",
+    "fr_render_normal_backward":                      "i:pipipppiiiiiiipzp",
+    "fr_debug_render_normal_bwd_geom":                "v:iiiiI",
+    "fr_render_texture_backward_workspace_bytes":     "z:iiiii",
+    "fr_render_texture_backward":                     "i:pipppiiiiiiipzp",
+    "fr_debug_render_texture_bwd_geom":               "v:iiiiiI",
+    "fr_sfs_state_bytes":                             "z:ii",
+    "fr_sfs_intensity_forward":                       "i:pppppiiidppzp",
+    "fr_sfs_intensity_backward":                      "i:ppppppziiippp",
+    "fr_sfs_intensity_backward_tex":                  "i:ppppppziiipppp",
+    "fr_debug_sfs_geom":                              "v:iiiI",
+    "fr_debug_sfs_pinv":                              "i:DdDI",
+    "fr_sfs_moments_bytes":                           "z:ii",
+    "fr_sfs_moments":                                 "i:pppiiipzp",
+    "fr_sfs_solve_shade":                             "i:pippiiidppzp",
+    "fr_sfs_q_bytes":                                 "z:ii",
+    "fr_sfs_backward_q":                              "i:pppiiipzp",
+    "fr_sfs_backward_apply":                          "i:ppppppzpiiiipppp",
+    "fr_debug_sfs_split_geom":                        "v:iiiI",
+    "fr_depth_normals_forward":                       "i:ppiiipp",
+    "fr_depth_normals_backward":                      "i:pppiiipp",
+    "fr_debug_depth_normals_geom":                    "v:iiiI",
+    "fr_debug_render_geom":                           "v:iiiiiI",
+    "fr_debug_decode_bwd_geom":                       "v:iiiiI",
+    "fr_debug_decode_geom":                           "i:iiiiiI",
+    "fr_debug_decode_q_geom":                         "i:iiiiiiI",
+    "fr_debug_decode_walk":                           "i:iiiiI",
+    "fr_debug_pose_bwd_geom":                         "v:iiI",
+    "fr_debug_render_bwd_geom":                       "v:iiiiI",
+    "fr_debug_div3_sweep":                            "i:uupp",
+    "fr_debug_clock_probe":                           "i:piip",
+}
+EXPORTS = list(SIGNATURES)
 
 
-EXPORTS = ["fr_version", "fr_strerror", "fr_render_depth_workspace_bytes", "fr_render_depth_forward",
-           "fr_render_depth_backward", "fr_decode_packed_basis_bytes", "fr_decode_pack_basis", "fr_decode_3dmm",
-           "fr_decode_backward_workspace_bytes", "fr_decode_3dmm_backward", "fr_rendering_layer_forward",
-           "fr_render_depth_forward_phases", "fr_debug_render_geom", "fr_debug_decode_bwd_geom", "fr_debug_render_bwd_geom",
-           "fr_debug_div3_sweep",
-           "fr_render_depth_backward_workspace_bytes", "fr_render_depth_backward_ws", "fr_set_option", "fr_get_option",
-           "fr_decode_q30_image_bytes", "fr_decode_q30_pack", "fr_decode_q30_workspace_bytes", "fr_decode_3dmm_q30",
-           "fr_decode_3dmm_q30_lv", "fr_decode_render_forward_q30",
-           "fr_decode_render_vertex_pitch", "fr_decode_render_vertex_bytes", "fr_decode_render_forward",
-           "fr_decode_backward_basis_bytes", "fr_decode_backward_pack_basis", "fr_decode_3dmm_backward_packed",
-           "fr_debug_clock_probe", "fr_rendering_layer_forward_phases", "fr_decode_3dmm_backward_packed_mu",
-           "fr_render_depth_strip_rows", "fr_decode_rendering_layer_forward", "fr_decode_render_backward_workspace_bytes",
-           "fr_decode_render_backward", "fr_decode_pose_backward_workspace_bytes", "fr_decode_pose_backward",
-           "fr_decode_render_backward_pose_workspace_bytes", "fr_decode_render_backward_pose", "fr_debug_pose_bwd_geom",
-           "fr_render_normal_backward_workspace_bytes", "fr_render_normal_backward", "fr_debug_render_normal_bwd_geom",
-           "fr_sfs_state_bytes", "fr_sfs_intensity_forward", "fr_sfs_intensity_backward", "fr_debug_sfs_geom",
-           "fr_debug_sfs_pinv", "fr_debug_decode_geom", "fr_debug_decode_walk", "fr_debug_decode_q_geom",
-           "fr_render_texture_backward_workspace_bytes", "fr_render_texture_backward", "fr_debug_render_texture_bwd_geom",
-           "fr_sfs_intensity_backward_tex",
-           "fr_sfs_moments_bytes", "fr_sfs_moments", "fr_sfs_solve_shade", "fr_sfs_q_bytes", "fr_sfs_backward_q",
-           "fr_sfs_backward_apply", "fr_debug_sfs_split_geom",
-           "fr_depth_normals_forward", "fr_depth_normals_backward", "fr_debug_depth_normals_geom"]
+def bind(cdll, names=None):
+    """Sets restype / argtypes on a loaded library, ours or another build of it: every entry point of SIGNATURES, or `names`
+    alone (a library built from one source file exports only that file's)."""
+    for name in (SIGNATURES if names is None else names):
+        ret, args = SIGNATURES[name].split(":")
+        fn = getattr(cdll, name)
+        fn.restype = _CTYPE[ret]
+        fn.argtypes = [_CTYPE[c] for c in args]
+    return cdll
 
 
 def lib():
@@ -301,7 +211,7 @@ def lib():
                 if is_stale():
                     compile()
                 try:
-                    L = _bind(ctypes.CDLL(LIB_PATH))
+                    L = bind(ctypes.CDLL(LIB_PATH))
                 except OSError as e:
                     raise RuntimeError("fr_hotpath: cannot load %s (%s); run compile() -- there is no CPU fallback"
                                        % (LIB_PATH, e))

@@ -83,17 +83,43 @@ size_t fr_render_depth_workspace_bytes(int B, int nver, int ntri, int H, int W) 
     return fr_render_workspace_bytes_impl(B, ntri, H, W);  // per-segment hit records + bucket offsets
 }
 
-int fr_render_depth_forward(const float* vertex, const float* tri, const float* texture, int B, int nver, int ntri,
-                            int H, int W, int C, int tex_batch, float* depth, float* tex_img, float* normal,
-                            float* tri_ind, void* workspace, size_t ws_bytes, void* hip_stream) {
+// ---- the render forward's argument checks, stated once ------------------------------------------------------------------------
+// Every entry point that ends in a render forward makes them in this order: render_shape_check, its own "nothing to render"
+// return, render_call_check.
+static int render_shape_check(int B, int nver, int ntri, int H, int W, int C, int tex_batch) {
     if (B < 0 || nver < 0 || ntri < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
     if (C != 3) return FR_ERR_INVALID_ARG;                         // render_depth_op.cc:418
     if (tex_batch != 1 && tex_batch != B) return FR_ERR_INVALID_ARG;
-    if ((size_t)B * H * W == 0) return FR_OK;                      // empty batch / image: nothing to write
-    if (!depth || !tex_img || !normal || !tri_ind) return FR_ERR_INVALID_ARG;
+    return FR_OK;
+}
+
+enum RenderKind {
+    RENDER_PLAIN,        // render_depth
+    RENDER_LAYER,        // the fused rendering layer: it also refuses an empty mesh (nothing to fuse: use the plain op)
+    RENDER_LAYER_SERVED  // the fused layer behind a decode: whatever fr_rendering_layer_supported does not serve is refused
+};
+// outs: the entry point's own outputs (and the layer's im_gray) are all there.  vertex: the caller's, or the decode's hand-off.
+static int render_call_check(bool outs, const float* vertex, const float* tri, const float* texture, int B, int nver, int ntri,
+                             int H, int W, size_t ws_bytes, RenderKind kind) {
+    if (!outs) return FR_ERR_INVALID_ARG;
     if (ntri > 0 && (!tri || (nver > 0 && (!vertex || !texture)))) return FR_ERR_INVALID_ARG;
-    if (ntri >= (1 << 24)) return FR_ERR_UNSUPPORTED;              // float-stored ids stop being exact
+    if (kind == RENDER_LAYER_SERVED) {
+        if (!fr_rendering_layer_supported(B, nver, ntri, H, W)) return FR_ERR_UNSUPPORTED;
+    } else {
+        if (ntri >= (1 << 24)) return FR_ERR_UNSUPPORTED;              // float-stored ids stop being exact
+        if (kind == RENDER_LAYER && (ntri == 0 || nver == 0)) return FR_ERR_UNSUPPORTED;
+    }
     if (ws_bytes < fr_render_depth_workspace_bytes(B, nver, ntri, H, W)) return FR_ERR_WORKSPACE;
+    return FR_OK;
+}
+
+int fr_render_depth_forward(const float* vertex, const float* tri, const float* texture, int B, int nver, int ntri,
+                            int H, int W, int C, int tex_batch, float* depth, float* tex_img, float* normal,
+                            float* tri_ind, void* workspace, size_t ws_bytes, void* hip_stream) {
+    int rc = render_shape_check(B, nver, ntri, H, W, C, tex_batch);
+    if (rc != FR_OK || (size_t)B * H * W == 0) return rc;          // empty batch / image: nothing to write
+    rc = render_call_check(depth && tex_img && normal && tri_ind, vertex, tri, texture, B, nver, ntri, H, W, ws_bytes, RENDER_PLAIN);
+    if (rc != FR_OK) return rc;
     return fr_launch_render_forward(vertex, tri, texture, B, nver, ntri, H, W, tex_batch, depth, tex_img, normal,
                                     tri_ind, workspace, ws_bytes, (hipStream_t)hip_stream);
 }
@@ -102,13 +128,10 @@ int fr_render_depth_forward_phases(const float* vertex, const float* tri, const 
                                    int H, int W, int C, int tex_batch, float* depth, float* tex_img, float* normal,
                                    float* tri_ind, void* workspace, size_t ws_bytes, void* hip_stream, int phases) {
     if (phases < 1 || phases > 7) return FR_ERR_INVALID_ARG;
-    if (B < 0 || nver < 0 || ntri < 0 || H < 0 || W < 0 || C != 3) return FR_ERR_INVALID_ARG;
-    if (tex_batch != 1 && tex_batch != B) return FR_ERR_INVALID_ARG;
-    if ((size_t)B * H * W == 0) return FR_OK;
-    if (!depth || !tex_img || !normal || !tri_ind) return FR_ERR_INVALID_ARG;
-    if (ntri > 0 && (!tri || (nver > 0 && (!vertex || !texture)))) return FR_ERR_INVALID_ARG;
-    if (ntri >= (1 << 24)) return FR_ERR_UNSUPPORTED;
-    if (ws_bytes < fr_render_depth_workspace_bytes(B, nver, ntri, H, W)) return FR_ERR_WORKSPACE;
+    int rc = render_shape_check(B, nver, ntri, H, W, C, tex_batch);
+    if (rc != FR_OK || (size_t)B * H * W == 0) return rc;
+    rc = render_call_check(depth && tex_img && normal && tri_ind, vertex, tri, texture, B, nver, ntri, H, W, ws_bytes, RENDER_PLAIN);
+    if (rc != FR_OK) return rc;
     return fr_launch_render_forward_phases(vertex, tri, texture, B, nver, ntri, H, W, tex_batch, depth, tex_img, normal,
                                            tri_ind, workspace, ws_bytes, (hipStream_t)hip_stream, phases);
 }
@@ -117,14 +140,11 @@ static int rendering_layer_checked(const float* vertex, const float* tri, const 
                                    int nver, int ntri, int H, int W, int tex_batch, float* net_input, float* depth_img,
                                    float* depth, float* tri_ind, void* workspace, size_t ws_bytes, void* hip_stream, int phases) {
     if (phases < 1 || phases > 7) return FR_ERR_INVALID_ARG;
-    if (B < 0 || nver < 0 || ntri < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (tex_batch != 1 && tex_batch != B) return FR_ERR_INVALID_ARG;
-    if ((size_t)B * H * W == 0) return FR_OK;
-    if (!net_input || !depth_img || !depth || !tri_ind || !im_gray) return FR_ERR_INVALID_ARG;
-    if (ntri > 0 && (!tri || (nver > 0 && (!vertex || !texture)))) return FR_ERR_INVALID_ARG;
-    if (ntri >= (1 << 24)) return FR_ERR_UNSUPPORTED;
-    if (ntri == 0 || nver == 0) return FR_ERR_UNSUPPORTED;  // nothing to fuse: use the plain op
-    if (ws_bytes < fr_render_depth_workspace_bytes(B, nver, ntri, H, W)) return FR_ERR_WORKSPACE;
+    int rc = render_shape_check(B, nver, ntri, H, W, 3, tex_batch);
+    if (rc != FR_OK || (size_t)B * H * W == 0) return rc;
+    rc = render_call_check(net_input && depth_img && depth && tri_ind && im_gray, vertex, tri, texture, B, nver, ntri, H, W,
+                           ws_bytes, RENDER_LAYER);
+    if (rc != FR_OK) return rc;
     return fr_launch_rendering_layer(vertex, tri, texture, im_gray, B, nver, ntri, H, W, tex_batch, net_input, depth_img,
                                      depth, tri_ind, workspace, ws_bytes, (hipStream_t)hip_stream, phases);
 }
@@ -187,12 +207,18 @@ int fr_decode_pack_basis(const float* mu, const float* pc_shape, const float* pc
     return fr_launch_pack_basis(mu, pc_shape, pc_exp, N, n_shape, n_exp, packed, (hipStream_t)hip_stream);
 }
 
+// what fr_launch_decode reads: the parameters and a 16-byte aligned image
+static int decode_inputs_check(const float* params, const void* packed_basis) {
+    if (!params || !packed_basis) return FR_ERR_INVALID_ARG;
+    if (((uintptr_t)packed_basis & 15) != 0) return FR_ERR_INVALID_ARG;
+    return FR_OK;
+}
+
 int fr_decode_3dmm(const float* params, const void* packed_basis, const float* R_override, int B, int N, int n_shape,
                    int n_exp, float im_size, float* vertex_proj, void* hip_stream) {
     if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0) return FR_ERR_INVALID_ARG;
     if ((size_t)B * N == 0) return FR_OK;
-    if (!params || !packed_basis || !vertex_proj) return FR_ERR_INVALID_ARG;
-    if (((uintptr_t)packed_basis & 15) != 0) return FR_ERR_INVALID_ARG;
+    if (!vertex_proj || decode_inputs_check(params, packed_basis) != FR_OK) return FR_ERR_INVALID_ARG;
     return fr_launch_decode(params, packed_basis, R_override, B, N, n_shape, n_exp, im_size, vertex_proj, N,
                             (hipStream_t)hip_stream);
 }
@@ -205,30 +231,42 @@ size_t fr_decode_render_vertex_bytes(int B, int N) {
     return (size_t)B * 3 * (size_t)fr_decode_render_vertex_pitch(N) * sizeof(float);
 }
 
+// The prologue of the three decode -> render entry points: phase bits, sizes, the empty batch, the hand-off buffer.  Returns
+// true when the entry point goes on; otherwise *rc is its answer (FR_OK for an empty batch).
+// What follows it differs, and is kept as it is: fr_decode_rendering_layer_forward makes ALL its remaining checks (decode
+// inputs, then the layer's) before it enqueues anything; fr_decode_render_forward and fr_decode_render_forward_q30 check the
+// decode's inputs, ENQUEUE THE DECODE, and only then look at the render's arguments -- a bad render argument there is
+// answered with the decode already on the stream.
+static bool decode_render_prologue(int phases, int B, int N, int n_shape, int n_exp, int ntri, int H, int W, int tex_batch,
+                                   const float* vertex_handoff, size_t vertex_bytes, int* rc) {
+    *rc = FR_ERR_INVALID_ARG;
+    if ((phases & 15) < 1 || (phases & ~0xFF0F)) return false;   // bits 0-3: phases; bits 8-15: strip-height hint
+    if (n_shape < 0 || n_exp < 0 || render_shape_check(B, N, ntri, H, W, 3, tex_batch) != FR_OK) return false;
+    *rc = FR_OK;
+    if (B == 0) return false;
+    if (N > 0 && !ws_ok(vertex_handoff, vertex_bytes, fr_decode_render_vertex_bytes(B, N), 128)) *rc = FR_ERR_WORKSPACE;
+    return *rc == FR_OK;
+}
+
 int fr_decode_render_forward(const float* params, const void* packed_basis, const float* R_override, const float* tri,
                              const float* texture, int B, int N, int n_shape, int n_exp, int ntri, int H, int W,
                              int tex_batch, float im_size, float* vertex_handoff, size_t vertex_bytes, float* depth,
                              float* tex_img, float* normal, float* tri_ind, void* workspace, size_t ws_bytes,
                              void* hip_stream, int phases) {
-    if ((phases & 15) < 1 || (phases & ~0xFF0F)) return FR_ERR_INVALID_ARG;   // bits 0-3: phases; bits 8-15: strip-height hint
-    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0 || ntri < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (tex_batch != 1 && tex_batch != B) return FR_ERR_INVALID_ARG;
-    if (B == 0) return FR_OK;
+    int rc;
+    if (!decode_render_prologue(phases, B, N, n_shape, n_exp, ntri, H, W, tex_batch, vertex_handoff, vertex_bytes, &rc)) return rc;
     const int pitch = fr_decode_render_vertex_pitch(N);
-    if (N > 0 && (!vertex_handoff || vertex_bytes < fr_decode_render_vertex_bytes(B, N) || ((uintptr_t)vertex_handoff & 127)))
-        return FR_ERR_WORKSPACE;
     if ((phases & 8) && N > 0) {
-        if (!params || !packed_basis) return FR_ERR_INVALID_ARG;
-        if (((uintptr_t)packed_basis & 15) != 0) return FR_ERR_INVALID_ARG;
-        const int rc = fr_launch_decode(params, packed_basis, R_override, B, N, n_shape, n_exp, im_size, vertex_handoff, pitch,
-                                        (hipStream_t)hip_stream);
+        rc = decode_inputs_check(params, packed_basis);
+        if (rc == FR_OK)
+            rc = fr_launch_decode(params, packed_basis, R_override, B, N, n_shape, n_exp, im_size, vertex_handoff, pitch,
+                                  (hipStream_t)hip_stream);
         if (rc != FR_OK) return rc;
     }
     if (!(phases & 7) || (size_t)H * W == 0) return FR_OK;
-    if (!depth || !tex_img || !normal || !tri_ind) return FR_ERR_INVALID_ARG;
-    if (ntri > 0 && (!tri || (N > 0 && !texture))) return FR_ERR_INVALID_ARG;
-    if (ntri >= (1 << 24)) return FR_ERR_UNSUPPORTED;
-    if (ws_bytes < fr_render_depth_workspace_bytes(B, N, ntri, H, W)) return FR_ERR_WORKSPACE;
+    rc = render_call_check(depth && tex_img && normal && tri_ind, vertex_handoff, tri, texture, B, N, ntri, H, W, ws_bytes,
+                           RENDER_PLAIN);
+    if (rc != FR_OK) return rc;
     return fr_launch_render_forward_phases(vertex_handoff, tri, texture, B, N, ntri, H, W, tex_batch, depth, tex_img, normal,
                                            tri_ind, workspace, ws_bytes, (hipStream_t)hip_stream, phases & 7, pitch, (phases >> 8) & 0xFF);
 }
@@ -263,8 +301,7 @@ static int decode_q30_checked(const float* params, const void* qimage, const flo
     if ((size_t)B * N == 0) return FR_OK;
     if (!params || !qimage || !vertex_proj || pitch < N) return FR_ERR_INVALID_ARG;
     if (((uintptr_t)qimage & 255) != 0) return FR_ERR_INVALID_ARG;
-    if (!workspace || ws_bytes < fr_decode_q_workspace_bytes_impl(n_shape, n_exp) || ((uintptr_t)workspace & 15))
-        return FR_ERR_WORKSPACE;
+    if (!ws_ok(workspace, ws_bytes, fr_decode_q_workspace_bytes_impl(n_shape, n_exp), 16)) return FR_ERR_WORKSPACE;
     return fr_launch_decode_q(params, qimage, R_override, B, N, n_shape, n_exp, im_size, vertex_proj, pitch, levels, workspace,
                               ws_bytes, (hipStream_t)hip_stream);
 }
@@ -287,24 +324,19 @@ int fr_decode_render_forward_q30(const float* params, const void* qimage, const 
                                  int tex_batch, float im_size, int levels, float* vertex_handoff, size_t vertex_bytes,
                                  float* depth, float* tex_img, float* normal, float* tri_ind, void* workspace, size_t ws_bytes,
                                  void* q_workspace, size_t q_ws_bytes, void* hip_stream, int phases) {
-    if ((phases & 15) < 1 || (phases & ~0xFF0F)) return FR_ERR_INVALID_ARG;   // bits 0-3: phases; bits 8-15: strip-height hint
-    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0 || ntri < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (tex_batch != 1 && tex_batch != B) return FR_ERR_INVALID_ARG;
-    if (!fr_decode_q_levels_ok(levels)) return FR_ERR_INVALID_ARG;
-    if (B == 0) return FR_OK;
+    int rc;
+    if (!fr_decode_q_levels_ok(levels)) return FR_ERR_INVALID_ARG;   // (ahead of the empty batch, like every argument error)
+    if (!decode_render_prologue(phases, B, N, n_shape, n_exp, ntri, H, W, tex_batch, vertex_handoff, vertex_bytes, &rc)) return rc;
     const int pitch = fr_decode_render_vertex_pitch(N);
-    if (N > 0 && (!vertex_handoff || vertex_bytes < fr_decode_render_vertex_bytes(B, N) || ((uintptr_t)vertex_handoff & 127)))
-        return FR_ERR_WORKSPACE;
     if ((phases & 8) && N > 0) {
-        const int rc = decode_q30_checked(params, qimage, R_override, B, N, n_shape, n_exp, im_size, vertex_handoff, pitch,
-                                          levels, q_workspace, q_ws_bytes, hip_stream);
+        rc = decode_q30_checked(params, qimage, R_override, B, N, n_shape, n_exp, im_size, vertex_handoff, pitch, levels,
+                                q_workspace, q_ws_bytes, hip_stream);
         if (rc != FR_OK) return rc;
     }
     if (!(phases & 7) || (size_t)H * W == 0) return FR_OK;
-    if (!depth || !tex_img || !normal || !tri_ind) return FR_ERR_INVALID_ARG;
-    if (ntri > 0 && (!tri || (N > 0 && !texture))) return FR_ERR_INVALID_ARG;
-    if (ntri >= (1 << 24)) return FR_ERR_UNSUPPORTED;
-    if (ws_bytes < fr_render_depth_workspace_bytes(B, N, ntri, H, W)) return FR_ERR_WORKSPACE;
+    rc = render_call_check(depth && tex_img && normal && tri_ind, vertex_handoff, tri, texture, B, N, ntri, H, W, ws_bytes,
+                           RENDER_PLAIN);
+    if (rc != FR_OK) return rc;
     return fr_launch_render_forward_phases(vertex_handoff, tri, texture, B, N, ntri, H, W, tex_batch, depth, tex_img, normal,
                                            tri_ind, workspace, ws_bytes, (hipStream_t)hip_stream, phases & 7, pitch, (phases >> 8) & 0xFF);
 }
@@ -319,17 +351,33 @@ size_t fr_decode_backward_workspace_bytes(int B, int N, int n_shape, int n_exp) 
     return fr_decode_backward_workspace_impl(N, n_shape, n_exp);
 }
 
+// The argument list of the three decode backwards.  They take the basis in three forms, so the caller states what is its own:
+// point = vertex_proj, or mu; basis = the basis pointers this shape reads are there; aligned = those that must be are 16-byte
+// aligned; fused_only = the entry point serves only what the fused kernel does.  Returns true when the entry point launches;
+// otherwise *rc is its answer (FR_OK for an empty batch).
+static bool decode_backward_check(int B, int N, int n_shape, int n_exp, bool fused_only, const float* grad_vertex_proj,
+                                  const float* params, const float* point, bool basis, bool aligned, const float* grad_params,
+                                  const void* workspace, size_t ws_bytes, int* rc) {
+    *rc = FR_OK;
+    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0) *rc = FR_ERR_INVALID_ARG;
+    else if (fused_only && fr_decode_backward_basis_bytes(N, n_shape, n_exp) == 0) *rc = FR_ERR_UNSUPPORTED;
+    else if (B == 0) return false;
+    else if (!grad_params || !params) *rc = FR_ERR_INVALID_ARG;
+    else if (N > 0 && (!grad_vertex_proj || !point || !basis)) *rc = FR_ERR_INVALID_ARG;
+    else if (!aligned) *rc = FR_ERR_INVALID_ARG;
+    else if (N > 0 && !ws_ok(workspace, ws_bytes, fr_decode_backward_workspace_bytes(B, N, n_shape, n_exp), 16))
+        *rc = FR_ERR_WORKSPACE;
+    return *rc == FR_OK;
+}
+
 int fr_decode_3dmm_backward(const float* grad_vertex_proj, const float* params, const float* vertex_proj,
                             const float* pc_shape, const float* pc_exp, const float* R_override, int B, int N, int n_shape,
                             int n_exp, float im_size, float* grad_params, void* workspace, size_t ws_bytes,
                             void* hip_stream) {
-    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0) return FR_ERR_INVALID_ARG;
-    if (B == 0) return FR_OK;
-    if (!grad_params || !params) return FR_ERR_INVALID_ARG;
-    if (N > 0 && (!grad_vertex_proj || !vertex_proj || (n_shape > 0 && !pc_shape) || (n_exp > 0 && !pc_exp)))
-        return FR_ERR_INVALID_ARG;
-    if (ws_bytes < fr_decode_backward_workspace_bytes(B, N, n_shape, n_exp)) return FR_ERR_WORKSPACE;
-    if (N > 0 && (!workspace || ((uintptr_t)workspace & 15))) return FR_ERR_WORKSPACE;
+    int rc;
+    if (!decode_backward_check(B, N, n_shape, n_exp, false, grad_vertex_proj, params, vertex_proj,
+                               (n_shape <= 0 || pc_shape) && (n_exp <= 0 || pc_exp), true, grad_params, workspace, ws_bytes, &rc))
+        return rc;
     return fr_launch_decode_backward(grad_vertex_proj, params, vertex_proj, pc_shape, pc_exp, R_override, B, N, n_shape,
                                      n_exp, im_size, grad_params, workspace, (hipStream_t)hip_stream);
 }
@@ -352,13 +400,10 @@ int fr_decode_backward_pack_basis(const float* pc_shape, const float* pc_exp, in
 int fr_decode_3dmm_backward_packed(const float* grad_vertex_proj, const float* params, const float* vertex_proj,
                                    const void* packed_t, const float* R_override, int B, int N, int n_shape, int n_exp,
                                    float im_size, float* grad_params, void* workspace, size_t ws_bytes, void* hip_stream) {
-    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0) return FR_ERR_INVALID_ARG;
-    if (B == 0) return FR_OK;
-    if (!grad_params || !params) return FR_ERR_INVALID_ARG;
-    if (N > 0 && (!grad_vertex_proj || !vertex_proj || (n_shape + n_exp > 0 && !packed_t))) return FR_ERR_INVALID_ARG;
-    if (((uintptr_t)packed_t & 15) != 0) return FR_ERR_INVALID_ARG;
-    if (ws_bytes < fr_decode_backward_workspace_bytes(B, N, n_shape, n_exp)) return FR_ERR_WORKSPACE;
-    if (N > 0 && (!workspace || ((uintptr_t)workspace & 15))) return FR_ERR_WORKSPACE;
+    int rc;
+    if (!decode_backward_check(B, N, n_shape, n_exp, false, grad_vertex_proj, params, vertex_proj, n_shape + n_exp <= 0 || packed_t,
+                               ((uintptr_t)packed_t & 15) == 0, grad_params, workspace, ws_bytes, &rc))
+        return rc;
     return fr_launch_decode_backward(grad_vertex_proj, params, vertex_proj, nullptr, nullptr, R_override, B, N, n_shape, n_exp,
                                      im_size, grad_params, workspace, (hipStream_t)hip_stream, n_shape + n_exp > 0 ? packed_t : nullptr);
 }
@@ -366,13 +411,10 @@ int fr_decode_3dmm_backward_packed(const float* grad_vertex_proj, const float* p
 int fr_decode_3dmm_backward_packed_mu(const float* grad_vertex_proj, const float* params, const float* mu, const void* packed_t,
                                       const float* R_override, int B, int N, int n_shape, int n_exp, float im_size,
                                       float* grad_params, void* workspace, size_t ws_bytes, void* hip_stream) {
-    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0) return FR_ERR_INVALID_ARG;
-    if (fr_decode_backward_basis_bytes(N, n_shape, n_exp) == 0) return FR_ERR_UNSUPPORTED;   // what the fused kernel does not serve
-    if (B == 0) return FR_OK;
-    if (!grad_params || !params || !grad_vertex_proj || !mu || !packed_t) return FR_ERR_INVALID_ARG;
-    if (((uintptr_t)packed_t & 15) != 0 || ((uintptr_t)mu & 15) != 0) return FR_ERR_INVALID_ARG;
-    if (ws_bytes < fr_decode_backward_workspace_bytes(B, N, n_shape, n_exp)) return FR_ERR_WORKSPACE;
-    if (!workspace || ((uintptr_t)workspace & 15)) return FR_ERR_WORKSPACE;
+    int rc;   // (fused_only: N > 0 wherever the list below is reached)
+    if (!decode_backward_check(B, N, n_shape, n_exp, true, grad_vertex_proj, params, mu, packed_t != nullptr,
+                               ((uintptr_t)packed_t & 15) == 0 && ((uintptr_t)mu & 15) == 0, grad_params, workspace, ws_bytes, &rc))
+        return rc;
     return fr_launch_decode_backward(grad_vertex_proj, params, nullptr, nullptr, nullptr, R_override, B, N, n_shape, n_exp,
                                      im_size, grad_params, workspace, (hipStream_t)hip_stream, packed_t, mu);
 }
@@ -383,27 +425,19 @@ int fr_decode_rendering_layer_forward(const float* params, const void* packed_ba
                                       int H, int W, int tex_batch, float im_size, float* vertex_handoff, size_t vertex_bytes,
                                       float* net_input, float* depth_img, float* depth, float* tri_ind, void* workspace,
                                       size_t ws_bytes, void* hip_stream, int phases) {
-    if ((phases & 15) < 1 || (phases & ~0xFF0F)) return FR_ERR_INVALID_ARG;   // bits 0-3: phases; bits 8-15: strip-height hint
-    if (B < 0 || N < 0 || n_shape < 0 || n_exp < 0 || ntri < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (tex_batch != 1 && tex_batch != B) return FR_ERR_INVALID_ARG;
-    if (B == 0) return FR_OK;
+    int rc;
+    if (!decode_render_prologue(phases, B, N, n_shape, n_exp, ntri, H, W, tex_batch, vertex_handoff, vertex_bytes, &rc)) return rc;
     const int pitch = fr_decode_render_vertex_pitch(N);
-    if (N > 0 && (!vertex_handoff || vertex_bytes < fr_decode_render_vertex_bytes(B, N) || ((uintptr_t)vertex_handoff & 127)))
-        return FR_ERR_WORKSPACE;
-    const bool layer = (phases & 7) && (size_t)H * W > 0;
-    if ((phases & 8) && N > 0) {
-        if (!params || !packed_basis) return FR_ERR_INVALID_ARG;
-        if (((uintptr_t)packed_basis & 15) != 0) return FR_ERR_INVALID_ARG;
-    }
+    const bool decode = (phases & 8) && N > 0, layer = (phases & 7) && (size_t)H * W > 0;
+    if (decode && (rc = decode_inputs_check(params, packed_basis)) != FR_OK) return rc;
     if (layer) {   // the checks of fr_rendering_layer_forward, all of them BEFORE the decode is launched
-        if (!net_input || !depth_img || !depth || !tri_ind || !im_gray) return FR_ERR_INVALID_ARG;
-        if (ntri > 0 && (!tri || (N > 0 && !texture))) return FR_ERR_INVALID_ARG;
-        if (!fr_rendering_layer_supported(B, N, ntri, H, W)) return FR_ERR_UNSUPPORTED;
-        if (ws_bytes < fr_render_depth_workspace_bytes(B, N, ntri, H, W)) return FR_ERR_WORKSPACE;
+        rc = render_call_check(net_input && depth_img && depth && tri_ind && im_gray, vertex_handoff, tri, texture, B, N, ntri, H, W,
+                               ws_bytes, RENDER_LAYER_SERVED);
+        if (rc != FR_OK) return rc;
     }
-    if ((phases & 8) && N > 0) {
-        const int rc = fr_launch_decode(params, packed_basis, R_override, B, N, n_shape, n_exp, im_size, vertex_handoff, pitch,
-                                        (hipStream_t)hip_stream);
+    if (decode) {
+        rc = fr_launch_decode(params, packed_basis, R_override, B, N, n_shape, n_exp, im_size, vertex_handoff, pitch,
+                              (hipStream_t)hip_stream);
         if (rc != FR_OK) return rc;
     }
     if (!layer) return FR_OK;
@@ -446,8 +480,7 @@ int fr_decode_render_backward(const float* g_depth, const float* g_depth_img, co
     if (!grad_params || !params || !mu || !packed_t || !tri_ind || (ntri > 0 && !tri)) return FR_ERR_INVALID_ARG;
     if (((uintptr_t)packed_t & 15) != 0 || ((uintptr_t)mu & 15) != 0) return FR_ERR_INVALID_ARG;
     if ((long long)H * W > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
-    if (!workspace || ((uintptr_t)workspace & 255) || ws_bytes < fr_decode_render_backward_workspace_bytes(B, N, n_shape, n_exp, H, W))
-        return FR_ERR_WORKSPACE;
+    if (!ws_ok(workspace, ws_bytes, fr_decode_render_backward_workspace_bytes(B, N, n_shape, n_exp, H, W), 256)) return FR_ERR_WORKSPACE;
     const DrbLayout l = drb_layout(B, N, n_shape, n_exp, H, W);
     char* ws = reinterpret_cast<char*>(workspace);
     float* zplane = reinterpret_cast<float*>(ws + l.rec);
@@ -470,7 +503,7 @@ int fr_decode_pose_backward(const float* grad_vertex_proj, const float* vertex_p
     if (!grad_params && !grad_R) return FR_ERR_INVALID_ARG;
     if (!params || (N > 0 && (!grad_vertex_proj || !vertex_proj))) return FR_ERR_INVALID_ARG;
     const size_t need = fr_decode_pose_backward_workspace_impl(B, N);
-    if (ws_bytes < need || (need > 0 && (!workspace || ((uintptr_t)workspace & 15)))) return FR_ERR_WORKSPACE;
+    if (need > 0 && !ws_ok(workspace, ws_bytes, need, 16)) return FR_ERR_WORKSPACE;
     if (need / (9 * sizeof(float)) > 0x7FFFFFFFull) return FR_ERR_UNSUPPORTED;   // (face, chunk) workgroups beyond one grid
     return fr_launch_decode_pose_backward(grad_vertex_proj, vertex_proj, params, R_override, B, N, n_shape, n_exp, im_size,
                                           grad_params, grad_R, workspace, (hipStream_t)hip_stream);
@@ -492,11 +525,9 @@ int fr_decode_render_backward_pose(const float* g_depth, const float* g_depth_im
     if (fr_decode_backward_basis_bytes(N, n_shape, n_exp) == 0) return FR_ERR_UNSUPPORTED;   // as fr_decode_render_backward
     if (B == 0) return FR_OK;
     if ((long long)H * W > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
-    if (!vertex_handoff || vertex_bytes < fr_decode_render_vertex_bytes(B, N) || ((uintptr_t)vertex_handoff & 127))
-        return FR_ERR_WORKSPACE;
+    if (!ws_ok(vertex_handoff, vertex_bytes, fr_decode_render_vertex_bytes(B, N), 128)) return FR_ERR_WORKSPACE;
     const size_t base = fr_decode_render_backward_workspace_bytes(B, N, n_shape, n_exp, H, W);
-    if (!workspace || ((uintptr_t)workspace & 255) || ws_bytes < fr_decode_render_backward_pose_workspace_bytes(B, N, n_shape, n_exp, H, W))
-        return FR_ERR_WORKSPACE;
+    if (!ws_ok(workspace, ws_bytes, fr_decode_render_backward_pose_workspace_bytes(B, N, n_shape, n_exp, H, W), 256)) return FR_ERR_WORKSPACE;
     // (every remaining check is fr_decode_render_backward's own, made before its first launch)
     const int rc = fr_decode_render_backward(g_depth, g_depth_img, g_net_input, im_gray, depth, tri, tri_ind, params, mu, packed_t,
                                              R_override, B, N, n_shape, n_exp, ntri, H, W, im_size, grad_params, workspace, base,
@@ -527,8 +558,7 @@ int fr_render_normal_backward(const float* normal_grad, int grad_stride, const f
     const bool work = (size_t)H * W > 0 && ntri > 0;
     if (work && (!normal_grad || !vertex || !tri || !tri_ind)) return FR_ERR_INVALID_ARG;
     if (ntri >= (1 << 24)) return FR_ERR_UNSUPPORTED;   // float-stored ids stop being exact
-    if (work && (!workspace || ((uintptr_t)workspace & 15) || ws_bytes < fr_render_normal_backward_workspace_impl(B, H, W)))
-        return FR_ERR_WORKSPACE;
+    if (work && !ws_ok(workspace, ws_bytes, fr_render_normal_backward_workspace_impl(B, H, W), 16)) return FR_ERR_WORKSPACE;
     return fr_launch_render_normal_backward(normal_grad, grad_stride, vertex, vertex_pitch, tri, tri_ind, vertex_grad, B, nver,
                                             ntri, H, W, mode, accumulate, workspace, (hipStream_t)hip_stream);
 }
@@ -551,8 +581,7 @@ int fr_render_texture_backward(const float* tex_grad, int grad_stride, const flo
     if (work && (!tex_grad || !tri || !tri_ind)) return FR_ERR_INVALID_ARG;
     if (ntri >= (1 << 24)) return FR_ERR_UNSUPPORTED;   // float-stored ids stop being exact
     if ((long long)H * W > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;   // (a shape no workspace serves: answered before the workspace)
-    if (work && (!workspace || ((uintptr_t)workspace & 15) ||
-                 ws_bytes < fr_render_texture_backward_workspace_impl(B, nver, H, W, tex_batch)))
+    if (work && !ws_ok(workspace, ws_bytes, fr_render_texture_backward_workspace_impl(B, nver, H, W, tex_batch), 16))
         return FR_ERR_WORKSPACE;
     return fr_launch_render_texture_backward(tex_grad, grad_stride, tri, tri_ind, texture_grad, B, nver, ntri, H, W, tex_batch,
                                              accumulate, workspace, (hipStream_t)hip_stream);

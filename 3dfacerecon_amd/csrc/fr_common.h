@@ -110,6 +110,12 @@ inline hipError_t fr_allow_full_lds(const void* kernel, fr_lds_flags_t* done /*[
     return e;
 }
 
+// A caller-owned buffer an entry point may hand to its kernels: there, aligned to `align` bytes (a power of two) and of at least
+// `need` bytes.  Every entry point answers a buffer that fails this with FR_ERR_WORKSPACE.
+inline bool ws_ok(const void* p, size_t have, size_t need, size_t align) {
+    return p && !((uintptr_t)p & (align - 1)) && have >= need;
+}
+
 // Tuning / A-B knobs of the launchers.  Each has an initial value taken ONCE per process from its environment variable
 // (first use of any knob) and can be changed afterwards through fr_set_option() only: the launch path never calls getenv.
 namespace fr {

@@ -189,6 +189,22 @@ bool dn_size_ok(int B, int H, int W) {
     return (long long)H * W <= 0x7FFFFFFFll - 64 && B <= 65535 && (H + fr::DN_TH - 1) / fr::DN_TH <= 65535;
 }
 constexpr size_t DN_LDS_BWD = (size_t)(fr::DN_TH * (fr::DN_TW + 2) + (fr::DN_TH + 2) * fr::DN_TW) * sizeof(double);
+
+// What the two entry points share, in the order both answer: a negative size (FR_ERR_INVALID_ARG), an empty shape (FR_OK,
+// nothing launched), the entry point's own pointers (FR_ERR_INVALID_ARG), a shape beyond one grid (FR_ERR_UNSUPPORTED); then
+// the geometry, H and W of `a`, and the launch.
+template <typename Kernel>
+int dn_launch(Kernel kernel, fr::DnArgs& a, int B, int H, int W, bool pointers_ok, void* hip_stream) {
+    if (B < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
+    if (B == 0 || H == 0 || W == 0) return FR_OK;
+    if (!pointers_ok) return FR_ERR_INVALID_ARG;
+    if (!dn_size_ok(B, H, W)) return FR_ERR_UNSUPPORTED;
+    const DnGeom geo = dn_geom(H, W);
+    a.H = H; a.W = W;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)geo.tiles_x, (unsigned)geo.tiles_y, (unsigned)B), dim3(fr::DN_TW, fr::DN_TH, 1), 0,
+                       (hipStream_t)hip_stream, a);
+    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
 }  // namespace
 
 extern "C" {
@@ -204,32 +220,16 @@ void fr_debug_depth_normals_geom(int B, int H, int W, int* out) {
 }
 
 int fr_depth_normals_forward(const float* depth, const float* mask, int B, int H, int W, float* normal, void* hip_stream) {
-    using namespace fr;
-    if (B < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (B == 0 || H == 0 || W == 0) return FR_OK;
-    if (!depth || !normal) return FR_ERR_INVALID_ARG;
-    if (!dn_size_ok(B, H, W)) return FR_ERR_UNSUPPORTED;
-    const DnGeom geo = dn_geom(H, W);
-    DnArgs a{};
-    a.depth = depth; a.mask = mask; a.normal = normal; a.H = H; a.W = W;
-    hipLaunchKernelGGL(depth_normals_forward_kernel, dim3((unsigned)geo.tiles_x, (unsigned)geo.tiles_y, (unsigned)B),
-                       dim3(DN_TW, DN_TH, 1), 0, (hipStream_t)hip_stream, a);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    fr::DnArgs a{};
+    a.depth = depth; a.mask = mask; a.normal = normal;
+    return dn_launch(fr::depth_normals_forward_kernel, a, B, H, W, depth && normal, hip_stream);
 }
 
 int fr_depth_normals_backward(const float* grad_normal, const float* depth, const float* mask, int B, int H, int W,
                               float* grad_depth, void* hip_stream) {
-    using namespace fr;
-    if (B < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (B == 0 || H == 0 || W == 0) return FR_OK;
-    if (!grad_normal || !depth || !grad_depth) return FR_ERR_INVALID_ARG;
-    if (!dn_size_ok(B, H, W)) return FR_ERR_UNSUPPORTED;
-    const DnGeom geo = dn_geom(H, W);
-    DnArgs a{};
-    a.depth = depth; a.mask = mask; a.gn = grad_normal; a.gd = grad_depth; a.H = H; a.W = W;
-    hipLaunchKernelGGL(depth_normals_backward_kernel, dim3((unsigned)geo.tiles_x, (unsigned)geo.tiles_y, (unsigned)B),
-                       dim3(DN_TW, DN_TH, 1), 0, (hipStream_t)hip_stream, a);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    fr::DnArgs a{};
+    a.depth = depth; a.mask = mask; a.gn = grad_normal; a.gd = grad_depth;
+    return dn_launch(fr::depth_normals_backward_kernel, a, B, H, W, grad_normal && depth && grad_depth, hip_stream);
 }
 
 }  // extern "C"

@@ -337,7 +337,30 @@ SfsGeom sfs_geom(int B, long long npix) {
 }
 bool sfs_shape_empty(int B, int H, int W) { return B == 0 || H == 0 || W == 0; }
 constexpr int SFS_PARTS_MAX = 4096;
-bool sfs_buffer_ok(const void* p, size_t have, size_t need) { return p && !((uintptr_t)p & 15) && have >= need; }
+bool sfs_rcond_ok(double rcond) { return rcond >= 0.0 && std::isfinite(rcond); }
+
+// What the launching entry points share, in the order all of them answer: a negative size or a bad scalar (FR_ERR_INVALID_ARG),
+// an empty shape (FR_OK, nothing launched), the entry point's OWN verdict on its pointers and buffers, an image beyond one
+// grid (FR_ERR_UNSUPPORTED); then the geometry, the geometry fields of `a`, and the launch.  `a` arrives with the entry point's
+// own fields set; lds = the kernel's dynamic LDS size in SfsGeom (null: none).
+template <typename Kernel>
+int sfs_launch(Kernel kernel, size_t SfsGeom::*lds, fr::SfsArgs& a, int B, int H, int W, bool scalars_ok, bool empty, int own,
+               void* hip_stream) {
+    if (B < 0 || H < 0 || W < 0 || !scalars_ok) return FR_ERR_INVALID_ARG;
+    if (empty) return FR_OK;
+    if (own != FR_OK) return own;
+    const long long npix = (long long)H * W;
+    if (npix > 0x7FFFFFFFll - fr::SFS_PX) return FR_ERR_UNSUPPORTED;
+    const SfsGeom geo = sfs_geom(B, npix);
+    a.B = B; a.npix = (int)npix; a.S = geo.slices; a.chunk = geo.chunk;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)geo.blocks), dim3(fr::SFS_PX * geo.slices), lds ? geo.*lds : 0,
+                       (hipStream_t)hip_stream, a);
+    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
+// an entry point's own verdict: its pointers, then its buffer
+int sfs_own(bool pointers_ok, bool buffer_ok) {
+    return !pointers_ok ? FR_ERR_INVALID_ARG : !buffer_ok ? FR_ERR_WORKSPACE : FR_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -359,7 +382,7 @@ void fr_debug_sfs_geom(int B, int H, int W, int* out) {
 
 // HOST instantiation of the kernel's solver (no GPU): m6, p6 = xx, xy, xz, yy, yz, zz
 int fr_debug_sfs_pinv(const double* m6, double rcond, double* p6, int* rank) {
-    if (!m6 || !p6 || !rank || !(rcond >= 0.0) || !std::isfinite(rcond)) return FR_ERR_INVALID_ARG;
+    if (!m6 || !p6 || !rank || !sfs_rcond_ok(rcond)) return FR_ERR_INVALID_ARG;
     fr_sfs_pinv3(m6, rcond, p6, rank);
     return FR_OK;
 }
@@ -367,44 +390,26 @@ int fr_debug_sfs_pinv(const double* m6, double rcond, double* p6, int* rank) {
 int fr_sfs_intensity_forward(const float* abedo, const float* normal, const float* im_gray, const float* abedo_new,
                              const float* normal_new, int B, int H, int W, double rcond, float* intensity, void* state,
                              size_t state_bytes, void* hip_stream) {
-    using namespace fr;
-    if (B < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (!(rcond >= 0.0) || !std::isfinite(rcond)) return FR_ERR_INVALID_ARG;
-    if (sfs_shape_empty(B, H, W)) return FR_OK;
-    if (!abedo || !normal || !im_gray || !abedo_new || !normal_new || !intensity) return FR_ERR_INVALID_ARG;
-    if (!state || ((uintptr_t)state & 15) || state_bytes < fr_sfs_state_bytes(H, W)) return FR_ERR_WORKSPACE;
-    const long long npix = (long long)H * W;
-    if (npix > 0x7FFFFFFFll - SFS_PX) return FR_ERR_UNSUPPORTED;
-    const SfsGeom geo = sfs_geom(B, npix);
-    SfsArgs a{};
+    fr::SfsArgs a{};
     a.abedo = abedo; a.normal = normal; a.im_gray = im_gray; a.abedo_new = abedo_new; a.normal_new = normal_new;
     a.intensity = intensity; a.state = reinterpret_cast<double*>(state); a.rcond = rcond;
-    a.B = B; a.npix = (int)npix; a.S = geo.slices; a.chunk = geo.chunk;
-    hipLaunchKernelGGL(sfs_forward_kernel, dim3((unsigned)geo.blocks), dim3(SFS_PX * geo.slices), geo.lds_fwd,
-                       (hipStream_t)hip_stream, a);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    const int own = sfs_own(abedo && normal && im_gray && abedo_new && normal_new && intensity,
+                            ws_ok(state, state_bytes, fr_sfs_state_bytes(H, W), 16));
+    return sfs_launch(fr::sfs_forward_kernel, &SfsGeom::lds_fwd, a, B, H, W, sfs_rcond_ok(rcond), sfs_shape_empty(B, H, W), own,
+                      hip_stream);
 }
 
 int fr_sfs_intensity_backward_tex(const float* grad_intensity, const float* abedo, const float* im_gray, const float* abedo_new,
                                   const float* normal_new, const void* state, size_t state_bytes, int B, int H, int W,
                                   float* grad_normal, float* grad_normal_new, float* grad_abedo_new, void* hip_stream) {
-    using namespace fr;
-    if (B < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (sfs_shape_empty(B, H, W)) return FR_OK;
-    if (!grad_normal && !grad_normal_new && !grad_abedo_new) return FR_ERR_INVALID_ARG;
-    if (!grad_intensity || !abedo || !im_gray || !abedo_new || !normal_new) return FR_ERR_INVALID_ARG;
-    if (!state || ((uintptr_t)state & 15) || state_bytes < fr_sfs_state_bytes(H, W)) return FR_ERR_WORKSPACE;
-    const long long npix = (long long)H * W;
-    if (npix > 0x7FFFFFFFll - SFS_PX) return FR_ERR_UNSUPPORTED;
-    const SfsGeom geo = sfs_geom(B, npix);
-    SfsArgs a{};
+    fr::SfsArgs a{};
     a.g = grad_intensity; a.abedo = abedo; a.im_gray = im_gray; a.abedo_new = abedo_new; a.normal_new = normal_new;
     a.gn = grad_normal; a.gnn = grad_normal_new; a.gan = grad_abedo_new;
     a.state = const_cast<double*>(reinterpret_cast<const double*>(state));
-    a.B = B; a.npix = (int)npix; a.S = geo.slices; a.chunk = geo.chunk;
-    hipLaunchKernelGGL(sfs_backward_kernel, dim3((unsigned)geo.blocks), dim3(SFS_PX * geo.slices), geo.lds_bwd,
-                       (hipStream_t)hip_stream, a);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    const int own = sfs_own((grad_normal || grad_normal_new || grad_abedo_new) && grad_intensity && abedo && im_gray && abedo_new &&
+                                normal_new,
+                            ws_ok(state, state_bytes, fr_sfs_state_bytes(H, W), 16));
+    return sfs_launch(fr::sfs_backward_kernel, &SfsGeom::lds_bwd, a, B, H, W, true, sfs_shape_empty(B, H, W), own, hip_stream);
 }
 
 int fr_sfs_intensity_backward(const float* grad_intensity, const float* abedo, const float* im_gray, const float* abedo_new,
@@ -439,85 +444,45 @@ void fr_debug_sfs_split_geom(int B, int H, int W, int* out) {
 
 int fr_sfs_moments(const float* abedo, const float* normal, const float* im_gray, int B, int H, int W, void* moments,
                    size_t moments_bytes, void* hip_stream) {
-    using namespace fr;
-    if (B < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (H == 0 || W == 0) return FR_OK;
-    if (B > 0 && (!abedo || !normal || !im_gray)) return FR_ERR_INVALID_ARG;
-    if (!sfs_buffer_ok(moments, moments_bytes, fr_sfs_moments_bytes(H, W))) return FR_ERR_WORKSPACE;
-    const long long npix = (long long)H * W;
-    if (npix > 0x7FFFFFFFll - SFS_PX) return FR_ERR_UNSUPPORTED;
-    const SfsGeom geo = sfs_geom(B, npix);
-    SfsArgs a{};
+    fr::SfsArgs a{};
     a.abedo = abedo; a.normal = normal; a.im_gray = im_gray; a.parts_out = reinterpret_cast<double*>(moments);
-    a.B = B; a.npix = (int)npix; a.S = geo.slices; a.chunk = geo.chunk;
-    hipLaunchKernelGGL(sfs_moments_kernel, dim3((unsigned)geo.blocks), dim3(SFS_PX * geo.slices), geo.lds_moments,
-                       (hipStream_t)hip_stream, a);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    const int own = sfs_own(B <= 0 || (abedo && normal && im_gray), ws_ok(moments, moments_bytes, fr_sfs_moments_bytes(H, W), 16));
+    return sfs_launch(fr::sfs_moments_kernel, &SfsGeom::lds_moments, a, B, H, W, true, H == 0 || W == 0, own, hip_stream);
 }
 
 int fr_sfs_solve_shade(const void* moment_parts, int nparts, const float* abedo_new, const float* normal_new, int B, int H, int W,
                        double rcond, float* intensity, void* state, size_t state_bytes, void* hip_stream) {
-    using namespace fr;
-    if (B < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (!(rcond >= 0.0) || !std::isfinite(rcond)) return FR_ERR_INVALID_ARG;
-    if (nparts < 1 || nparts > SFS_PARTS_MAX) return FR_ERR_INVALID_ARG;
-    if (sfs_shape_empty(B, H, W)) return FR_OK;
-    if (!moment_parts || !abedo_new || !normal_new || !intensity) return FR_ERR_INVALID_ARG;
-    if (!sfs_buffer_ok(state, state_bytes, fr_sfs_state_bytes(H, W))) return FR_ERR_WORKSPACE;
-    const long long npix = (long long)H * W;
-    if (npix > 0x7FFFFFFFll - SFS_PX) return FR_ERR_UNSUPPORTED;
-    const SfsGeom geo = sfs_geom(B, npix);
-    SfsArgs a{};
+    fr::SfsArgs a{};
     a.parts_in = reinterpret_cast<const double*>(moment_parts); a.nparts = nparts;
     a.abedo_new = abedo_new; a.normal_new = normal_new;
     a.intensity = intensity; a.state = reinterpret_cast<double*>(state); a.rcond = rcond;
-    a.B = B; a.npix = (int)npix; a.S = geo.slices; a.chunk = geo.chunk;
-    hipLaunchKernelGGL(sfs_solve_shade_kernel, dim3((unsigned)geo.blocks), dim3(SFS_PX * geo.slices), geo.lds_solve,
-                       (hipStream_t)hip_stream, a);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    const int own = sfs_own(moment_parts && abedo_new && normal_new && intensity,
+                            ws_ok(state, state_bytes, fr_sfs_state_bytes(H, W), 16));
+    return sfs_launch(fr::sfs_solve_shade_kernel, &SfsGeom::lds_solve, a, B, H, W,
+                      sfs_rcond_ok(rcond) && nparts >= 1 && nparts <= SFS_PARTS_MAX, sfs_shape_empty(B, H, W), own, hip_stream);
 }
 
 int fr_sfs_backward_q(const float* grad_intensity, const float* abedo_new, const float* normal_new, int B, int H, int W, void* q,
                       size_t q_bytes, void* hip_stream) {
-    using namespace fr;
-    if (B < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (H == 0 || W == 0) return FR_OK;
-    if (B > 0 && (!grad_intensity || !abedo_new || !normal_new)) return FR_ERR_INVALID_ARG;
-    if (!sfs_buffer_ok(q, q_bytes, fr_sfs_q_bytes(H, W))) return FR_ERR_WORKSPACE;
-    const long long npix = (long long)H * W;
-    if (npix > 0x7FFFFFFFll - SFS_PX) return FR_ERR_UNSUPPORTED;
-    const SfsGeom geo = sfs_geom(B, npix);
-    SfsArgs a{};
+    fr::SfsArgs a{};
     a.g = grad_intensity; a.abedo_new = abedo_new; a.normal_new = normal_new; a.parts_out = reinterpret_cast<double*>(q);
-    a.B = B; a.npix = (int)npix; a.S = geo.slices; a.chunk = geo.chunk;
-    hipLaunchKernelGGL(sfs_backward_q_kernel, dim3((unsigned)geo.blocks), dim3(SFS_PX * geo.slices), geo.lds_q,
-                       (hipStream_t)hip_stream, a);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    const int own = sfs_own(B <= 0 || (grad_intensity && abedo_new && normal_new), ws_ok(q, q_bytes, fr_sfs_q_bytes(H, W), 16));
+    return sfs_launch(fr::sfs_backward_q_kernel, &SfsGeom::lds_q, a, B, H, W, true, H == 0 || W == 0, own, hip_stream);
 }
 
 int fr_sfs_backward_apply(const float* grad_intensity, const float* abedo, const float* im_gray, const float* abedo_new,
                           const float* normal_new, const void* state, size_t state_bytes, const void* q_parts, int nparts, int B,
                           int H, int W, float* grad_normal, float* grad_normal_new, float* grad_abedo_new, void* hip_stream) {
-    using namespace fr;
-    if (B < 0 || H < 0 || W < 0) return FR_ERR_INVALID_ARG;
-    if (nparts < 1 || nparts > SFS_PARTS_MAX) return FR_ERR_INVALID_ARG;
-    if (sfs_shape_empty(B, H, W)) return FR_OK;
-    if (!grad_normal && !grad_normal_new && !grad_abedo_new) return FR_ERR_INVALID_ARG;
-    if (!grad_intensity || !abedo || !im_gray || !abedo_new || !normal_new) return FR_ERR_INVALID_ARG;
-    if (grad_normal && !q_parts) return FR_ERR_INVALID_ARG;
-    if (!sfs_buffer_ok(state, state_bytes, fr_sfs_state_bytes(H, W))) return FR_ERR_WORKSPACE;
-    const long long npix = (long long)H * W;
-    if (npix > 0x7FFFFFFFll - SFS_PX) return FR_ERR_UNSUPPORTED;
-    const SfsGeom geo = sfs_geom(B, npix);
-    SfsArgs a{};
+    fr::SfsArgs a{};
     a.g = grad_intensity; a.abedo = abedo; a.im_gray = im_gray; a.abedo_new = abedo_new; a.normal_new = normal_new;
     a.gn = grad_normal; a.gnn = grad_normal_new; a.gan = grad_abedo_new;
     a.state = const_cast<double*>(reinterpret_cast<const double*>(state));
     a.parts_in = reinterpret_cast<const double*>(q_parts); a.nparts = nparts;
-    a.B = B; a.npix = (int)npix; a.S = geo.slices; a.chunk = geo.chunk;
-    hipLaunchKernelGGL(sfs_backward_apply_kernel, dim3((unsigned)geo.blocks), dim3(SFS_PX * geo.slices), 0,
-                       (hipStream_t)hip_stream, a);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    const int own = sfs_own((grad_normal || grad_normal_new || grad_abedo_new) && grad_intensity && abedo && im_gray && abedo_new &&
+                                normal_new && (!grad_normal || q_parts),
+                            ws_ok(state, state_bytes, fr_sfs_state_bytes(H, W), 16));
+    return sfs_launch(fr::sfs_backward_apply_kernel, nullptr, a, B, H, W, nparts >= 1 && nparts <= SFS_PARTS_MAX,
+                      sfs_shape_empty(B, H, W), own, hip_stream);
 }
 
 }  // extern "C"

@@ -135,6 +135,18 @@ def _table_packed(ent, pending):
         ent.tri_ref, ent.tri_key = pending
 
 
+def _render_with_workspace(dev, ws_bytes, tri_c, geom, call):
+    """The step every render forward makes as one, under the entry's lock: take the stream's workspace, choose the phases, make the
+    call -- call(workspace buffer, phases) -> rc -- and, where it returned 0, record the table it packed.  -> rc"""
+    ent, cached = _workspace(dev, ws_bytes)
+    with ent.lock:
+        phases, pending = _render_phases(ent, cached, tri_c, geom)
+        rc = call(ent.buf, phases)
+        if rc == 0:
+            _table_packed(ent, pending)
+    return rc
+
+
 def _check_forward_shapes(ver, tri, texture, image):
     # the OP_REQUIRES checks of RenderDepthOp::Compute (render_depth_op.cc:397-418), same messages
     if image.dim() != 4 or ver.dim() != 3 or tri.dim() != 2 or texture.dim() not in (2, 3):
@@ -177,101 +189,6 @@ def _normal_backward_call(h, g, g_offset, g_stride, ver_c, tri_c, tri_ind, verte
     h.check(rc, "fr_render_normal_backward")
 
 
-class _RenderDepth(torch.autograd.Function):
-    """RenderDepth / RenderDepthGrad (render_depth_op.cc:535-589) as one autograd node."""
-
-    @staticmethod
-    def forward(ctx, ver, tri, texture, image):
-        return _RenderDepth._fwd(ctx, ver, tri, texture, image, False)
-
-    @staticmethod
-    def _fwd(ctx, ver, tri, texture, image, keep_ver):   # (keep_ver: _RenderDepthNormal also saves `ver` for the normal backward)
-        h = _host()
-        _check_forward_shapes(ver, tri, texture, image)
-        ver_c = h.require_gpu_f32(ver, "ver")
-        tri_c = h.require_gpu_f32(tri, "tri")
-        tex_c = h.require_gpu_f32(texture, "texture")
-        if not image.is_cuda:
-            raise RuntimeError("image is on %s: the fr_hotpath kernels run on an MI355X only" % image.device)
-        B, H, W = int(image.shape[0]), int(image.shape[1]), int(image.shape[2])
-        nver, ntri = int(ver_c.shape[2]), int(tri_c.shape[1])
-        tex_batch = 1 if tex_c.dim() == 2 else int(tex_c.shape[0])
-        if tex_batch not in (1, B):
-            raise ValueError("The texture's batch is neither 1 nor the image batch")
-        dev = ver_c.device
-        opts = dict(dtype=torch.float32, device=dev)
-        depth = torch.empty((B, H, W, 1), **opts)
-        tex_img = torch.empty((B, H, W, 3), **opts)
-        normal = torch.empty((B, H, W, 3), **opts)
-        tri_ind = torch.empty((B, H, W, 1), **opts)
-        L = h.lib()
-        with torch.cuda.device(dev):
-            ws_bytes = L.fr_render_depth_workspace_bytes(B, nver, ntri, H, W)
-            if ws_bytes:
-                ent, cached = _workspace(dev, ws_bytes)
-                with ent.lock:
-                    phases, pending = _render_phases(ent, cached, tri_c, (B, nver, ntri, H, W))
-                    rc = L.fr_render_depth_forward_phases(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), B, nver, ntri, H, W, 3,
-                                                          tex_batch, h.ptr(depth), h.ptr(tex_img), h.ptr(normal), h.ptr(tri_ind),
-                                                          h.ptr(ent.buf), ws_bytes, h.stream_ptr(dev), phases)
-                    if rc == 0:
-                        _table_packed(ent, pending)
-            else:
-                rc = L.fr_render_depth_forward(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), B, nver, ntri, H, W, 3, tex_batch,
-                                               h.ptr(depth), h.ptr(tex_img), h.ptr(normal), h.ptr(tri_ind), None, 0,
-                                               h.stream_ptr(dev))
-        h.check(rc, "fr_render_depth_forward")
-        if keep_ver:
-            ctx.save_for_backward(tri_c, tri_ind, ver_c)
-        else:
-            ctx.save_for_backward(tri_c, tri_ind)
-        ctx.dims = (B, nver, ntri, H, W)
-        ctx.set_materialize_grads(False)  # an unused depth output (the SfS renders, network.py:423, 454) costs no backward
-        return depth, tex_img, normal, tri_ind
-
-    @staticmethod
-    def backward(ctx, depth_grad, texture_image_grad, normal_grad, tri_ind_grad):
-        # only depth_grad is used; vertex has gradients, tri / texture / image do not (reference ops.py:86-95)
-        h = _host()
-        tri_c, tri_ind = ctx.saved_tensors
-        B, nver, ntri, H, W = ctx.dims
-        dev = tri_c.device
-        if depth_grad is None:   # nothing downstream used `depth`: the vertices get no gradient (reference ops.py:95)
-            return None, None, None, None
-        vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=dev)
-        g = h.require_gpu_f32(depth_grad, "depth_grad")
-        with torch.cuda.device(dev):
-            _backward_call(h, g, tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, dev)
-        return vertex_grad, None, None, None
-
-
-class _RenderDepthNormal(_RenderDepth):
-    """render_depth(normal_grad=True): the same forward; the node also keeps `ver` ([B,3,nver] fp32: 41 MB at 64 faces of the
-    full mesh) and its backward runs the depth backward, then fr_render_normal_backward (raw mode, accumulate=1) where a
-    gradient of `normal` arrives: all three rows of the vertex gradient are filled."""
-
-    @staticmethod
-    def forward(ctx, ver, tri, texture, image):
-        return _RenderDepth._fwd(ctx, ver, tri, texture, image, True)
-
-    @staticmethod
-    def backward(ctx, depth_grad, texture_image_grad, normal_grad, tri_ind_grad):
-        h = _host()
-        tri_c, tri_ind, ver_c = ctx.saved_tensors
-        B, nver, ntri, H, W = ctx.dims
-        dev = tri_c.device
-        if depth_grad is None and normal_grad is None:
-            return None, None, None, None
-        vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            if depth_grad is not None:
-                _backward_call(h, h.require_gpu_f32(depth_grad, "depth_grad"), tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, dev)
-            if normal_grad is not None:
-                _normal_backward_call(h, h.require_gpu_f32(normal_grad, "normal_grad"), 0, 3, ver_c, tri_c, tri_ind, vertex_grad,
-                                      B, nver, ntri, H, W, 0, 1 if depth_grad is not None else 0, dev)
-        return vertex_grad, None, None, None
-
-
 def _texture_backward_call(h, g, g_offset, g_stride, tri_c, tri_ind, texture_grad, B, nver, ntri, H, W, tex_batch, accumulate, dev):
     """fr_render_texture_backward with its workspace (24 bytes per pixel, plus the slabs of a shared texture): the gradient read
     at `g_offset` floats into `g`, `g_stride` floats between pixels; texture_grad is dense [tex_batch,3,nver]."""
@@ -302,47 +219,88 @@ def _texture_grad_of(ctx, texture_image_grad):
     return texture_grad.reshape(shape)
 
 
-class _RenderDepthTex(_RenderDepth):
-    """render_depth(texture_grad=True): the same forward and the same saved tensors (the texture's shape is all the node adds);
-    a gradient arriving at `tex_img` reaches `texture` through fr_render_texture_backward.  The vertex gradient is
-    _RenderDepth's, launched only where `depth` was used."""
+class _RenderDepth(torch.autograd.Function):
+    """RenderDepth / RenderDepthGrad (render_depth_op.cc:535-589) as one autograd node.
+    normal_grad: the node also keeps `ver` ([B,3,nver] fp32: 41 MB at 64 faces of the full mesh) and, where a gradient of `normal`
+    arrives, its backward runs fr_render_normal_backward (raw mode) behind the depth backward: all three rows of the vertex
+    gradient are filled.  texture_grad: the same saved tensors (the texture's shape is all the node adds); a gradient arriving at
+    `tex_img` reaches `texture` through fr_render_texture_backward."""
 
     @staticmethod
-    def forward(ctx, ver, tri, texture, image):
-        ctx.tex_shape = tuple(texture.shape)
-        return _RenderDepth._fwd(ctx, ver, tri, texture, image, False)
+    def forward(ctx, ver, tri, texture, image, normal_grad, texture_grad):
+        h = _host()
+        _check_forward_shapes(ver, tri, texture, image)
+        ver_c = h.require_gpu_f32(ver, "ver")
+        tri_c = h.require_gpu_f32(tri, "tri")
+        tex_c = h.require_gpu_f32(texture, "texture")
+        if not image.is_cuda:
+            raise RuntimeError("image is on %s: the fr_hotpath kernels run on an MI355X only" % image.device)
+        B, H, W = int(image.shape[0]), int(image.shape[1]), int(image.shape[2])
+        nver, ntri = int(ver_c.shape[2]), int(tri_c.shape[1])
+        tex_batch = 1 if tex_c.dim() == 2 else int(tex_c.shape[0])
+        if tex_batch not in (1, B):
+            raise ValueError("The texture's batch is neither 1 nor the image batch")
+        dev = ver_c.device
+        opts = dict(dtype=torch.float32, device=dev)
+        depth = torch.empty((B, H, W, 1), **opts)
+        tex_img = torch.empty((B, H, W, 3), **opts)
+        normal = torch.empty((B, H, W, 3), **opts)
+        tri_ind = torch.empty((B, H, W, 1), **opts)
+        L = h.lib()
+        with torch.cuda.device(dev):
+            ws_bytes = L.fr_render_depth_workspace_bytes(B, nver, ntri, H, W)
+            if ws_bytes:
+                rc = _render_with_workspace(dev, ws_bytes, tri_c, (B, nver, ntri, H, W), lambda ws, phases: (
+                    L.fr_render_depth_forward_phases(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), B, nver, ntri, H, W, 3, tex_batch,
+                                                     h.ptr(depth), h.ptr(tex_img), h.ptr(normal), h.ptr(tri_ind), h.ptr(ws), ws_bytes,
+                                                     h.stream_ptr(dev), phases)))
+            else:
+                rc = L.fr_render_depth_forward(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), B, nver, ntri, H, W, 3, tex_batch,
+                                               h.ptr(depth), h.ptr(tex_img), h.ptr(normal), h.ptr(tri_ind), None, 0,
+                                               h.stream_ptr(dev))
+        h.check(rc, "fr_render_depth_forward")
+        if normal_grad:
+            ctx.save_for_backward(tri_c, tri_ind, ver_c)
+        else:
+            ctx.save_for_backward(tri_c, tri_ind)
+        if texture_grad:
+            ctx.tex_shape = tuple(texture.shape)
+        ctx.normal_grad, ctx.texture_grad = bool(normal_grad), bool(texture_grad)
+        ctx.dims = (B, nver, ntri, H, W)
+        ctx.set_materialize_grads(False)  # an unused depth output (the SfS renders, network.py:423, 454) costs no backward
+        return depth, tex_img, normal, tri_ind
 
     @staticmethod
     def backward(ctx, depth_grad, texture_image_grad, normal_grad, tri_ind_grad):
-        vertex_grad = _RenderDepth.backward(ctx, depth_grad, None, None, None)[0]
-        return vertex_grad, None, _texture_grad_of(ctx, texture_image_grad), None
-
-
-class _RenderDepthNormalTex(_RenderDepthNormal):
-    """render_depth(normal_grad=True, texture_grad=True): _RenderDepthNormal's vertex gradient and _RenderDepthTex's texture
-    gradient from one node."""
-
-    @staticmethod
-    def forward(ctx, ver, tri, texture, image):
-        ctx.tex_shape = tuple(texture.shape)
-        return _RenderDepth._fwd(ctx, ver, tri, texture, image, True)
-
-    @staticmethod
-    def backward(ctx, depth_grad, texture_image_grad, normal_grad, tri_ind_grad):
-        vertex_grad = _RenderDepthNormal.backward(ctx, depth_grad, None, normal_grad, None)[0]
-        return vertex_grad, None, _texture_grad_of(ctx, texture_image_grad), None
+        # by default only depth_grad is used; vertex has gradients, tri / texture / image do not (reference ops.py:86-95)
+        h = _host()
+        tri_c, tri_ind = ctx.saved_tensors[:2]
+        B, nver, ntri, H, W = ctx.dims
+        dev = tri_c.device
+        if not ctx.normal_grad:
+            normal_grad = None
+        vertex_grad = None   # nothing downstream used `depth` (or `normal`): the vertices get no gradient (reference ops.py:95)
+        if depth_grad is not None or normal_grad is not None:
+            vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                if depth_grad is not None:
+                    _backward_call(h, h.require_gpu_f32(depth_grad, "depth_grad"), tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W,
+                                   dev)
+                if normal_grad is not None:
+                    _normal_backward_call(h, h.require_gpu_f32(normal_grad, "normal_grad"), 0, 3, ctx.saved_tensors[2], tri_c,
+                                          tri_ind, vertex_grad, B, nver, ntri, H, W, 0, 1 if depth_grad is not None else 0, dev)
+        texture_grad = _texture_grad_of(ctx, texture_image_grad) if ctx.texture_grad else None
+        return vertex_grad, None, texture_grad, None, None, None
 
 
 class _RenderingLayerFused(torch.autograd.Function):
     """render_depth + the post-processing of FaceRecNet.rendering_layer (nets/network.py:185-199) as one kernel pass:
-    (ver, tri, texture, im_gray) -> (net_input [B,H,W,7], depth_img [B,H,W,1], depth, tri_ind)."""
+    (ver, tri, texture, im_gray) -> (net_input [B,H,W,7], depth_img [B,H,W,1], depth, tri_ind).
+    normal_grad: the node also keeps `ver` ([B,3,nver] fp32: 41 MB at 64 faces of the full mesh) and its backward completes the
+    depth backward's tensor with fr_render_normal_backward (post mode on channels 4-6 of the net_input gradient, accumulate=1)."""
 
     @staticmethod
-    def forward(ctx, ver, tri, texture, im_gray):
-        return _RenderingLayerFused._fwd(ctx, ver, tri, texture, im_gray, False)
-
-    @staticmethod
-    def _fwd(ctx, ver, tri, texture, im_gray, keep_ver):   # (keep_ver: _RenderingLayerFusedNormal also saves `ver`)
+    def forward(ctx, ver, tri, texture, im_gray, normal_grad):
         h = _host()
         image = im_gray
         _check_forward_shapes(ver, tri, texture, image)
@@ -364,22 +322,19 @@ class _RenderingLayerFused(torch.autograd.Function):
         L = h.lib()
         with torch.cuda.device(dev):
             ws_bytes = L.fr_render_depth_workspace_bytes(B, nver, ntri, H, W)
-            ent, cached = _workspace(dev, ws_bytes)
-            with ent.lock:
-                # the same "pack once while the same `tri` tensor is passed" rule as render_depth (the table is the same table)
-                phases, pending = _render_phases(ent, cached, tri_c, (B, nver, ntri, H, W))
-                rc = L.fr_rendering_layer_forward_phases(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), h.ptr(img_c), B, nver, ntri, H,
-                                                         W, tex_batch, h.ptr(net_in), h.ptr(depth_img), h.ptr(depth),
-                                                         h.ptr(tri_ind), h.ptr(ent.buf), ws_bytes, h.stream_ptr(dev), phases)
-                if rc == 0:
-                    _table_packed(ent, pending)
+            # the same "pack once while the same `tri` tensor is passed" rule as render_depth (the table is the same table)
+            rc = _render_with_workspace(dev, ws_bytes, tri_c, (B, nver, ntri, H, W), lambda ws, phases: (
+                L.fr_rendering_layer_forward_phases(h.ptr(ver_c), h.ptr(tri_c), h.ptr(tex_c), h.ptr(img_c), B, nver, ntri, H, W,
+                                                    tex_batch, h.ptr(net_in), h.ptr(depth_img), h.ptr(depth), h.ptr(tri_ind),
+                                                    h.ptr(ws), ws_bytes, h.stream_ptr(dev), phases)))
         if rc == -4:
             raise NotImplementedError("fused rendering layer: shape only covered by the fallback rasteriser")
         h.check(rc, "fr_rendering_layer_forward")
-        if keep_ver:
+        if normal_grad:
             ctx.save_for_backward(tri_c, tri_ind, depth, img_c, ver_c)
         else:
             ctx.save_for_backward(tri_c, tri_ind, depth, img_c)
+        ctx.normal_grad = bool(normal_grad)
         ctx.dims = (B, nver, ntri, H, W)
         ctx.mark_non_differentiable(tri_ind)
         return net_in, depth_img, depth, tri_ind
@@ -388,7 +343,7 @@ class _RenderingLayerFused(torch.autograd.Function):
     def backward(ctx, g_net_in, g_depth_img, g_depth, g_tri_ind):
         # only the mask channel and the depth image depend on the vertices (through depth, hence vertex z):
         #   mask = clip(depth, 1e-6, 1) * im  ->  g * im where 1e-6 <= depth <= 1;   depth_img = max(depth, 1e-6)
-        # (_RenderingLayerFusedNormal adds the normal channels: all three rows, through the saved vertices)
+        # (normal_grad adds the normal channels: all three rows, through the saved vertices)
         h = _host()
         tri_c, tri_ind, depth, img = ctx.saved_tensors[:4]
         B, nver, ntri, H, W = ctx.dims
@@ -403,22 +358,12 @@ class _RenderingLayerFused(torch.autograd.Function):
         vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=depth.device)
         with torch.cuda.device(depth.device):
             _backward_call(h, dg, tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, depth.device)
-            if len(ctx.saved_tensors) == 5 and g_net_in is not None:
+            if ctx.normal_grad and g_net_in is not None:
                 # channels 4-6 of g_net_input are the gradient of the normalised map: post mode, read in place at stride 7
                 gn = h.require_gpu_f32(g_net_in, "net_input_grad")
                 _normal_backward_call(h, gn, 4, 7, ctx.saved_tensors[4], tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, 1, 1,
                                       depth.device)
-        return vertex_grad, None, None, None
-
-
-class _RenderingLayerFusedNormal(_RenderingLayerFused):
-    """rendering_layer_fused(normal_grad=True): the same forward; the node also keeps `ver` ([B,3,nver] fp32: 41 MB at 64 faces
-    of the full mesh) and its backward completes the depth backward's tensor with fr_render_normal_backward (post mode on
-    channels 4-6 of the net_input gradient, accumulate=1)."""
-
-    @staticmethod
-    def forward(ctx, ver, tri, texture, im_gray):
-        return _RenderingLayerFused._fwd(ctx, ver, tri, texture, im_gray, True)
+        return vertex_grad, None, None, None, None
 
 
 # Per-stream scratch of the decode -> rendering-layer node, kept like the render workspace (least recently used dropped, a
@@ -486,18 +431,18 @@ class _DecodeRenderingLayer(torch.autograd.Function):
         with torch.cuda.device(dev):
             ws_bytes = L.fr_render_depth_workspace_bytes(B, N, ntri, H, W)
             hand_bytes = L.fr_decode_render_vertex_bytes(B, N)
-            ent, cached = _workspace(dev, ws_bytes)
-            with ent.lock:
+            hand = None
+
+            def call(ws, phases):
                 # (the hand-off is taken under the entry's lock: threads that share the stream share both buffers)
+                nonlocal hand
                 hand = (torch.empty((max(hand_bytes, 256),), dtype=torch.uint8, device=dev) if pose_grad
                         else _scratch("hand", dev, hand_bytes))
-                phases, pending = _render_phases(ent, cached, tri_c, (B, N, ntri, H, W))
-                rc = L.fr_decode_rendering_layer_forward(h.ptr(p), h.ptr(basis.image), h.ptr(R), h.ptr(tri_c), h.ptr(tex_c),
-                                                         h.ptr(img_c), B, N, ns, ne, ntri, H, W, tex_batch, float(im_size),
-                                                         h.ptr(hand), hand_bytes, h.ptr(net_in), h.ptr(depth_img), h.ptr(depth),
-                                                         h.ptr(tri_ind), h.ptr(ent.buf), ws_bytes, h.stream_ptr(dev), 8 | phases)
-                if rc == 0:
-                    _table_packed(ent, pending)
+                return L.fr_decode_rendering_layer_forward(h.ptr(p), h.ptr(basis.image), h.ptr(R), h.ptr(tri_c), h.ptr(tex_c),
+                                                           h.ptr(img_c), B, N, ns, ne, ntri, H, W, tex_batch, float(im_size),
+                                                           h.ptr(hand), hand_bytes, h.ptr(net_in), h.ptr(depth_img), h.ptr(depth),
+                                                           h.ptr(tri_ind), h.ptr(ws), ws_bytes, h.stream_ptr(dev), 8 | phases)
+            rc = _render_with_workspace(dev, ws_bytes, tri_c, (B, N, ntri, H, W), call)
         if rc == -4:
             raise NotImplementedError("decode -> rendering layer: shape only covered by the fallback rasteriser")
         h.check(rc, "fr_decode_rendering_layer_forward")
@@ -560,35 +505,53 @@ def decode_rendering_layer(params, R, im_gray, tri, texture, basis, im_size, pos
     return _DecodeRenderingLayer.apply(params, R, im_gray, tri, texture, basis, im_size, bool(pose_grad))
 
 
+def _sfs_inputs(op, h, abedo, normal, im_gray, abedo_new, normal_new, abedo_grad):
+    """The argument checks and conversions of `op` (sfs_intensity, sfs_intensity_sharded) -> (a_c, n_c, i_c, a2_c, n2_c, B, H, W)"""
+    for t, name in ((abedo, "abedo"), (im_gray, "im_gray")) + (() if abedo_grad else ((abedo_new, "abedo_new"),)):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError("%s: %s requires grad, but the albedos and im_gray are constants of this model "
+                             "(detach it)" % (op, name))
+    a_c = h.require_gpu_f32(abedo, "abedo")
+    n_c = h.require_gpu_f32(normal, "normal")
+    i_c = h.require_gpu_f32(im_gray, "im_gray")
+    a2_c = h.require_gpu_f32(abedo_new, "abedo_new")
+    n2_c = n_c if normal_new is normal else h.require_gpu_f32(normal_new, "normal_new")
+    if n_c.dim() != 4 or n_c.shape[3] != 3:
+        raise ValueError("%s expects normal [B,H,W,3]" % op)
+    B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+    for t, name, c in ((a_c, "abedo", 1), (i_c, "im_gray", 1), (a2_c, "abedo_new", 1), (n2_c, "normal_new", 3)):
+        if tuple(t.shape) != (B, H, W, c):
+            raise ValueError("%s: %s must be [%d,%d,%d,%d] (got %s)" % (op, name, B, H, W, c, tuple(t.shape)))
+        if t.device != n_c.device:
+            raise ValueError("%s: %s is on %s, normal on %s" % (op, name, t.device, n_c.device))
+    return a_c, n_c, i_c, a2_c, n2_c, B, H, W
+
+
+def _sfs_grad_buffers(ctx):
+    """-> (grad_normal, grad_normal_new, grad_abedo_new) of an SfS node's backward, None where the input needs none; None where
+    no input needs any (then nothing is launched)"""
+    B, H, W, _ = ctx.dims
+    dev = ctx.saved_tensors[0].device
+    want_n, want_n2 = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
+    want_a2 = ctx.abedo_grad and ctx.needs_input_grad[3]
+    if not (want_n or want_n2 or want_a2):
+        return None
+    gn = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n else None
+    gn2 = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n2 else None
+    ga2 = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev) if want_a2 else None
+    return gn, gn2, ga2
+
+
 class _SfsIntensity(torch.autograd.Function):
     """fr_sfs_intensity_forward / _backward (include/fr_hotpath.h, "shape-from-shading term") as one autograd node: the per-pixel
-    lighting solve over the batch and the shading, P held constant in the backward."""
+    lighting solve over the batch and the shading, P held constant in the backward.  abedo_grad: `abedo_new` may require grad and
+    the backward also returns grad_abedo_new (fr_sfs_intensity_backward_tex); `abedo` and `im_gray` stay constants."""
 
     @staticmethod
-    def forward(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond):
-        return _SfsIntensity._fwd(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond, False)
-
-    @staticmethod
-    def _fwd(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond, abedo_grad):   # (abedo_grad: _SfsIntensityTex)
+    def forward(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond, abedo_grad):
         h = _host()
         ctx.abedo_grad = bool(abedo_grad)
-        for t, name in ((abedo, "abedo"), (im_gray, "im_gray")) + (() if abedo_grad else ((abedo_new, "abedo_new"),)):
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise ValueError("sfs_intensity: %s requires grad, but the albedos and im_gray are constants of this model "
-                                 "(detach it)" % name)
-        a_c = h.require_gpu_f32(abedo, "abedo")
-        n_c = h.require_gpu_f32(normal, "normal")
-        i_c = h.require_gpu_f32(im_gray, "im_gray")
-        a2_c = h.require_gpu_f32(abedo_new, "abedo_new")
-        n2_c = n_c if normal_new is normal else h.require_gpu_f32(normal_new, "normal_new")
-        if n_c.dim() != 4 or n_c.shape[3] != 3:
-            raise ValueError("sfs_intensity expects normal [B,H,W,3]")
-        B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
-        for t, name, c in ((a_c, "abedo", 1), (i_c, "im_gray", 1), (a2_c, "abedo_new", 1), (n2_c, "normal_new", 3)):
-            if tuple(t.shape) != (B, H, W, c):
-                raise ValueError("sfs_intensity: %s must be [%d,%d,%d,%d] (got %s)" % (name, B, H, W, c, tuple(t.shape)))
-            if t.device != n_c.device:
-                raise ValueError("sfs_intensity: %s is on %s, normal on %s" % (name, t.device, n_c.device))
+        a_c, n_c, i_c, a2_c, n2_c, B, H, W = _sfs_inputs("sfs_intensity", h, abedo, normal, im_gray, abedo_new, normal_new, abedo_grad)
         dev = n_c.device
         L = h.lib()
         nst = L.fr_sfs_state_bytes(H, W)
@@ -608,16 +571,13 @@ class _SfsIntensity(torch.autograd.Function):
         a_c, i_c, a2_c, n2_c, state = ctx.saved_tensors
         B, H, W, nst = ctx.dims
         dev = a_c.device
-        want_n, want_n2 = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
-        want_a2 = ctx.abedo_grad and ctx.needs_input_grad[3]
-        if not (want_n or want_n2 or want_a2):
-            return None, None, None, None, None, None
+        grads = _sfs_grad_buffers(ctx)
+        if grads is None:
+            return (None,) * 7
+        gn, gn2, ga2 = grads
         g_c = h.require_gpu_f32(g, "grad_intensity")
-        gn = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n else None
-        gn2 = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n2 else None
-        ga2 = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev) if want_a2 else None
         with torch.cuda.device(dev):
-            if want_a2:
+            if ga2 is not None:
                 rc = h.lib().fr_sfs_intensity_backward_tex(h.ptr(g_c), h.ptr(a_c), h.ptr(i_c), h.ptr(a2_c), h.ptr(n2_c),
                                                            h.ptr(state), nst, B, H, W, h.ptr(gn), h.ptr(gn2), h.ptr(ga2),
                                                            h.stream_ptr(dev))
@@ -625,16 +585,7 @@ class _SfsIntensity(torch.autograd.Function):
                 rc = h.lib().fr_sfs_intensity_backward(h.ptr(g_c), h.ptr(a_c), h.ptr(i_c), h.ptr(a2_c), h.ptr(n2_c), h.ptr(state),
                                                        nst, B, H, W, h.ptr(gn), h.ptr(gn2), h.stream_ptr(dev))
         h.check(rc, "fr_sfs_intensity_backward")
-        return None, gn, None, ga2, gn2, None
-
-
-class _SfsIntensityTex(_SfsIntensity):
-    """sfs_intensity(abedo_grad=True): the same forward; `abedo_new` may require grad and the backward also returns
-    grad_abedo_new (fr_sfs_intensity_backward_tex).  `abedo` and `im_gray` stay constants."""
-
-    @staticmethod
-    def forward(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond):
-        return _SfsIntensity._fwd(ctx, abedo, normal, im_gray, abedo_new, normal_new, rcond, True)
+        return None, gn, None, ga2, gn2, None, None
 
 
 def sfs_intensity(abedo, normal, im_gray, abedo_new, normal_new, rcond=1e-15, abedo_grad=False):
@@ -646,9 +597,7 @@ def sfs_intensity(abedo, normal, im_gray, abedo_new, normal_new, rcond=1e-15, ab
     constants of this model.  The node keeps a state tensor of ten float64 planes (3.2 MB at 200 x 200) for its backward.
     abedo_grad=True: `abedo_new` may require grad and receives g * (l . normal_new), the lighting held as the state holds it
     (fr_sfs_intensity_backward_tex); `abedo` and `im_gray` are still refused.  Same intensity, bit for bit."""
-    if abedo_grad:
-        return _SfsIntensityTex.apply(abedo, normal, im_gray, abedo_new, normal_new, float(rcond))
-    return _SfsIntensity.apply(abedo, normal, im_gray, abedo_new, normal_new, float(rcond))
+    return _SfsIntensity.apply(abedo, normal, im_gray, abedo_new, normal_new, float(rcond), bool(abedo_grad))
 
 
 def _dist():
@@ -682,23 +631,8 @@ class _SfsIntensitySharded(torch.autograd.Function):
         h = _host()
         ctx.abedo_grad = bool(abedo_grad)
         ctx.exchange = exchange
-        for t, name in ((abedo, "abedo"), (im_gray, "im_gray")) + (() if abedo_grad else ((abedo_new, "abedo_new"),)):
-            if isinstance(t, torch.Tensor) and t.requires_grad:
-                raise ValueError("sfs_intensity_sharded: %s requires grad, but the albedos and im_gray are constants of this model "
-                                 "(detach it)" % name)
-        a_c = h.require_gpu_f32(abedo, "abedo")
-        n_c = h.require_gpu_f32(normal, "normal")
-        i_c = h.require_gpu_f32(im_gray, "im_gray")
-        a2_c = h.require_gpu_f32(abedo_new, "abedo_new")
-        n2_c = n_c if normal_new is normal else h.require_gpu_f32(normal_new, "normal_new")
-        if n_c.dim() != 4 or n_c.shape[3] != 3:
-            raise ValueError("sfs_intensity_sharded expects normal [B,H,W,3]")
-        B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
-        for t, name, c in ((a_c, "abedo", 1), (i_c, "im_gray", 1), (a2_c, "abedo_new", 1), (n2_c, "normal_new", 3)):
-            if tuple(t.shape) != (B, H, W, c):
-                raise ValueError("sfs_intensity_sharded: %s must be [%d,%d,%d,%d] (got %s)" % (name, B, H, W, c, tuple(t.shape)))
-            if t.device != n_c.device:
-                raise ValueError("sfs_intensity_sharded: %s is on %s, normal on %s" % (name, t.device, n_c.device))
+        a_c, n_c, i_c, a2_c, n2_c, B, H, W = _sfs_inputs("sfs_intensity_sharded", h, abedo, normal, im_gray, abedo_new, normal_new,
+                                                         abedo_grad)
         dev = n_c.device
         L = h.lib()
         nst = L.fr_sfs_state_bytes(H, W)
@@ -725,20 +659,16 @@ class _SfsIntensitySharded(torch.autograd.Function):
         a_c, i_c, a2_c, n2_c, state = ctx.saved_tensors
         B, H, W, nst = ctx.dims
         dev = a_c.device
-        want_n, want_n2 = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
-        want_a2 = ctx.abedo_grad and ctx.needs_input_grad[3]
-        none = (None,) * 8
-        if not (want_n or want_n2 or want_a2):
-            return none
+        grads = _sfs_grad_buffers(ctx)
+        if grads is None:
+            return (None,) * 8
+        gn, gn2, ga2 = grads
         g_c = h.require_gpu_f32(g, "grad_intensity")
-        gn = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n else None
-        gn2 = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if want_n2 else None
-        ga2 = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev) if want_a2 else None
         if H * W == 0:
             return None, gn, None, ga2, gn2, None, None, None
         L = h.lib()
         parts = None
-        if want_n:   # the one collective of the backward: issued by every rank or by none (same graph on every rank)
+        if gn is not None:   # the one collective of the backward: issued by every rank or by none (same graph on every rank)
             mine = torch.empty((3, H, W), dtype=torch.float64, device=dev)
             with torch.cuda.device(dev):
                 rc = L.fr_sfs_backward_q(h.ptr(g_c), h.ptr(a2_c), h.ptr(n2_c), B, H, W, h.ptr(mine), mine.numel() * 8,
@@ -841,9 +771,7 @@ def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     normal_grad=True: the gradient of channels 4-6 reaches all three coordinates of the winning triangles' vertices
     (fr_render_normal_backward, post mode, behind the depth backward); same outputs, bit for bit.  The node then keeps the
     vertex tensor: [B,3,nver] fp32, 41 MB at 64 faces of the full mesh."""
-    if normal_grad:
-        return _RenderingLayerFusedNormal.apply(ver, tri, texture, im_gray)
-    return _RenderingLayerFused.apply(ver, tri, texture, im_gray)
+    return _RenderingLayerFused.apply(ver, tri, texture, im_gray, bool(normal_grad))
 
 
 def render_depth(ver, tri, texture, image, normal_grad=False, texture_grad=False, **kwargs):
@@ -861,11 +789,7 @@ def render_depth(ver, tri, texture, image, normal_grad=False, texture_grad=False
     lookup (t[p1] + t[p2] + t[p3]) / 3 (fr_render_texture_backward; tri_ind held fixed).  Same outputs, bit for bit; the node
     saves no tensor beyond what it keeps anyway, and no backward is launched for an output nobody used.  Combines with normal_grad.
     """
-    if texture_grad:
-        return (_RenderDepthNormalTex if normal_grad else _RenderDepthTex).apply(ver, tri, texture, image)
-    if normal_grad:
-        return _RenderDepthNormal.apply(ver, tri, texture, image)
-    return _RenderDepth.apply(ver, tri, texture, image)
+    return _RenderDepth.apply(ver, tri, texture, image, bool(normal_grad), bool(texture_grad))
 
 
 def render_depth_grad(depth_grad, ver, tri, depth, tri_ind, image):

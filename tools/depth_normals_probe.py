@@ -59,14 +59,10 @@ dev = torch.device("cuda:0")
 H = W = 200
 
 
-_vp, _i = ctypes.c_void_p, ctypes.c_int
 ALT = {}
 for spec in args.alt_lib:
     name, path = spec.split("=", 1)
-    lib = ctypes.CDLL(path)
-    lib.fr_depth_normals_forward.argtypes = [_vp, _vp, _i, _i, _i, _vp, _vp]
-    lib.fr_depth_normals_backward.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]
-    ALT[name] = lib
+    ALT[name] = h.bind(ctypes.CDLL(path), ("fr_depth_normals_forward", "fr_depth_normals_backward"))
 
 
 def _sh(a, dr, dc, fill):

@@ -70,16 +70,11 @@ L = h.lib()
 A = synth.make_assets()
 dev = torch.device("cuda:0")
 H = W = 200
-_vp, _i = ctypes.c_void_p, ctypes.c_int
 
 
 def bind_alt(path):
     """only the SfS entry points of a library built from fr_sfs.hip alone"""
-    lib = ctypes.CDLL(path)
-    lib.fr_sfs_intensity_forward.argtypes = [_vp] * 5 + [_i, _i, _i, ctypes.c_double, _vp, _vp, ctypes.c_size_t, _vp]
-    lib.fr_sfs_intensity_backward.argtypes = [_vp] * 6 + [ctypes.c_size_t, _i, _i, _i, _vp, _vp, _vp]
-    lib.fr_debug_sfs_geom.argtypes = [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]
-    return lib
+    return h.bind(ctypes.CDLL(path), ("fr_sfs_intensity_forward", "fr_sfs_intensity_backward", "fr_debug_sfs_geom"))
 
 
 ALT = {}
