@@ -2,7 +2,8 @@
 BASELINE.json config 4.  Stock torch ops, except where the objective itself calls the hot path:
 
   * the geometry loss's basis product [pc_shape | pc_exp] . coeff (network.py:347-353) runs on the MFMA decode kernel
-    (FaceRecNet.geometry_product), and
+    (FaceRecNet.geometry_product) -- or, opt-in (geometry_gram=True), on no pass of the basis at all: the loss is a quadratic
+    form in the coefficient differences, evaluated from the basis's Gram matrix (FaceRecNet.geometry_loss(gram=True)) -- and
   * the shape-from-shading model issues two more render_depth calls (network.py:423, 454 through compute_abedo_image).
 
 Names and weights follow the reference: pose MSE (lambda 1e-3), geometry MSE through the basis (1e-6), spherical
@@ -176,7 +177,7 @@ def combine_losses(losses):
 
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
              gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False,
-             sfs_fused_gather=False, sfs_fine=False):
+             sfs_fused_gather=False, sfs_fine=False, geometry_gram=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
     sfs_normal_grad / sfs_fused / sfs_rcond (defaults: off, off, the reference's 1e-15): the normal_grad / fused / rcond of
     get_spherical_harmonics_model.  With them off spherical_harmonics_loss is a reported scalar with no gradient, as in the
@@ -187,7 +188,10 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     the fused kernels under any world size, the ranks exchanging per-pixel sums (get_spherical_harmonics_model(fused_gather=True)).
     sfs_fine=True (default off): the term shades the normals of pred_depth_map instead of the coarse mesh's a second time
     (get_spherical_harmonics_model(fine_depth=pred_depth_map)), so spherical_harmonics_loss has a gradient with respect to
-    pred_depth_map on either route; ValueError when pred_depth_map is None."""
+    pred_depth_map on either route; ValueError when pred_depth_map is None.
+    geometry_gram=True (default off): geometry_loss comes from the Gram matrix of the basis (FaceRecNet.geometry_loss(gram=True)):
+    the same quantity, from float64 chains over 228 numbers per face instead of two passes over the basis; the second packed image
+    of the basis is then never built.  Each rank takes the mean over its own faces, as on the default route: no collective."""
     fn = face_net
     B = pred_params.shape[0]
     pred = pred_params.reshape(B, fn.ndim)
@@ -196,8 +200,11 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     losses['pose_loss'] = F.mse_loss(pred[:, :fn.ndim_pose], label[:, :fn.ndim_pose])
     # geometry: MSE(basis . label^T, basis . pred^T) == mean over (3N x B) of (basis . (pred - label)^T)^2 up to fp32
     # rounding of the two products; the difference form needs one pass of the basis instead of two
-    g = fn.geometry_product(pred[:, fn.ndim_pose:] - label[:, fn.ndim_pose:])
-    losses['geometry_loss'] = (g * g).mean()
+    if geometry_gram:
+        losses['geometry_loss'] = fn.geometry_loss(pred[:, fn.ndim_pose:] - label[:, fn.ndim_pose:], gram=True)
+    else:
+        g = fn.geometry_product(pred[:, fn.ndim_pose:] - label[:, fn.ndim_pose:])
+        losses['geometry_loss'] = (g * g).mean()
     kw_tex = {"tex_grad": True} if sfs_tex_grad else {}
     if sfs_fused_gather:
         kw_tex["fused_gather"] = True

@@ -239,6 +239,52 @@ class _Decode3DMM(torch.autograd.Function):
         return gp, None, gR, None, None, None
 
 
+class _GeometryGramLoss(torch.autograd.Function):
+    """The geometry loss in its Gram form as one autograd node: diff [B,K] fp32 -> mean(([pc_shape | pc_exp] diff^T)^2), a 0-dim
+    fp32 tensor, from G = U^T U (FaceRecNet.gram()) -- fr_geometry_loss_forward, fr_geometry_loss_backward; no pass of the basis,
+    no [B,3,N] tensor.  The forward leaves y = G d in its state buffer and the backward scales it, so a buffer belongs to ONE call
+    from its forward to its backward: the node takes it from FaceRecNet.gram_state() and hands it back when its backward has
+    been enqueued (the same stream: launches are ordered).  A second backward through one node (retain_graph) finds the buffer
+    gone and raises.  The kernels take 18 us at 64 faces, so the node is host-bound: it makes one stream query per direction and
+    passes addresses as plain integers (the binding's argtypes convert them)."""
+
+    @staticmethod
+    def forward(ctx, diff, net, gram):
+        L = _host().lib()
+        dev = diff.device
+        B = int(diff.shape[0])
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            key, nst, state = net.gram_state(B, dev, stream)
+            rc = L.fr_geometry_loss_forward(diff.data_ptr(), gram.data_ptr(), B, net.nvert, net.ndim_shape, net.ndim_exp,
+                                            loss.data_ptr(), state.data_ptr(), nst, stream)
+        if rc:
+            _host().check(rc, "fr_geometry_loss_forward")
+        ctx.net, ctx.key, ctx.nst, ctx.state, ctx.shape = net, key, nst, state, (B, int(diff.shape[1]))
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        h = _host()
+        if ctx.state is None:
+            raise RuntimeError("geometry_loss(gram=True): the node's state went back to the pool with its first backward; "
+                               "call the loss again for a second backward")
+        net = ctx.net
+        g = h.require_gpu_f32(grad_loss, "grad_loss")
+        B, K = ctx.shape
+        dev = g.device
+        gd = torch.empty((B, K), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = h.lib().fr_geometry_loss_backward(g.data_ptr(), ctx.state.data_ptr(), ctx.nst, B, net.nvert, net.ndim_shape,
+                                                   net.ndim_exp, gd.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc:
+            h.check(rc, "fr_geometry_loss_backward")
+        net.gram_state_done(ctx.key, ctx.state)
+        ctx.state = None
+        return gd, None, None
+
+
 class FaceRecNet:
     def __init__(self, im_gray=None, params_label=None, mesh_data=None, nIter=4, batch_size=64, im_size=200,
                  weight_decay=1e-4, device="cuda"):
@@ -287,6 +333,10 @@ class FaceRecNet:
         self._basis = PackedBasis(self.mu, self.pc_shape, self.pc_exp, self.nvert, self.ndim_shape, self.ndim_exp,
                                   self.device)
         self._basis_nomu = None  # second image with mu = 0, built on first use by geometry_product()
+        self._gram = None        # U^T U in float64 (fr_geometry_gram_build), built on first use by gram()
+        self._gram_state = {}    # free state buffers of the Gram-form loss by (device, stream, bytes): gram_state()
+        self._gram_nst = {}      # fr_geometry_loss_state_bytes by batch
+        self._gram_lock = threading.Lock()
 
         # initial parameters (network.py:57-62)
         geo = torch.zeros((batch_size, self.ndim_shape + self.ndim_exp), **f32)
@@ -340,6 +390,74 @@ class FaceRecNet:
         pose[:, 6] = 1.0
         eye = torch.eye(3, dtype=torch.float32, device=g.device)[None].repeat(B, 1, 1).contiguous()
         return _Decode3DMM.apply(torch.cat([pose, g], 1), self, eye, self._basis_nomu, 1.0)
+
+    def gram(self):
+        """G = U^T U of U = [pc_shape | pc_exp] as a [Kp,Kp] float64 tensor (Kp = ndim_shape + ndim_exp rounded up to 16), built
+        on first use by fr_geometry_gram_build -- one pass over the basis in its reference layout, float64 MFMA -- and cached: a
+        caller that never asks for the Gram-form loss never holds it.  None where the kernels do not serve the basis (more than
+        256 coefficients)."""
+        with self._gram_lock:
+            if self._gram is None:
+                h = _host()
+                L = h.lib()
+                nbytes = L.fr_geometry_gram_bytes(self.ndim_shape, self.ndim_exp)
+                if nbytes == 0:
+                    return None
+                kp = (self.ndim_shape + self.ndim_exp + 15) // 16 * 16
+                G = torch.empty((kp, kp), dtype=torch.float64, device=self.device)
+                nws = L.fr_geometry_gram_workspace_bytes(self.nvert, self.ndim_shape, self.ndim_exp)
+                ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=self.device)
+                with torch.cuda.device(self.device):
+                    rc = L.fr_geometry_gram_build(h.ptr(self.pc_shape), h.ptr(self.pc_exp), self.nvert, self.ndim_shape,
+                                                  self.ndim_exp, h.ptr(G), nbytes, h.ptr(ws), nws, h.stream_ptr(self.device))
+                h.check(rc, "fr_geometry_gram_build")
+                _publish(self.device)
+                self._gram = G
+            return self._gram
+
+    def gram_state(self, B, dev, stream):
+        """(key, bytes, buffer): a state buffer of the Gram-form loss for B faces on `stream` (torch's current stream of `dev`, as
+        its address), the caller's until it hands it back through gram_state_done(key, buffer).  Free buffers are kept per
+        (stream, size), like PackedBasis.backward_workspace -- launches on one stream are ordered, so the next call may reuse
+        what the last one's backward has read -- at most four in all; a buffer that never comes back (a forward without a
+        backward) is the allocator's again when its node dies.  Under graph capture a fresh one is taken and never pooled."""
+        nst = self._gram_nst.get(B)
+        if nst is None:
+            nst = self._gram_nst[B] = _host().lib().fr_geometry_loss_state_bytes(B, self.ndim_shape, self.ndim_exp)
+        if torch.cuda.is_current_stream_capturing():
+            return None, nst, torch.empty((nst,), dtype=torch.uint8, device=dev)
+        key = (dev.index, stream, nst)
+        with self._gram_lock:
+            free = self._gram_state.get(key)
+            buf = free.pop() if free else None
+        if buf is None:
+            buf = torch.empty((nst,), dtype=torch.uint8, device=dev)
+        return key, nst, buf
+
+    def gram_state_done(self, key, buf):
+        if key is None:
+            return
+        with self._gram_lock:
+            if sum(len(v) for v in self._gram_state.values()) < 4:
+                self._gram_state.setdefault(key, []).append(buf)
+
+    def geometry_loss(self, geometry_diff, gram=False):
+        """(B, ndim_shape + ndim_exp) coefficient differences -> the geometry loss mean(([pc_shape | pc_exp] diff^T)^2), 0-dim.
+        gram=False (default): the product route, `g = geometry_product(diff); (g * g).mean()` -- two passes over the basis per
+        step, a [B,3,N] tensor kept for the backward.
+        gram=True: the same quantity from G = U^T U (gram(), built at the first call), in float64 chains of a fixed order
+        (include/fr_hotpath.h, "Gram-form geometry loss"): no basis traffic per step, and the second packed image of the basis is
+        never built.  An empty batch, or a basis gram() does not serve, takes the product route."""
+        G = None
+        if gram and int(geometry_diff.shape[0]) > 0:
+            G = self._gram if self._gram is not None else self.gram()
+        if G is not None:
+            d = _host().require_gpu_f32(geometry_diff, "geometry_diff")
+            if d.dim() != 2 or d.shape[1] != self.ndim_shape + self.ndim_exp:
+                raise ValueError("geometry_diff must be (B,%d)" % (self.ndim_shape + self.ndim_exp))
+            return _GeometryGramLoss.apply(d, self, G)
+        g = self.geometry_product(geometry_diff)
+        return (g * g).mean()
 
     # ---- rendering layer wrapper --------------------------------------------------------------------------
     def rendering_layer(self, vertex_proj, triangles, colors, im_gray=None, normal_grad=False):

@@ -74,7 +74,8 @@ def build_harness(args, dev, rank, world, local):
                                     sfs_fused=args.sfs_fused, sfs_rcond=args.sfs_rcond,
                                     **({"sfs_tex_grad": True} if args.sfs_tex_grad else {}),
                                     **({"sfs_fused_gather": True} if args.sfs_fused_gather else {}),
-                                    **({"sfs_fine": True} if args.sfs_fine else {}))
+                                    **({"sfs_fine": True} if args.sfs_fine else {}),
+                                    **({"geometry_gram": True} if args.geometry_gram else {}))
 
     def step():
         if not args.train:
@@ -235,6 +236,10 @@ def build_parser():
                     help="the SfS term shades the normals of the predicted FINE depth map (depth_normals: fr_depth_normals_forward / "
                          "_backward, masked by the render's tri_ind) instead of the coarse mesh's a second time, so the term's gradient "
                          "reaches pred_depth_map (get_loss(sfs_fine=True)); needs --fine; off: as the reference")
+    ap.add_argument("--geometry-gram", action="store_true",
+                    help="the geometry loss from the Gram matrix of the basis, built once in float64 (fr_geometry_gram_build; "
+                         "get_loss(geometry_gram=True)): no pass over the basis per step and no second packed image of it; off: the "
+                         "basis product on the decode kernel and its packed backward")
     ap.add_argument("--sfs-rcond", type=float, default=1e-15,
                     help="eigenvalue cutoff of the SfS pseudo-inverse, relative to the largest.  With float64 sums a rank-deficient "
                          "pixel (fewer than three faces cover it, or their normals are parallel) has null eigenvalues near 1e-16 "

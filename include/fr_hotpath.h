@@ -715,6 +715,63 @@ int fr_depth_normals_backward(const float* grad_normal, const float* depth, cons
  * the tile's edges and by tests/test_depth_normals_cpu.py. */
 void fr_debug_depth_normals_geom(int B, int H, int W, int* out);
 
+/* ---- Gram-form geometry loss: one pass of the basis at load time, none per step (opt-in) ------------------------------------------
+ * The geometry loss (nets/network.py:347-355) is a quadratic form in K = n_shape + n_exp numbers per face,
+ *   mean((U d)^2) = (1 / (3N B)) sum_b d_b^T (U^T U) d_b,      d / d d_b = (2 / (3N B)) (U^T U) d_b,      U = [pc_shape | pc_exp],
+ * and U is a constant of the model, so G = U^T U is one too.  fr_geometry_gram_build forms it once, in float64; after that the
+ * loss and its gradient are a Kp x Kp matrix against B short vectors: no basis traffic per step, no second packed image of the
+ * basis, no [B,3,N] tensor kept for the backward.  Notation: Kp = K rounded up to a multiple of 16, rows = 3N.
+ *   pc_shape [3N, n_shape], pc_exp [3N, n_exp]   the reference layouts (row strides of 199 and 29 floats: no alignment assumed);
+ *                                                either may have 0 columns, its pointer is then not read
+ *   gram   [Kp][Kp] float64, row-major, full storage;   diff, grad_diff  [B, K] fp32;   loss, grad_loss  one fp32 on the DEVICE
+ * NAMES.  The stream parameter of these entry points is called `stream`, not `hip_stream` as everywhere above: tests/
+ * test_capi_codes_cpu.py replays a fixture recorded from exactly the prototypes that have a parameter named hip_stream, and that
+ * fixture is not re-recorded for an opt-in addition; tests/test_geometry_gram_cpu.py holds these entry points' return codes.
+ * GRAM.  G[i][j] = sum_r U[r][i] U[r][j] in float64 on the widened fp32 entries (every product is exact).  The row axis is cut into
+ * chunks of 1,024 rows -- a compile-time constant: no function of the device, of B or of a knob -- each chunk's partial comes from
+ * v_mfma_f64_16x16x4_f64 accumulations over its rows in row order, and the chunk partials are added in chunk order from +0.0.  Only
+ * i <= j is computed; the one value is written to G[i][j] and G[j][i], so G equals its transpose bit for bit.  Every element with
+ * i >= K or j >= K is exactly +0, whatever the basis holds.  G's bits are a function of (N, n_shape, n_exp, the basis) alone: the
+ * same run to run and device to device.  For a finite basis, |G[i][j] - exact| <= 3N 2^-53 sum_r |U[r][i] U[r][j]| (a sum of 3N
+ * exact terms, at most 3N - 1 roundings of relative size 2^-53 in any association).  The workspace holds the chunk
+ * partials and is free again when the build has run; neither buffer needs to be cleared.
+ * LOSS.  Float64, every multiplication and every addition rounded on its own (no fma):
+ *   d_j       = (double) diff[b][j]
+ *   y[b][k]   = chain over j = 0 .. K-1 from +0.0:   y = y + G[j][k] * d_j
+ *   q[b]      = chain over k = 0 .. K-1 from +0.0:   q = q + d_k * y[b][k]
+ *   S         = chain over b = 0 .. B-1 from +0.0:   S = S + q[b]
+ *   loss      = (float)( S / ((double)(3N) * (double)B) )
+ *   grad_diff[b][k] = (float)( ((double)grad_loss[0] * (2.0 / ((double)(3N) * (double)B))) * y[b][k] )
+ * (tests/ref_geometry_gram.py is this in numpy).  A non-finite diff entry makes that face's y row and the loss non-finite by the
+ * IEEE rules and leaves every other face's gradient row untouched.  Under data parallelism each rank takes the mean over its own
+ * faces, as it does with the product form: no collective.
+ * STATE.  `state` is caller-owned, 16-byte aligned, fr_geometry_loss_state_bytes(B, ..) bytes: y [B][Kp], q [B], S, float64.  It
+ * carries y from the forward to the backward, so there is one per call in flight; the backward reads grad_loss from the device.
+ * Nothing is allocated or synchronised; reentrant under the rules at the top of this file.
+ * Checks, all before any HIP call, in this order: (1) a negative size or N < 1 is FR_ERR_INVALID_ARG; (2) K < 1 or K > 256 is
+ * FR_ERR_UNSUPPORTED (the size functions answer 0 for both); (3) B == 0 is FR_OK with nothing written; (4) a NULL diff, loss,
+ * grad_loss, grad_diff, or basis matrix that has columns, is FR_ERR_INVALID_ARG; (5) a missing, small or misaligned gram,
+ * workspace or state is FR_ERR_WORKSPACE.
+ * Kernels (csrc/fr_geometry.hip): the build is a workgroup of 8 waves per chunk that stages 32-row slabs in LDS and deals the 16 x 16
+ * tile pairs of the upper triangle to its waves (K = 228: 120 pairs, 15 per wave), then one thread per element for the chunk sum;
+ * the forward is one workgroup per face (d in LDS, one thread per k) and a one-wave launch for S and the loss; the backward one
+ * elementwise launch.  tools/geometry_gram_probe.py (profiles/geometry_gram.json) measures both routes and the build. */
+size_t fr_geometry_gram_bytes(int n_shape, int n_exp);
+size_t fr_geometry_gram_workspace_bytes(int N, int n_shape, int n_exp);
+int fr_geometry_gram_build(const float* pc_shape, const float* pc_exp, int N, int n_shape, int n_exp, void* gram, size_t gram_bytes,
+                           void* workspace, size_t ws_bytes, void* stream);
+size_t fr_geometry_loss_state_bytes(int B, int n_shape, int n_exp);
+int fr_geometry_loss_forward(const float* diff, const void* gram, int B, int N, int n_shape, int n_exp, float* loss, void* state,
+                             size_t state_bytes, void* stream);
+int fr_geometry_loss_backward(const float* grad_loss, const void* state, size_t state_bytes, int B, int N, int n_shape, int n_exp,
+                              float* grad_diff, void* stream);
+
+/* The Gram build's geometry (no GPU needed; the launcher reads the same function): out[6] = {rows per chunk (the same for every
+ * shape), chunks, Kp, 16 x 16 tile pairs with ti <= tj, workgroups of the chunk kernel, its static LDS bytes}.  All zero for a shape
+ * the build refuses.  Used by tests/test_geometry_gram_gpu.py to place its shapes on the chunk's edges and by
+ * tests/test_geometry_gram_cpu.py. */
+void fr_debug_geometry_gram_geom(int N, int n_shape, int n_exp, int* out);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
