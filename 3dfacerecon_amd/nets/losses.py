@@ -4,7 +4,9 @@ BASELINE.json config 4.  Stock torch ops, except where the
   * the geometry loss's basis product [pc_shape | pc_exp] . coeff (network.py:347-353) runs on the MFMA decode kernel
     (FaceRecNet.geometry_product) -- or, opt-in (geometry_gram=True), on no pass of the basis at all: the loss is a quadratic
     form in the coefficient differences, evaluated from the basis's Gram matrix (FaceRecNet.geometry_loss(gram=True)) -- and
-  * the shape-from-shading model issues two more render_depth calls (network.py:423, 454 through compute_abedo_image).
+  * the shape-from-shading model issues two more render_depth calls (network.py:423, 454 through compute_abedo_image), and
+  * opt-in (fine_fused=True), the fidelity and the smoothness term of the fine depth map are one kernel pass per direction
+    (rendering_layer/ops.py::fine_depth_losses) instead of a chain of elementwise ops, a convolution and two reductions.
 
 Names and weights follow the reference: pose MSE (lambda 1e-3), geometry MSE through the basis (1e-6), spherical
 harmonics / SfS MSE (1e-3), fidelity MSE between the coarse and the fine depth map (100), Laplacian-L1 smoothness (1e-5)
@@ -177,7 +179,7 @@ def combine_losses(losses):
 
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
              gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False,
-             sfs_fused_gather=False, sfs_fine=False, geometry_gram=False):
+             sfs_fused_gather=False, sfs_fine=False, fine_fused=False, geometry_gram=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
     sfs_normal_grad / sfs_fused / sfs_rcond (defaults: off, off, the reference's 1e-15): the normal_grad / fused / rcond of
     get_spherical_harmonics_model.  With them off spherical_harmonics_loss is a reported scalar with no gradient, as in the
@@ -191,8 +193,15 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     pred_depth_map on either route; ValueError when pred_depth_map is None.
     geometry_gram=True (default off): geometry_loss comes from the Gram matrix of the basis (FaceRecNet.geometry_loss(gram=True)):
     the same quantity, from float64 chains over 228 numbers per face instead of two passes over the basis; the second packed image
-    of the basis is then never built.  Each rank takes the mean over its own faces, as on the default route: no collective."""
+    of the basis is then never built.  Each rank takes the mean over its own faces, as on the default route: no collective.
+    fine_fused=True (default off): fidelity_loss and smoothness_loss come from one autograd node (rendering_layer/ops.py::
+    fine_depth_losses, fr_fine_losses_forward / _backward): the same two quantities as float64 sums in a fixed association, one
+    kernel pass and a finish launch forward, one gather pass backward -- no convolution, no plane-sized intermediate.  The gradient
+    reaches pred_depth_map and, where it requires grad, coarse_depth_map, as on the default route; ValueError when pred_depth_map
+    is None.  Each rank sums over its own faces: no collective."""
     fn = face_net
+    if fine_fused and pred_depth_map is None:
+        raise ValueError("fine_fused=True needs pred_depth_map (the fine depth map the two terms are taken of)")
     B = pred_params.shape[0]
     pred = pred_params.reshape(B, fn.ndim)
     label = params_label.reshape(B, fn.ndim).to(pred.dtype)
@@ -215,8 +224,11 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     intensity_recover = get_spherical_harmonics_model(fn, vertices_proj, im_gray, gather=gather_sfs, normal_grad=sfs_normal_grad,
                                                       fused=sfs_fused, rcond=sfs_rcond, **kw_tex)
     losses['spherical_harmonics_loss'] = F.mse_loss(intensity_recover, im_gray)
-    losses['fidelity_loss'] = F.mse_loss(pred_depth_map, coarse_depth_map)
-    filtered_depth = laplace_transform(pred_depth_map[..., 0])
-    losses['smoothness_loss'] = filtered_depth.abs().sum()    # tf.contrib.layers.l1_regularizer(1.0), network.py:367
+    if fine_fused:
+        losses['fidelity_loss'], losses['smoothness_loss'] = _ops().fine_depth_losses(pred_depth_map, coarse_depth_map)
+    else:
+        losses['fidelity_loss'] = F.mse_loss(pred_depth_map, coarse_depth_map)
+        filtered_depth = laplace_transform(pred_depth_map[..., 0])
+        losses['smoothness_loss'] = filtered_depth.abs().sum()    # tf.contrib.layers.l1_regularizer(1.0), network.py:367
     losses['total_loss'] = combine_losses(losses)
     return losses

@@ -764,6 +764,88 @@ def depth_normals(depth, mask=None):
     return _DepthNormals.apply(depth, mask)
 
 
+_LAPLACE_K = ((0.5, 1.0, 0.5), (1.0, -6.0, 1.0), (0.5, 1.0, 0.5))  # network.py:383-385
+_FL_LOCK = threading.Lock()
+
+
+def _fine_losses_planes(h, pred, coarse):
+    """-> (pred, coarse) contiguous fp32 on one GPU, and (B, H, W)"""
+    p_c = h.require_gpu_f32(pred, "pred")
+    c_c = h.require_gpu_f32(coarse, "coarse")
+    if p_c.dim() == 4 and p_c.shape[3] == 1:
+        B, H, W = int(p_c.shape[0]), int(p_c.shape[1]), int(p_c.shape[2])
+    elif p_c.dim() == 3:
+        B, H, W = (int(v) for v in p_c.shape)
+    else:
+        raise ValueError("fine_depth_losses expects pred [B,H,W,1] or [B,H,W] (got %s)" % (tuple(p_c.shape),))
+    if tuple(c_c.shape) not in ((B, H, W, 1), (B, H, W)):
+        raise ValueError("fine_depth_losses: coarse must be [%d,%d,%d,1] or [%d,%d,%d] (got %s)" % (B, H, W, B, H, W, tuple(c_c.shape)))
+    if c_c.device != p_c.device:
+        raise ValueError("fine_depth_losses: coarse is on %s, pred on %s" % (c_c.device, p_c.device))
+    return p_c, c_c, (B, H, W)
+
+
+class _FineDepthLosses(torch.autograd.Function):
+    """fr_fine_losses_forward / _backward (include/fr_hotpath.h, "fine-depth losses") as one autograd node: (pred, coarse) ->
+    (fidelity, smoothness), two 0-dim fp32 tensors.  It saves pred and coarse and nothing plane-sized of its own: the backward
+    recomputes the signs from pred.  The forward's state (two float64 partials per tile) is dead once the forward has run, so it
+    is the per-(stream) scratch buffer that consecutive calls share (_scratch; a fresh one under graph capture); _FL_LOCK keeps the
+    forward's two launches of one call together where host threads share a stream.  A gradient that never arrives (an output
+    nobody used) is passed as NULL and its term is not evaluated."""
+
+    @staticmethod
+    def forward(ctx, pred, coarse):
+        h = _host()
+        L = h.lib()
+        p_c, c_c, (B, H, W) = _fine_losses_planes(h, pred, coarse)
+        dev = p_c.device
+        out = torch.empty((2,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), _FL_LOCK:
+            nst = L.fr_fine_losses_state_bytes(B, H, W)
+            state = _scratch("fine_losses", dev, nst)
+            rc = L.fr_fine_losses_forward(p_c.data_ptr(), c_c.data_ptr(), B, H, W, out.data_ptr(), out.data_ptr() + 4,
+                                          state.data_ptr(), nst, torch.cuda.current_stream(dev).cuda_stream)
+        if rc:
+            h.check(rc, "fr_fine_losses_forward")
+        ctx.save_for_backward(p_c, c_c)
+        ctx.dims = (B, H, W)
+        ctx.shapes = (tuple(pred.shape), tuple(coarse.shape))
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_fidelity, g_smoothness):
+        h = _host()
+        p_c, c_c = ctx.saved_tensors
+        B, H, W = ctx.dims
+        dev = p_c.device
+        gf = h.require_gpu_f32(g_fidelity, "grad_fidelity") if g_fidelity is not None else None
+        gs = h.require_gpu_f32(g_smoothness, "grad_smoothness") if g_smoothness is not None else None
+        gp = torch.empty(ctx.shapes[0], dtype=torch.float32, device=dev)
+        gc = torch.empty(ctx.shapes[1], dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            rc = h.lib().fr_fine_losses_backward(h.ptr(gf), h.ptr(gs), p_c.data_ptr(), c_c.data_ptr(), B, H, W, gp.data_ptr(),
+                                                 h.ptr(gc), torch.cuda.current_stream(dev).cuda_stream)
+        if rc:
+            h.check(rc, "fr_fine_losses_backward")
+        return (gp if ctx.needs_input_grad[0] else None), gc
+
+
+def fine_depth_losses(pred, coarse):
+    """(fidelity, smoothness) of the fine depth map `pred` against the coarse one, both [B,H,W,1] (or [B,H,W]): 0-dim fp32 tensors
+    equal to `F.mse_loss(pred, coarse)` and `laplace_transform(pred[..., 0]).abs().sum()` (nets/losses.py) up to rounding -- float64
+    sums in a fixed association instead of fp32 reductions (fr_fine_losses_forward: one pass and a finish launch).  The gradient
+    goes to `pred` and, where it requires grad, to `coarse`, each in its own shape (fr_fine_losses_backward: one gather pass,
+    bit-reproducible, the incoming scalar gradients read from the device).  The node saves `pred` and `coarse`.  An empty batch
+    or image takes the stock torch expressions."""
+    if pred.numel() == 0:
+        import torch.nn.functional as F
+        x = pred.reshape(pred.shape[0], pred.shape[1], pred.shape[2])
+        k = torch.tensor(_LAPLACE_K, dtype=x.dtype, device=x.device)[None, None]
+        return F.mse_loss(pred, coarse), F.conv2d(x[:, None], k, padding=1)[:, 0].abs().sum()
+    return _FineDepthLosses.apply(pred, coarse)
+
+
 def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     """One-pass rendering layer: returns (net_input [B,H,W,7] = [mask*im | pncc | normal],
     depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers.

@@ -75,7 +75,8 @@ def build_harness(args, dev, rank, world, local):
                                     **({"sfs_tex_grad": True} if args.sfs_tex_grad else {}),
                                     **({"sfs_fused_gather": True} if args.sfs_fused_gather else {}),
                                     **({"sfs_fine": True} if args.sfs_fine else {}),
-                                    **({"geometry_gram": True} if args.geometry_gram else {}))
+                                    **({"geometry_gram": True} if args.geometry_gram else {}),
+                                    **({"fine_fused": True} if args.fine_fused else {}))
 
     def step():
         if not args.train:
@@ -240,6 +241,10 @@ def build_parser():
                     help="the geometry loss from the Gram matrix of the basis, built once in float64 (fr_geometry_gram_build; "
                          "get_loss(geometry_gram=True)): no pass over the basis per step and no second packed image of it; off: the "
                          "basis product on the decode kernel and its packed backward")
+    ap.add_argument("--fine-fused", action="store_true",
+                    help="the fidelity and the smoothness term of the fine depth map from one kernel pass per direction "
+                         "(fine_depth_losses: fr_fine_losses_forward / _backward; get_loss(fine_fused=True)): float64 sums in a fixed "
+                         "association, no convolution; needs --fine; off: mse_loss and a conv2d / abs / sum chain")
     ap.add_argument("--sfs-rcond", type=float, default=1e-15,
                     help="eigenvalue cutoff of the SfS pseudo-inverse, relative to the largest.  With float64 sums a rank-deficient "
                          "pixel (fewer than three faces cover it, or their normals are parallel) has null eigenvalues near 1e-16 "

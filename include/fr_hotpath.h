@@ -772,6 +772,71 @@ int fr_geometry_loss_backward(const float* grad_loss, const void* state, size_t 
  * tests/test_geometry_gram_cpu.py. */
 void fr_debug_geometry_gram_geom(int N, int n_shape, int n_exp, int* out);
 
+/* ---- fine-depth losses: the fidelity and the smoothness term in one pass, with a backward (opt-in) ---------------------------------
+ * The two terms that train the fine depth map (nets/network.py:364-367, 381-392),
+ *   fidelity = mse(pred_depth_map, coarse_depth_map)          smoothness = sum |laplace(pred_depth_map)|,
+ * are one streaming pass over two planes per direction.  z = pred and c = coarse are [B,H,W] fp32, dense (a trailing channel of 1 is
+ * the caller's); pixel (r, c) is row-major.  All arithmetic is float64 on the widened fp32 inputs, every product and every sum
+ * rounded on its own (no contraction).
+ * NAMES.  The stream parameter is called `stream`, as in the Gram-form geometry loss above and for its reason;
+ * tests/test_fine_losses_cpu.py holds these entry points' return codes.
+ * LAPLACIAN.  k = ((0.5, 1, 0.5), (1, -6, 1), (0.5, 1, 0.5)).  L(p) = chain over the nine taps t in row-major tap order from +0.0:
+ * L = L + k_t * (double)z(p + t), for the taps inside the image; a tap outside contributes nothing (the reference's zero 'SAME'
+ * padding).  A face never reads another face.
+ * SUMS.  S_f = sum (z - c)^2 and S_s = sum |L| over all B H W pixels, each term formed as above ((double)z - (double)c, squared).
+ * Their association is a function of (B, H, W) alone -- not of the stream, an option, the device or a launch geometry chosen at
+ * run time -- and both sums use the same one:
+ *   tile     the image is cut into tiles of TW x TH = 32 x 16 pixels (fr_debug_fine_losses_geom), tiles across = ceil(W / TW), tiles
+ *            down = ceil(H / TH).  A tile has TW TH = 512 slots, slot i = (row in tile) TW + (column in tile); a slot outside the
+ *            image holds +0.0.  The slots are taken in groups of 64 consecutive ones (w = 0 .. 7); inside a group, for k = 32, 16, 8,
+ *            4, 2, 1 in turn: v[i] = v[i] + v[i + k] for every i < k; the group's sum is v[0].  The eight group sums the same way with
+ *            k = 4, 2, 1.  That is the tile's partial.
+ *   all      partial p = (face * tiles down + tile row) * tiles across + tile column, p < P.  With F = 1,024: a[i] = chain over
+ *            j = 0, 1, .. from +0.0 of partial[i + F j] (while i + F j < P), i < F; then the a[i] in 16 groups of 64 as above, and the
+ *            16 group sums with k = 8, 4, 2, 1.
+ * (tests/ref_fine_losses.py is this in numpy.)  Every term is >= +0 or NaN, so for finite input each sum lies within
+ * n 2^-53 sum |term| of the exact one, n = B H W, in this or any association.
+ * OUTPUTS.  fidelity = fl32(S_f / ((double)B (double)H (double)W)), smoothness = fl32(S_s): one fp32 each, on the device.
+ * STATE.  `state` is caller-owned, 16-byte aligned, fr_fine_losses_state_bytes(B, H, W) bytes of float64: S_f, S_s, the P fidelity
+ * partials, the P smoothness partials.  The forward writes all of it and needs none of it cleared; the backward does not read it
+ * (it recomputes what it needs from z and c), so the state is free again when the forward has run.
+ * BACKWARD.  s(x) = (x > 0) - (x < 0), so s(+-0) = 0 and s(NaN) = 0 (torch.sign's definition).  The kernel is symmetric, so the
+ * adjoint of the stencil is the stencil:
+ *   T(p)          = chain over the nine taps in row-major order from +0.0:  T = T + k_t * s(L(p + t)),  taps inside the image
+ *                   (a sum of multiples of 0.5: exact)
+ *   a             = (double)grad_fidelity[0] * c_f,      c_f = 2.0 / ((double)B (double)H (double)W) formed on the host
+ *   grad_pred[p]  = fl32( a * ((double)z - (double)c)  +  (double)grad_smoothness[0] * T(p) )
+ *   grad_coarse[p] = fl32( -(a * ((double)z - (double)c)) )
+ * grad_fidelity and grad_smoothness are one fp32 each, read from the DEVICE (no host synchronisation).  Either may be NULL: that
+ * term is absent -- not evaluated, not added -- so grad_pred is fl32 of the other term alone, exactly +0 with both NULL, and
+ * grad_coarse is exactly +0 without grad_fidelity.  grad_coarse may be NULL: not wanted.  Every output bit is fixed by the above,
+ * whatever the kernels' design; a gather, no atomics, bit-reproducible.
+ * NON-FINITE INPUT.  A non-finite z or c makes the losses non-finite by the IEEE rules.  In the backward the fidelity part is
+ * non-finite at that pixel only; a NaN z makes L NaN on its 3 x 3 ring, whose signs are then 0, so T stays finite and changes on the
+ * 5 x 5 ring of that face.  No other face's gradient changes by a bit.
+ * Checks, all before any HIP call, in this order: a negative size is FR_ERR_INVALID_ARG; then B == 0 or an empty image is FR_OK with
+ * nothing launched or written; then a NULL pred, coarse, fidelity, smoothness or grad_pred is FR_ERR_INVALID_ARG; a state that is
+ * missing, too small or not 16-byte aligned is FR_ERR_WORKSPACE; more than 2^31 - 65 pixels per face, more than 65,535 faces or
+ * more than 65,535 tile rows is FR_ERR_UNSUPPORTED, and fr_fine_losses_state_bytes answers 0 for it (as for an empty or negative
+ * shape).  Nothing is allocated or synchronised; reentrant under the rules at the top of this file with a state per call in flight.
+ * Kernels (csrc/fr_fine_losses.hip): a workgroup owns a tile, one lane per pixel.  The forward reads its nine-point stencil from
+ * global memory (the workgroup's own L1 lines), reduces by lane shuffles and 128 bytes of LDS and writes two partials; a second
+ * launch of one 1,024-thread workgroup finishes.  The backward stages z with a 2-pixel halo and s(L) with a 1-pixel halo in LDS
+ * (5,328 bytes; 1.2 Laplacians per output) and gathers; the halo runs the device function the forward runs.  At 64 faces of
+ * 200 x 200 the forward must move 20 MB and the backward 31 MB (41 with grad_coarse); tools/fine_losses_probe.py
+ * (profiles/fine_losses.json) measures both beside the stock-torch route. */
+size_t fr_fine_losses_state_bytes(int B, int H, int W);
+int fr_fine_losses_forward(const float* pred, const float* coarse, int B, int H, int W, float* fidelity, float* smoothness,
+                           void* state, size_t state_bytes, void* stream);
+int fr_fine_losses_backward(const float* grad_fidelity, const float* grad_smoothness, const float* pred, const float* coarse, int B,
+                            int H, int W, float* grad_pred, float* grad_coarse, void* stream);
+
+/* The fine-losses launch geometry (no GPU needed; the launchers read the same function): out[7] = {tile width, tile height, threads
+ * per workgroup, tiles across, tiles down, threads of the finish workgroup (F above), static LDS bytes of a backward workgroup}; the
+ * grid is tiles across x tiles down x B.  All zero for an empty shape or one the launchers refuse.  Used by tests/ref_fine_losses.py
+ * for the sums' association and by the tests to place their shapes on the tile's edges. */
+void fr_debug_fine_losses_geom(int B, int H, int W, int* out);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
