@@ -1,6 +1,6 @@
-// The owner-scatter scheme of the render backwards, stated once.  fr_render_bwd.hip (depth), fr_render_nbwd.hip (normal) and
-// fr_render_tbwd.hip (texture) are built from these pieces; none of the pieces knows which gradient it serves -- what differs
-// between the three enters as a template parameter, a value or a functor.
+// The owner-scatter scheme of the render backwards, stated once.  fr_render_bwd.hip (depth), fr_render_nbwd.hip (normal),
+// fr_render_tbwd.hip (texture) and fr_depth_interp.hip (interpolated depth) are built from these pieces; none of the pieces knows which gradient it serves -- what differs
+// between them enters as a template parameter, a value or a functor.
 //
 // The scheme: a pixel covered by triangle t adds fp32 terms to the three vertices of t.  The reference is a serial loop (one
 // fixed summation order); float atomics would make the per-vertex order depend on the schedule.  Here the sum is made
@@ -151,6 +151,85 @@ __device__ __forceinline__ void owner_stream(const int4* __restrict__ r0, int np
     }
 }
 
+// ---- the owner of nine terms per pixel over three rows --------------------------------------------------------------------------
+// What the normal backward (fr_render_nbwd.hip) and the interpolated-depth backward (fr_depth_interp.hip) share beyond the pieces
+// above: their records kernels differ (what a term is), their owner is this one.  Record planes [B][3][npix] of 16 bytes:
+// {p1 p2 p3 t1x | t1y t1z t2x t2y | t2z t3x t3y t3z}, t_k the (x, y, z) terms of vertex p_k; vertex_grad dense [B,3,nver].
+constexpr int ROWS3_RANGE_MAX = 6656;  // vertices per owner: 3 accumulators x 8 B each = 156 KiB of the CU's 160 KiB of LDS
+constexpr int ROWS3_TOP = 39;          // the face's largest finite |term| lands in [2^39, 2^40); an element receives at most three terms
+                                       // per pixel (a triangle naming one vertex three times), 3 * 2^20 of them stay below 2^62
+struct OwnerRows3 {
+    int4* rec;
+    uint2* partial;         // [B,chunks] {largest finite |term| bits, non-finite flag}
+    float* vertex_grad;
+    int B, chunks, nver, npix;
+    int splits, range, shift;
+    int accumulate;
+};
+// one workgroup of OWNER_BLOCK threads per (face, vertex range); acc: the kernel's dynamic LDS (the launcher raises the limit to the
+// CU's 160 KiB): [3][range] 64-bit accumulators, then the reduction array
+__device__ __forceinline__ void owner_rows3(const OwnerRows3& a, unsigned long long* acc) {
+    uint32_t* red = reinterpret_cast<uint32_t*>(acc + 3 * (size_t)a.range);  // [2 * OWNER_BLOCK / 64]
+    const int tid = threadIdx.x;
+    int b, sp;
+    owner_block_map(a.B, a.splits, &b, &sp);
+    const int range = a.range, npix = a.npix, nver = a.nver;
+    const int v0 = sp * range;
+    const int v1 = min(nver, v0 + range);
+    const int n = v1 - v0;
+    for (int i = tid; i < 3 * range; i += OWNER_BLOCK) acc[i] = 0ull;
+    const uint2 mb = scope_max<OWNER_BLOCK>(a.partial + (size_t)b * a.chunks, a.chunks, red);
+    const uint32_t m = mb.x, bad = mb.y;
+    const FixedScale<ROWS3_TOP> fx(m, a.shift);
+    float* facc = reinterpret_cast<float*>(acc);   // a face with an Inf / NaN term: fp32 LDS atomics, [3][range] floats
+    if (bad) {
+        __syncthreads();
+        for (int i = tid; i < 3 * range; i += OWNER_BLOCK) facc[i] = 0.0f;
+    }
+    __syncthreads();
+    const int4* __restrict__ r0 = a.rec + (size_t)b * 3 * npix;
+    const int4* __restrict__ r1 = r0 + npix;
+    const int4* __restrict__ r2 = r1 + npix;
+    auto add3 = [&](int local, float tx, float ty, float tz) {
+        if (bad) {
+            atomicAdd(&facc[local], tx);
+            atomicAdd(&facc[range + local], ty);
+            atomicAdd(&facc[2 * range + local], tz);
+        } else {
+            const unsigned long long qx = fx.to_fixed(tx), qy = fx.to_fixed(ty), qz = fx.to_fixed(tz);
+            fixed_add(&acc[local], qx);
+            fixed_add(&acc[range + local], qy);
+            fixed_add(&acc[2 * range + local], qz);
+        }
+    };
+    if (m != 0 || bad) {
+        // the two term planes are fetched for the pixels that land in this range only
+        owner_stream<OWNER_BLOCK>(r0, npix, v0, v1, [&](int i, const int4& q0, bool in1, bool in2, bool in3) {
+            const int4 q1 = r1[i], q2 = r2[i];
+            if (in1) add3(q0.x - v0, __int_as_float(q0.w), __int_as_float(q1.x), __int_as_float(q1.y));
+            if (in2) add3(q0.y - v0, __int_as_float(q1.z), __int_as_float(q1.w), __int_as_float(q2.x));
+            if (in3) add3(q0.z - v0, __int_as_float(q2.y), __int_as_float(q2.z), __int_as_float(q2.w));
+        });
+    }
+    __syncthreads();
+    float* out = a.vertex_grad + (size_t)b * 3 * nver;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float* row = out + (size_t)c * nver + v0;
+        for (int i = tid; i < n; i += OWNER_BLOCK) {
+            const float v = bad ? facc[c * range + i] : fx.round(acc[c * range + i]);
+            row[i] = a.accumulate ? row[i] + v : v;
+        }
+    }
+}
+// the nine fp32 terms of an ok pixel to its three record planes
+__device__ __forceinline__ void store_rows3(int4* __restrict__ r0, int4* __restrict__ r1, int4* __restrict__ r2, int i,
+                                            const int (&id)[3], const float (&t)[9]) {
+    r0[i] = make_int4(id[0], id[1], id[2], (int)__float_as_uint(t[0]));
+    r1[i] = make_int4((int)__float_as_uint(t[1]), (int)__float_as_uint(t[2]), (int)__float_as_uint(t[3]), (int)__float_as_uint(t[4]));
+    r2[i] = make_int4((int)__float_as_uint(t[5]), (int)__float_as_uint(t[6]), (int)__float_as_uint(t[7]), (int)__float_as_uint(t[8]));
+}
+
 // ---- host: the launch geometry -------------------------------------------------------------------------------------------------
 struct OwnerGeom {
     int splits, range;  // owner workgroups per group, vertices per owner
@@ -181,6 +260,14 @@ inline OwnerGeom owner_geom(int groups, int nver, long long npix, long long term
 // a test hook's common part: out = {owners per group, vertices per owner, shift, chunks, LDS bytes of an owner, XCD-map flag}
 inline void owner_geom_report(const OwnerGeom& g, int groups, int* out) {
     out[0] = g.splits; out[1] = g.range; out[2] = g.shift; out[3] = g.chunks; out[4] = (int)g.lds; out[5] = owner_xcd_map(groups) ? 1 : 0;
+}
+// the three-row owner's geometry (the splits are clamped to one vertex per owner) and the workspace of its call: the three record
+// planes, then the chunk partials
+inline OwnerGeom rows3_geom(int B, int nver, long long npix) { return owner_geom(B, nver, npix, npix, ROWS3_RANGE_MAX, 1, 3); }
+inline size_t rows3_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    const size_t npix = (size_t)H * W, chunks = (npix + REC_PX - 1) / REC_PX;
+    return (size_t)B * npix * 3 * sizeof(int4) + (size_t)B * chunks * sizeof(uint2);
 }
 // no term exists: zeros, or (accumulate) the tensor as it is
 inline int owner_no_terms(float* out, size_t bytes, bool accumulate, hipStream_t stream) {

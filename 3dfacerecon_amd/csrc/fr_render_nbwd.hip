@@ -17,9 +17,6 @@
 namespace fr {
 
 constexpr int NB_BLOCK = OWNER_BLOCK;
-constexpr int NB_RANGE_MAX = 6656;  // vertices per owner: 3 accumulators x 8 B each = 156 KiB of the CU's 160 KiB of LDS
-constexpr int NB_TOP = 39;          // the face's largest finite |term| lands in [2^39, 2^40); an element receives at most three terms
-                                    // per pixel (a triangle naming one vertex three times), 3 * 2^20 of them stay below 2^62
 
 struct NbwdArgs {
     const float* ngrad;     // three floats per pixel, `gstride` floats between pixels
@@ -119,83 +116,20 @@ __global__ __launch_bounds__(256) void nbwd_records_kernel(NbwdArgs a) {
         nbwd_terms(P[u], g[u], a.mode, t);
 #pragma unroll
         for (int j = 0; j < 9; j++) track_term(__float_as_uint(t[j]), m, bad);   // over the OK pixels
-        r0[i] = make_int4(id[u][0], id[u][1], id[u][2], (int)__float_as_uint(t[0]));
-        r1[i] = make_int4((int)__float_as_uint(t[1]), (int)__float_as_uint(t[2]), (int)__float_as_uint(t[3]), (int)__float_as_uint(t[4]));
-        r2[i] = make_int4((int)__float_as_uint(t[5]), (int)__float_as_uint(t[6]), (int)__float_as_uint(t[7]), (int)__float_as_uint(t[8]));
+        store_rows3(r0, r1, r2, i, id[u], t);
     }
     chunk_publish(m, bad, red, &a.partial[(size_t)b * a.chunks + ch]);
 }
 
 __global__ __launch_bounds__(NB_BLOCK) void nbwd_owner_kernel(NbwdArgs a) {
-    // all LDS is dynamic (the launcher raises the limit to the CU's 160 KiB): [3][range] accumulators, then the reduction array
-    extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];  // [3 * range]
-    uint32_t* red = reinterpret_cast<uint32_t*>(acc + 3 * (size_t)a.range);  // [2 * NB_BLOCK / 64]
-    const int tid = threadIdx.x;
-    int b, sp;
-    owner_block_map(a.B, a.splits, &b, &sp);
-    const int range = a.range, npix = a.npix, nver = a.nver;
-    const int v0 = sp * range;
-    const int v1 = min(nver, v0 + range);
-    const int n = v1 - v0;
-    for (int i = tid; i < 3 * range; i += NB_BLOCK) acc[i] = 0ull;
-    const uint2 mb = scope_max<NB_BLOCK>(a.partial + (size_t)b * a.chunks, a.chunks, red);
-    const uint32_t m = mb.x, bad = mb.y;
-    const FixedScale<NB_TOP> fx(m, a.shift);
-    float* facc = reinterpret_cast<float*>(acc);   // a face with an Inf / NaN term: fp32 LDS atomics, [3][range] floats
-    if (bad) {
-        __syncthreads();
-        for (int i = tid; i < 3 * range; i += NB_BLOCK) facc[i] = 0.0f;
-    }
-    __syncthreads();
-    const int4* __restrict__ r0 = a.rec + (size_t)b * 3 * npix;
-    const int4* __restrict__ r1 = r0 + npix;
-    const int4* __restrict__ r2 = r1 + npix;
-    auto add3 = [&](int local, float tx, float ty, float tz) {
-        if (bad) {
-            atomicAdd(&facc[local], tx);
-            atomicAdd(&facc[range + local], ty);
-            atomicAdd(&facc[2 * range + local], tz);
-        } else {
-            const unsigned long long qx = fx.to_fixed(tx), qy = fx.to_fixed(ty), qz = fx.to_fixed(tz);
-            fixed_add(&acc[local], qx);
-            fixed_add(&acc[range + local], qy);
-            fixed_add(&acc[2 * range + local], qz);
-        }
-    };
-    if (m != 0 || bad) {
-        // the two term planes are fetched for the pixels that land in this range only
-        owner_stream<NB_BLOCK>(r0, npix, v0, v1, [&](int i, const int4& q0, bool in1, bool in2, bool in3) {
-            const int4 q1 = r1[i], q2 = r2[i];
-            if (in1) add3(q0.x - v0, __int_as_float(q0.w), __int_as_float(q1.x), __int_as_float(q1.y));
-            if (in2) add3(q0.y - v0, __int_as_float(q1.z), __int_as_float(q1.w), __int_as_float(q2.x));
-            if (in3) add3(q0.z - v0, __int_as_float(q2.y), __int_as_float(q2.z), __int_as_float(q2.w));
-        });
-    }
-    __syncthreads();
-    float* out = a.vertex_grad + (size_t)b * 3 * nver;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        float* row = out + (size_t)c * nver + v0;
-        for (int i = tid; i < n; i += NB_BLOCK) {
-            const float v = bad ? facc[c * range + i] : fx.round(acc[c * range + i]);
-            row[i] = a.accumulate ? row[i] + v : v;
-        }
-    }
+    extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];  // all LDS is dynamic: owner_rows3's
+    owner_rows3({a.rec, a.partial, a.vertex_grad, a.B, a.chunks, a.nver, a.npix, a.splits, a.range, a.shift, a.accumulate}, acc);
 }
 
 }  // namespace fr
 
-// The launch geometry, chosen in ONE place: the launcher and the test hook both read it from here.  (The splits are clamped to
-// one vertex per owner.)
-static fr::OwnerGeom nbwd_geom(int B, int nver, long long npix) {
-    return fr::owner_geom(B, nver, npix, npix, fr::NB_RANGE_MAX, 1, 3);
-}
-
-size_t fr_render_normal_backward_workspace_impl(int B, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t npix = (size_t)H * W, chunks = (npix + fr::REC_PX - 1) / fr::REC_PX;
-    return (size_t)B * npix * 3 * sizeof(int4) + (size_t)B * chunks * sizeof(uint2);
-}
+// The launch geometry is chosen in ONE place (fr_owner_scatter.h rows3_geom): the launcher and the test hook both read it there.
+size_t fr_render_normal_backward_workspace_impl(int B, int H, int W) { return fr::rows3_workspace_bytes(B, H, W); }
 
 // test hook (tests/test_normal_backward_*.py): out = {owners per face, vertices per owner, shift, 1,024-pixel record chunks,
 // LDS bytes of an owner, XCD-map flag}; all zero for a shape that launches no kernel or is refused
@@ -203,7 +137,7 @@ extern "C" void fr_debug_render_normal_bwd_geom(int B, int nver, int H, int W, i
     for (int i = 0; i < 6; i++) out[i] = 0;
     const long long npix = (long long)H * W;
     if (B <= 0 || nver <= 0 || H <= 0 || W <= 0 || npix > 0x7FFFFFFFll) return;
-    fr::owner_geom_report(nbwd_geom(B, nver, npix), B, out);
+    fr::owner_geom_report(fr::rows3_geom(B, nver, npix), B, out);
 }
 
 int fr_launch_render_normal_backward(const float* normal_grad, int grad_stride, const float* vertex, int vertex_pitch,
@@ -213,7 +147,7 @@ int fr_launch_render_normal_backward(const float* normal_grad, int grad_stride, 
     const long long npix = (long long)H * W;
     if (npix == 0 || ntri == 0) return owner_no_terms(vertex_grad, (size_t)B * 3 * nver * sizeof(float), accumulate, stream);
     if (npix > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
-    const OwnerGeom geo = nbwd_geom(B, nver, npix);
+    const OwnerGeom geo = fr::rows3_geom(B, nver, npix);
     if ((long long)B * geo.splits > 0x7FFFFFFFll || (long long)B * geo.chunks > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
     NbwdArgs a;
     a.ngrad = normal_grad; a.gstride = grad_stride; a.vertex = vertex; a.vpitch = vertex_pitch;

@@ -116,9 +116,11 @@ class CoarseNet(nn.Module):
     (FaceRecNet.vertices_transform / decode_rendering_layer, pose_grad); the default gives them 0, as the reference does.
     normal_grad=True lets the three normal channels of every iteration's input carry their gradient back to x, y and z of the
     vertices (FaceRecNet.coarse_net_input, normal_grad; with fused_step the step is then the two-step route, whose render node
-    keeps the vertex tensor); the default leaves them constants to autograd, as the reference does."""
+    keeps the vertex tensor); the default leaves them constants to autograd, as the reference does.
+    depth_interp=True: depth() returns the interpolated depth image (FaceRecNet.coarse_net_input, depth_interp; the two-step
+    route).  The iterations read net_input alone, which the flag does not change by a bit, so they are not touched."""
 
-    def __init__(self, face_net, nIter=4, fused_step=False, pose_grad=False, normal_grad=False):
+    def __init__(self, face_net, nIter=4, fused_step=False, pose_grad=False, normal_grad=False, depth_interp=False):
         super().__init__()
         _warn_if_exposed()
         self.face_net = face_net        # nets.network.FaceRecNet (holds the 3DMM constants on the GPU)
@@ -127,6 +129,7 @@ class CoarseNet(nn.Module):
         self._pose_kw = {"pose_grad": True} if self.pose_grad else {}   # (the default call is the one every face net already takes)
         self.normal_grad = bool(normal_grad)
         self._normal_kw = {"normal_grad": True} if self.normal_grad else {}
+        self.depth_interp = bool(depth_interp)
         self.iters = nn.ModuleList([CoarseNetIter(face_net.ndim) for _ in range(nIter)])
 
     def forward(self, im_gray, pred_params=None):
@@ -148,6 +151,8 @@ class CoarseNet(nn.Module):
     def depth(self, im_gray, pred_params):
         """depth_rendering_layer (network.py:300-309) on the final parameters: coarse depth map [B,H,W,1]."""
         fn = self.face_net
+        if self.depth_interp:
+            return fn.decode_rendering_layer(pred_params, im_gray=im_gray, depth_interp=True, **self._pose_kw)[1]
         if self.fused_step:
             return fn.decode_rendering_layer(pred_params, im_gray=im_gray, **self._pose_kw)[1]
         v = fn.vertices_transform(pred_params, **self._pose_kw)
@@ -194,18 +199,25 @@ class FaceReconModel(nn.Module):
     (forward(..., with_vertices=True), the default).
     pose_grad=True: every decode of the module also returns the pose-angle gradients (default: 0, as in the reference).
     normal_grad=True: the CoarseNet iterations' normal channels carry gradients (CoarseNet, normal_grad; default: none).
+    depth_interp=True: 'coarse_depth_map' -- FineNet's input and the fidelity target -- is the interpolated depth image
+    (FaceRecNet.coarse_net_input, depth_interp: no facets, and a gradient to x, y and z of the vertices; with fused_step the
+    depth rendering layer is then the two-step route).  Default: the reference's flat depth.
     learn_tex=True: the albedo coefficients face_net.param_tex become an nn.Parameter of this module (an optimiser and DDP see
     it) and face_net.param_tex points at it; get_loss(sfs_tex_grad=True) gives it a gradient.  Default: a constant tensor, as the
     reference's frozen param_tex (network.py:447-448)."""
 
-    def __init__(self, face_net, nIter=4, fine=True, fused_step=False, pose_grad=False, normal_grad=False, learn_tex=False):
+    def __init__(self, face_net, nIter=4, fine=True, fused_step=False, pose_grad=False, normal_grad=False, learn_tex=False,
+                 depth_interp=False):
         super().__init__()
         self.face_net = face_net
         self.fused_step = bool(fused_step)
         self.pose_grad = bool(pose_grad)
         self._pose_kw = {"pose_grad": True} if self.pose_grad else {}
         self.normal_grad = bool(normal_grad)
-        self.coarse = CoarseNet(face_net, nIter=nIter, fused_step=fused_step, pose_grad=pose_grad, normal_grad=normal_grad)
+        self.depth_interp = bool(depth_interp)
+        self._depth_kw = {"depth_interp": True} if self.depth_interp else {}
+        self.coarse = CoarseNet(face_net, nIter=nIter, fused_step=fused_step, pose_grad=pose_grad, normal_grad=normal_grad,
+                                depth_interp=depth_interp)
         self.fine = FineNet() if fine else None
         self.learn_tex = bool(learn_tex)
         if self.learn_tex:
@@ -220,14 +232,14 @@ class FaceReconModel(nn.Module):
         params = self.coarse(im_gray)
         out = {"pred_params": params, "vertices_proj": None, "coarse_depth_map": None, "pred_depth_map": None}
         if with_depth or self.fine is not None:
-            if self.fused_step:
+            if self.fused_step and not self.depth_interp:
                 out["coarse_depth_map"] = fn.decode_rendering_layer(params, im_gray=im_gray, **self._pose_kw)[1]
                 if with_vertices:
                     out["vertices_proj"] = fn.vertices_transform(params, **self._pose_kw)
             else:
                 v = fn.vertices_transform(params, **self._pose_kw)    # depth_rendering_layer, network.py:300-309
                 out["vertices_proj"] = v
-                out["coarse_depth_map"] = fn.coarse_net_input(v, im_gray=im_gray)[1]
+                out["coarse_depth_map"] = fn.coarse_net_input(v, im_gray=im_gray, **self._depth_kw)[1]
             if self.fine is not None:
                 out["pred_depth_map"] = self.fine(im_gray, out["coarse_depth_map"])
         return out

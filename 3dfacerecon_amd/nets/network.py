@@ -460,10 +460,13 @@ class FaceRecNet:
         return (g * g).mean()
 
     # ---- rendering layer wrapper --------------------------------------------------------------------------
-    def rendering_layer(self, vertex_proj, triangles, colors, im_gray=None, normal_grad=False):
+    def rendering_layer(self, vertex_proj, triangles, colors, im_gray=None, normal_grad=False, depth_interp=False):
         """(network.py:174-201) -> pncc_batch, normalimg_batch, maskimg_batch, depthimg_batch.
         normal_grad=True: the op's `normal` output has a backward (rendering_layer/ops.py::render_depth), so normalimg_batch
-        carries its gradient to x, y and z of the vertices; the default leaves it a constant to autograd, as the reference."""
+        carries its gradient to x, y and z of the vertices; the default leaves it a constant to autograd, as the reference.
+        depth_interp=True: depthimg_batch is clamp_min of the interpolated plane (rendering_layer/ops.py::depth_interpolate over
+        this render's tri_ind: the winner's plane at the pixel, with an x, y, z backward); the coverage mask -- maskimg_batch --
+        keeps coming from the flat plane, bit for bit, as do the other two outputs.  Default: the reference's flat depth."""
         im_gray = self.im_gray if im_gray is None else im_gray
         ver = vertex_proj.float()
         tri = torch.as_tensor(triangles, dtype=torch.float32, device=ver.device)
@@ -473,7 +476,7 @@ class FaceRecNet:
             im_gray = torch.ones((B, self.im_size, self.im_size, 1), dtype=torch.float32, device=ver.device)
         image = im_gray.expand(-1, -1, -1, 3)
         kw = {"normal_grad": True} if normal_grad else {}
-        depth, tex_img, normal, _ = _ops().render_depth(ver=ver, tri=tri, texture=tex, image=image, **kw)
+        depth, tex_img, normal, tri_ind = _ops().render_depth(ver=ver, tri=tri, texture=tex, image=image, **kw)
         # 1. pncc result
         pncc_batch = torch.clamp(tex_img, 1e-6, 1.0)
         # 2. normal map: flip normals with negative z, normalise by magnitude
@@ -486,15 +489,19 @@ class FaceRecNet:
         mask = torch.clamp(depth, 1e-6, 1.0)
         maskimg_batch = mask * im_gray
         # 4. depth image
-        depthimg_batch = torch.clamp_min(depth, 1e-6)
+        # (tri_ind is an output of the render node, hence part of the graph: the winners are held fixed)
+        depthimg_batch = torch.clamp_min(_ops().depth_interpolate(ver, tri, tri_ind.detach()) if depth_interp else depth, 1e-6)
         return pncc_batch, normalimg_batch, maskimg_batch, depthimg_batch
 
-    def coarse_net_input(self, vertex_proj, triangles=None, colors=None, im_gray=None, normal_grad=False):
+    def coarse_net_input(self, vertex_proj, triangles=None, colors=None, im_gray=None, normal_grad=False, depth_interp=False):
         """The 7-channel CoarseNet input [maskimg | pncc | normal] (network.py:122) and the depth image, produced by
         the fused kernel pass (falls back to rendering_layer + concat for shapes it does not cover).
         normal_grad=True: channels 4-6 carry their gradient to x, y and z of the vertices (fr_render_normal_backward behind the
         depth backward; the render node keeps the vertex tensor, 41 MB at 64 faces of the full mesh).  Default: none, as the
-        reference -- the vertex gradient is z-only."""
+        reference -- the vertex gradient is z-only.
+        depth_interp=True: net_input is the default call's, bit for bit (the fused kernel's; its mask channel is the flat
+        plane's); depth_img is clamp_min(depth_interpolate(ver, tri, tri_ind), 1e-6) of the same render's winners, and its
+        gradient reaches x, y and z.  Default: the flat depth image."""
         im_gray = self.im_gray if im_gray is None else im_gray
         ver = vertex_proj.float()
         tri = self.tri if triangles is None else torch.as_tensor(triangles, dtype=torch.float32, device=ver.device)
@@ -503,13 +510,17 @@ class FaceRecNet:
             im_gray = torch.ones((ver.shape[0], self.im_size, self.im_size, 1), dtype=torch.float32, device=ver.device)
         try:
             kw = {"normal_grad": True} if normal_grad else {}
-            net_in, depth_img, _, _ = _ops().rendering_layer_fused(ver, tri, tex, im_gray, **kw)
+            net_in, depth_img, _, tri_ind = _ops().rendering_layer_fused(ver, tri, tex, im_gray, **kw)
+            if depth_interp:
+                depth_img = torch.clamp_min(_ops().depth_interpolate(ver, tri, tri_ind), 1e-6)
         except NotImplementedError:
+            if depth_interp:
+                kw["depth_interp"] = True
             pncc, normal, mask, depth_img = self.rendering_layer(ver, tri, tex, im_gray=im_gray, **kw)
             net_in = torch.cat([mask, pncc, normal], dim=3)
         return net_in, depth_img
 
-    def decode_rendering_layer(self, pred_params, im_gray=None, R=None, pose_grad=False, normal_grad=False):
+    def decode_rendering_layer(self, pred_params, im_gray=None, R=None, pose_grad=False, normal_grad=False, depth_interp=False):
         """vertices_transform -> coarse_net_input in one call and ONE autograd node: (B,1,1,d) or (B,d) parameters ->
         (net_input [B,H,W,7], depth_img [B,H,W,1]), the same bits as the two-step route.  Forward
         fr_decode_rendering_layer_forward, backward fr_decode_render_backward (rendering_layer/ops.py::_DecodeRenderingLayer):
@@ -522,7 +533,10 @@ class FaceRecNet:
         two-step route takes the flag through vertices_transform.
         normal_grad=True: the call IS the two-step route -- vertices_transform, then coarse_net_input(normal_grad=True).  The
         one-call backward does not apply: it is z-only by construction (only the z plane of the vertex gradient ever exists in
-        it), and the normal gradient fills x, y and z."""
+        it), and the normal gradient fills x, y and z.
+        depth_interp=True: likewise the two-step route -- vertices_transform, then coarse_net_input(depth_interp=True) -- and for
+        the same reason: the interpolated depth's gradient fills x, y and z.  With pose_grad=True that is what turns the head
+        from a depth loss."""
         h = _host()
         p = pred_params
         if p.dim() == 4:
@@ -539,8 +553,11 @@ class FaceRecNet:
             Rc = h.require_gpu_f32(torch.as_tensor(R, dtype=torch.float32, device=p.device), "R")
             if tuple(Rc.shape) != (B, 3, 3):
                 raise ValueError("R must be (B,3,3)")
-        if normal_grad:
-            return self.coarse_net_input(self.vertices_transform(p, R=Rc, pose_grad=pose_grad), im_gray=im_gray, normal_grad=True)
+        if normal_grad or depth_interp:
+            kw = {"normal_grad": True} if normal_grad else {}
+            if depth_interp:
+                kw["depth_interp"] = True
+            return self.coarse_net_input(self.vertices_transform(p, R=Rc, pose_grad=pose_grad), im_gray=im_gray, **kw)
         if self._basis.backward_packed_ok() and not self._basis.use_q30():
             try:
                 return _ops().decode_rendering_layer(p, Rc, im_gray, self.tri, self.vertex_code, self._basis, self.im_size,

@@ -7,7 +7,7 @@ Same names and argument meaning as the reference module (rendering_layer/ops.py:
     render_depth(ver, tri, texture, image, **kwargs)
                                    -> (depth [B,H,W,1], texture_image [B,H,W,3], normal [B,H,W,3], tri_ind [B,H,W,1])
     gradient                       flows to `ver` only (d depth / d vertex z); tri, texture, image get None
-                                   (opt-in: normal_grad=True, texture_grad=True -- see render_depth)
+                                   (opt-in: normal_grad=True, texture_grad=True, depth_interp=True -- see render_depth)
 
 Tensors are torch.Tensors on an MI355X instead of tf.Tensors; the op is a torch.autograd.Function calling the
 C ABI of include/fr_hotpath.h through ctypes on torch's current HIP stream.  Like the reference, importing the
@@ -201,6 +201,29 @@ def _texture_backward_call(h, g, g_offset, g_stride, tri_c, tri_ind, texture_gra
     h.check(rc, "fr_render_texture_backward")
 
 
+def _depth_interp_forward_call(h, ver_c, tri_c, tri_ind, B, nver, ntri, H, W, dev):
+    """fr_depth_interp_forward on the dense vertex tensor -> the interpolated plane [B,H,W,1]."""
+    depth = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev)
+    rc = h.lib().fr_depth_interp_forward(h.ptr(ver_c), nver, h.ptr(tri_c), h.ptr(tri_ind), B, nver, ntri, H, W, h.ptr(depth),
+                                         h.stream_ptr(dev))
+    h.check(rc, "fr_depth_interp_forward")
+    return depth
+
+
+def _depth_interp_backward_call(h, g, ver_c, tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, accumulate, dev):
+    """fr_depth_interp_backward with its workspace (48 bytes per pixel): all three rows of vertex_grad."""
+    if B * H * W == 0:   # the entry point writes nothing for an empty image
+        if not accumulate:
+            vertex_grad.zero_()
+        return
+    L = h.lib()
+    nws = L.fr_depth_interp_backward_workspace_bytes(B, nver, H, W)
+    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
+    rc = L.fr_depth_interp_backward(h.ptr(g), h.ptr(ver_c), nver, h.ptr(tri_c), h.ptr(tri_ind), h.ptr(vertex_grad), B, nver, ntri,
+                                    H, W, accumulate, h.ptr(ws), nws, h.stream_ptr(dev))
+    h.check(rc, "fr_depth_interp_backward")
+
+
 def _texture_grad_of(ctx, texture_image_grad):
     """The `texture` gradient of a render_depth node built with texture_grad=True, in the input's own shape ([3,N], [1,3,N] or
     [B,3,N]); None -- and no launch -- when nothing downstream used tex_img or the texture needs no gradient."""
@@ -224,10 +247,12 @@ class _RenderDepth(torch.autograd.Function):
     normal_grad: the node also keeps `ver` ([B,3,nver] fp32: 41 MB at 64 faces of the full mesh) and, where a gradient of `normal`
     arrives, its backward runs fr_render_normal_backward (raw mode) behind the depth backward: all three rows of the vertex
     gradient are filled.  texture_grad: the same saved tensors (the texture's shape is all the node adds); a gradient arriving at
-    `tex_img` reaches `texture` through fr_render_texture_backward."""
+    `tex_img` reaches `texture` through fr_render_texture_backward.  depth_interp: the first output is the interpolated plane
+    (fr_depth_interp_forward over this call's tri_ind; the flat plane is not returned), the node keeps `ver`, and a gradient of
+    `depth` runs fr_depth_interp_backward in place of the flat backward."""
 
     @staticmethod
-    def forward(ctx, ver, tri, texture, image, normal_grad, texture_grad):
+    def forward(ctx, ver, tri, texture, image, normal_grad, texture_grad, depth_interp):
         h = _host()
         _check_forward_shapes(ver, tri, texture, image)
         ver_c = h.require_gpu_f32(ver, "ver")
@@ -259,13 +284,16 @@ class _RenderDepth(torch.autograd.Function):
                                                h.ptr(depth), h.ptr(tex_img), h.ptr(normal), h.ptr(tri_ind), None, 0,
                                                h.stream_ptr(dev))
         h.check(rc, "fr_render_depth_forward")
-        if normal_grad:
+        if depth_interp:
+            with torch.cuda.device(dev):
+                depth = _depth_interp_forward_call(h, ver_c, tri_c, tri_ind, B, nver, ntri, H, W, dev)
+        if normal_grad or depth_interp:
             ctx.save_for_backward(tri_c, tri_ind, ver_c)
         else:
             ctx.save_for_backward(tri_c, tri_ind)
         if texture_grad:
             ctx.tex_shape = tuple(texture.shape)
-        ctx.normal_grad, ctx.texture_grad = bool(normal_grad), bool(texture_grad)
+        ctx.normal_grad, ctx.texture_grad, ctx.depth_interp = bool(normal_grad), bool(texture_grad), bool(depth_interp)
         ctx.dims = (B, nver, ntri, H, W)
         ctx.set_materialize_grads(False)  # an unused depth output (the SfS renders, network.py:423, 454) costs no backward
         return depth, tex_img, normal, tri_ind
@@ -283,14 +311,17 @@ class _RenderDepth(torch.autograd.Function):
         if depth_grad is not None or normal_grad is not None:
             vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
-                if depth_grad is not None:
+                if depth_grad is not None and ctx.depth_interp:
+                    _depth_interp_backward_call(h, h.require_gpu_f32(depth_grad, "depth_grad"), ctx.saved_tensors[2], tri_c, tri_ind,
+                                                vertex_grad, B, nver, ntri, H, W, 0, dev)
+                elif depth_grad is not None:
                     _backward_call(h, h.require_gpu_f32(depth_grad, "depth_grad"), tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W,
                                    dev)
                 if normal_grad is not None:
                     _normal_backward_call(h, h.require_gpu_f32(normal_grad, "normal_grad"), 0, 3, ctx.saved_tensors[2], tri_c,
                                           tri_ind, vertex_grad, B, nver, ntri, H, W, 0, 1 if depth_grad is not None else 0, dev)
         texture_grad = _texture_grad_of(ctx, texture_image_grad) if ctx.texture_grad else None
-        return vertex_grad, None, texture_grad, None, None, None
+        return vertex_grad, None, texture_grad, None, None, None, None
 
 
 class _RenderingLayerFused(torch.autograd.Function):
@@ -764,6 +795,59 @@ def depth_normals(depth, mask=None):
     return _DepthNormals.apply(depth, mask)
 
 
+class _DepthInterpolate(torch.autograd.Function):
+    """fr_depth_interp_forward / _backward (include/fr_hotpath.h, "interpolated depth") as one autograd node."""
+
+    @staticmethod
+    def forward(ctx, ver, tri, tri_ind):
+        h = _host()
+        if isinstance(tri_ind, torch.Tensor) and tri_ind.requires_grad:
+            raise ValueError("depth_interpolate: tri_ind requires grad, but the winning triangles are held fixed (detach it)")
+        ver_c = h.require_gpu_f32(ver, "ver")
+        tri_c = h.require_gpu_f32(tri, "tri")
+        ti_c = h.require_gpu_f32(tri_ind, "tri_ind")
+        if ver_c.dim() != 3 or ver_c.shape[1] != 3:
+            raise ValueError("The vertex is not Batch x 3 x nver")
+        if tri_c.dim() != 2 or tri_c.shape[0] != 3:
+            raise ValueError("The tri is not 3 x ntri")
+        if ti_c.dim() != 4 or ti_c.shape[0] != ver_c.shape[0] or ti_c.shape[3] != 1:
+            raise ValueError("depth_interpolate expects tri_ind [B,H,W,1] with the vertex's batch (got %s)" % (tuple(ti_c.shape),))
+        if tri_c.device != ver_c.device or ti_c.device != ver_c.device:
+            raise ValueError("depth_interpolate: ver, tri and tri_ind must be on one device")
+        B, H, W = int(ti_c.shape[0]), int(ti_c.shape[1]), int(ti_c.shape[2])
+        nver, ntri = int(ver_c.shape[2]), int(tri_c.shape[1])
+        dev = ver_c.device
+        with torch.cuda.device(dev):
+            depth = _depth_interp_forward_call(h, ver_c, tri_c, ti_c, B, nver, ntri, H, W, dev)
+        ctx.save_for_backward(ver_c, tri_c, ti_c)
+        ctx.dims = (B, nver, ntri, H, W)
+        return depth
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        h = _host()
+        ver_c, tri_c, ti_c = ctx.saved_tensors
+        B, nver, ntri, H, W = ctx.dims
+        dev = ver_c.device
+        vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _depth_interp_backward_call(h, h.require_gpu_f32(g, "depth_grad"), ver_c, tri_c, ti_c, vertex_grad, B, nver, ntri, H, W,
+                                        0, dev)
+        return vertex_grad, None, None
+
+
+def depth_interpolate(ver, tri, tri_ind):
+    """The interpolated depth [B,H,W,1] of a render's winners: per pixel whose tri_ind ([B,H,W,1], e.g. render_depth's fourth
+    output) names a triangle of `tri` [3,ntri], the z of that triangle's plane at the pixel by the barycentric weights of
+    get_point_weight (fr_depth_interp_forward: float64, one gather pass); the op's background elsewhere, the flat centroid depth
+    for a triangle without area.  Which triangle wins is not re-decided.  The gradient goes to `ver` [B,3,nver] only, to all three
+    rows: moving a vertex sideways slides the plane under the pixel (fr_depth_interp_backward: bit-reproducible); a tri_ind that
+    requires grad is refused.  The node saves `ver`, `tri` and `tri_ind`."""
+    return _DepthInterpolate.apply(ver, tri, tri_ind)
+
+
 _LAPLACE_K = ((0.5, 1.0, 0.5), (1.0, -6.0, 1.0), (0.5, 1.0, 0.5))  # network.py:383-385
 _FL_LOCK = threading.Lock()
 
@@ -856,7 +940,7 @@ def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     return _RenderingLayerFused.apply(ver, tri, texture, im_gray, bool(normal_grad))
 
 
-def render_depth(ver, tri, texture, image, normal_grad=False, texture_grad=False, **kwargs):
+def render_depth(ver, tri, texture, image, normal_grad=False, texture_grad=False, depth_interp=False, **kwargs):
     """Forward function of RenderDepth (reference ops.py:78-81).
 
     The first output is the rendered depth, the fourth the triangle index each depth pixel corresponds to.
@@ -870,8 +954,14 @@ def render_depth(ver, tri, texture, image, normal_grad=False, texture_grad=False
     second output, `tex_img`, reaches `texture` in the input's own shape ([3,N], [1,3,N] or [B,3,N]) -- the adjoint of the
     lookup (t[p1] + t[p2] + t[p3]) / 3 (fr_render_texture_backward; tri_ind held fixed).  Same outputs, bit for bit; the node
     saves no tensor beyond what it keeps anyway, and no backward is launched for an output nobody used.  Combines with normal_grad.
+    depth_interp=False (default): `depth` is the reference's flat value, (z1 + z2 + z3) / 3 at every pixel a triangle wins.
+    depth_interp=True: the first output is depth_interpolate(ver, tri, tri_ind) of this render -- the winner's plane at the pixel;
+    the other three outputs are the default call's, bit for bit (the winner is still chosen on the flat value, so a pixel's z may
+    exceed a neighbour's winner by less than its triangle's z range).  A gradient of `depth` then fills x, y and z
+    (fr_depth_interp_backward; the flat backward is not launched) and the node keeps the vertex tensor, as with normal_grad.
+    Combines with normal_grad (the normal backward follows with accumulate) and texture_grad.
     """
-    return _RenderDepth.apply(ver, tri, texture, image, bool(normal_grad), bool(texture_grad))
+    return _RenderDepth.apply(ver, tri, texture, image, bool(normal_grad), bool(texture_grad), bool(depth_interp))
 
 
 def render_depth_grad(depth_grad, ver, tri, depth, tri_ind, image):

@@ -53,7 +53,8 @@ def build_harness(args, dev, rank, world, local):
     # the reference's graph always holds FineNet (build(), network.py:69-101); the forward-only config 3 is CoarseNet + render
     model = cn.FaceReconModel(face, nIter=args.nIter, fine=args.fine or args.train, fused_step=args.fused_step,
                               pose_grad=args.pose_grad, normal_grad=args.normal_grad,
-                              **({"learn_tex": True} if args.sfs_tex_grad else {})).to(dev)
+                              **({"learn_tex": True} if args.sfs_tex_grad else {}),
+                              **({"depth_interp": True} if args.depth_interp else {})).to(dev)
     net = model
     if args.train and world > 1:
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local] if dev.type == "cuda" else None)
@@ -216,6 +217,10 @@ def build_parser():
     ap.add_argument("--normal-grad", action="store_true",
                     help="let the normal channels of every CoarseNet input carry their gradient to x, y and z of the vertices "
                          "(fr_render_normal_backward); off: they are constants to autograd, as in the reference")
+    ap.add_argument("--depth-interp", action="store_true",
+                    help="the coarse depth map (FineNet's input, the fidelity target) is the winners' interpolated depth, with a "
+                         "gradient to x, y and z of the vertices (fr_depth_interp_forward / _backward); off: the reference's flat "
+                         "per-triangle depth")
     ap.add_argument("--gather-sfs", action="store_true", help="whole-batch SfS lighting estimate across ranks")
     ap.add_argument("--sfs-grad", action="store_true",
                     help="let the shape-from-shading term reach the geometry: its two renders carry the normal map's gradient to "

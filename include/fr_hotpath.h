@@ -837,6 +837,78 @@ int fr_fine_losses_backward(const float* grad_fidelity, const float* grad_smooth
  * for the sums' association and by the tests to place their shapes on the tile's edges. */
 void fr_debug_fine_losses_geom(int B, int H, int W, int* out);
 
+/* ---- interpolated depth: barycentric z with an x, y, z backward (opt-in) --------------------------------------------------------------
+ * Every `depth` plane of the render forward is flat per triangle, h = fl32((z1 + z2) + z3) / 3.0f: the reference's definition, which
+ * has no x or y derivative.  The reference also carries get_point_weight (render_depth_op.cc:29-74: the barycentric weights
+ * (1 - u - v, v, u) of a point), which nothing calls.  These entry points are a post-pass over a forward's tri_ind that evaluates the
+ * winning triangle's PLANE at the pixel, and its gradient with respect to all three coordinates of the triangle's vertices.  Which
+ * triangle wins a pixel is not theirs to say: it stays the forward's rule on the flat h, so a pixel's interpolated z may exceed a
+ * neighbouring pixel's winner by less than its triangle's z range.  tri_ind, tex_img and normal are not touched.
+ *   vertex [B,3,vertex_pitch] (vertex_pitch >= nver: nver for the dense tensor, fr_decode_render_vertex_pitch(N) for the hand-off);
+ *   tri [3,ntri], float-stored ids;  tri_ind, depth, depth_grad dense [B,H,W,1];  vertex_grad dense [B,3,nver].
+ * NAMES.  The stream parameter is called `stream`, as in the Gram-form geometry loss above and for its reason;
+ * tests/test_depth_interp_cpu.py holds these entry points' return codes.
+ * WHICH PIXEL.  Pixel (row j, column i) of face b is OK exactly as in the render backwards: tri_ind names t in [0, ntri) and all three
+ * ids (p1, p2, p3) of t lie in [0, nver).  NaN, -1, a value >= ntri or a bad id is not OK.  P_k = vertex[b][.][p_k].
+ * FORWARD.  Float64 on the widened fp32 inputs, every product and every sum rounded on its own, in get_point_weight's source order
+ * (no contraction); x and y only in the first three lines:
+ *   v0 = P3 - P1,  v1 = P2 - P1,  v2 = (i, j) - P1
+ *   dot00 = v0x v0x + v0y v0y   dot01 = v0x v1x + v0y v1y   dot02 = v0x v2x + v0y v2y
+ *   dot11 = v1x v1x + v1y v1y   dot12 = v1x v2x + v1y v2y
+ *   den = dot00 dot11 - dot01 dot01
+ *   den != 0:  inv = 1 / den
+ *              u = (dot11 dot02 - dot01 dot12) inv      v = (dot00 dot12 - dot01 dot02) inv
+ *              w1 = (1 - u) - v,  w2 = v,  w3 = u
+ *              depth = fl32((w1 z1 + w2 z2) + w3 z3)
+ *   den == 0:  depth = the op's own h, formed in fp32 as the forward forms it: fl32(fl32(fl32(z1 + z2) + z3) / 3.0f)
+ *   not OK:    depth = the op's background, fl32(-99999999999999.0)
+ * (tests/ref_depth_interp.py is this in numpy.)  A pixel outside its triangle (a hand-made tri_ind) is extrapolated by the same lines.
+ * BACKWARD.  tri_ind is held fixed and the forward's fp32 rounding is treated as the identity.  G = (double)depth_grad.  For an OK
+ * pixel with den != 0, with the forward's values:
+ *   gu = ((dot11 v0x - dot01 v1x) inv, (dot11 v0y - dot01 v1y) inv)
+ *   gv = ((dot00 v1x - dot01 v0x) inv, (dot00 v1y - dot01 v0y) inv)
+ *   A  = ((z2 - z1) gvx + (z3 - z1) gux,  (z2 - z1) gvy + (z3 - z1) guy)          the plane's screen-space slope
+ *   for k = 1, 2, 3:   c = G w_k      term_z(p_k) = fl32(c)      term_x(p_k) = fl32(-(c Ax))      term_y(p_k) = fl32(-(c Ay))
+ * (d depth / d P_k = -w_k A in x and y: moving a vertex sideways slides the plane under the pixel.)  For an OK pixel with den == 0
+ * the z terms are the flat backward's fl32(fl32(g * 1.0f) / 3.0f) for each of the three vertices and the x, y terms are +0.
+ * Each (face, row, vertex) sum of terms is formed exactly as fr_render_normal_backward forms its own -- the same record planes, the
+ * same owner workgroups (csrc/fr_owner_scatter.h): the terms as 64-bit fixed-point integers on a grid of 2^(e - 39 + shift),
+ * e = floor(log2 M), M the face's largest finite |term| over all three rows, shift as above 2^20 pixels; integer addition in LDS by
+ * per-face owner workgroups; one rounding to fp32.  No float atomics, bit-reproducible, independent of the launch geometry;
+ * |result - exact sum| <= 2^-24 |sum| + n 2^(shift - 39) M for n terms.  A face with a non-finite term takes fp32 LDS atomics: the
+ * vertices that receive such a term come out non-finite, the others finite.
+ *   accumulate 0: all three rows of every vertex are written (exactly +0 where no OK pixel names the vertex).  accumulate 1: each
+ *                 element becomes fl32(old + new), one add; fr_render_normal_backward(.., accumulate = 1) may follow on the same stream.
+ *   workspace:    fr_depth_interp_backward_workspace_bytes(B, nver, H, W) = B H W 48 + B ceil(H W / 1024) 8 bytes (0 for an empty
+ *                 shape), 16-byte aligned, caller-owned, per call in flight.  The forward needs none.
+ * Checks, all before any HIP call, in this order: (1) a negative size, accumulate outside {0, 1} or vertex_pitch < nver is
+ * FR_ERR_INVALID_ARG; (2) B == 0 or an empty image is FR_OK with nothing launched and nothing written (so is the backward with
+ * nver == 0); (3) a NULL tri_ind, depth or vertex_grad -- or, where triangles exist, a NULL tri, vertex or depth_grad -- is
+ * FR_ERR_INVALID_ARG; ntri >= 2^24 or more than 2^31 - 1 pixels per face is FR_ERR_UNSUPPORTED; (4) a workspace that is missing, too
+ * small or misaligned is FR_ERR_WORKSPACE.  With ntri == 0 the forward writes the background and the backward zeros (or, accumulate 1,
+ * nothing).  Nothing is allocated or synchronised; reentrant under the rules at the top of this file.
+ * Kernels (csrc/fr_depth_interp.hip): the forward is one gather pass, one lane per pixel: three id gathers and nine vertex gathers out
+ * of L2 (neighbouring lanes hold neighbouring triangles), about 40 fp64 operations, one store; no LDS, no atomics.  The backward is the
+ * normal backward's pair: a records pass that makes the same gathers once and writes nine terms per pixel, then the shared owner.
+ * Time: tools/depth_interp_probe.py (profiles/depth_interp.json) measures both at 64 and 32 faces of the full mesh at 200 x 200, beside
+ * fr_render_depth_backward_ws and fr_render_normal_backward (raw mode, dense stride) on the same inputs and a 512 MiB copy.  MI355X,
+ * medians of 6 rounds of 40 calls: forward 25.9 / 14.5 us, where it must move 59 / 29 MB = 11.8 / 5.9 us at the 4.98 TB/s that run's
+ * copy reached (0.46 / 0.40 of it); backward 75.4 / 42.6 us beside the normal backward's 76.7 / 43.3 us and the flat backward's
+ * 34.2 / 25.9 us, where it must move 100 / 50 MB = 20.0 / 10.0 us (0.27 / 0.23); the rest is the scheme's own records and the id plane
+ * that each of a face's 8 owners streams, as in the normal backward. */
+int fr_depth_interp_forward(const float* vertex, int vertex_pitch, const float* tri, const float* tri_ind, int B, int nver, int ntri,
+                            int H, int W, float* depth, void* stream);
+size_t fr_depth_interp_backward_workspace_bytes(int B, int nver, int H, int W);
+int fr_depth_interp_backward(const float* depth_grad, const float* vertex, int vertex_pitch, const float* tri, const float* tri_ind,
+                             float* vertex_grad, int B, int nver, int ntri, int H, int W, int accumulate, void* workspace,
+                             size_t ws_bytes, void* stream);
+
+/* The interpolated-depth backward's launch geometry (no GPU needed; the launcher reads the same function): out[6] as
+ * fr_debug_render_normal_bwd_geom -- {owner workgroups per face, vertices per owner (three 64-bit accumulators each), shift,
+ * 1,024-pixel record chunks, dynamic LDS bytes of an owner workgroup, 1 if a face's owners are kept on one XCD (batch a multiple of 8)
+ * else 0}; all zero for a shape that launches no kernel.  Used by tests/test_depth_interp_cpu.py and tests/test_depth_interp_gpu.py. */
+void fr_debug_depth_interp_bwd_geom(int B, int nver, int H, int W, int* out);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
