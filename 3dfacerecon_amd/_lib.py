@@ -16,7 +16,8 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG_DIR, "csrc")
 LIB_PATH = os.path.join(_PKG_DIR, "libfr_hotpath.so")
 SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_bwd.hip", "fr_render_nbwd.hip",
-           "fr_render_tbwd.hip", "fr_sfs.hip", "fr_depth_normals.hip", "fr_geometry.hip", "fr_fine_losses.hip", "fr_depth_interp.hip"]
+           "fr_render_tbwd.hip", "fr_sfs.hip", "fr_depth_normals.hip", "fr_geometry.hip", "fr_fine_losses.hip", "fr_depth_interp.hip",
+           "fr_albedo_lse.hip"]
 HEADERS = [os.path.join(_CSRC, "fr_common.h"), os.path.join(_CSRC, "fr_decode_shared.h"), os.path.join(_CSRC, "fr_sfs_pinv.h"),
            os.path.join(_CSRC, "fr_owner_scatter.h"), os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -190,6 +191,12 @@ SIGNATURES = {
     "fr_depth_interp_backward_workspace_bytes":       "z:iiii",
     "fr_depth_interp_backward":                       "i:ppipppiiiiiipzp",
     "fr_debug_depth_interp_bwd_geom":                 "v:iiiiI",
+    "fr_albedo_basis_bytes":                          "z:ii",
+    "fr_albedo_basis_build":                          "i:ppiiipzp",
+    "fr_sfs_lighting":                                "i:piiidpzp",
+    "fr_albedo_lse_workspace_bytes":                  "z:iiii",
+    "fr_albedo_lse_forward":                          "i:ppppppiiiiidppppzp",
+    "fr_debug_albedo_lse_geom":                       "v:iiiiI",
     "fr_debug_render_geom":                           "v:iiiiiI",
     "fr_debug_decode_bwd_geom":                       "v:iiiiI",
     "fr_debug_decode_geom":                           "i:iiiiiI",

@@ -312,6 +312,20 @@ __global__ __launch_bounds__(SFS_PX* FR_SFS_SLICES_MAX) void sfs_backward_apply_
     sfs_write_grads(a, b0, b1, p, sx, sy, sz);
 }
 
+// the solve half of sfs_solve_shade_kernel without the shade (opt-in; "per-face albedo fit": the fit needs l before abedo_new exists):
+// one wave per 64 pixels adds the parts, solves and writes the state -- the same device functions, hence the same bits
+__global__ __launch_bounds__(SFS_PX) void sfs_lighting_kernel(SfsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sfs_lds[];   // [3][64] l (written by sfs_solve_pixel, not read here)
+    const int lane = threadIdx.x & 63;
+    const size_t p = (size_t)blockIdx.x * SFS_PX + lane;
+    const bool active = p < (size_t)a.npix;
+    double m[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) m[k] = 0.0;
+    if (active) sfs_sum_parts<9>(a, p, m);
+    sfs_solve_pixel(a, m, p, active, sfs_lds, lane);
+}
+
 }  // namespace fr
 
 // The launch geometry, chosen in ONE place: the launchers and the test hook both read it from here.
@@ -483,6 +497,16 @@ int fr_sfs_backward_apply(const float* grad_intensity, const float* abedo, const
                             ws_ok(state, state_bytes, fr_sfs_state_bytes(H, W), 16));
     return sfs_launch(fr::sfs_backward_apply_kernel, nullptr, a, B, H, W, nparts >= 1 && nparts <= SFS_PARTS_MAX,
                       sfs_shape_empty(B, H, W), own, hip_stream);
+}
+
+// the lighting alone: B = 1 stands for "one wave per workgroup" in the shared launcher (the kernel reads no face)
+int fr_sfs_lighting(const void* moment_parts, int nparts, int H, int W, double rcond, void* state, size_t state_bytes, void* stream) {
+    fr::SfsArgs a{};
+    a.parts_in = reinterpret_cast<const double*>(moment_parts); a.nparts = nparts;
+    a.state = reinterpret_cast<double*>(state); a.rcond = rcond;
+    const int own = sfs_own(moment_parts != nullptr, ws_ok(state, state_bytes, fr_sfs_state_bytes(H, W), 16));
+    return sfs_launch(fr::sfs_lighting_kernel, &SfsGeom::lds_solve, a, 1, H, W,
+                      sfs_rcond_ok(rcond) && nparts >= 1 && nparts <= SFS_PARTS_MAX, H == 0 || W == 0, own, stream);
 }
 
 }  // extern "C"

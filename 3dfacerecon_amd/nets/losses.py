@@ -125,7 +125,7 @@ def spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_image_
 
 
 def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False, normal_grad=False, fused=False, rcond=1e-15,
-                                  tex_grad=False, fused_gather=False, fine_depth=None):
+                                  tex_grad=False, fused_gather=False, fine_depth=None, alpha_lse=False, alpha_ridge=1e-6):
     """Recovered intensity (B,H,W,1) of the first-order spherical-harmonics shading model (network.py:420-462): two
     more render_depth calls (mean albedo, then mean + pc_tex . param_tex) feed spherical_harmonics_intensity.
     normal_grad=False (default): as the reference, both renders hand autograd constant normal maps, so the term has no gradient
@@ -140,13 +140,32 @@ def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False
     grid -- depth_normals(fine_depth, mask = tri_ind of the second render) -- instead of the second render's normal map, which is
     the coarse mesh's a second time (the reference's own complaint, network.py:451-453); the term then constrains the fine depth
     and its gradient reaches fine_depth.  The lighting still comes from the first render and abedo_new from the second.  Works with
-    every flag above (the gradient of the shaded normals is local to the rank)."""
+    every flag above (the gradient of the shaded normals is local to the rank).
+    alpha_lse=True (default off; alpha_ridge: its ridge, relative to the mean diagonal of a face's Gram matrix): texture_new is no
+    longer mean + pc_tex . param_tex, one albedo for every face, but PER FACE mean + pc_tex . alpha_b with alpha_b the least-squares
+    fit of that face's own SfS residual given the lighting -- the estimate the reference wanted and gave up (network.py:436-455).
+    The first render also returns its tri_ind, the map from pixels to rows of the texture basis; the shaded normals are chosen
+    (the render's own, or depth_normals(fine_depth, mask = that tri_ind)); sfs_lighting gives l; albedo_lse fits alpha_b
+    (rendering_layer/ops.py); the second render and spherical_harmonics_intensity then run as above.  alpha_b is a fitted
+    quantity held constant in the backward, like the lighting's pseudo-inverse.  Works with fused, rcond, normal_grad and
+    fine_depth; each rank fits its own faces (no collective).  ValueError unless fused (the lighting must be the fused solve's),
+    with tex_grad (param_tex is no longer what the term uses), and with gather or fused_gather (the whole-batch lighting across
+    ranks is not served)."""
     fn = face_net
     if fused_gather and not (gather and fused):
         raise ValueError("fused_gather=True needs gather=True and fused=True")
+    if alpha_lse:
+        if not fused:
+            raise ValueError("alpha_lse=True needs fused=True (the fit uses the fused solve's lighting)")
+        if tex_grad:
+            raise ValueError("alpha_lse=True excludes tex_grad=True (param_tex is no longer what the term uses)")
+        if gather or fused_gather:
+            raise ValueError("alpha_lse=True excludes gather / fused_gather (the whole-batch lighting across ranks is not served)")
     if fn.mu_tex is None or fn.pc_tex is None or fn.param_tex is None:
         raise ValueError("the asset dict has no texture model (mu_tex / pc_tex / param_tex)")
     kw = {"normal_grad": True} if normal_grad else {}
+    if alpha_lse:
+        return _sfs_model_alpha_lse(fn, vertices_proj, im_gray, kw, normal_grad, rcond, fine_depth, alpha_ridge)
     abedo_image, normal_map = fn.compute_abedo_image(vertices_proj, fn.tri, fn.mu_tex, **kw)   # (B,H,W,1), (B,H,W,3)
     texture_new = fn.mu_tex + (fn.pc_tex @ fn.param_tex).reshape(3, -1)                    # network.py:446-448
     kw_new = dict(kw, texture_grad=True) if tex_grad else kw
@@ -170,6 +189,27 @@ def get_spherical_harmonics_model(face_net, vertices_proj, im_gray, gather=False
                                          rcond=rcond, **kw_tex)
 
 
+def _sfs_model_alpha_lse(fn, vertices_proj, im_gray, kw, normal_grad, rcond, fine_depth, ridge):
+    """get_spherical_harmonics_model(alpha_lse=True, fused=True): the steps of its docstring, in order"""
+    ops = _ops()
+    abedo_image, normal_map, tri_ind = fn.compute_abedo_image(vertices_proj, fn.tri, fn.mu_tex, with_tri_ind=True, **kw)
+    tri_ind = tri_ind.detach()
+    shaded = normal_map if fine_depth is None else ops.depth_normals(fine_depth, mask=tri_ind)
+    lighting = ops.sfs_lighting(abedo_image, normal_map, im_gray, rcond=rcond)
+    alpha, _ = ops.albedo_lse(fn.albedo_basis(), tri_ind, lighting, shaded, abedo_image, im_gray, ridge=ridge)
+    texture_new = fn.mu_tex[None] + (alpha @ fn.pc_tex.t()).reshape(alpha.shape[0], 3, -1)     # [B,3,N]: one albedo per face
+    if fine_depth is None:
+        abedo_new, normal_new = fn.compute_abedo_image(vertices_proj, fn.tri, texture_new, **kw)
+    else:
+        abedo_new, _, tri_ind_new = fn.compute_abedo_image(vertices_proj, fn.tri, texture_new, with_tri_ind=True, **kw)
+        normal_new = ops.depth_normals(fine_depth, mask=tri_ind_new.detach())
+    if not normal_grad:
+        normal_map = normal_map.detach()
+        if fine_depth is None:
+            normal_new = normal_new.detach()
+    return spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_new, normal_new, fused=True, rcond=rcond)
+
+
 def combine_losses(losses):
     """total = 1e-3 pose + 1e-6 geometry + 1e-3 SfS + 100 fidelity + 1e-5 smoothness (network.py:27-31, 373)"""
     return (LAMBDA_POSE * losses['pose_loss'] + LAMBDA_GEO * losses['geometry_loss'] +
@@ -179,7 +219,8 @@ def combine_losses(losses):
 
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
              gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False,
-             sfs_fused_gather=False, sfs_fine=False, fine_fused=False, geometry_gram=False):
+             sfs_fused_gather=False, sfs_fine=False, fine_fused=False, sfs_alpha_lse=False, sfs_alpha_ridge=1e-6,
+             geometry_gram=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
     sfs_normal_grad / sfs_fused / sfs_rcond (defaults: off, off, the reference's 1e-15): the normal_grad / fused / rcond of
     get_spherical_harmonics_model.  With them off spherical_harmonics_loss is a reported scalar with no gradient, as in the
@@ -198,7 +239,10 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     fine_depth_losses, fr_fine_losses_forward / _backward): the same two quantities as float64 sums in a fixed association, one
     kernel pass and a finish launch forward, one gather pass backward -- no convolution, no plane-sized intermediate.  The gradient
     reaches pred_depth_map and, where it requires grad, coarse_depth_map, as on the default route; ValueError when pred_depth_map
-    is None.  Each rank sums over its own faces: no collective."""
+    is None.  Each rank sums over its own faces: no collective.
+    sfs_alpha_lse=True / sfs_alpha_ridge (default off, 1e-6): the alpha_lse / alpha_ridge of get_spherical_harmonics_model -- the
+    term's albedo is fitted per face instead of shared; needs sfs_fused, excludes sfs_tex_grad, gather_sfs and sfs_fused_gather
+    (ValueError)."""
     fn = face_net
     if fine_fused and pred_depth_map is None:
         raise ValueError("fine_fused=True needs pred_depth_map (the fine depth map the two terms are taken of)")
@@ -221,6 +265,8 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
         if pred_depth_map is None:
             raise ValueError("sfs_fine=True needs pred_depth_map (the fine depth map whose normals the term shades)")
         kw_tex["fine_depth"] = pred_depth_map
+    if sfs_alpha_lse:
+        kw_tex.update(alpha_lse=True, alpha_ridge=sfs_alpha_ridge)
     intensity_recover = get_spherical_harmonics_model(fn, vertices_proj, im_gray, gather=gather_sfs, normal_grad=sfs_normal_grad,
                                                       fused=sfs_fused, rcond=sfs_rcond, **kw_tex)
     losses['spherical_harmonics_loss'] = F.mse_loss(intensity_recover, im_gray)

@@ -337,6 +337,7 @@ class FaceRecNet:
         self._gram_state = {}    # free state buffers of the Gram-form loss by (device, stream, bytes): gram_state()
         self._gram_nst = {}      # fr_geometry_loss_state_bytes by batch
         self._gram_lock = threading.Lock()
+        self._albedo_basis = None   # the texture basis per triangle in float64 (fr_albedo_basis_build), built on first use
 
         # initial parameters (network.py:57-62)
         geo = torch.zeros((batch_size, self.ndim_shape + self.ndim_exp), **f32)
@@ -414,6 +415,19 @@ class FaceRecNet:
                 _publish(self.device)
                 self._gram = G
             return self._gram
+
+    def albedo_basis(self):
+        """Phi [T,ndim_tex] float64: pc_tex seen through the rasteriser's lookup, per triangle (rendering_layer/ops.py::
+        albedo_basis), built on first use and cached under the lock gram() uses: a caller that never asks for the per-face albedo
+        fit never holds it (8.5 MB at the full mesh).  ValueError without a texture model."""
+        with self._gram_lock:
+            if self._albedo_basis is None:
+                if self.pc_tex is None:
+                    raise ValueError("the asset dict has no texture model (mu_tex / pc_tex / param_tex)")
+                with torch.cuda.device(self.device):
+                    self._albedo_basis = _ops().albedo_basis(self.tri, self.pc_tex)
+                _publish(self.device)
+            return self._albedo_basis
 
     def gram_state(self, B, dev, stream):
         """(key, bytes, buffer): a state buffer of the Gram-form loss for B faces on `stream` (torch's current stream of `dev`, as

@@ -930,6 +930,111 @@ def fine_depth_losses(pred, coarse):
     return _FineDepthLosses.apply(pred, coarse)
 
 
+def albedo_basis(tri, pc_tex):
+    """Phi [T,K] float64: the texture basis `pc_tex` [3N,K] seen through the rasteriser's lookup for the triangles `tri` [3,T]
+    (float ids) -- Phi[t][k] = (1/9) sum over the three channels and the three vertices of pc_tex[c N + v_j(t), k]
+    (fr_albedo_basis_build: nine widened terms in a fixed order, bit-exact against numpy).  Built once per mesh
+    (FaceRecNet.albedo_basis caches it); 1 <= K <= 15.  Runs on the current stream."""
+    h = _host()
+    tri_c = h.require_gpu_f32(tri, "tri")
+    pc_c = h.require_gpu_f32(pc_tex, "pc_tex")
+    if tri_c.dim() != 2 or tri_c.shape[0] != 3:
+        raise ValueError("The tri is not 3 x ntri")
+    if pc_c.dim() != 2 or pc_c.shape[0] % 3 != 0:
+        raise ValueError("albedo_basis expects pc_tex [3N,K] (got %s)" % (tuple(pc_c.shape),))
+    if pc_c.device != tri_c.device:
+        raise ValueError("albedo_basis: pc_tex is on %s, tri on %s" % (pc_c.device, tri_c.device))
+    T, K, nver = int(tri_c.shape[1]), int(pc_c.shape[1]), int(pc_c.shape[0]) // 3
+    dev = tri_c.device
+    L = h.lib()
+    basis = torch.empty((T, K), dtype=torch.float64, device=dev)
+    nbytes = L.fr_albedo_basis_bytes(T, K)
+    with torch.cuda.device(dev):
+        rc = L.fr_albedo_basis_build(h.ptr(tri_c), h.ptr(pc_c), nver, T, K, h.ptr(basis), nbytes, h.stream_ptr(dev))
+    h.check(rc, "fr_albedo_basis_build")
+    return basis
+
+
+def sfs_lighting(abedo, normal, im_gray, rcond=1e-15):
+    """The per-pixel lighting l [3,H,W] float64 of the fused SfS solve, without the shading: fr_sfs_moments then fr_sfs_lighting,
+    planes 6-8 of the state -- the very bits sfs_intensity's forward holds for the same maps.  abedo, im_gray [B,H,W,1] and normal
+    [B,H,W,3] are constants here (the result does not require grad).  Runs on the current stream; the moments live in the
+    per-stream scratch, the state is the call's own (the result is a view of it)."""
+    h = _host()
+    a_c = h.require_gpu_f32(abedo.detach(), "abedo")
+    n_c = h.require_gpu_f32(normal.detach(), "normal")
+    i_c = h.require_gpu_f32(im_gray.detach(), "im_gray")
+    if n_c.dim() != 4 or n_c.shape[3] != 3:
+        raise ValueError("sfs_lighting expects normal [B,H,W,3]")
+    B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+    for t, name in ((a_c, "abedo"), (i_c, "im_gray")):
+        if tuple(t.shape) != (B, H, W, 1):
+            raise ValueError("sfs_lighting: %s must be [%d,%d,%d,1] (got %s)" % (name, B, H, W, tuple(t.shape)))
+        if t.device != n_c.device:
+            raise ValueError("sfs_lighting: %s is on %s, normal on %s" % (name, t.device, n_c.device))
+    dev = n_c.device
+    L = h.lib()
+    state = torch.empty((10, H, W), dtype=torch.float64, device=dev)
+    if H * W == 0:
+        return state[6:9]
+    nst, nmo = L.fr_sfs_state_bytes(H, W), L.fr_sfs_moments_bytes(H, W)
+    with torch.cuda.device(dev), _AL_LOCK:
+        mom = _scratch("sfs_lighting", dev, nmo)
+        rc = L.fr_sfs_moments(h.ptr(a_c), h.ptr(n_c), h.ptr(i_c), B, H, W, h.ptr(mom), nmo, h.stream_ptr(dev))
+        h.check(rc, "fr_sfs_moments")
+        rc = L.fr_sfs_lighting(h.ptr(mom), 1, H, W, float(rcond), h.ptr(state), nst, h.stream_ptr(dev))
+    h.check(rc, "fr_sfs_lighting")
+    return state[6:9]
+
+
+_AL_LOCK = threading.Lock()   # keeps the launches of one call together where host threads share a stream's scratch
+
+
+def albedo_lse(basis, tri_ind, lighting, normal_new, abedo, im_gray, ridge=1e-6):
+    """The per-face least-squares albedo coefficients (fr_albedo_lse_forward): per face b the alpha_b that minimises
+    sum_p (I - (a + Phi[tri_ind] . alpha) (l . n'))^2 + lambda |alpha|^2 over the pixels the face covers, lambda = ridge x the mean
+    diagonal of the face's Gram matrix.  basis [T,K] float64 (albedo_basis), tri_ind / abedo / im_gray [B,H,W,1], lighting [3,H,W]
+    float64 (sfs_lighting), normal_new [B,H,W,3].  -> (alpha [B,K] fp32, stats [B,4] float64 = {counted pixels, E0 = the residual
+    energy at alpha = 0, E1 = at the returned alpha, ok}); a face that cannot be fitted (no pixel, a pivot that vanishes, a
+    non-finite input) gets alpha = 0 and ok = 0.  alpha is a fitted quantity: neither output requires grad, every input is read as
+    a constant.  float64 sums in a fixed association (a function of H, W and K alone), bit-reproducible.  Runs on the current
+    stream with the per-stream scratch as its workspace."""
+    h = _host()
+    ti_c = h.require_gpu_f32(tri_ind.detach(), "tri_ind")
+    n_c = h.require_gpu_f32(normal_new.detach(), "normal_new")
+    a_c = h.require_gpu_f32(abedo.detach(), "abedo")
+    i_c = h.require_gpu_f32(im_gray.detach(), "im_gray")
+    if n_c.dim() != 4 or n_c.shape[3] != 3:
+        raise ValueError("albedo_lse expects normal_new [B,H,W,3]")
+    B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+    dev = n_c.device
+    for t, name in ((ti_c, "tri_ind"), (a_c, "abedo"), (i_c, "im_gray")):
+        if tuple(t.shape) != (B, H, W, 1):
+            raise ValueError("albedo_lse: %s must be [%d,%d,%d,1] (got %s)" % (name, B, H, W, tuple(t.shape)))
+    if not (isinstance(basis, torch.Tensor) and basis.dtype == torch.float64 and basis.dim() == 2):
+        raise ValueError("albedo_lse: basis must be a float64 tensor [T,K] (albedo_basis)")
+    if not (isinstance(lighting, torch.Tensor) and lighting.dtype == torch.float64 and tuple(lighting.shape) == (3, H, W)):
+        raise ValueError("albedo_lse: lighting must be a float64 tensor [3,%d,%d] (sfs_lighting)" % (H, W))
+    for t, name in ((ti_c, "tri_ind"), (a_c, "abedo"), (i_c, "im_gray"), (basis, "basis"), (lighting, "lighting")):
+        if t.device != dev:
+            raise ValueError("albedo_lse: %s is on %s, normal_new on %s" % (name, t.device, dev))
+    b_c, l_c = basis.detach().contiguous(), lighting.detach().contiguous()
+    T, K = int(b_c.shape[0]), int(b_c.shape[1])
+    L = h.lib()
+    make = torch.zeros if B * H * W == 0 else torch.empty   # (an empty shape launches nothing: alpha = 0, ok = 0)
+    alpha = make((B, K), dtype=torch.float32, device=dev)
+    moments = make((B, 16, 16), dtype=torch.float64, device=dev)   # (the C call's third output; not returned)
+    stats = make((B, 4), dtype=torch.float64, device=dev)
+    nws = L.fr_albedo_lse_workspace_bytes(B, H, W, K)
+    with torch.cuda.device(dev), _AL_LOCK:
+        ws = _scratch("albedo_lse", dev, nws)
+        rc = L.fr_albedo_lse_forward(h.ptr(b_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(n_c), h.ptr(a_c), h.ptr(i_c), B, T, H, W, K,
+                                     float(ridge), h.ptr(alpha), h.ptr(moments), h.ptr(stats), h.ptr(ws), ws.numel(),
+                                     h.stream_ptr(dev))
+    h.check(rc, "fr_albedo_lse_forward")
+    return alpha, stats
+
+
 def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     """One-pass rendering layer: returns (net_input [B,H,W,7] = [mask*im | pncc | normal],
     depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers.

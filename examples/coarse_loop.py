@@ -77,7 +77,8 @@ def build_harness(args, dev, rank, world, local):
                                     **({"sfs_fused_gather": True} if args.sfs_fused_gather else {}),
                                     **({"sfs_fine": True} if args.sfs_fine else {}),
                                     **({"geometry_gram": True} if args.geometry_gram else {}),
-                                    **({"fine_fused": True} if args.fine_fused else {}))
+                                    **({"fine_fused": True} if args.fine_fused else {}),
+                                    **({"sfs_alpha_lse": True, "sfs_alpha_ridge": args.sfs_alpha_ridge} if args.sfs_alpha_lse else {}))
 
     def step():
         if not args.train:
@@ -250,6 +251,12 @@ def build_parser():
                     help="the fidelity and the smoothness term of the fine depth map from one kernel pass per direction "
                          "(fine_depth_losses: fr_fine_losses_forward / _backward; get_loss(fine_fused=True)): float64 sums in a fixed "
                          "association, no convolution; needs --fine; off: mse_loss and a conv2d / abs / sum chain")
+    ap.add_argument("--sfs-alpha-lse", action="store_true",
+                    help="fit the SfS term's albedo coefficients PER FACE by least squares given the lighting (fr_albedo_lse_forward; "
+                         "get_loss(sfs_alpha_lse=True)) instead of the one shared param_tex -- the estimate the reference gave up; "
+                         "needs --sfs-fused, excludes --sfs-tex-grad, --gather-sfs and --sfs-fused-gather; off: as the reference")
+    ap.add_argument("--sfs-alpha-ridge", type=float, default=1e-6,
+                    help="ridge of the per-face albedo fit, relative to the mean diagonal of a face's Gram matrix")
     ap.add_argument("--sfs-rcond", type=float, default=1e-15,
                     help="eigenvalue cutoff of the SfS pseudo-inverse, relative to the largest.  With float64 sums a rank-deficient "
                          "pixel (fewer than three faces cover it, or their normals are parallel) has null eigenvalues near 1e-16 "

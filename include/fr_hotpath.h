@@ -909,6 +909,91 @@ int fr_depth_interp_backward(const float* depth_grad, const float* vertex, int v
  * else 0}; all zero for a shape that launches no kernel.  Used by tests/test_depth_interp_cpu.py and tests/test_depth_interp_gpu.py. */
 void fr_debug_depth_interp_bwd_geom(int B, int nver, int H, int W, int* out);
 
+/* ---- per-face albedo fit: the least-squares alpha of the shape-from-shading term, on the pixel grid (opt-in) -----------------------
+ * The reference's SfS block wanted a least-squares estimate of the albedo coefficients alpha per face given the lighting, and gave it
+ * up (nets/network.py:436-455, "The following step cannot be fulfilled!!") for want of a map between the pixel grid and the (3N, 10)
+ * texture basis; it uses one param_tex for every face instead.  That map is the rasteriser's tri_ind.  Per face b, all else fixed,
+ *   alpha_b = argmin over alpha of  sum_p ( I_b(p) - (a_b(p) + phi_b(p) . alpha) d_b(p) )^2  +  lambda_b |alpha|^2
+ * over the pixels the face covers: I = im_gray, a = the albedo image of the MEAN texture (abedo), d = l . n' the shading of the
+ * normals the term shades, l = state planes 6-8 of the fused solve, phi(p) = Phi[tri_ind(p)].  Linear in alpha: one Gram matrix of a
+ * K-column design per face.  alpha is a fitted quantity, held constant in the backward like the lighting's pseudo-inverse: there is
+ * no backward entry point.
+ * NAMES.  The stream parameter is called `stream`, as in the Gram-form geometry loss above and for its reason;
+ * tests/test_albedo_lse_cpu.py holds these entry points' return codes.
+ * BASIS.  Phi is [ntri][K] float64, fr_albedo_basis_bytes(ntri, K) = ntri K 8 bytes (0 for ntri <= 0 or an unserved K), built once:
+ *   Phi[t][k] = (1/9) sum_c sum_j pc_tex[c nver + v_j(t)][k],   tri [3,ntri] float-stored ids, pc_tex [3 nver, K] fp32 row-major
+ * -- the rasteriser's lookup (t[p1] + t[p2] + t[p3]) / 3 averaged over the three channels.  The nine widened fp32 terms are added in
+ * float64 channel-major, then vertex 1, 2, 3, onto the first term (c = 0, j = 1), and the sum is divided by 9.0.  A triangle with a
+ * vertex id outside [0, nver) (NaN included; x86 conversion) gets a row of +0.0.  Every bit is fixed by this.  Checks, in this order:
+ * a negative size is FR_ERR_INVALID_ARG; K outside 1 .. 15 is FR_ERR_UNSUPPORTED; ntri == 0 is FR_OK; a NULL tri (or pc_tex with
+ * nver > 0) is FR_ERR_INVALID_ARG; a basis that is missing, too small or not 16-byte aligned is FR_ERR_WORKSPACE; ntri > 2^24 is
+ * FR_ERR_UNSUPPORTED.
+ * LIGHTING.  fr_sfs_lighting is the solve half of fr_sfs_solve_shade without the shade: it adds the nparts parts ([nparts][9][H*W],
+ * "across ranks" above) in ascending part index starting from part 0, runs fr_sfs_pinv3 and writes the ten state planes -- built from
+ * the same device functions, so its state is bit-identical to what fr_sfs_solve_shade and fr_sfs_intensity_forward write for the same
+ * maps.  It exists because the fit needs l before abedo_new exists.  Checks as fr_sfs_solve_shade's without the faces: a negative
+ * size, a bad rcond, nparts outside 1 .. 4096 is FR_ERR_INVALID_ARG; an empty image is FR_OK; a NULL moment_parts is
+ * FR_ERR_INVALID_ARG; a bad state is FR_ERR_WORKSPACE; more than 2^31 - 65 pixels is FR_ERR_UNSUPPORTED.
+ * FIT, per pixel p of face b.  Float64 on the widened fp32 inputs, every operation rounded on its own (no contraction).  The pixel is
+ * COUNTED iff 0 <= (int)tri_ind < ntri (the x86 conversion of the render backwards: NaN and -1 are not).  With t = (int)tri_ind,
+ *   d = (l_x n'_x + l_y n'_y) + l_z n'_z          rho = I - a d
+ *   x_k = d Phi[t][k] for k < K,   x_K = rho,   x_k = +0.0 for K < k < 16;   an uncounted pixel gives x = 0 whatever its maps hold.
+ *   lighting [3][H*W] float64 (state planes 6-8, shared by the faces);  tri_ind, abedo, im_gray [B,H,W,1], normal_new [B,H,W,3] fp32.
+ * MOMENTS.  M_b = sum_p x x^T, 16 x 16, written to moments [B][16][16] float64 (row-major; symmetric bit for bit; rows and columns
+ * above K are +0.0).  G = M[:K,:K], r = M[:K,K], E0 = M[K][K]: the residual energy at alpha = 0.
+ * ASSOCIATION.  A face's pixels in row-major order are cut into tiles of T = 256 (fr_debug_albedo_lse_geom), tiles = ceil(H W / T).
+ * Within a tile, consecutive groups of four pixels are added in ascending order onto +0.0 accumulators by v_mfma_f64_16x16x4_f64
+ * (the four products of a group are summed by the instruction, then added to the accumulator).  The tile partials are added in
+ * ascending tile order from +0.0; element (i <= j) is written to (i, j) and (j, i).  The bits are a function of the inputs and of
+ * (H, W, K) alone -- not of B, the device, a knob or the launch geometry.  No atomics.  Every M_ij lies within n 2^-53 / (1 - n 2^-53)
+ * sum_p |x_i x_j| of the exact sum of the rounded products, n = H W.
+ * SOLVE.  Per face, float64; every element's chain of products and sums is that of this sequential source order (the kernel forms the
+ * elements of a column side by side on the lanes of one wave; tests/ref_albedo_lse.py):
+ *   tr = chain over k < K from +0.0 of M_kk;   lambda = (ridge tr) / (double)K;   G' = G + lambda I
+ *   Cholesky G' = L L^T by columns c = 0 .. K-1:  piv = G'_cc - (chain over m < c from +0.0 of L_cm L_cm);  L_cc = sqrt(piv);
+ *       L_rc = (G_rc - (chain over m < c from +0.0 of L_rm L_cm)) / L_cc  for r > c
+ *   L y = r forward (y_r = (r_r - chain over m < r of L_rm y_m) / L_rr),  L^T alpha = y backward (chain over m = r+1 .. K-1 ascending)
+ * A face FAILS when it has no counted pixel, when any M_ij (i, j <= K) is not finite, when a pivot is not finite or not
+ * > 2^-40 G'_cc, or when an alpha_k is not finite.  A failed face gets alpha_b = +0 (the mean albedo), ok = 0 and E1 = E0, and
+ * leaves every other face's bits untouched.
+ * OUTPUTS.  alpha [B][K] fp32, rounded once.  stats [B][4] float64 = {counted pixels, E0, E1, ok}, with alpha^ = the rounded alpha
+ * widened and the UNRIDGED G:  S1 = chain over k from +0.0 of alpha^_k r_k;  (G alpha^)_k = chain over j from +0.0 of G_kj alpha^_j;
+ * S2 = chain over k from +0.0 of alpha^_k (G alpha^)_k;  E1 = (E0 - 2.0 S1) + S2.
+ * WORKSPACE.  fr_albedo_lse_workspace_bytes(B, H, W, K) = B tiles 257 doubles (the tile partials as they lie in the registers, then
+ * the tiles' counts; 0 for an empty or refused shape), 16-byte aligned, caller-owned, one per call in flight; written before it is read.
+ * Checks, all before any HIP call, in this order: a negative size, or a ridge that is negative or not finite, is FR_ERR_INVALID_ARG;
+ * K outside 1 .. 15 is FR_ERR_UNSUPPORTED; then B == 0 or an empty image is FR_OK with nothing launched or written; then a NULL
+ * pointer is FR_ERR_INVALID_ARG; a workspace that is missing, too small or misaligned is FR_ERR_WORKSPACE; more than 2^31 - 65
+ * pixels per face, or more than 2^31 - 1 tile workgroups, is FR_ERR_UNSUPPORTED.  ntri == 0 counts no pixel: every face fails.
+ * Nothing is allocated or synchronised; the call makes two launches, can be captured in a graph and is reentrant under the rules at
+ * the top of this file with buffers per call in flight.
+ * Kernels (csrc/fr_albedo_lse.hip).  The reduction over pixels IS the matrix instruction: X X^T with X = [x(p0) x(p1) x(p2) x(p3)]
+ * takes the same register as both operands, lane l holding x_(l mod 16) of pixel 4 g + l / 16, so a wave keeps the whole 16 x 16 sum
+ * in four float64 per lane with no cross-lane reduction.  One wave owns a tile (four tiles per workgroup, nothing shared): it reads
+ * 64 pixels' maps once, coalesced, and hands d, rho and t to the 16 lanes of each pixel by lane shuffles; lanes k < K gather
+ * Phi[t][k], 8 K contiguous bytes per pixel out of a table of 8.5 MB at the full mesh.  The second launch is one workgroup per face:
+ * 136 threads chain the tile partials, then one wave solves: lane r holds row r of G' and of L in registers, the rows meet by lane
+ * shuffles.
+ * Time: tools/albedo_lse_probe.py (profiles/albedo_lse.json) measures the basis build, fr_sfs_lighting and this call at 32 and 64
+ * faces of the full mesh at 200 x 200 beside the bytes each must move and the same fit from stock torch ops.
+ * MI355X, medians of 6 rounds of 40 calls: the fit 52.8 / 73.8 us, where it must move 84 / 167 MB = 17.7 / 35.3 us at the 4.75 TB/s
+ * that run's copy reached (0.33 / 0.48 of it; 52.6 us of the 64-face figure is the tile kernel, 22.9 us finish and solve), beside
+ * 2.95 / 3.48 ms for the stock-torch fit; fr_sfs_lighting 7.9 / 8.0 us; the basis build 8.8 / 8.6 us.  Not tuned further. */
+size_t fr_albedo_basis_bytes(int ntri, int K);
+int fr_albedo_basis_build(const float* tri, const float* pc_tex, int nver, int ntri, int K, void* basis, size_t basis_bytes,
+                          void* stream);
+int fr_sfs_lighting(const void* moment_parts, int nparts, int H, int W, double rcond, void* state, size_t state_bytes, void* stream);
+size_t fr_albedo_lse_workspace_bytes(int B, int H, int W, int K);
+int fr_albedo_lse_forward(const void* basis, const float* tri_ind, const void* lighting, const float* normal_new, const float* abedo,
+                          const float* im_gray, int B, int ntri, int H, int W, int K, double ridge, float* alpha, void* moments,
+                          void* stats, void* workspace, size_t ws_bytes, void* stream);
+
+/* The albedo fit's launch geometry (no GPU needed; the launcher reads the same function): out[5] = {pixels per tile (T above), tiles
+ * per face, workgroups of the tile kernel (B ceil(tiles / 4)), workgroups of the finish kernel (B), static LDS bytes of a finish
+ * workgroup}; all zero for an empty shape, an unserved K or a shape the launcher refuses.  Used by tests/test_albedo_lse_cpu.py and
+ * by tests/test_albedo_lse_gpu.py to place their shapes on the tile's edges. */
+void fr_debug_albedo_lse_geom(int B, int H, int W, int K, int* out);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
