@@ -587,4 +587,42 @@ int fr_render_texture_backward(const float* tex_grad, int grad_stride, const flo
                                              accumulate, workspace, (hipStream_t)hip_stream);
 }
 
+// ---- synthetic batches ------------------------------------------------------------------------------------------------------------
+// n (lo, hi) pairs on the host: finite, lo <= hi
+static bool synth_ranges_ok(const float* r, int n) {
+    for (int k = 0; k < n; k++)
+        if (!(r[2 * k] <= r[2 * k + 1]) || !(r[2 * k] - r[2 * k] == 0.0f) || !(r[2 * k + 1] - r[2 * k + 1] == 0.0f)) return false;
+    return true;
+}
+
+int fr_synth_params(unsigned long long seed, unsigned long long first_face, int B, int n_shape, int n_exp, int K, float im_size,
+                    float beta, float focal, const float* light_ranges, const float* alpha_ranges, float* params, float* light,
+                    float* alpha, void* stream) {
+    if (B < 1 || n_shape < 0 || n_exp < 0 || K < 0) return FR_ERR_INVALID_ARG;
+    if (!(beta >= 0.0f && beta <= 1.0f) || !(im_size - im_size == 0.0f) || !(focal - focal == 0.0f)) return FR_ERR_INVALID_ARG;
+    if (K > FR_SYNTH_MAX_TEX || B > 65535) return FR_ERR_UNSUPPORTED;
+    if ((long long)n_shape + n_exp + K > 0x7FFFFFFFll - 64) return FR_ERR_UNSUPPORTED;   // (the draw index stays an int)
+    if (!params || !light || !light_ranges || (K > 0 && (!alpha || !alpha_ranges))) return FR_ERR_INVALID_ARG;
+    if (!synth_ranges_ok(light_ranges, 4) || !synth_ranges_ok(alpha_ranges, K)) return FR_ERR_INVALID_ARG;
+    return fr_launch_synth_params(seed, first_face, B, n_shape, n_exp, K, im_size, beta, focal, light_ranges, alpha_ranges, params,
+                                  light, alpha, (hipStream_t)stream);
+}
+
+int fr_synth_texture(const float* mu_tex, const float* pc_tex, const float* alpha, int B, int N, int K, float* tex, void* stream) {
+    if (B < 1 || N < 1 || K < 0) return FR_ERR_INVALID_ARG;
+    if (B > 65535) return FR_ERR_UNSUPPORTED;
+    if (!mu_tex || !tex || (K > 0 && (!pc_tex || !alpha))) return FR_ERR_INVALID_ARG;
+    return fr_launch_synth_texture(mu_tex, pc_tex, alpha, B, N, K, tex, (hipStream_t)stream);
+}
+
+int fr_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* background,
+                   int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray, float* mask, void* stream) {
+    if (B < 1 || H < 1 || W < 1) return FR_ERR_INVALID_ARG;
+    if (background ? (bg_batch != 1 && bg_batch != B) : bg_batch != 0) return FR_ERR_INVALID_ARG;
+    if (!tex_img || !normal || !tri_ind || !light || !im_gray || !mask) return FR_ERR_INVALID_ARG;
+    if ((long long)H * W > 0x7FFFFFFFll || B > 65535) return FR_ERR_UNSUPPORTED;
+    return fr_launch_synth_shade(tex_img, normal, tri_ind, light, background, bg_batch, B, H, W, gain, offset, im_gray, mask,
+                                 (hipStream_t)stream);
+}
+
 }  // extern "C"

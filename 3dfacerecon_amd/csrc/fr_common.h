@@ -211,3 +211,12 @@ size_t fr_render_texture_backward_workspace_impl(int B, int nver, int H, int W, 
 int fr_launch_render_texture_backward(const float* tex_grad, int grad_stride, const float* tri, const float* tri_ind,
                                       float* texture_grad, int B, int nver, int ntri, int H, int W, int tex_batch, int accumulate,
                                       void* workspace, hipStream_t stream);
+// synthetic batches (fr_synth.hip): the ranges are host arrays of (lo, hi) pairs, copied into the launch's arguments
+int fr_launch_synth_params(unsigned long long seed, unsigned long long first_face, int B, int ns, int ne, int K, float im_size,
+                           float beta, float focal, const float* light_ranges, const float* alpha_ranges, float* params,
+                           float* light, float* alpha, hipStream_t stream);
+int fr_launch_synth_texture(const float* mu_tex, const float* pc_tex, const float* alpha, int B, int N, int K, float* tex,
+                            hipStream_t stream);
+int fr_launch_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light,
+                          const float* background, int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray,
+                          float* mask, hipStream_t stream);

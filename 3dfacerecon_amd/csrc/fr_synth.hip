@@ -1,0 +1,176 @@
+// On-device synthetic training batches (include/fr_hotpath.h, "synthetic batches"): the counter-based parameter sampler, the per-face
+// albedo blend and the shading / compositing post-pass over a render's planes.  All three are streaming or tiny: one lane per
+// element, coalesced, no atomics; LDS only to turn the texture basis' row-major reads into coalesced ones.  fp32 in the header's
+// stated order, one rounding per operation (-ffp-contract=off).
+#include "fr_common.h"
+
+namespace fr {
+
+// Philox4x32-10 (Salmon et al., SC'11): counter c[4], key k[2]
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t* out) {
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+struct SynthParamsArgs {
+    unsigned long long seed, first_face;
+    int B, ns, ne, K, draws;
+    float half_im, beta, focal;
+    float* params;
+    float* light;
+    float* alpha;
+    float light_lo[4], light_hi[4];
+    float alpha_lo[FR_SYNTH_MAX_TEX], alpha_hi[FR_SYNTH_MAX_TEX];
+};
+
+// one lane per draw j of face b: draw j is word j & 3 of the block with counter (j >> 2, g_lo, g_hi, 0), g = first_face + b
+__global__ __launch_bounds__(256) void synth_params_kernel(const SynthParamsArgs a) {
+    const int j = (int)(blockIdx.x * 256u + threadIdx.x);
+    const int b = (int)blockIdx.y;
+    if (j >= a.draws) return;
+    const unsigned long long g = a.first_face + (unsigned long long)b;
+    uint32_t w[4];
+    philox4x32_10((uint32_t)j >> 2, (uint32_t)g, (uint32_t)(g >> 32), 0u, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), w);
+    const uint32_t word = (j & 3) == 0 ? w[0] : (j & 3) == 1 ? w[1] : (j & 3) == 2 ? w[2] : w[3];
+    const float u = (float)(word >> 8) * 5.9604644775390625e-8f;   // 2^-24: exact, in [0,1)
+    const int d = 7 + a.ns + a.ne;
+    float* prm = a.params + (size_t)b * d;
+    if (j < 6) {   // pose = beta base + (1 - beta) rand, base = (0, 0, 0, im/2, im/2, 0, focal)
+        const float c = 0.01745329238474369049072265625f;   // fl32(pi / 180)
+        const float omb = 1.0f - a.beta;
+        float rnd, base;
+        int col;
+        if (j == 0) { rnd = (-75.0f + 120.0f * u) * c; base = 0.0f; col = 0; }
+        else if (j == 1) { rnd = (-90.0f + 180.0f * u) * c; base = 0.0f; col = 1; }
+        else if (j == 2) { rnd = (-30.0f + 60.0f * u) * c; base = 0.0f; col = 2; }
+        else if (j == 3) { rnd = u * a.focal; base = a.focal; col = 6; }
+        else { rnd = 60.0f * u; base = a.half_im; col = j - 1; }   // tx -> 3, ty -> 4
+        prm[col] = a.beta * base + omb * rnd;
+        if (j == 5) prm[5] = 0.0f;   // tz = beta 0 + (1 - beta) 0 with beta in [0, 1]: no draw
+        return;
+    }
+    int k = j - 6;
+    if (k < a.ns) { prm[7 + k] = u * 1.0e4f; return; }
+    k -= a.ns;
+    if (k < a.ne) { prm[7 + a.ns + k] = -1.5f + 3.0f * u; return; }
+    k -= a.ne;
+    if (k < 4) { a.light[(size_t)b * 4 + k] = a.light_lo[k] + (a.light_hi[k] - a.light_lo[k]) * u; return; }
+    k -= 4;
+    a.alpha[(size_t)b * a.K + k] = a.alpha_lo[k] + (a.alpha_hi[k] - a.alpha_lo[k]) * u;
+}
+
+// One lane per (c, p) row and per face of its workgroup's group of TX_FACES: acc = mu_tex[c][p]; acc = acc + pc_tex[c N + p][k] *
+// alpha[b][k], k ascending -- each output's own chain, whatever the tiling.  A workgroup's 256 rows of pc_tex are one contiguous
+// run of 256 K floats: it is fetched ONCE per group of faces, coalesced, TX_KC columns at a time into LDS (row pitch TX_KC + 1: a
+// lane's walk along its row is conflict-free), instead of each lane striding K floats through the cache once per face.  alpha is
+// wave-uniform (scalar loads).  The stores are 64 contiguous floats per wave and face.
+constexpr int TX_ROWS = 256, TX_KC = 16, TX_FACES = 8;
+__global__ __launch_bounds__(TX_ROWS) void synth_texture_kernel(const float* __restrict__ mu_tex, const float* __restrict__ pc_tex,
+                                                                const float* __restrict__ alpha, int B, int N, int K,
+                                                                float* __restrict__ tex) {
+    __shared__ float tile[TX_ROWS * (TX_KC + 1)];
+    const int tid = (int)threadIdx.x;
+    const int row0 = (int)blockIdx.x * TX_ROWS;
+    const int c = (int)blockIdx.y, b0 = (int)blockIdx.z * TX_FACES;
+    const int nb = min(TX_FACES, B - b0), nrows = min(TX_ROWS, N - row0);
+    const bool live = tid < nrows;
+    const size_t row = (size_t)c * N + row0 + (live ? tid : 0);
+    float acc[TX_FACES];
+    const float mu = mu_tex[row];
+#pragma unroll
+    for (int f = 0; f < TX_FACES; f++) acc[f] = mu;
+    const float* src = pc_tex + ((size_t)c * N + row0) * (size_t)K;   // rows row0 .. row0 + nrows of channel c
+    for (int k0 = 0; k0 < K; k0 += TX_KC) {
+        const int kc = min(TX_KC, K - k0);
+        if (k0) __syncthreads();
+        for (int e = tid; e < nrows * kc; e += TX_ROWS) {
+            const int r = e / kc, kk = e - r * kc;
+            tile[r * (TX_KC + 1) + kk] = src[(size_t)r * K + k0 + kk];
+        }
+        __syncthreads();
+        if (live) {
+            for (int kk = 0; kk < kc; kk++) {
+                const float pc = tile[tid * (TX_KC + 1) + kk];
+#pragma unroll
+                for (int f = 0; f < TX_FACES; f++)
+                    if (f < nb) acc[f] = acc[f] + pc * alpha[(size_t)(b0 + f) * K + k0 + kk];
+            }
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int f = 0; f < TX_FACES; f++)
+        if (f < nb) tex[(size_t)(b0 + f) * 3 * N + row] = acc[f];
+}
+
+// one lane per pixel
+__global__ __launch_bounds__(256) void synth_shade_kernel(const float* __restrict__ tex_img, const float* __restrict__ normal,
+                                                          const float* __restrict__ tri_ind, const float* __restrict__ light,
+                                                          const float* __restrict__ background, int bg_batch, int HW, float gain,
+                                                          float offset, float* __restrict__ im_gray, float* __restrict__ mask) {
+    const unsigned int pix = blockIdx.x * 256u + threadIdx.x;
+    const int b = (int)blockIdx.y;
+    if (pix >= (unsigned int)HW) return;
+    const size_t i = (size_t)b * (size_t)HW + pix;
+    if (!(tri_ind[i] >= 0.0f)) {
+        im_gray[i] = background ? background[(bg_batch == 1 ? (size_t)0 : (size_t)b * (size_t)HW) + pix] : 0.0f;
+        mask[i] = 0.0f;
+        return;
+    }
+    const float t0 = tex_img[3 * i], t1 = tex_img[3 * i + 1], t2 = tex_img[3 * i + 2];
+    // (x < 1e-6 ? 1e-6 : x: a NaN stays a NaN, as torch.clamp_min)
+    const float a = fr::div3(((t0 < 1e-6f ? 1e-6f : t0) + (t1 < 1e-6f ? 1e-6f : t1)) + (t2 < 1e-6f ? 1e-6f : t2));
+    float nx = normal[3 * i], ny = normal[3 * i + 1], nz = normal[3 * i + 2];
+    if (nz < 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+    float mag = (nx * nx + ny * ny) + nz * nz;
+    mag = (mag > 1e-6f) ? mag : 1.0f;
+    const float d = sqrtf(mag) + 1e-6f;
+    const float* l = light + (size_t)b * 4;
+    const float s = ((l[0] + l[1] * (nx / d)) + l[2] * (ny / d)) + l[3] * (nz / d);
+    const float I = a * (s < 0.0f ? 0.0f : s);
+    im_gray[i] = I * gain + offset;
+    mask[i] = 1.0f;
+}
+
+}  // namespace fr
+
+int fr_launch_synth_params(unsigned long long seed, unsigned long long first_face, int B, int ns, int ne, int K, float im_size,
+                           float beta, float focal, const float* light_ranges, const float* alpha_ranges, float* params,
+                           float* light, float* alpha, hipStream_t stream) {
+    fr::SynthParamsArgs a{};
+    a.seed = seed; a.first_face = first_face;
+    a.B = B; a.ns = ns; a.ne = ne; a.K = K; a.draws = 6 + ns + ne + 4 + K;
+    a.half_im = im_size * 0.5f; a.beta = beta; a.focal = focal;
+    a.params = params; a.light = light; a.alpha = alpha;
+    for (int k = 0; k < 4; k++) { a.light_lo[k] = light_ranges[2 * k]; a.light_hi[k] = light_ranges[2 * k + 1]; }
+    for (int k = 0; k < K; k++) { a.alpha_lo[k] = alpha_ranges[2 * k]; a.alpha_hi[k] = alpha_ranges[2 * k + 1]; }
+    hipLaunchKernelGGL(fr::synth_params_kernel, dim3((unsigned)((a.draws + 255) / 256), (unsigned)B, 1), dim3(256, 1, 1), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
+
+int fr_launch_synth_texture(const float* mu_tex, const float* pc_tex, const float* alpha, int B, int N, int K, float* tex,
+                            hipStream_t stream) {
+    const dim3 grid((unsigned)((N + fr::TX_ROWS - 1) / fr::TX_ROWS), 3, (unsigned)((B + fr::TX_FACES - 1) / fr::TX_FACES));
+    hipLaunchKernelGGL(fr::synth_texture_kernel, grid, dim3(fr::TX_ROWS, 1, 1), 0, stream, mu_tex, pc_tex, alpha, B, N, K, tex);
+    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
+
+int fr_launch_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light,
+                          const float* background, int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray,
+                          float* mask, hipStream_t stream) {
+    const int HW = H * W;
+    hipLaunchKernelGGL(fr::synth_shade_kernel, dim3((unsigned)(((long long)HW + 255) / 256), (unsigned)B, 1), dim3(256, 1, 1), 0, stream,
+                       tex_img, normal, tri_ind, light, background, bg_batch, HW, gain, offset, im_gray, mask);
+    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}

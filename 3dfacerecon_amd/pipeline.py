@@ -334,3 +334,124 @@ class _Slot(DecodeRenderPlan):
 
     def make_current_stream_wait(self):
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
+
+
+def synth_face_range(step, rank, world, batch):
+    """(first_face, end) of the batch rank `rank` of `world` draws at step `step`: first_face = (step world + rank) batch.  The
+    ranks' ranges of one step lie side by side and the steps follow one another, so the union over ranks is exactly the face
+    sequence one process draws with batch `world batch` -- a face's values depend on (seed, global face index) alone."""
+    step, rank, world, batch = int(step), int(rank), int(world), int(batch)
+    if step < 0 or world < 1 or not 0 <= rank < world or batch < 1:
+        raise ValueError("synth_face_range: step >= 0, 0 <= rank < world, batch >= 1")
+    first = (step * world + rank) * batch
+    return first, first + batch
+
+
+class _SynthSlot:
+    """One buffer set of SynthBatches and the stream its five launches go down."""
+
+    def __init__(self, owner, stream):
+        net, B, H, W = owner.net, owner.B, owner.H, owner.W
+        f32 = dict(dtype=torch.float32, device=owner.device)
+        self.stream = stream
+        self.event = torch.cuda.Event()
+        self.tex = torch.empty((B, 3, net.nvert), **f32)
+        # decode -> render of the slot's own parameters with the slot's per-face texture, bound to the slot's stream
+        self.plan = DecodeRenderPlan(net, B, H, W, texture=self.tex, stream=stream)
+        self.params = self.plan.params
+        self.light = torch.empty((B, 4), **f32)
+        self.alpha = torch.empty((B, owner.K), **f32)
+        self.im_gray = torch.empty((B, H, W, 1), **f32)
+        self.mask = torch.empty((B, H, W, 1), **f32)
+        self.depth = torch.empty((B, H, W, 1), **f32)
+        self.first_face = None
+
+    def batch(self):
+        return {"im_gray": self.im_gray, "params": self.params, "depth": self.depth, "mask": self.mask,
+                "tri_ind": self.plan.tri_ind, "light": self.light, "alpha": self.alpha}
+
+
+class SynthBatches:
+    """Training batches made on the device: every `next()` returns a batch whose image DEPICTS its label -- random parameters, the
+    face they decode to rendered with a random per-face albedo under a random first-order lighting, and that face's ground-truth
+    depth and mask.  Per batch, on a side stream, with no host work, no copy and no dataset:
+        synth_params -> fr_decode_3dmm -> synth_texture -> render (per-face [B,3,N] texture) -> synth_shade
+    (rendering_layer/ops.py; decode and render are one DecodeRenderPlan step).  Modelled on BatchesInFlight: every slot owns its
+    buffers and a stream.  `next()` makes torch's current stream wait for the slot that holds the batch, starts the FOLLOWING
+    batch on the following slot's stream, and returns
+        {"im_gray" [B,H,W,1], "params" [B,d], "depth" [B,H,W,1], "mask" [B,H,W,1], "tri_ind" [B,H,W,1], "light" [B,4], "alpha" [B,K]}
+    -- views of the slot's buffers, nothing requires grad.  `depth` is the clamped flat depth image FaceRecNet.rendering_layer
+    returns for those parameters; `mask` is 1.0 where a triangle covers the pixel.  A returned batch stays as it is until `slots`
+    calls later: `slots` batches are the caller's, and one more buffer set holds the batch in the making, so slots + 1 sets exist.
+    Before a set is written again its stream waits for torch's current stream of that moment (the consumer's reads enqueued so far).
+    Faces are numbered globally: call n draws faces first_face + n stride .. + batch (stride: default `batch`).  A rank of a
+    sharded loop passes first_face = synth_face_range(0, rank, world, batch)[0] and stride = world batch; the ranks' streams
+    together are then the single-process stream, face for face.  Two streams with different seeds are independent.
+    The launches go out eagerly: first_face travels in the sampler's launch arguments, which a captured graph would freeze."""
+
+    def __init__(self, net, batch, seed, slots=2, first_face=0, stride=None, light_ranges=None, alpha_ranges=1.0, background=None,
+                 gain=1.0, offset=0.0, beta=0.7, focal=1e-3, height=None, width=None):
+        if int(slots) < 1:
+            raise ValueError("slots must be >= 1")
+        if net.mu_tex is None:
+            raise ValueError("the asset dict has no texture model (mu_tex)")
+        # the operator module the net itself renders through: the loader of the module that defines FaceRecNet (nets/network.py)
+        self._ops = ops = next(m._ops for m in (sys.modules.get(c.__module__) for c in type(net).__mro__) if hasattr(m, "_ops"))()
+        self.net = net
+        self.device = net.device
+        self.B = int(batch)
+        self.H = int(net.im_size if height is None else height)
+        self.W = int(net.im_size if width is None else width)
+        self.K = 0 if net.pc_tex is None else int(net.pc_tex.shape[1])
+        self.seed = int(seed)
+        self.first_face = int(first_face)
+        self.stride = self.B if stride is None else int(stride)
+        self.light_ranges = ops.SYNTH_LIGHT_RANGES if light_ranges is None else light_ranges
+        self.alpha_ranges = alpha_ranges
+        self.gain, self.offset, self.beta, self.focal = float(gain), float(offset), float(beta), float(focal)
+        self.background = None
+        if background is not None:
+            self.background = _host().require_gpu_f32(background, "background")
+        self.lifetime = int(slots)
+        with torch.cuda.device(self.device):
+            self.slots = [_SynthSlot(self, torch.cuda.Stream(device=self.device)) for _ in range(int(slots) + 1)]
+            torch.cuda.synchronize(self.device)   # every slot's triangle table is packed before anything else touches the slots
+            self._made = 0     # batches started
+            self._taken = 0    # batches returned
+            self._generate()
+
+    def _generate(self):
+        """Starts batch number self._made on its slot's stream, behind whatever torch's current stream holds now."""
+        n = self._made
+        sl = self.slots[n % len(self.slots)]
+        ops, net = self._ops, self.net
+        sl.first_face = self.first_face + n * self.stride
+        sl.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.device(self.device), torch.cuda.stream(sl.stream):
+            ops.synth_params(self.seed, sl.first_face, self.B, net.ndim_shape, net.ndim_exp, self.K, net.im_size, beta=self.beta,
+                             light_ranges=self.light_ranges, alpha_ranges=self.alpha_ranges, focal=self.focal,
+                             out=(sl.params, sl.light, sl.alpha))
+            ops.synth_texture(net.mu_tex, net.pc_tex, sl.alpha, out=sl.tex)
+            sl.plan.step()
+            ops.synth_shade(sl.plan.texture_image, sl.plan.normal, sl.plan.tri_ind, sl.light, background=self.background,
+                            gain=self.gain, offset=self.offset, out=(sl.im_gray, sl.mask))
+            torch.clamp_min(sl.plan.depth, 1e-6, out=sl.depth)
+            sl.event.record(sl.stream)
+        self._made = n + 1
+
+    def next(self):
+        sl = self.slots[self._taken % len(self.slots)]
+        self._taken += 1
+        torch.cuda.current_stream(self.device).wait_event(sl.event)
+        self._generate()
+        return sl.batch()
+
+    def synchronize(self):
+        for sl in self.slots:
+            sl.stream.synchronize()
+
+    def __del__(self):   # the slots' buffers go back to torch's allocator: not while their streams still run
+        try:
+            self.synchronize()
+        except Exception:
+            pass

@@ -1035,6 +1035,128 @@ def albedo_lse(basis, tri_ind, lighting, normal_new, abedo, im_gray, ridge=1e-6)
     return alpha, stats
 
 
+SYNTH_LIGHT_RANGES = ((0.3, 0.7), (-0.4, 0.4), (-0.4, 0.4), (0.2, 0.9))   # (l0, lx, ly, lz): ambient, then a frontal light
+
+
+def _synth_ranges(ranges, n, name):
+    """n (lo, hi) pairs -> a host float array the C call reads; a scalar s means (-s, s) for every component"""
+    if n == 0:
+        return None
+    if isinstance(ranges, (int, float)):
+        ranges = [(-abs(float(ranges)), abs(float(ranges)))] * n
+    flat = [float(v) for pair in ranges for v in pair]
+    if len(flat) != 2 * n:
+        raise ValueError("%s must be %d (lo, hi) pairs" % (name, n))
+    return (ctypes.c_float * (2 * n))(*flat)
+
+
+def synth_params(seed, first_face, batch, n_shape, n_exp, n_tex, im_size, beta=0.7, light_ranges=SYNTH_LIGHT_RANGES,
+                 alpha_ranges=1.0, focal=1e-3, device=None, out=None):
+    """`batch` faces of random parameters drawn on the device (fr_synth_params): Philox4x32-10 keyed by `seed`, counted by the
+    GLOBAL face index first_face + b, so a face's values do not depend on the batch, the call or the rank that drew it.
+    -> (params [B, 7 + n_shape + n_exp] in the 235-d layout with the distributions of utils/synth.get_random_params, light [B,4],
+    alpha [B,n_tex]), the last two uniform in light_ranges / alpha_ranges ((lo, hi) pairs per component; a scalar s means
+    (-s, s)).  focal: the reference's 1e-3; a smaller image takes a smaller one.  out: three tensors to write instead of fresh
+    ones.  A data source: nothing requires grad.  Runs on the current stream."""
+    h = _host()
+    B, ns, ne, K = int(batch), int(n_shape), int(n_exp), int(n_tex)
+    if out is None:
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise RuntimeError("synth_params draws on an MI355X only (no CPU fallback); got %s" % dev)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = (torch.empty((B, 7 + ns + ne), **f32), torch.empty((B, 4), **f32), torch.empty((B, K), **f32))
+    params, light, alpha = out
+    for t, name, shape in ((params, "params", (B, 7 + ns + ne)), (light, "light", (B, 4)), (alpha, "alpha", (B, K))):
+        if h.require_gpu_f32(t, name) is not t or tuple(t.shape) != shape:
+            raise ValueError("synth_params: out %s must be a contiguous float32 tensor %s" % (name, shape))
+    dev = params.device
+    lr = _synth_ranges(light_ranges, 4, "light_ranges")
+    ar = _synth_ranges(alpha_ranges, K, "alpha_ranges")
+    with torch.cuda.device(dev):
+        rc = h.lib().fr_synth_params(int(seed) & (2 ** 64 - 1), int(first_face) & (2 ** 64 - 1), B, ns, ne, K, float(im_size),
+                                     float(beta), float(focal), lr, ar, h.ptr(params), h.ptr(light),
+                                     h.ptr(alpha) if K > 0 else None, h.stream_ptr(dev))
+    h.check(rc, "fr_synth_params")
+    return params, light, alpha
+
+
+def synth_texture(mu_tex, pc_tex, alpha, out=None):
+    """The per-face albedo tex [B,3,N] = mu_tex + pc_tex . alpha_b (fr_synth_texture: the chain acc = acc + pc alpha in ascending
+    k from mu_tex, bit-exact against numpy): mu_tex [3,N], pc_tex [3N,K], alpha [B,K].  What render_depth takes as a per-face
+    texture.  K = 0 repeats mu_tex.  Nothing requires grad.  Runs on the current stream."""
+    h = _host()
+    mu_c = h.require_gpu_f32(mu_tex.detach(), "mu_tex")
+    al_c = h.require_gpu_f32(alpha.detach(), "alpha")
+    if mu_c.dim() != 2 or mu_c.shape[0] != 3:
+        raise ValueError("synth_texture expects mu_tex [3,N]")
+    if al_c.dim() != 2:
+        raise ValueError("synth_texture expects alpha [B,K]")
+    N, B, K = int(mu_c.shape[1]), int(al_c.shape[0]), int(al_c.shape[1])
+    dev = mu_c.device
+    pc_c = None
+    if K > 0:
+        pc_c = h.require_gpu_f32(pc_tex.detach(), "pc_tex")
+        if tuple(pc_c.shape) != (3 * N, K):
+            raise ValueError("synth_texture: pc_tex must be [%d,%d] (got %s)" % (3 * N, K, tuple(pc_c.shape)))
+    for t, name in ((al_c, "alpha"), (pc_c, "pc_tex")):
+        if t is not None and t.device != dev:
+            raise ValueError("synth_texture: %s is on %s, mu_tex on %s" % (name, t.device, dev))
+    if out is None:
+        out = torch.empty((B, 3, N), dtype=torch.float32, device=dev)
+    elif h.require_gpu_f32(out, "out") is not out or tuple(out.shape) != (B, 3, N) or out.device != dev:
+        raise ValueError("synth_texture: out must be a contiguous float32 tensor [%d,3,%d] on %s" % (B, N, dev))
+    with torch.cuda.device(dev):
+        rc = h.lib().fr_synth_texture(h.ptr(mu_c), h.ptr(pc_c), h.ptr(al_c) if K > 0 else None, B, N, K, h.ptr(out),
+                                      h.stream_ptr(dev))
+    h.check(rc, "fr_synth_texture")
+    return out
+
+
+def synth_shade(tex_img, normal, tri_ind, light, background=None, gain=1.0, offset=0.0, out=None):
+    """The gray image of a render's planes under a first-order lighting (fr_synth_shade, one lane per pixel): where tri_ind >= 0,
+    im_gray = a max(l0 + l . n^, 0) gain + offset with a = the mean of clamp_min(tex_img, 1e-6) over the channels and n^ the
+    normal map of FaceRecNet.compute_abedo_image (flipped to n_z >= 0, normalised); elsewhere the background pixel ([1,H,W,1]
+    or [B,H,W,1]; 0 without one).  tex_img, normal [B,H,W,3] (the op's raw normal), tri_ind [B,H,W,1], light [B,4].
+    -> (im_gray, mask) [B,H,W,1], mask = 1.0 where tri_ind >= 0 else 0.0.  fp32 in a stated order, bit-exact against numpy
+    (include/fr_hotpath.h).  Nothing requires grad.  Runs on the current stream."""
+    h = _host()
+    t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
+    n_c = h.require_gpu_f32(normal.detach(), "normal")
+    ti_c = h.require_gpu_f32(tri_ind.detach(), "tri_ind")
+    l_c = h.require_gpu_f32(light.detach(), "light")
+    if n_c.dim() != 4 or n_c.shape[3] != 3:
+        raise ValueError("synth_shade expects normal [B,H,W,3]")
+    B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+    dev = n_c.device
+    bg_c, bg_batch = None, 0
+    if background is not None:
+        bg_c = h.require_gpu_f32(background.detach(), "background")
+        bg_batch = int(bg_c.shape[0]) if bg_c.dim() == 4 else -1
+        if bg_batch not in (1, B) or tuple(bg_c.shape[1:]) != (H, W, 1):
+            raise ValueError("synth_shade: background must be [1,%d,%d,1] or [%d,%d,%d,1] (got %s)"
+                             % (H, W, B, H, W, tuple(bg_c.shape)))
+    for t, name, shape in ((t_c, "tex_img", (B, H, W, 3)), (ti_c, "tri_ind", (B, H, W, 1)), (l_c, "light", (B, 4))):
+        if tuple(t.shape) != shape:
+            raise ValueError("synth_shade: %s must be %s (got %s)" % (name, list(shape), tuple(t.shape)))
+    for t, name in ((t_c, "tex_img"), (ti_c, "tri_ind"), (l_c, "light"), (bg_c, "background")):
+        if t is not None and t.device != dev:
+            raise ValueError("synth_shade: %s is on %s, normal on %s" % (name, t.device, dev))
+    if out is None:
+        out = (torch.empty((B, H, W, 1), dtype=torch.float32, device=dev), torch.empty((B, H, W, 1), dtype=torch.float32, device=dev))
+    im_gray, mask = out
+    for t, name in ((im_gray, "im_gray"), (mask, "mask")):
+        if h.require_gpu_f32(t, name) is not t or tuple(t.shape) != (B, H, W, 1) or t.device != dev:
+            raise ValueError("synth_shade: out %s must be a contiguous float32 tensor [%d,%d,%d,1] on %s" % (name, B, H, W, dev))
+    with torch.cuda.device(dev):
+        rc = h.lib().fr_synth_shade(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(bg_c), bg_batch, B, H, W, float(gain),
+                                    float(offset), h.ptr(im_gray), h.ptr(mask), h.stream_ptr(dev))
+    h.check(rc, "fr_synth_shade")
+    return im_gray, mask
+
+
 def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     """One-pass rendering layer: returns (net_input [B,H,W,7] = [mask*im | pncc | normal],
     depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers.

@@ -67,6 +67,21 @@ def build_harness(args, dev, rank, world, local):
                                                         beta=0.7, seed=seed + rank), device=dev)
         return im, lab
     train_b, val_b = batch(200), batch(300)
+    train_s = val_s = None
+    if args.synth_data:
+        # --synth-data: a fresh batch every step whose image depicts its label (pipeline.SynthBatches: sampled, decoded, rendered
+        # and shaded on a side stream); train and validation draw from two streams with disjoint seeds, every rank its own faces
+        pipe = pkg("pipeline")
+        kw = dict(slots=2, first_face=pipe.synth_face_range(0, rank, world, B)[0], stride=world * B,
+                  focal=1e-3 * S / 200.0 if args.small else 1e-3)
+        train_s = pipe.SynthBatches(face, B, args.synth_seed, **kw)
+        val_s = pipe.SynthBatches(face, B, args.synth_seed + 1, **kw)
+
+    def draw(stream, resident):
+        if stream is None:
+            return resident
+        b = stream.next()
+        return b["im_gray"], b["params"]
 
     def forward_loss(im, lab):
         out = net(im)
@@ -83,16 +98,16 @@ def build_harness(args, dev, rank, world, local):
     def step():
         if not args.train:
             with torch.no_grad():
-                return net(*train_b[:1]), None
+                return net(*draw(train_s, train_b)[:1]), None
         model.train()
-        out, L = forward_loss(*train_b)
+        out, L = forward_loss(*draw(train_s, train_b))
         opt.zero_grad(set_to_none=True)
         L["total_loss"].backward()
         opt.step()
         if args.val:  # trainval.py:96-99: a second full forward on a validation batch every iteration
             model.eval()
             with torch.no_grad():
-                forward_loss(*val_b)
+                forward_loss(*draw(val_s, val_b))
         return out, L
 
     return model, net, opt, step
@@ -118,12 +133,28 @@ def run_test_phase(args, dev, rank, world, local, dist_u):
     flights = pipe.BatchesInFlight(face, B, S, S, slots=2)
     g = torch.Generator(device="cpu").manual_seed(100 + rank)
     images = [torch.rand((B, S, S, 1), generator=g).to(dev) for _ in range(4)]   # the "test generator": four resident batches
+    # --synth-data: the test generator is a pipeline.SynthBatches stream instead -- rendered faces of known parameters, with the
+    # ground-truth depth and mask the reference's evaluation never had (trainval.py:204: "TODO: Load ground truth ...")
+    n_warm = max(args.warmup, 1)
+    synth_kw = dict(slots=2, stride=world * B, focal=1e-3 * S / 200.0 if args.small else 1e-3)
+    stream = None
+    if args.synth_data:
+        stream = pipe.SynthBatches(face, B, args.synth_seed + 2, first_face=pipe.synth_face_range(0, rank, world, B)[0], **synth_kw)
+    # squared depth error over the mask, and the mask's pixels
+    err = torch.zeros(2, dtype=torch.float64, device=dev) if stream is not None else None
+
+    def draw(k, src=None):
+        src = stream if src is None else src
+        return src.next() if src is not None else {"im_gray": images[k % len(images)]}
 
     dumped = []   # --dump-batches: what every timed batch left in its slot (copied out by the CONSUMER, on the current stream)
 
-    def consume(slot, keep=False):
+    def consume(slot, batch, keep=False):
         """trainval.py:196: depth_images = pred_depth * 255.0, one image per face (written to disk there)."""
         slot.make_current_stream_wait()
+        if err is not None:   # coarse_depth_map against the ground truth, over the ground truth's mask
+            d = (slot.depth.clamp_min(1e-6) - batch["depth"]).double()
+            err.add_(torch.stack([(d * d * batch["mask"]).sum(), batch["mask"].sum().double()]))
         if keep:
             dumped.append([t.clone() for t in (slot.params, slot.vertex_proj.contiguous()) + tuple(slot.outputs())])
         return (slot.depth.clamp_min(1e-6) * 255.0).sum(dim=(1, 2, 3))
@@ -132,34 +163,47 @@ def run_test_phase(args, dev, rank, world, local, dist_u):
         sums, pending = [], None
         with torch.no_grad():
             for k in range(n):
-                params = coarse(images[k % len(images)])           # the dependent chain of THIS batch (current stream)
+                batch = draw(k)
+                params = coarse(batch["im_gray"])                   # the dependent chain of THIS batch (current stream)
                 slot = flights.submit(params)                       # its depth rendering: the slot's stream, nothing waits for it yet
                 if pending is not None:
-                    sums.append(consume(pending, keep))             # batch k-1's planes, behind ITS slot
-                pending = slot
-            sums.append(consume(pending, keep))
+                    sums.append(consume(*pending, keep))            # batch k-1's planes, behind ITS slot
+                pending = (slot, batch)                             # (a synthetic batch stays valid for two draws)
+            sums.append(consume(*pending, keep))
         return sums
 
-    loop(max(args.warmup, 1))
+    loop(n_warm)
     torch.cuda.synchronize(dev)
+    if err is not None:
+        err.zero_()
     dist_u.barrier()
     t0 = time.perf_counter()
     sums = loop(args.steps, keep=bool(args.dump_batches))
     torch.cuda.synchronize(dev)
     dt = dist_u.max_over_ranks(time.perf_counter() - t0, device=dev)
+    depth_rmse = None
+    if stream is not None:
+        se, px = (dist_u.sum_over_ranks(float(v), device=dev) for v in err.tolist())
+        depth_rmse = (se / px) ** 0.5 if px > 0 else float("nan")
     if args.dump_batches and rank == 0:
         # every timed batch's predicted parameters, vertices and four planes as the consumer saw them: tests/test_programs_gpu.py
         # holds them to the CPU oracle (this program never loads it)
         import numpy as np
         names = ("params", "vertex_proj", "depth", "texture_image", "normal", "tri_ind")
         np.savez(args.dump_batches, steps=len(dumped), mu=A["mu"], pc_shape=A["pc_shape"], pc_exp=A["pc_exp"], tri=A["tri"], vertex=A["vertex"],
-                 im_size=S, **{"%s_%d" % (n, k): t.cpu().numpy() for k, rec in enumerate(dumped) for n, t in zip(names, rec)})
+                 im_size=S, **({} if depth_rmse is None else {"depth_rmse": depth_rmse}),
+                 **{"%s_%d" % (n, k): t.cpu().numpy() for k, rec in enumerate(dumped) for n, t in zip(names, rec)})
     # the same batches one at a time through the plain surface: the in-flight loop must reproduce them bit for bit
     with torch.no_grad():
         ref = []
+        again = None
+        if stream is not None:   # the timed loop's faces once more: a face's bits depend on (seed, global face index) alone
+            again = pipe.SynthBatches(face, B, args.synth_seed + 2, first_face=pipe.synth_face_range(n_warm, rank, world, B)[0],
+                                      **synth_kw)
         for k in range(min(args.steps, len(images))):
-            p = coarse(images[k])
-            d = face.coarse_net_input(face.vertices_transform(p), im_gray=images[k])[1]
+            im = draw(k, again)["im_gray"]
+            p = coarse(im)
+            d = face.coarse_net_input(face.vertices_transform(p), im_gray=im)[1]
             ref.append((d * 255.0).sum(dim=(1, 2, 3)))
     same = all(torch.equal(a, b) for a, b in zip(sums, ref))
     dist_info = dist_u.describe(device=dev)
@@ -171,7 +215,9 @@ def run_test_phase(args, dev, rank, world, local, dist_u):
                           "route": "CoarseNet on torch's current stream; depth_rendering_layer of batch k through "
                                    "pipeline.BatchesInFlight.submit() beside the network of batch k + 1; consumer ordered with "
                                    "make_current_stream_wait()",
-                          "depth_identical_to_one_batch_at_a_time": bool(same), "dist": dist_info}))
+                          "depth_identical_to_one_batch_at_a_time": bool(same), "dist": dist_info},
+                   **({} if depth_rmse is None else {"data": "synthetic, rendered on the device (pipeline.SynthBatches)",
+                                                     "depth_rmse": depth_rmse, "synth_seed": args.synth_seed})))
     dist_u.finalize()
     return 0 if same else 1
 
@@ -263,6 +309,13 @@ def build_parser():
                          "of the largest, so the reference's 1e-15 cuts them unpredictably -- as it does in the reference itself.  "
                          "A cutoff such as 1e-6 makes the term well defined everywhere and is the sensible choice once the term "
                          "carries a gradient (--sfs-grad)")
+    ap.add_argument("--synth-data", action="store_true",
+                    help="train, validate and test on batches made on the device (pipeline.SynthBatches): random parameters, the face "
+                         "they decode to rendered with a random per-face albedo and lighting, a fresh batch every step -- the image "
+                         "depicts its label.  With --phase test the loop also reports depth_rmse, the RMSE of the coarse depth map "
+                         "against the ground-truth depth over its mask; off: random images beside unrelated random labels")
+    ap.add_argument("--synth-seed", type=int, default=3456, help="with --synth-data: the seed of the training stream (validation "
+                                                                 "takes seed + 1, the test phase seed + 2)")
     ap.add_argument("--small", action="store_true", help="tiny synthetic assets (smoke runs)")
     ap.add_argument("--dump-batches", default=None, metavar="FILE.npz",
                     help="--phase test: save every timed batch's parameters, vertices and planes (as its consumer saw them) for an "
@@ -324,6 +377,9 @@ def main():
                "params_finite": bool(torch.isfinite(out["pred_params"]).all())}
         if L is not None:
             rec["losses"] = {k: float(v) for k, v in L.items()}
+        if args.synth_data:
+            rec["data"] = "synthetic, rendered on the device (pipeline.SynthBatches)"
+            rec["synth_seed"] = args.synth_seed
         _emit(rec)
     dist_u.finalize()
 

@@ -994,6 +994,59 @@ int fr_albedo_lse_forward(const void* basis, const float* tri_ind, const void* l
  * by tests/test_albedo_lse_gpu.py to place their shapes on the tile's edges. */
 void fr_debug_albedo_lse_geom(int B, int H, int W, int K, int* out);
 
+/* ---- synthetic batches: sample, blend the albedo, shade (opt-in; a data source, no backward) ----------------------------------------
+ * The method trains CoarseNet on RENDERED faces of random parameters; the reference pairs a photograph with an unrelated random
+ * vector instead (prepare_data/script_generate_dataset.m:105-106).  The decode, the rasteriser with a per-face [B,3,N] texture and
+ * the normal map are here already; these three entry points are the rest: parameters drawn where they are consumed, the albedo per
+ * face, and the gray image of (tex_img, normal, tri_ind) under a first-order lighting.  pipeline.SynthBatches strings them together.
+ * ARITHMETIC.  fp32 in the written order, every operation rounded on its own (no contraction), IEEE division and square root: a
+ * float32 model reproduces every output bit (tests/ref_synth_batch.py).  No entry point needs a workspace; nothing is allocated
+ * or synchronised; each makes one launch, can be captured in a graph and is reentrant under the rules at the top of this file.
+ * NAMES.  The stream parameter is called `stream`, as in the sections above.
+ * SAMPLER.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key = (seed lo, seed hi),
+ * counter = (j >> 2, g lo, g hi, 0) with g = first_face + b the GLOBAL face index (mod 2^64) and j the draw's index within the
+ * face; draw j takes output word j & 3, and u = (float)(word >> 8) * 2^-24 in [0, 1).  A face's values depend on (seed, g) and the
+ * sizes alone -- not on B, on the launch geometry, or on which call or rank drew them.  Draw order:
+ *   phi, gamma, theta, f, tx, ty, shape[0 .. n_shape), exp[0 .. n_exp), light[0 .. 4), alpha[0 .. K)
+ * with the distributions of the reference's get_random_params.m (utils/synth.get_random_params), c = fl32(pi / 180):
+ *   phi = (-75 + 120 u) c    gamma = (-90 + 180 u) c    theta = (-30 + 60 u) c    f = u focal    tx, ty = 60 u    tz = 0
+ *   pose = beta base + (1 - beta) rand,  base = (0, 0, 0, im_size / 2, im_size / 2, 0, focal);  (1 - beta) is formed once
+ *   shape = u 1e4    exp = -1.5 + 3 u    light_k = lo_k + (hi_k - lo_k) u    alpha_k = lo_k + (hi_k - lo_k) u
+ * focal is the reference's 1e-3 (a smaller image takes a smaller one).  The kernel holds no transcendental function.
+ *   params [B, 7 + n_shape + n_exp] in the 235-d layout [phi, gamma, theta, tx, ty, tz, f | shape | exp], light [B,4], alpha [B,K]:
+ *   device fp32.  light_ranges [4][2], alpha_ranges [K][2]: HOST arrays of (lo, hi) pairs, read before the call returns.
+ * Checks, in this order: B < 1, a negative n_shape, n_exp or K, a beta outside [0, 1], an im_size or focal that is not finite is
+ * FR_ERR_INVALID_ARG; K > FR_SYNTH_MAX_TEX, B > 65,535 or 2^31 - 64 draws per face is FR_ERR_UNSUPPORTED; a NULL params, light or light_ranges -- or, with
+ * K > 0, alpha or alpha_ranges -- is FR_ERR_INVALID_ARG; a range pair that is not finite or has lo > hi is FR_ERR_INVALID_ARG.
+ * K == 0 draws no albedo and touches neither alpha pointer.  One lane per draw: the four lanes of a block each run the ten rounds.
+ * TEXTURE.  tex[b][c][p] = mu_tex[c][p] + sum_k pc_tex[c N + p][k] alpha[b][k] as the chain acc = acc + pc alpha, k ascending from
+ * acc = mu_tex: mu_tex [3,N], pc_tex [3N,K] row-major, alpha [B,K], tex [B,3,N] -- what fr_render_depth_forward takes as a
+ * per-face texture (tex_batch = B).  Checks: B < 1, N < 1 or K < 0 is FR_ERR_INVALID_ARG; B > 65,535 is FR_ERR_UNSUPPORTED; a NULL
+ * mu_tex or tex -- or, with K > 0, pc_tex or alpha -- is FR_ERR_INVALID_ARG.  K == 0 gives tex = mu_tex for every face.  One lane
+ * per (c, p) row and face of a group of eight: a workgroup fetches its 256 rows of pc_tex (256 K contiguous floats) once per group,
+ * coalesced, through LDS, and writes 64 contiguous floats per wave and face; every output keeps its own chain.
+ * SHADE, per pixel, over the planes of a render: tex_img, normal (the op's RAW normal) [B,H,W,3], tri_ind [B,H,W,1], light [B,4],
+ * background NULL (bg_batch 0), [1,H,W,1] (bg_batch 1) or [B,H,W,1] (bg_batch B).  A pixel is COVERED iff tri_ind >= 0.  An
+ * uncovered pixel gets im_gray = its background pixel (0 without one) and mask = 0.  A covered one gets mask = 1 and
+ *   a = ((m(t0) + m(t1)) + m(t2)) / 3.0f,  m(t) = t < 1e-6 ? 1e-6 : t                  (a NaN stays a NaN)
+ *   n = -n where n_z < 0;  mag = (nx nx + ny ny) + nz nz, replaced by 1 unless mag > 1e-6;  n^ = n / (sqrt(mag) + 1e-6)
+ *   s = ((l0 + l1 n^x) + l2 n^y) + l3 n^z;   I = a (s < 0 ? 0 : s);   im_gray = I gain + offset
+ * -- the conventions of FaceRecNet.compute_abedo_image, then a relu(l . n^).  A pixel's outputs depend on that pixel's inputs and
+ * its face's light alone: a NaN in a covered pixel's tex_img or normal makes that pixel's im_gray a NaN and no other's.  Two
+ * exceptions follow from the rules above: a NaN tri_ind is not >= 0, so the pixel is UNCOVERED and gets its (finite) background;
+ * and a NaN in light[b] reaches every covered pixel of face b.  The rasteriser writes neither.  Checks: B, H or W < 1, or a bg_batch that is not 0, 1
+ * or B (0 with a background, or not 0 without one), is FR_ERR_INVALID_ARG; a NULL tex_img, normal, tri_ind, light, im_gray or mask
+ * is FR_ERR_INVALID_ARG; more than 2^31 - 1 pixels per face or B > 65,535 is FR_ERR_UNSUPPORTED.  One lane per pixel: 28 bytes
+ * read and 8 written per covered pixel, 4 (+ 4 of background) and 8 per uncovered one.
+ * Time: tools/synth_batch_probe.py (profiles/synth_batch.json). */
+enum { FR_SYNTH_MAX_TEX = 64 }; /* albedo coefficients per face the sampler serves (their ranges travel in the launch's arguments) */
+int fr_synth_params(unsigned long long seed, unsigned long long first_face, int B, int n_shape, int n_exp, int K, float im_size,
+                    float beta, float focal, const float* light_ranges, const float* alpha_ranges, float* params, float* light,
+                    float* alpha, void* stream);
+int fr_synth_texture(const float* mu_tex, const float* pc_tex, const float* alpha, int B, int N, int K, float* tex, void* stream);
+int fr_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* background,
+                   int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray, float* mask, void* stream);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
