@@ -17,9 +17,9 @@ _CSRC = os.path.join(_PKG_DIR, "csrc")
 LIB_PATH = os.path.join(_PKG_DIR, "libfr_hotpath.so")
 SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_bwd.hip", "fr_render_nbwd.hip",
            "fr_render_tbwd.hip", "fr_sfs.hip", "fr_depth_normals.hip", "fr_geometry.hip", "fr_fine_losses.hip", "fr_depth_interp.hip",
-           "fr_albedo_lse.hip", "fr_synth.hip"]
+           "fr_albedo_lse.hip", "fr_synth.hip", "fr_photo.hip"]
 HEADERS = [os.path.join(_CSRC, "fr_common.h"), os.path.join(_CSRC, "fr_decode_shared.h"), os.path.join(_CSRC, "fr_sfs_pinv.h"),
-           os.path.join(_CSRC, "fr_owner_scatter.h"), os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
+           os.path.join(_CSRC, "fr_owner_scatter.h"), os.path.join(_CSRC, "fr_shade.h"), os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]  # single-lane LDS atomics stay single instructions
 
@@ -200,6 +200,12 @@ SIGNATURES = {
     "fr_synth_params":                                "i:uuiiiifffpppppp",
     "fr_synth_texture":                               "i:pppiiipp",
     "fr_synth_shade":                                 "i:pppppiiiiffppp",
+    "fr_synth_texture_backward_workspace_bytes":      "z:iii",
+    "fr_synth_texture_backward":                      "i:ppiiippzp",
+    "fr_photo_loss_state_bytes":                      "z:iii",
+    "fr_photo_loss_forward":                          "i:ppppppiiiffppzp",
+    "fr_photo_loss_backward":                         "i:ppppppppiiiffpppp",
+    "fr_debug_photo_loss_geom":                       "v:iiiI",
     "fr_debug_render_geom":                           "v:iiiiiI",
     "fr_debug_decode_bwd_geom":                       "v:iiiiI",
     "fr_debug_decode_geom":                           "i:iiiiiI",

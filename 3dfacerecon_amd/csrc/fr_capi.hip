@@ -615,6 +615,18 @@ int fr_synth_texture(const float* mu_tex, const float* pc_tex, const float* alph
     return fr_launch_synth_texture(mu_tex, pc_tex, alpha, B, N, K, tex, (hipStream_t)stream);
 }
 
+size_t fr_synth_texture_backward_workspace_bytes(int B, int N, int K) { return fr_synth_texture_backward_workspace_impl(B, N, K); }
+
+int fr_synth_texture_backward(const float* pc_tex, const float* grad_tex, int B, int N, int K, float* grad_alpha, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (B < 1 || N < 1 || K < 0) return FR_ERR_INVALID_ARG;
+    if (B > 65535 || (long long)N * 3 > 0x7FFFFFFFll - 256 || (long long)B * K > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
+    if (K == 0) return FR_OK;   // an empty gradient: nothing launched, nothing read
+    if (!pc_tex || !grad_tex || !grad_alpha) return FR_ERR_INVALID_ARG;
+    if (!ws_ok(workspace, workspace_bytes, fr_synth_texture_backward_workspace_impl(B, N, K), 16)) return FR_ERR_WORKSPACE;
+    return fr_launch_synth_texture_backward(pc_tex, grad_tex, B, N, K, grad_alpha, workspace, (hipStream_t)stream);
+}
+
 int fr_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* background,
                    int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray, float* mask, void* stream) {
     if (B < 1 || H < 1 || W < 1) return FR_ERR_INVALID_ARG;

@@ -93,6 +93,28 @@ __device__ __forceinline__ bool point_in_tri(const TriSetup& s, int x, int y) {
     return u + v < 1;
 }
 
+// The float64 lane tree of the photometric loss and the albedo blend's adjoint: v[i] = v[i] + v[i + k] for k = 32, 16, 8, 4, 2, 1;
+// lane 0 ends with the wave's sum, every lane takes part.  Only the lanes i < k of a step feed the result, and for k <= 8 those and
+// their sources i + k lie in the first row of 16 lanes: these four steps move the two words by DPP row_shl (lane i <- lane i + k
+// of its row; a lane whose source lies past its row gets 0, never a lane the tree reads) instead of through the LDS crossbar that
+// __shfl_down takes.  Same additions in the same order as six __shfl_down steps: same bits.
+template <int K>
+__device__ __forceinline__ double row_shl_f64(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(0, lo, 0x100 + K, 0xF, 0xF, true);
+    hi = __builtin_amdgcn_update_dpp(0, hi, 0x100 + K, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double wave_tree_f64(double v) {
+    v = v + __shfl_down(v, 32u, 64);
+    v = v + __shfl_down(v, 16u, 64);
+    v = v + row_shl_f64<8>(v);
+    v = v + row_shl_f64<4>(v);
+    v = v + row_shl_f64<2>(v);
+    v = v + row_shl_f64<1>(v);
+    return v;
+}
+
 }  // namespace fr
 
 // Raise a kernel's dynamic-LDS limit to the CU's full 160 KiB, once per (kernel, device): not a stream operation, so
@@ -220,3 +242,7 @@ int fr_launch_synth_texture(const float* mu_tex, const float* pc_tex, const floa
 int fr_launch_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light,
                           const float* background, int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray,
                           float* mask, hipStream_t stream);
+// the blend's adjoint: partials [row tile][b][k] in the workspace, then the finish step
+size_t fr_synth_texture_backward_workspace_impl(int B, int N, int K);
+int fr_launch_synth_texture_backward(const float* pc_tex, const float* grad_tex, int B, int N, int K, float* grad_alpha,
+                                     void* workspace, hipStream_t stream);

@@ -1,8 +1,10 @@
 // On-device synthetic training batches (include/fr_hotpath.h, "synthetic batches"): the counter-based parameter sampler, the per-face
 // albedo blend and the shading / compositing post-pass over a render's planes.  All three are streaming or tiny: one lane per
 // element, coalesced, no atomics; LDS only to turn the texture basis' row-major reads into coalesced ones.  fp32 in the header's
-// stated order, one rounding per operation (-ffp-contract=off).
+// stated order, one rounding per operation (-ffp-contract=off).  The blend has an adjoint (synth_texture_bwd_kernel and its finish
+// step): float64 sums of exact products in an association that is a function of (N, K) alone.
 #include "fr_common.h"
+#include "fr_shade.h"
 
 namespace fr {
 
@@ -114,6 +116,61 @@ __global__ __launch_bounds__(TX_ROWS) void synth_texture_kernel(const float* __r
         if (f < nb) tex[(size_t)(b0 + f) * 3 * N + row] = acc[f];
 }
 
+// The blend's adjoint, grad_alpha[b][k] = sum over the 3N rows r of pc_tex[r][k] * grad_tex[b][r], mirrors the forward's tiling over the
+// FLAT row index r: a workgroup owns TX_ROWS consecutive rows and a group of TX_FACES faces, one lane per row; it stages its run of
+// pc_tex TX_KC columns at a time in LDS (fetched once per group of faces, coalesced) and keeps its rows of grad_tex in registers.
+// Every product of two widened fp32 values is exact in float64; the 256 products of a (face, column) meet in the fixed lane tree
+// (groups of 64 with k = 32 .. 1, then (w0 + w2) + (w1 + w3); a row past 3N holds +0.0) and go out as one partial
+// [b][k][row tile].  synth_texture_bwd_finish_kernel: one wave per (b, k); lane i chains the partials of the row tiles i, i + 64, ..
+// in ascending order from +0.0 (contiguous reads), the 64 chains meet in the same lane tree, one rounding to fp32.  No atomics.
+__global__ __launch_bounds__(TX_ROWS) void synth_texture_bwd_kernel(const float* __restrict__ pc_tex, const float* __restrict__ grad_tex,
+                                                                    int B, int R, int K, double* __restrict__ part) {
+    __shared__ float tile[TX_ROWS * (TX_KC + 1)];
+    __shared__ double wsum[TX_FACES][TX_KC][TX_ROWS / 64];
+    const int tid = (int)threadIdx.x;
+    const int row0 = (int)blockIdx.x * TX_ROWS;
+    const int b0 = (int)blockIdx.y * TX_FACES;
+    const int nb = min(TX_FACES, B - b0), nrows = min(TX_ROWS, R - row0);
+    const bool live = tid < nrows;
+    double g[TX_FACES];
+#pragma unroll
+    for (int f = 0; f < TX_FACES; f++) g[f] = (live && f < nb) ? (double)grad_tex[(size_t)(b0 + f) * R + row0 + tid] : 0.0;
+    const float* src = pc_tex + (size_t)row0 * (size_t)K;
+    for (int k0 = 0; k0 < K; k0 += TX_KC) {
+        const int kc = min(TX_KC, K - k0);
+        if (k0) __syncthreads();   // (the last chunk's tile and wave sums have been read)
+        for (int e = tid; e < nrows * kc; e += TX_ROWS) {
+            const int r = e / kc, kk = e - r * kc;
+            tile[r * (TX_KC + 1) + kk] = src[(size_t)r * K + k0 + kk];
+        }
+        __syncthreads();
+        for (int kk = 0; kk < kc; kk++) {
+            const double pc = live ? (double)tile[tid * (TX_KC + 1) + kk] : 0.0;
+#pragma unroll
+            for (int f = 0; f < TX_FACES; f++) {
+                if (f < nb) {   // (workgroup-uniform)
+                    const double v = wave_tree_f64(live ? pc * g[f] : 0.0);
+                    if ((tid & 63) == 0) wsum[f][kk][tid >> 6] = v;
+                }
+            }
+        }
+        __syncthreads();
+        if (tid < nb * kc) {
+            const int f = tid / kc, kk = tid - f * kc;
+            part[((size_t)(b0 + f) * K + k0 + kk) * gridDim.x + blockIdx.x] =
+                (wsum[f][kk][0] + wsum[f][kk][2]) + (wsum[f][kk][1] + wsum[f][kk][3]);
+        }
+    }
+}
+__global__ __launch_bounds__(64) void synth_texture_bwd_finish_kernel(const double* __restrict__ part, int tiles,
+                                                                      float* __restrict__ grad_alpha) {
+    const double* mine = part + (size_t)blockIdx.x * tiles;   // blockIdx.x = b K + k
+    double acc = 0.0;
+    for (int t = (int)threadIdx.x; t < tiles; t += 64) acc = acc + mine[t];
+    acc = wave_tree_f64(acc);
+    if (threadIdx.x == 0) grad_alpha[blockIdx.x] = (float)acc;
+}
+
 // one lane per pixel
 __global__ __launch_bounds__(256) void synth_shade_kernel(const float* __restrict__ tex_img, const float* __restrict__ normal,
                                                           const float* __restrict__ tri_ind, const float* __restrict__ light,
@@ -128,17 +185,9 @@ __global__ __launch_bounds__(256) void synth_shade_kernel(const float* __restric
         mask[i] = 0.0f;
         return;
     }
-    const float t0 = tex_img[3 * i], t1 = tex_img[3 * i + 1], t2 = tex_img[3 * i + 2];
-    // (x < 1e-6 ? 1e-6 : x: a NaN stays a NaN, as torch.clamp_min)
-    const float a = fr::div3(((t0 < 1e-6f ? 1e-6f : t0) + (t1 < 1e-6f ? 1e-6f : t1)) + (t2 < 1e-6f ? 1e-6f : t2));
-    float nx = normal[3 * i], ny = normal[3 * i + 1], nz = normal[3 * i + 2];
-    if (nz < 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
-    float mag = (nx * nx + ny * ny) + nz * nz;
-    mag = (mag > 1e-6f) ? mag : 1.0f;
-    const float d = sqrtf(mag) + 1e-6f;
-    const float* l = light + (size_t)b * 4;
-    const float s = ((l[0] + l[1] * (nx / d)) + l[2] * (ny / d)) + l[3] * (nz / d);
-    const float I = a * (s < 0.0f ? 0.0f : s);
+    fr::Shade sh;
+    const float I = fr::shade_pixel(tex_img[3 * i], tex_img[3 * i + 1], tex_img[3 * i + 2], normal[3 * i], normal[3 * i + 1],
+                                    normal[3 * i + 2], light + (size_t)b * 4, sh);   // (fr_shade.h: the photometric loss runs it too)
     im_gray[i] = I * gain + offset;
     mask[i] = 1.0f;
 }
@@ -172,5 +221,22 @@ int fr_launch_synth_shade(const float* tex_img, const float* normal, const float
     const int HW = H * W;
     hipLaunchKernelGGL(fr::synth_shade_kernel, dim3((unsigned)(((long long)HW + 255) / 256), (unsigned)B, 1), dim3(256, 1, 1), 0, stream,
                        tex_img, normal, tri_ind, light, background, bg_batch, HW, gain, offset, im_gray, mask);
+    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
+
+size_t fr_synth_texture_backward_workspace_impl(int B, int N, int K) {
+    if (B < 1 || N < 1 || K < 1 || B > 65535 || (long long)N * 3 > 0x7FFFFFFFll - fr::TX_ROWS || (long long)B * K > 0x7FFFFFFFll) return 0;
+    const size_t tiles = (size_t)((3ll * N + fr::TX_ROWS - 1) / fr::TX_ROWS);
+    return tiles * (size_t)B * (size_t)K * sizeof(double);
+}
+
+int fr_launch_synth_texture_backward(const float* pc_tex, const float* grad_tex, int B, int N, int K, float* grad_alpha,
+                                     void* workspace, hipStream_t stream) {
+    const int R = 3 * N, tiles = (R + fr::TX_ROWS - 1) / fr::TX_ROWS, BK = B * K;
+    double* part = (double*)workspace;
+    hipLaunchKernelGGL(fr::synth_texture_bwd_kernel, dim3((unsigned)tiles, (unsigned)((B + fr::TX_FACES - 1) / fr::TX_FACES), 1),
+                       dim3(fr::TX_ROWS, 1, 1), 0, stream, pc_tex, grad_tex, B, R, K, part);
+    hipLaunchKernelGGL(fr::synth_texture_bwd_finish_kernel, dim3((unsigned)BK, 1, 1), dim3(64, 1, 1), 0, stream, (const double*)part, tiles,
+                       grad_alpha);
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }

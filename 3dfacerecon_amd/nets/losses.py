@@ -6,7 +6,10 @@ BASELINE.json config 4.  Stock torch ops, except where the
     form in the coefficient differences, evaluated from the basis's Gram matrix (FaceRecNet.geometry_loss(gram=True)) -- and
   * the shape-from-shading model issues two more render_depth calls (network.py:423, 454 through compute_abedo_image), and
   * opt-in (fine_fused=True), the fidelity and the smoothness term of the fine depth map are one kernel pass per direction
-    (rendering_layer/ops.py::fine_depth_losses) instead of a chain of elementwise ops, a convolution and two reductions.
+    (rendering_layer/ops.py::fine_depth_losses) instead of a chain of elementwise ops, a convolution and two reductions, and
+  * opt-in (photo_light / photo_alpha), a photometric term compares the face rendered and shaded under a given lighting and albedo
+    with the picture itself (photometric_loss: synth_texture -> render_depth -> rendering_layer/ops.py::photo_loss), with a
+    gradient to the geometry, the lighting and the albedo coefficients.
 
 Names and weights follow the reference: pose MSE (lambda 1e-3), geometry MSE through the basis (1e-6), spherical
 harmonics / SfS MSE (1e-3), fidelity MSE between the coarse and the fine depth map (100), Laplacian-L1 smoothness (1e-5)
@@ -210,6 +213,24 @@ def _sfs_model_alpha_lse(fn, vertices_proj, im_gray, kw, normal_grad, rcond, fin
     return spherical_harmonics_intensity(abedo_image, normal_map, im_gray, abedo_new, normal_new, fused=True, rcond=rcond)
 
 
+def photometric_loss(face_net, vertices_proj, im_gray, light, alpha, weight=None, gain=1.0, offset=0.0):
+    """The analysis-by-synthesis term: the mean over the covered pixels of weight (I^ - im_gray)^2, with I^ the face of
+    vertices_proj [B,3,N] rendered with the per-face albedo mu_tex + pc_tex . alpha_b and shaded under the first-order lighting
+    light [B,4] -- the image pipeline.SynthBatches makes of the same quantities, bit for bit (gain, offset: that stream's).
+    synth_texture -> render_depth(normal_grad=True, texture_grad=True) -> photo_loss (rendering_layer/ops.py): the gradient reaches
+    vertices_proj (x, y and z, through the normal map; tri_ind held fixed), light and alpha, wherever they require grad.  im_gray
+    [B,H,W,1] and weight (None = 1) are constants.  -> a 0-dim float64 tensor, sse.sum() / count.sum().clamp_min(1); each rank
+    takes the mean over its own faces (no collective)."""
+    fn = face_net
+    if fn.mu_tex is None or fn.pc_tex is None:
+        raise ValueError("the asset dict has no texture model (mu_tex / pc_tex)")
+    ops = _ops()
+    tex = ops.synth_texture(fn.mu_tex, fn.pc_tex, alpha)
+    _, tex_img, normal, tri_ind = ops.render_depth(vertices_proj.float(), fn.tri, tex, im_gray, normal_grad=True, texture_grad=True)
+    sse, count = ops.photo_loss(tex_img, normal, tri_ind.detach(), light, im_gray.detach(), weight, gain, offset)
+    return sse.sum() / count.sum().clamp_min(1)
+
+
 def combine_losses(losses):
     """total = 1e-3 pose + 1e-6 geometry + 1e-3 SfS + 100 fidelity + 1e-5 smoothness (network.py:27-31, 373)"""
     return (LAMBDA_POSE * losses['pose_loss'] + LAMBDA_GEO * losses['geometry_loss'] +
@@ -220,6 +241,7 @@ def combine_losses(losses):
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
              gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False,
              sfs_fused_gather=False, sfs_fine=False, fine_fused=False, sfs_alpha_lse=False, sfs_alpha_ridge=1e-6,
+             photo_light=None, photo_alpha=None, photo_weight=None, photo_gain=1.0, photo_offset=0.0, lambda_photo=1.0,
              geometry_gram=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
     sfs_normal_grad / sfs_fused / sfs_rcond (defaults: off, off, the reference's 1e-15): the normal_grad / fused / rcond of
@@ -242,8 +264,14 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     is None.  Each rank sums over its own faces: no collective.
     sfs_alpha_lse=True / sfs_alpha_ridge (default off, 1e-6): the alpha_lse / alpha_ridge of get_spherical_harmonics_model -- the
     term's albedo is fitted per face instead of shared; needs sfs_fused, excludes sfs_tex_grad, gather_sfs and sfs_fused_gather
-    (ValueError)."""
+    (ValueError).
+    photo_light [B,4] / photo_alpha [B,K] (default None: the term is absent, the dict and every bit are today's; one without the
+    other is a ValueError): adds losses['photometric_loss'] = photometric_loss(face_net, vertices_proj, im_gray, photo_light,
+    photo_alpha, photo_weight, photo_gain, photo_offset) -- the rendered and shaded face against im_gray itself -- and lambda_photo
+    times it to total_loss.  Its gradient reaches vertices_proj, and photo_light / photo_alpha where they require grad."""
     fn = face_net
+    if (photo_light is None) != (photo_alpha is None):
+        raise ValueError("photo_light and photo_alpha go together: the photometric term needs the lighting and the albedo coefficients")
     if fine_fused and pred_depth_map is None:
         raise ValueError("fine_fused=True needs pred_depth_map (the fine depth map the two terms are taken of)")
     B = pred_params.shape[0]
@@ -277,4 +305,8 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
         filtered_depth = laplace_transform(pred_depth_map[..., 0])
         losses['smoothness_loss'] = filtered_depth.abs().sum()    # tf.contrib.layers.l1_regularizer(1.0), network.py:367
     losses['total_loss'] = combine_losses(losses)
+    if photo_light is not None:
+        losses['photometric_loss'] = photometric_loss(fn, vertices_proj, im_gray, photo_light, photo_alpha, weight=photo_weight,
+                                                      gain=photo_gain, offset=photo_offset)
+        losses['total_loss'] = losses['total_loss'] + (lambda_photo * losses['photometric_loss']).to(losses['total_loss'].dtype)
     return losses

@@ -1083,10 +1083,8 @@ def synth_params(seed, first_face, batch, n_shape, n_exp, n_tex, im_size, beta=0
     return params, light, alpha
 
 
-def synth_texture(mu_tex, pc_tex, alpha, out=None):
-    """The per-face albedo tex [B,3,N] = mu_tex + pc_tex . alpha_b (fr_synth_texture: the chain acc = acc + pc alpha in ascending
-    k from mu_tex, bit-exact against numpy): mu_tex [3,N], pc_tex [3N,K], alpha [B,K].  What render_depth takes as a per-face
-    texture.  K = 0 repeats mu_tex.  Nothing requires grad.  Runs on the current stream."""
+def _synth_texture_call(mu_tex, pc_tex, alpha, out=None):
+    """fr_synth_texture on constants -> (tex [B,3,N], the contiguous pc_tex it read or None)"""
     h = _host()
     mu_c = h.require_gpu_f32(mu_tex.detach(), "mu_tex")
     al_c = h.require_gpu_f32(alpha.detach(), "alpha")
@@ -1112,7 +1110,164 @@ def synth_texture(mu_tex, pc_tex, alpha, out=None):
         rc = h.lib().fr_synth_texture(h.ptr(mu_c), h.ptr(pc_c), h.ptr(al_c) if K > 0 else None, B, N, K, h.ptr(out),
                                       h.stream_ptr(dev))
     h.check(rc, "fr_synth_texture")
-    return out
+    return out, pc_c
+
+
+def synth_texture_backward(pc_tex, grad_tex):
+    """The adjoint of the albedo blend (fr_synth_texture_backward): grad_alpha [B,K] = grad_tex [B,3,N] read as [B,3N] times
+    pc_tex [3N,K], as float64 sums of exact products in an association that is a function of (N, K) alone, rounded once to fp32;
+    bit-reproducible.  Both inputs are constants.  Runs on the current stream with the per-stream scratch as its workspace."""
+    h = _host()
+    g_c = h.require_gpu_f32(grad_tex.detach(), "grad_tex")
+    if g_c.dim() != 3 or g_c.shape[1] != 3:
+        raise ValueError("synth_texture_backward expects grad_tex [B,3,N]")
+    B, N = int(g_c.shape[0]), int(g_c.shape[2])
+    dev = g_c.device
+    K = 0 if pc_tex is None else int(pc_tex.shape[1])
+    grad_alpha = torch.empty((B, K), dtype=torch.float32, device=dev)
+    if K == 0:
+        return grad_alpha
+    pc_c = h.require_gpu_f32(pc_tex.detach(), "pc_tex")
+    if tuple(pc_c.shape) != (3 * N, K) or pc_c.device != dev:
+        raise ValueError("synth_texture_backward: pc_tex must be [%d,%d] on %s (got %s on %s)" % (3 * N, K, dev, tuple(pc_c.shape),
+                                                                                                 pc_c.device))
+    L = h.lib()
+    nws = L.fr_synth_texture_backward_workspace_bytes(B, N, K)
+    with torch.cuda.device(dev), _PH_LOCK:
+        ws = _scratch("synth_texture_backward", dev, nws)
+        rc = L.fr_synth_texture_backward(h.ptr(pc_c), h.ptr(g_c), B, N, K, h.ptr(grad_alpha), h.ptr(ws), ws.numel(), h.stream_ptr(dev))
+    h.check(rc, "fr_synth_texture_backward")
+    return grad_alpha
+
+
+class _SynthTexture(torch.autograd.Function):
+    """fr_synth_texture / fr_synth_texture_backward as one autograd node: (mu_tex, pc_tex, alpha) -> tex [B,3,N], the gradient going
+    to alpha alone.  The node saves pc_tex (by reference) and nothing else: the blend is linear in alpha."""
+
+    @staticmethod
+    def forward(ctx, mu_tex, pc_tex, alpha):
+        tex, pc_c = _synth_texture_call(mu_tex, pc_tex, alpha)
+        ctx.has_pc = pc_c is not None
+        ctx.alpha_shape = tuple(alpha.shape)
+        if ctx.has_pc:
+            ctx.save_for_backward(pc_c)
+        ctx.set_materialize_grads(False)
+        return tex
+
+    @staticmethod
+    def backward(ctx, grad_tex):
+        if grad_tex is None or not ctx.needs_input_grad[2]:
+            return None, None, None
+        if not ctx.has_pc:   # K = 0: an empty gradient
+            return None, None, torch.zeros(ctx.alpha_shape, dtype=torch.float32, device=grad_tex.device)
+        return None, None, synth_texture_backward(ctx.saved_tensors[0], grad_tex)
+
+
+def synth_texture(mu_tex, pc_tex, alpha, out=None):
+    """The per-face albedo tex [B,3,N] = mu_tex + pc_tex . alpha_b (fr_synth_texture: the chain acc = acc + pc alpha in ascending
+    k from mu_tex, bit-exact against numpy): mu_tex [3,N], pc_tex [3N,K], alpha [B,K].  What render_depth takes as a per-face
+    texture.  K = 0 repeats mu_tex.  Where alpha requires grad the call is an autograd node (same forward bits) whose backward
+    is the blend's adjoint, synth_texture_backward (fr_synth_texture_backward); the gradient goes to alpha alone, mu_tex and pc_tex
+    are constants.  out: a tensor to write instead of a fresh one; ValueError with an alpha that requires grad (a caller's buffer
+    cannot be the output of a node).  Runs on the current stream."""
+    if isinstance(alpha, torch.Tensor) and alpha.requires_grad and torch.is_grad_enabled():
+        if out is not None:
+            raise ValueError("synth_texture: out= cannot be combined with an alpha that requires grad")
+        return _SynthTexture.apply(mu_tex, pc_tex, alpha)
+    return _synth_texture_call(mu_tex, pc_tex, alpha, out)[0]
+
+
+_PH_LOCK = threading.Lock()   # keeps the launches of one call together where host threads share a stream's scratch
+
+
+def _photo_plane(h, t, name, B, H, W, dev):
+    t_c = h.require_gpu_f32(t.detach(), name)
+    if tuple(t_c.shape) not in ((B, H, W, 1), (B, H, W)):
+        raise ValueError("photo_loss: %s must be [%d,%d,%d,1] or [%d,%d,%d] (got %s)" % (name, B, H, W, B, H, W, tuple(t_c.shape)))
+    if t_c.device != dev:
+        raise ValueError("photo_loss: %s is on %s, normal on %s" % (name, t_c.device, dev))
+    return t_c
+
+
+class _PhotoLoss(torch.autograd.Function):
+    """fr_photo_loss_forward / _backward (include/fr_hotpath.h, "photometric loss") as one autograd node: (tex_img, normal, tri_ind,
+    light, target, weight, gain, offset) -> (sse [B], count [B]) float64.  It saves its inputs by reference and the forward's
+    sums [B,6] (the lighting gradient is linear in them); nothing plane-sized of its own.  The forward's state (six float64 partials
+    per tile) is dead once the forward has run: it is the per-stream scratch that consecutive calls share; _PH_LOCK keeps the
+    forward's two launches together where host threads share a stream.  The backward asks the kernel only for the outputs
+    needs_input_grad names; target, weight and tri_ind are constants."""
+
+    @staticmethod
+    def forward(ctx, tex_img, normal, tri_ind, light, target, weight, gain, offset):
+        h = _host()
+        L = h.lib()
+        n_c = h.require_gpu_f32(normal.detach(), "normal")
+        if n_c.dim() != 4 or n_c.shape[3] != 3:
+            raise ValueError("photo_loss expects normal [B,H,W,3]")
+        B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+        dev = n_c.device
+        t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
+        l_c = h.require_gpu_f32(light.detach(), "light")
+        if tuple(t_c.shape) != (B, H, W, 3) or t_c.device != dev:
+            raise ValueError("photo_loss: tex_img must be [%d,%d,%d,3] on %s (got %s on %s)" % (B, H, W, dev, tuple(t_c.shape), t_c.device))
+        if tuple(l_c.shape) != (B, 4) or l_c.device != dev:
+            raise ValueError("photo_loss: light must be [%d,4] on %s (got %s on %s)" % (B, dev, tuple(l_c.shape), l_c.device))
+        ti_c = _photo_plane(h, tri_ind, "tri_ind", B, H, W, dev)
+        tg_c = _photo_plane(h, target, "target", B, H, W, dev)
+        w_c = _photo_plane(h, weight, "weight", B, H, W, dev) if weight is not None else None
+        empty = B * H * W == 0
+        sums = (torch.zeros if empty else torch.empty)((B, 6), dtype=torch.float64, device=dev)
+        if not empty:
+            with torch.cuda.device(dev), _PH_LOCK:
+                nst = L.fr_photo_loss_state_bytes(B, H, W)
+                state = _scratch("photo_loss", dev, nst)
+                rc = L.fr_photo_loss_forward(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(tg_c), h.ptr(w_c), B, H, W,
+                                             float(gain), float(offset), h.ptr(sums), h.ptr(state), state.numel(), h.stream_ptr(dev))
+            h.check(rc, "fr_photo_loss_forward")
+        ctx.save_for_backward(t_c, n_c, ti_c, l_c, tg_c, sums, *(() if w_c is None else (w_c,)))
+        ctx.dims = (B, H, W)
+        ctx.scale = (float(gain), float(offset))
+        ctx.shapes = (tuple(tex_img.shape), tuple(normal.shape), tuple(light.shape))
+        ctx.set_materialize_grads(False)
+        sse, count = sums[:, 0].contiguous(), sums[:, 1].contiguous()
+        ctx.mark_non_differentiable(count)
+        return sse, count
+
+    @staticmethod
+    def backward(ctx, g_sse, g_count):
+        if g_sse is None:
+            return (None,) * 8
+        h = _host()
+        t_c, n_c, ti_c, l_c, tg_c, sums = ctx.saved_tensors[:6]
+        w_c = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
+        B, H, W = ctx.dims
+        dev = n_c.device
+        want = ctx.needs_input_grad
+        empty = B * H * W == 0
+        make = torch.zeros if empty else torch.empty
+        gt = make(ctx.shapes[0], dtype=torch.float32, device=dev) if want[0] else None
+        gn = make(ctx.shapes[1], dtype=torch.float32, device=dev) if want[1] else None
+        gl = make(ctx.shapes[2], dtype=torch.float32, device=dev) if want[3] else None
+        if not empty and (want[0] or want[1] or want[3]):
+            g = g_sse.detach().to(device=dev, dtype=torch.float64).contiguous()
+            with torch.cuda.device(dev):
+                rc = h.lib().fr_photo_loss_backward(h.ptr(g), h.ptr(sums), h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(tg_c),
+                                                    h.ptr(w_c), B, H, W, ctx.scale[0], ctx.scale[1], h.ptr(gt), h.ptr(gn), h.ptr(gl),
+                                                    h.stream_ptr(dev))
+            h.check(rc, "fr_photo_loss_backward")
+        return gt, gn, None, gl, None, None, None, None
+
+
+def photo_loss(tex_img, normal, tri_ind, light, target, weight=None, gain=1.0, offset=0.0):
+    """The photometric term of a render's planes against a picture (fr_photo_loss_forward / _backward): per face b,
+    sse[b] = sum over the covered pixels (tri_ind >= 0) of weight (I^ - target)^2 with I^ the image synth_shade makes of the same
+    planes, light, gain and offset -- the same bits -- and count[b] = the covered pixels.  tex_img, normal [B,H,W,3] (the op's raw
+    planes), tri_ind, target, weight [B,H,W,1] or [B,H,W] (weight None = 1), light [B,4]; -> (sse, count), float64 [B], float64
+    sums in an association that is a function of (H, W) alone (bit-reproducible; a face's numbers do not depend on its batch).
+    One autograd node: the gradient of sse reaches tex_img, normal and light (one map pass, no reduction; count is not
+    differentiable; tri_ind, target and weight are constants).  A mean squared error is sse.sum() / count.sum().clamp_min(1).
+    Runs on the current stream."""
+    return _PhotoLoss.apply(tex_img, normal, tri_ind, light, target, weight, gain, offset)
 
 
 def synth_shade(tex_img, normal, tri_ind, light, background=None, gain=1.0, offset=0.0, out=None):

@@ -81,9 +81,12 @@ def build_harness(args, dev, rank, world, local):
         if stream is None:
             return resident
         b = stream.next()
+        if args.photo_loss:   # the batch's own lighting and albedo, and the stream's gain and offset: the image is their shading
+            return b["im_gray"], b["params"], dict(photo_light=b["light"], photo_alpha=b["alpha"], photo_gain=stream.gain,
+                                                   photo_offset=stream.offset, lambda_photo=args.photo_lambda)
         return b["im_gray"], b["params"]
 
-    def forward_loss(im, lab):
+    def forward_loss(im, lab, photo={}):
         out = net(im)
         return out, losses.get_loss(face, out["pred_params"], lab, im, out["vertices_proj"], out["coarse_depth_map"],
                                     out["pred_depth_map"], gather_sfs=args.gather_sfs, sfs_normal_grad=args.sfs_grad,
@@ -93,7 +96,8 @@ def build_harness(args, dev, rank, world, local):
                                     **({"sfs_fine": True} if args.sfs_fine else {}),
                                     **({"geometry_gram": True} if args.geometry_gram else {}),
                                     **({"fine_fused": True} if args.fine_fused else {}),
-                                    **({"sfs_alpha_lse": True, "sfs_alpha_ridge": args.sfs_alpha_ridge} if args.sfs_alpha_lse else {}))
+                                    **({"sfs_alpha_lse": True, "sfs_alpha_ridge": args.sfs_alpha_ridge} if args.sfs_alpha_lse else {}),
+                                    **photo)
 
     def step():
         if not args.train:
@@ -316,6 +320,12 @@ def build_parser():
                          "against the ground-truth depth over its mask; off: random images beside unrelated random labels")
     ap.add_argument("--synth-seed", type=int, default=3456, help="with --synth-data: the seed of the training stream (validation "
                                                                  "takes seed + 1, the test phase seed + 2)")
+    ap.add_argument("--photo-loss", action="store_true",
+                    help="with --synth-data and --train: add the photometric term (get_loss(photo_light=, photo_alpha=); "
+                         "fr_photo_loss_forward / _backward) -- the predicted geometry rendered with the batch's ground-truth albedo "
+                         "and lighting against the batch's image; its gradient reaches the vertices (the pose angles too with "
+                         "--pose-grad); the record gains photometric_loss; off: no term compares a rendered face with the picture")
+    ap.add_argument("--photo-lambda", type=float, default=1.0, help="with --photo-loss: the term's weight in total_loss")
     ap.add_argument("--small", action="store_true", help="tiny synthetic assets (smoke runs)")
     ap.add_argument("--dump-batches", default=None, metavar="FILE.npz",
                     help="--phase test: save every timed batch's parameters, vertices and planes (as its consumer saw them) for an "
@@ -327,7 +337,10 @@ def build_parser():
 
 
 def main():
-    args = build_parser().parse_args()
+    ap = build_parser()
+    args = ap.parse_args()
+    if args.photo_loss and not args.synth_data:
+        ap.error("--photo-loss needs --synth-data (the term uses the batch's ground-truth lighting and albedo)")
     # (ONE line on stdout: RCCL prints a version banner to fd 1 when its first communicator comes up -- from here on fd 1 is
     # stderr and the JSON line goes to the saved real stdout)
     sys.stdout.flush()
@@ -380,6 +393,8 @@ def main():
         if args.synth_data:
             rec["data"] = "synthetic, rendered on the device (pipeline.SynthBatches)"
             rec["synth_seed"] = args.synth_seed
+        if args.photo_loss and L is not None:
+            rec["photometric_loss"] = float(L["photometric_loss"])
         _emit(rec)
     dist_u.finalize()
 

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Analysis by synthesis on one synthetic batch: fit the lighting and the albedo coefficients of every face to its picture by
+descending the photometric loss (nets/losses.py::photometric_loss: synth_texture -> render_depth -> photo_loss, every link with a
+HIP backward).
+
+    python examples/photo_fit.py --small                 # tiny assets, 32 x 32, 3 faces
+    python examples/photo_fit.py --batch 8 --steps 200   # the full mesh at 200 x 200
+    python examples/photo_fit.py --small --fit-shape     # also fit the shape and expression coefficients (pose held at the truth)
+
+A batch of pipeline.SynthBatches gives the picture and its ground truth (parameters, light, alpha).  The fit starts from the truth
+perturbed (light by --light-noise, alpha by --alpha-noise; with --fit-shape the coefficients from zero) and runs Adam.  By default the
+geometry is the ground truth's and stays fixed.  Prints ONE JSON record: the first and last loss and the parameter errors (RMS
+against the ground truth) before and after.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+
+def pkg(n):
+    return importlib.import_module("3dfacerecon_amd." + n)
+
+
+def rms(a, b):
+    return float((a.detach().double() - b.double()).pow(2).mean().sqrt())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--small", action="store_true", help="tiny synthetic assets at 32 x 32, 3 faces (smoke runs)")
+    ap.add_argument("--batch", type=int, default=None)
+    ap.add_argument("--im-size", type=int, default=None)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--lr", type=float, default=0.02)
+    ap.add_argument("--seed", type=int, default=77)
+    ap.add_argument("--light-noise", type=float, default=0.2)
+    ap.add_argument("--alpha-noise", type=float, default=0.5)
+    ap.add_argument("--fit-shape", action="store_true", help="also fit the shape and expression coefficients, from zero")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    synth, netm, pipe, losses = pkg("utils.synth"), pkg("nets.network"), pkg("pipeline"), pkg("nets.losses")
+    B = args.batch or (3 if args.small else 8)
+    S = args.im_size or (32 if args.small else 200)
+    A = synth.make_small_assets() if args.small else synth.make_assets()
+    face = netm.FaceRecNet(mesh_data=A, batch_size=B, im_size=S, device=dev)
+    stream = pipe.SynthBatches(face, B, args.seed, slots=1, focal=1e-3 * S / 200.0)
+    b = {k: v.clone() for k, v in stream.next().items()}
+    torch.cuda.synchronize(dev)
+    im, params, light_gt, alpha_gt = b["im_gray"], b["params"], b["light"], b["alpha"]
+    g = torch.Generator(device="cpu").manual_seed(args.seed)
+    noise = lambda t, s: (torch.rand(t.shape, generator=g) * 2 - 1).to(dev) * s   # noqa: E731
+    light = (light_gt + noise(light_gt, args.light_noise)).requires_grad_(True)
+    alpha = (alpha_gt + noise(alpha_gt, args.alpha_noise)).requires_grad_(True)
+    groups = [{"params": [light, alpha], "lr": args.lr}]
+    n0, ns = face.ndim_pose, face.ndim_shape
+    coef_gt = params[:, n0:]
+    coef = None
+    if args.fit_shape:
+        # unit-scale unknowns: the shape coefficients live on a scale of 1e4 (utils/synth.get_random_params), the expression's on 1
+        scale = torch.cat([torch.full((ns,), 1e4), torch.ones(face.ndim_exp)]).to(dev)
+        coef = torch.zeros_like(coef_gt, requires_grad=True)
+        groups.append({"params": [coef], "lr": args.lr})
+    opt = torch.optim.Adam(groups)
+
+    def vertices():
+        if coef is None:
+            with torch.no_grad():
+                return face.vertices_transform(params)
+        return face.vertices_transform(torch.cat([params[:, :n0], coef * scale], dim=1))
+
+    def loss_of():
+        return losses.photometric_loss(face, vertices(), im, light, alpha, gain=stream.gain, offset=stream.offset)
+
+    before = {"light_rms": rms(light, light_gt), "alpha_rms": rms(alpha, alpha_gt)}
+    if coef is not None:
+        before["coef_rms_scaled"] = rms(coef, coef_gt / scale)
+    first = last = None
+    for _ in range(args.steps):
+        opt.zero_grad(set_to_none=True)
+        L = loss_of()
+        L.backward()
+        opt.step()
+        first = float(L.detach()) if first is None else first
+    with torch.no_grad():
+        last = float(loss_of())
+    after = {"light_rms": rms(light, light_gt), "alpha_rms": rms(alpha, alpha_gt)}
+    if coef is not None:
+        after["coef_rms_scaled"] = rms(coef, coef_gt / scale)
+    print(json.dumps({"program": "photo_fit", "faces": B, "im_size": S, "steps": args.steps, "lr": args.lr, "fit_shape": bool(args.fit_shape),
+                      "first": first, "last": last, "ratio": last / first if first else None, "errors_before": before,
+                      "errors_after": after, "finite": bool(torch.isfinite(light).all() and torch.isfinite(alpha).all())}))
+
+
+if __name__ == "__main__":
+    main()

@@ -994,14 +994,14 @@ int fr_albedo_lse_forward(const void* basis, const float* tri_ind, const void* l
  * by tests/test_albedo_lse_gpu.py to place their shapes on the tile's edges. */
 void fr_debug_albedo_lse_geom(int B, int H, int W, int K, int* out);
 
-/* ---- synthetic batches: sample, blend the albedo, shade (opt-in; a data source, no backward) ----------------------------------------
+/* ---- synthetic batches: sample, blend the albedo, shade (opt-in; a data source; the blend has an adjoint) ---------------------------
  * The method trains CoarseNet on RENDERED faces of random parameters; the reference pairs a photograph with an unrelated random
  * vector instead (prepare_data/script_generate_dataset.m:105-106).  The decode, the rasteriser with a per-face [B,3,N] texture and
  * the normal map are here already; these three entry points are the rest: parameters drawn where they are consumed, the albedo per
  * face, and the gray image of (tex_img, normal, tri_ind) under a first-order lighting.  pipeline.SynthBatches strings them together.
  * ARITHMETIC.  fp32 in the written order, every operation rounded on its own (no contraction), IEEE division and square root: a
- * float32 model reproduces every output bit (tests/ref_synth_batch.py).  No entry point needs a workspace; nothing is allocated
- * or synchronised; each makes one launch, can be captured in a graph and is reentrant under the rules at the top of this file.
+ * float32 model reproduces every output bit (tests/ref_synth_batch.py).  No entry point but the blend's adjoint needs a workspace;
+ * nothing is allocated or synchronised; each of the three forward ones makes one launch, can be captured in a graph and is reentrant under the rules at the top of this file.
  * NAMES.  The stream parameter is called `stream`, as in the sections above.
  * SAMPLER.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key = (seed lo, seed hi),
  * counter = (j >> 2, g lo, g hi, 0) with g = first_face + b the GLOBAL face index (mod 2^64) and j the draw's index within the
@@ -1025,6 +1025,21 @@ void fr_debug_albedo_lse_geom(int B, int H, int W, int K, int* out);
  * mu_tex or tex -- or, with K > 0, pc_tex or alpha -- is FR_ERR_INVALID_ARG.  K == 0 gives tex = mu_tex for every face.  One lane
  * per (c, p) row and face of a group of eight: a workgroup fetches its 256 rows of pc_tex (256 K contiguous floats) once per group,
  * coalesced, through LDS, and writes 64 contiguous floats per wave and face; every output keeps its own chain.
+ * TEXTURE BACKWARD.  The blend's adjoint, what carries a gradient of tex to alpha (the photometric loss below is its user):
+ *   grad_alpha[b][k] = sum over r < 3N of pc_tex[r][k] grad_tex[b][r],     grad_tex [B,3,N] read as [B,3N], grad_alpha [B,K] fp32.
+ * Each product of two widened fp32 values is exact in float64; the sum is float64 in an association that is a function of (N, K)
+ * alone -- not of B, the stream or the device: the rows are cut into tiles of 256 consecutive r (the last one ragged; a slot past 3N
+ * holds +0.0); inside a tile the 256 products are taken in groups of 64 consecutive ones, v[i] = v[i] + v[i + k] for every i < k with
+ * k = 32, 16, .. 1, and the four group sums as (w0 + w2) + (w1 + w3); then a[i] = chain over j = 0, 1, .. from +0.0 of the partial of
+ * tile i + 64 j (while there is one), i < 64, the 64 a[i] by the same k = 32 .. 1 steps, and one rounding to fp32
+ * (tests/ref_photo_loss.py is this in numpy).  For finite input it lies within
+ * 3N 2^-53 sum |pc g| of the exact sum, plus that rounding.  The workspace is caller-owned, 16-byte aligned,
+ * fr_synth_texture_backward_workspace_bytes(B, N, K) bytes = ceil(3N / 256) B K float64 partials [b][k][row tile]; the call writes
+ * all of it that it reads.  Checks, in this order: B < 1, N < 1 or K < 0 is FR_ERR_INVALID_ARG; B > 65,535, 3N > 2^31 - 257 or
+ * B K > 2^31 - 1 is FR_ERR_UNSUPPORTED (the size query answers 0 for all of these); K == 0 is FR_OK with nothing launched, read or
+ * written; a NULL pc_tex, grad_tex or grad_alpha is FR_ERR_INVALID_ARG; a missing, short or misaligned workspace is
+ * FR_ERR_WORKSPACE.  Two launches: a workgroup owns a row tile and a group of eight faces, stages its run of pc_tex in LDS once,
+ * reduces by lane shuffles; a finish kernel adds the tiles, one wave per (b, k).  No atomics, bit-reproducible.
  * SHADE, per pixel, over the planes of a render: tex_img, normal (the op's RAW normal) [B,H,W,3], tri_ind [B,H,W,1], light [B,4],
  * background NULL (bg_batch 0), [1,H,W,1] (bg_batch 1) or [B,H,W,1] (bg_batch B).  A pixel is COVERED iff tri_ind >= 0.  An
  * uncovered pixel gets im_gray = its background pixel (0 without one) and mask = 0.  A covered one gets mask = 1 and
@@ -1046,6 +1061,74 @@ int fr_synth_params(unsigned long long seed, unsigned long long first_face, int 
 int fr_synth_texture(const float* mu_tex, const float* pc_tex, const float* alpha, int B, int N, int K, float* tex, void* stream);
 int fr_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* background,
                    int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray, float* mask, void* stream);
+size_t fr_synth_texture_backward_workspace_bytes(int B, int N, int K);
+int fr_synth_texture_backward(const float* pc_tex, const float* grad_tex, int B, int N, int K, float* grad_alpha, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
+/* ---- photometric loss: fused shade-and-compare with a backward (opt-in) ----------------------------------------------------------------
+ * The analysis-by-synthesis term: the image the shader above makes of a render's planes, compared with a picture, per face, in one
+ * streaming pass per direction.  tex_img, normal [B,H,W,3] are the render's RAW planes, tri_ind [B,H,W] (a trailing channel of 1 is
+ * the caller's), light [B,4], target [B,H,W], weight [B,H,W] or NULL (= 1 everywhere); all fp32, dense.  gain, offset: the shader's.
+ * MODEL.  A pixel is COVERED iff tri_ind >= 0 (a NaN tri_ind is uncovered, as in the shader).  At a covered pixel a, n (flipped), mag,
+ * d, n^, s and I^ = (a (s < 0 ? 0 : s)) gain + offset are the SHADE chain above in fp32 -- the same device function
+ * (csrc/fr_shade.h), the same bits as fr_synth_shade's im_gray.  Then, in float64 on the widened values, every product and sum rounded
+ * on its own (no contraction):
+ *   r = (double)I^ - (double)target        t = ((2.0 w) r) (double)gain        u = t (double)a where s > 0, else +0.0
+ * FORWARD.  sums [B][6] float64 per face:
+ *   sse = sum (w r) r      cnt = sum 1.0 (the covered pixels: exact)      L0 = sum u      Lk = sum u (double)n^_k,  k = 1, 2, 3
+ * An uncovered pixel contributes +0.0 to all six and nothing of it is read beyond tri_ind.  Only subtraction, multiplication and
+ * addition of float64 are involved, so numpy reproduces the sums bit for bit (tests/ref_photo_loss.py).
+ * CHOICE.  The four lighting sums are taken in the forward: they are linear in the upstream gradient, so the backward needs no
+ * reduction and no second launch, and the forward is memory-bound either way.
+ * ASSOCIATION.  A function of (H, W) alone, per face -- not of B (a face's six numbers are the same in any batch), the stream, the
+ * device or an option; all six sums use the same one:
+ *   tile     the face's H W pixels, row-major, are cut into tiles of T = 256 consecutive ones (fr_debug_photo_loss_geom), tiles =
+ *            ceil(H W / T); a slot past the image or off the face holds +0.0.  The slots are taken in groups of 64 consecutive ones;
+ *            inside a group, for k = 32, 16, 8, 4, 2, 1 in turn: v[i] = v[i] + v[i + k] for every i < k; the group's sum is v[0].
+ *            The four group sums as (w0 + w2) + (w1 + w3).  That is the tile's partial.
+ *   face     with F = 256: a[i] = chain over j = 0, 1, .. from +0.0 of partial[i + F j] (while i + F j < tiles), i < F; then the
+ *            a[i] in four groups of 64 as above, and the four group sums as (w0 + w2) + (w1 + w3).
+ * STATE.  Caller-owned, 16-byte aligned, fr_photo_loss_state_bytes(B, H, W) bytes: the partials [B][tiles][6], float64.  The forward
+ * writes all of it and needs none of it cleared; the backward does not read it.
+ * BACKWARD.  One pass, one launch; tri_ind is held fixed, target and weight are constants.  Inputs: the forward's, sums, and
+ * grad_sse [B] float64, read from the DEVICE (no host synchronisation).  Each output pointer may be NULL: not wanted, not written.
+ * Every element of a non-NULL plane is written, +0 at an uncovered pixel: no memset is needed.  With dI = grad_sse[b] t:
+ *   grad_tex_img[c] = fl32((dI (double)s) (1.0 / 3.0))   where s > 0 and not tex_c < 1e-6f (the clamp passes a NaN, as the forward
+ *                     does); +0 elsewhere
+ *   grad_light[b][k] = fl32(grad_sse[b] L_k),  k = 0 .. 3           (needs sums; written by the launch, not reduced again)
+ *   grad_normal: q = dI (double)a where s > 0, else +0.0;  g~ = (q (double)l1, q (double)l2, q (double)l3);  with n the flipped
+ *                normal, d and mag widened and rho = sqrt((double)mag):
+ *                  where the forward kept mag (mag > 1e-6f):  (g~ - n c) / d,  c = ((nx g~x + ny g~y) + nz g~z) / (d rho)
+ *                  where it replaced mag by 1:                g~ / d
+ *                negated where the forward flipped; rounded once to fp32 at the store.
+ * grad_tex_img and grad_light are fixed to the bit by the above; grad_normal up to the device's float64 division and square root
+ * (within 2^-24 |value| + 2^-40 (|g~|_1 + |n|_1 |n . g~| / (d rho)) / d of the numpy evaluation).
+ * SPECIAL VALUES.  A NaN in a covered pixel's tex_img or normal makes that pixel's r, hence its face's sse, NaN (and, through t, the
+ * lighting sums where the pixel is lit, and its own gradients); cnt stays the exact count.  No other face changes by a bit.  A NaN
+ * in light[b] or grad_sse[b] reaches face b alone.
+ * Checks, all before any HIP call, in this order: a negative size is FR_ERR_INVALID_ARG; then B == 0 or an empty image is FR_OK with
+ * nothing launched or written; then a NULL tex_img, normal, tri_ind, light, target or sums (forward), or a NULL grad_sse, tex_img,
+ * normal, tri_ind, light or target, or a NULL sums beside a non-NULL grad_light (backward), is FR_ERR_INVALID_ARG; a state that is
+ * missing, too small or not 16-byte aligned is FR_ERR_WORKSPACE (forward); more than 2^31 - 1 pixels per face or more than 65,535
+ * faces is FR_ERR_UNSUPPORTED, and fr_photo_loss_state_bytes answers 0 for it (as for an empty or negative shape).  A backward with
+ * all three outputs NULL launches nothing.  Nothing is allocated or synchronised; reentrant under the rules at the top of this file
+ * with a state per call in flight.
+ * Kernels (csrc/fr_photo.hip): one lane per pixel, 256 per workgroup, as the shader.  The forward must move about 32 bytes per covered
+ * pixel (tex_img, normal, tri_ind, target; 4 more with a weight) and 4 per uncovered one, the backward the same plus the 12 or 24 it
+ * writes per pixel; tools/photo_loss_probe.py (profiles/photo_loss.json) measures both beside the stock-torch route
+ * (DESIGN.md 4.4m). */
+size_t fr_photo_loss_state_bytes(int B, int H, int W);
+int fr_photo_loss_forward(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* target,
+                          const float* weight, int B, int H, int W, float gain, float offset, double* sums, void* state,
+                          size_t state_bytes, void* stream);
+int fr_photo_loss_backward(const double* grad_sse, const double* sums, const float* tex_img, const float* normal, const float* tri_ind,
+                           const float* light, const float* target, const float* weight, int B, int H, int W, float gain,
+                           float offset, float* grad_tex_img, float* grad_normal, float* grad_light, void* stream);
+
+/* The photometric loss's launch geometry (no GPU needed; the launchers read the same functions): out[4] = {pixels per tile (T above),
+ * tiles per face, threads of the finish workgroup (F above), sums per face}; the forward's grid is tiles x B, the finish step's B.
+ * All zero for an empty shape or one the launchers refuse.  Used by tests/ref_photo_loss.py for the sums' association. */
+void fr_debug_photo_loss_geom(int B, int H, int W, int* out);
 
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
