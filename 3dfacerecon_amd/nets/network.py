@@ -338,6 +338,7 @@ class FaceRecNet:
         self._gram_nst = {}      # fr_geometry_loss_state_bytes by batch
         self._gram_lock = threading.Lock()
         self._albedo_basis = None   # the texture basis per triangle in float64 (fr_albedo_basis_build), built on first use
+        self._adjacency = None      # the vertex -> triangle CSR table on the device (utils/mesh_io.vertex_adjacency), on first use
 
         # initial parameters (network.py:57-62)
         geo = torch.zeros((batch_size, self.ndim_shape + self.ndim_exp), **f32)
@@ -428,6 +429,36 @@ class FaceRecNet:
                     self._albedo_basis = _ops().albedo_basis(self.tri, self.pc_tex)
                 _publish(self.device)
             return self._albedo_basis
+
+    def adjacency(self):
+        """The vertex -> triangle CSR table of the mesh (utils/mesh_io.vertex_adjacency) as a rendering_layer/ops.py::MeshAdjacency
+        on the device, built on the host on first use and cached under the lock gram() uses: a caller that never asks for vertex
+        normals never holds it (1.5 MB at the full mesh)."""
+        with self._gram_lock:
+            if self._adjacency is None:
+                mesh_io = _load("_fr_hotpath_mesh_io", os.path.join("utils", "mesh_io.py"))
+                adj_start, adj_tri = mesh_io.vertex_adjacency(self.tri.cpu().numpy(), self.nvert)
+                self._adjacency = _ops().MeshAdjacency(adj_start, adj_tri, self.nvert, int(self.tri.shape[1]), self.device)
+            return self._adjacency
+
+    def fine_mesh(self, vertices_proj, pred_depth_map, coarse_depth_map, with_normals=True):
+        """The fine depth map taken back to the mesh: {"vertices": [B,3,N] fp32, "state": uint8 [B,N], "normals": [B,3,N] fp32 or
+        None}.  `vertices_proj` is rendered once for its tri_ind -- the same winners, bit for bit, that produced
+        `coarse_depth_map` (rendering_layer / coarse_net_input of the same vertices) -- then rendering_layer/ops.py::mesh_visible,
+        mesh_lift and (with_normals) vertex_normals of the lifted vertices over adjacency().  x and y do not move; a vertex with
+        state 1 has z + the bilinear sample of pred_depth_map - coarse_depth_map at its position, the others (0: hidden, 2: visible
+        without a pixel of the face around it) keep the coarse z.  Forward only: the inputs are read as constants and nothing
+        returned requires grad."""
+        ops = _ops()
+        with torch.no_grad():
+            ver = vertices_proj.detach().float()
+            B = int(ver.shape[0])
+            image = torch.zeros((B, self.im_size, self.im_size, 3), dtype=torch.float32, device=ver.device)
+            tri_ind = ops.render_depth(ver=ver, tri=self.tri, texture=self.vertex_code, image=image)[3]
+            visible = ops.mesh_visible(self.tri, tri_ind, self.nvert)
+            vertices, state = ops.mesh_lift(ver, tri_ind, visible, pred_depth_map, coarse_depth_map, ntri=int(self.tri.shape[1]))
+            normals = ops.vertex_normals(vertices, self.tri, self.adjacency()) if with_normals else None
+        return {"vertices": vertices, "state": state, "normals": normals}
 
     def gram_state(self, B, dev, stream):
         """(key, bytes, buffer): a state buffer of the Gram-form loss for B faces on `stream` (torch's current stream of `dev`, as

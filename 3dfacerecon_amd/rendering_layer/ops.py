@@ -848,6 +848,139 @@ def depth_interpolate(ver, tri, tri_ind):
     return _DepthInterpolate.apply(ver, tri, tri_ind)
 
 
+# ---- fine mesh (include/fr_hotpath.h, "fine mesh"): forward only, outside autograd ------------------------------------------------------
+def _mesh_plane(h, t, name, op, B, H, W, dev):
+    """a [B,H,W,1] or [B,H,W] fp32 plane on `dev`, detached and contiguous"""
+    t_c = h.require_gpu_f32(t.detach() if isinstance(t, torch.Tensor) else t, name)
+    if tuple(t_c.shape) not in ((B, H, W, 1), (B, H, W)):
+        raise ValueError("%s: %s must be [%d,%d,%d,1] or [%d,%d,%d] (got %s)" % (op, name, B, H, W, B, H, W, tuple(t_c.shape)))
+    if t_c.device != dev:
+        raise ValueError("%s: %s is on %s, expected %s" % (op, name, t_c.device, dev))
+    return t_c
+
+
+def _mesh_tri_ind(h, tri_ind, op):
+    ti_c = h.require_gpu_f32(tri_ind.detach() if isinstance(tri_ind, torch.Tensor) else tri_ind, "tri_ind")
+    if not (ti_c.dim() == 3 or (ti_c.dim() == 4 and ti_c.shape[3] == 1)):
+        raise ValueError("%s expects tri_ind [B,H,W,1] or [B,H,W] (got %s)" % (op, tuple(ti_c.shape)))
+    return ti_c, int(ti_c.shape[0]), int(ti_c.shape[1]), int(ti_c.shape[2])
+
+
+def mesh_visible(tri, tri_ind, nver):
+    """The per-vertex visibility of a render: uint8 [B,nver], 1 where at least one pixel of the face's tri_ind ([B,H,W,1] or
+    [B,H,W], e.g. render_depth's fourth output) names a triangle of `tri` [3,ntri] that has the vertex among its three ids, else 0
+    (fr_mesh_visible: one pass over the pixels; a function of the inputs alone).  A pixel counts exactly as in the render
+    backwards: -1, NaN, a value >= ntri or a triangle with an id outside [0, nver) marks nothing.  Outside autograd: the inputs are
+    read as constants and the result does not require grad.  Runs on the current stream."""
+    h = _host()
+    tri_c = h.require_gpu_f32(tri.detach() if isinstance(tri, torch.Tensor) else tri, "tri")
+    if tri_c.dim() != 2 or tri_c.shape[0] != 3:
+        raise ValueError("The tri is not 3 x ntri")
+    ti_c, B, H, W = _mesh_tri_ind(h, tri_ind, "mesh_visible")
+    if ti_c.device != tri_c.device:
+        raise ValueError("mesh_visible: tri_ind is on %s, tri on %s" % (ti_c.device, tri_c.device))
+    nver = int(nver)
+    if nver < 0:
+        raise ValueError("mesh_visible: nver must not be negative")
+    dev = tri_c.device
+    visible = torch.empty((B, nver), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = h.lib().fr_mesh_visible(h.ptr(tri_c), h.ptr(ti_c), B, nver, int(tri_c.shape[1]), H, W, h.ptr(visible),
+                                     h.stream_ptr(dev))
+    h.check(rc, "fr_mesh_visible")
+    return visible
+
+
+def mesh_lift(vertex, tri_ind, visible, fine_depth, coarse_depth, ntri=None):
+    """The fine depth map lifted onto the vertices -> (vertex_fine [B,3,nver] fp32, state uint8 [B,nver]).  Rows x and y are
+    `vertex`'s, bit for bit.  A visible vertex (`visible` uint8 [B,nver], mesh_visible) whose position (x = column, y = row) has
+    at least one of its four surrounding pixels on the face gets z + the bilinear sample of fine_depth - coarse_depth over those
+    of the four that are (state 1); a visible vertex without such a pixel, or at a non-finite position, keeps its z (state 2); a
+    hidden one keeps it (state 0) (fr_mesh_lift: float64, one gather pass, bit-exact against numpy).  tri_ind, fine_depth and
+    coarse_depth are [B,H,W,1] or [B,H,W]; a pixel is on the face when its tri_ind names a triangle in [0, ntri) (ntri=None: any
+    non-negative id does).  Outside autograd: every input is read as a constant, neither output requires grad.  Runs on the
+    current stream."""
+    h = _host()
+    ver_c = h.require_gpu_f32(vertex.detach() if isinstance(vertex, torch.Tensor) else vertex, "vertex")
+    if ver_c.dim() != 3 or ver_c.shape[1] != 3:
+        raise ValueError("The vertex is not Batch x 3 x nver")
+    dev = ver_c.device
+    ti_c, B, H, W = _mesh_tri_ind(h, tri_ind, "mesh_lift")
+    nver = int(ver_c.shape[2])
+    if B != int(ver_c.shape[0]) or ti_c.device != dev:
+        raise ValueError("mesh_lift: tri_ind must have the vertex's batch and device (got %s on %s)" % (tuple(ti_c.shape), ti_c.device))
+    if not (isinstance(visible, torch.Tensor) and visible.dtype == torch.uint8 and tuple(visible.shape) == (B, nver)
+            and visible.device == dev):
+        raise ValueError("mesh_lift: visible must be a uint8 tensor [%d,%d] on %s (mesh_visible)" % (B, nver, dev))
+    f_c = _mesh_plane(h, fine_depth, "fine_depth", "mesh_lift", B, H, W, dev)
+    c_c = _mesh_plane(h, coarse_depth, "coarse_depth", "mesh_lift", B, H, W, dev)
+    ntri = (1 << 24) - 1 if ntri is None else int(ntri)
+    vis_c = visible.contiguous()
+    out = torch.empty((B, 3, nver), dtype=torch.float32, device=dev)
+    state = torch.empty((B, nver), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = h.lib().fr_mesh_lift(h.ptr(ver_c), nver, h.ptr(ti_c), h.ptr(vis_c), h.ptr(f_c), h.ptr(c_c), B, nver,
+                                  ntri, H, W, h.ptr(out), nver, h.ptr(state), h.stream_ptr(dev))
+    h.check(rc, "fr_mesh_lift")
+    return out, state
+
+
+class MeshAdjacency:
+    """A vertex -> triangle CSR table (utils/mesh_io.vertex_adjacency) checked on the host and held on a device: adj_start int32
+    [nver + 1] starts at 0, never decreases and ends at most at 3 ntri (at 3 ntri unless a triangle names a vertex twice or an id
+    outside the mesh); adj_tri int32 [3 ntri] holds ids in [0, ntri).  ValueError otherwise -- the kernel trusts what passed."""
+
+    def __init__(self, adj_start, adj_tri, nver, ntri, device):
+        import numpy as np
+        s = np.ascontiguousarray(np.asarray(adj_start.cpu() if isinstance(adj_start, torch.Tensor) else adj_start))
+        t = np.ascontiguousarray(np.asarray(adj_tri.cpu() if isinstance(adj_tri, torch.Tensor) else adj_tri))
+        nver, ntri = int(nver), int(ntri)
+        if s.dtype.kind not in "iu" or t.dtype.kind not in "iu":
+            raise ValueError("adjacency: adj_start and adj_tri must be integer arrays")
+        if s.shape != (nver + 1,) or t.shape != (3 * ntri,):
+            raise ValueError("adjacency: adj_start must be [%d] and adj_tri [%d] (got %s, %s)" % (nver + 1, 3 * ntri, s.shape, t.shape))
+        s64, t64 = s.astype(np.int64), t.astype(np.int64)
+        if s64[0] != 0 or (np.diff(s64) < 0).any() or s64[-1] > 3 * ntri:
+            raise ValueError("adjacency: adj_start must start at 0, never decrease and end at most at 3 ntri = %d" % (3 * ntri))
+        if t64.size and (t64.min() < 0 or t64.max() >= ntri):
+            raise ValueError("adjacency: adj_tri names a triangle outside [0, %d)" % ntri)
+        self.nver, self.ntri = nver, ntri
+        self.adj_start = torch.as_tensor(s.astype(np.int32), device=device)
+        self.adj_tri = torch.as_tensor(t.astype(np.int32), device=device)
+
+
+def vertex_normals(vertex, tri, adjacency):
+    """Per-vertex unit normals [B,3,nver] fp32 of a vertex tensor [B,3,nver] over the triangles `tri` [3,ntri]: the area-weighted
+    sum of (P2 - P1) x (P3 - P1) -- the render's orientation -- over the vertex's triangles in the order of `adjacency`, normalised;
+    exactly (0, 0, 0) for a vertex without a triangle or whose sum vanishes (fr_mesh_vertex_normals: float64 chains in table
+    order, one gather pass, bit-exact against numpy).  adjacency: a MeshAdjacency (checked once, e.g. FaceRecNet.adjacency()) or
+    the (adj_start, adj_tri) pair of utils/mesh_io.vertex_adjacency (checked and uploaded by this call).  Outside autograd: the
+    inputs are read as constants, the result does not require grad.  Runs on the current stream."""
+    h = _host()
+    ver_c = h.require_gpu_f32(vertex.detach() if isinstance(vertex, torch.Tensor) else vertex, "vertex")
+    tri_c = h.require_gpu_f32(tri.detach() if isinstance(tri, torch.Tensor) else tri, "tri")
+    if ver_c.dim() != 3 or ver_c.shape[1] != 3:
+        raise ValueError("The vertex is not Batch x 3 x nver")
+    if tri_c.dim() != 2 or tri_c.shape[0] != 3:
+        raise ValueError("The tri is not 3 x ntri")
+    dev = ver_c.device
+    if tri_c.device != dev:
+        raise ValueError("vertex_normals: tri is on %s, vertex on %s" % (tri_c.device, dev))
+    B, nver, ntri = int(ver_c.shape[0]), int(ver_c.shape[2]), int(tri_c.shape[1])
+    if not hasattr(adjacency, "adj_start"):   # (not isinstance: this file is loaded under two module names)
+        adj_start, adj_tri = adjacency
+        adjacency = MeshAdjacency(adj_start, adj_tri, nver, ntri, dev)
+    if adjacency.nver != nver or adjacency.ntri != ntri or adjacency.adj_start.device != dev:
+        raise ValueError("vertex_normals: the adjacency is of a mesh of %d vertices and %d triangles on %s, the call's has %d and %d on %s"
+                         % (adjacency.nver, adjacency.ntri, adjacency.adj_start.device, nver, ntri, dev))
+    normal = torch.empty((B, 3, nver), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = h.lib().fr_mesh_vertex_normals(h.ptr(ver_c), nver, h.ptr(tri_c), h.ptr(adjacency.adj_start), h.ptr(adjacency.adj_tri),
+                                            B, nver, ntri, h.ptr(normal), nver, h.stream_ptr(dev))
+    h.check(rc, "fr_mesh_vertex_normals")
+    return normal
+
+
 _LAPLACE_K = ((0.5, 1.0, 0.5), (1.0, -6.0, 1.0), (0.5, 1.0, 0.5))  # network.py:383-385
 _FL_LOCK = threading.Lock()
 

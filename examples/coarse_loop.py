@@ -117,6 +117,56 @@ def build_harness(args, dev, rank, world, local):
     return model, net, opt, step
 
 
+class _MeshExport:
+    """--export-mesh: the first --export-count faces of the one-at-a-time pass as meshes, coarse and fine.  The fine depth map is
+    FineNet's of (im_gray, coarse depth) -- network.py:311-333, untrained here like everything else -- taken back to the vertices by
+    FaceRecNet.fine_mesh; rank 0 writes face_%06d_coarse.obj / face_%06d_fine.obj (upright: flip_y), every rank adds its faces'
+    squared z errors against the decode of the LABEL parameters (synthetic batches only) over the vertices the lift moved."""
+
+    def __init__(self, args, face, cn, dev, rank):
+        self.dir, self.count, self.face, self.rank, self.B = args.export_mesh, max(args.export_count, 0), face, rank, args.batch
+        self.fine = cn.FineNet().to(dev).eval()
+        self.mesh_io = pkg("utils.mesh_io")
+        self.tri = face.tri.cpu().numpy()
+        self.done = 0
+        self.err = torch.zeros(3, dtype=torch.float64, device=dev)   # squared z error coarse, fine; vertices counted
+        self.labelled = False
+        if rank == 0:
+            os.makedirs(self.dir, exist_ok=True)
+
+    def wants_more(self):
+        return self.done < self.count
+
+    def take(self, batch, params, coarse_depth):
+        face = self.face
+        V = face.vertices_transform(params)
+        mesh = face.fine_mesh(V, self.fine(batch["im_gray"], coarse_depth), coarse_depth)
+        n = min(self.B, self.count - self.done)
+        if "params" in batch:
+            self.labelled = True
+            moved = (mesh["state"][:n] == 1).double()
+            z_lab = face.vertices_transform(batch["params"])[:n, 2].double()
+            ec, ef = V[:n, 2].double() - z_lab, mesh["vertices"][:n, 2].double() - z_lab
+            self.err.add_(torch.stack([(ec * ec * moved).sum(), (ef * ef * moved).sum(), moved.sum()]))
+        if self.rank == 0:
+            Vc, Vf, Nf = V[:n].cpu().numpy(), mesh["vertices"][:n].cpu().numpy(), mesh["normals"][:n].cpu().numpy()
+            Nc = pkg("rendering_layer.ops").vertex_normals(V[:n], face.tri, face.adjacency()).cpu().numpy()
+            for i in range(n):
+                stem = os.path.join(self.dir, "face_%06d" % (self.done + i))
+                self.mesh_io.write_obj(stem + "_coarse.obj", Vc[i], self.tri, normals=Nc[i], flip_y=face.im_size)
+                self.mesh_io.write_obj(stem + "_fine.obj", Vf[i], self.tri, normals=Nf[i], flip_y=face.im_size)
+        self.done += n
+
+    def record(self, dist_u, dev):
+        rec = {"export_mesh": self.dir, "export_count": self.done}
+        if self.labelled:
+            sc, sf, cnt = (dist_u.sum_over_ranks(float(v), device=dev) for v in self.err.tolist())
+            rec["vertex_rmse_coarse"] = (sc / cnt) ** 0.5 if cnt > 0 else float("nan")
+            rec["vertex_rmse_fine"] = (sf / cnt) ** 0.5 if cnt > 0 else float("nan")
+            rec["vertex_rmse_vertices"] = int(cnt)
+        return rec
+
+
 def run_test_phase(args, dev, rank, world, local, dist_u):
     """The reference's evaluation loop (trainval.py:192-210: `while True: images = next(generator); pred_depth = sess.run(...);
     write depth * 255`) over INDEPENDENT test batches.  CoarseNet of a batch is a dependent chain (network -> decode -> render ->
@@ -198,6 +248,7 @@ def run_test_phase(args, dev, rank, world, local, dist_u):
                  im_size=S, **({} if depth_rmse is None else {"depth_rmse": depth_rmse}),
                  **{"%s_%d" % (n, k): t.cpu().numpy() for k, rec in enumerate(dumped) for n, t in zip(names, rec)})
     # the same batches one at a time through the plain surface: the in-flight loop must reproduce them bit for bit
+    export = _MeshExport(args, face, cn, dev, rank) if args.export_mesh else None
     with torch.no_grad():
         ref = []
         again = None
@@ -205,10 +256,13 @@ def run_test_phase(args, dev, rank, world, local, dist_u):
             again = pipe.SynthBatches(face, B, args.synth_seed + 2, first_face=pipe.synth_face_range(n_warm, rank, world, B)[0],
                                       **synth_kw)
         for k in range(min(args.steps, len(images))):
-            im = draw(k, again)["im_gray"]
+            batch = draw(k, again)
+            im = batch["im_gray"]
             p = coarse(im)
             d = face.coarse_net_input(face.vertices_transform(p), im_gray=im)[1]
             ref.append((d * 255.0).sum(dim=(1, 2, 3)))
+            if export is not None and export.wants_more():
+                export.take(batch, p, d)
     same = all(torch.equal(a, b) for a, b in zip(sums, ref))
     dist_info = dist_u.describe(device=dev)
     if rank == 0:
@@ -221,7 +275,8 @@ def run_test_phase(args, dev, rank, world, local, dist_u):
                                    "make_current_stream_wait()",
                           "depth_identical_to_one_batch_at_a_time": bool(same), "dist": dist_info},
                    **({} if depth_rmse is None else {"data": "synthetic, rendered on the device (pipeline.SynthBatches)",
-                                                     "depth_rmse": depth_rmse, "synth_seed": args.synth_seed})))
+                                                     "depth_rmse": depth_rmse, "synth_seed": args.synth_seed}),
+                   **({} if export is None else export.record(dist_u, dev))))
     dist_u.finalize()
     return 0 if same else 1
 
@@ -330,6 +385,14 @@ def build_parser():
     ap.add_argument("--dump-batches", default=None, metavar="FILE.npz",
                     help="--phase test: save every timed batch's parameters, vertices and planes (as its consumer saw them) for an "
                          "external checker")
+    ap.add_argument("--export-mesh", default=None, metavar="DIR",
+                    help="--phase test: write the first --export-count faces as DIR/face_%%06d_coarse.obj (the coarse decode) and "
+                         "DIR/face_%%06d_fine.obj (FaceRecNet.fine_mesh: FineNet's depth map lifted onto the visible vertices; "
+                         "fr_mesh_visible / fr_mesh_lift / fr_mesh_vertex_normals), upright, with vertex normals.  With --synth-data "
+                         "the record gains vertex_rmse_coarse and vertex_rmse_fine: the RMS z error against the decode of the label "
+                         "parameters over the vertices the lift moved.  The image size must be a multiple of 4 (FineNet); off: no mesh "
+                         "is built and the record is unchanged")
+    ap.add_argument("--export-count", type=int, default=4, help="with --export-mesh: how many faces to write")
     ap.add_argument("--phase", choices=("train", "test"), default="train",
                     help="trainval.py's phase switch (:223-225).  test = the forward-only evaluation loop over independent batches "
                          "with the depth rendering in flight (run_test_phase); train = everything else this script does")
@@ -341,6 +404,8 @@ def main():
     args = ap.parse_args()
     if args.photo_loss and not args.synth_data:
         ap.error("--photo-loss needs --synth-data (the term uses the batch's ground-truth lighting and albedo)")
+    if args.export_mesh and (args.phase != "test" or args.im_size % 4):
+        ap.error("--export-mesh needs --phase test and an image size that is a multiple of 4 (FineNet pools twice)")
     # (ONE line on stdout: RCCL prints a version banner to fd 1 when its first communicator comes up -- from here on fd 1 is
     # stderr and the JSON line goes to the saved real stdout)
     sys.stdout.flush()

@@ -1130,6 +1130,62 @@ int fr_photo_loss_backward(const double* grad_sse, const double* sums, const flo
  * All zero for an empty shape or one the launchers refuse.  Used by tests/ref_photo_loss.py for the sums' association. */
 void fr_debug_photo_loss_geom(int B, int H, int W, int* out);
 
+/* ---- fine mesh: the fine depth map lifted onto the vertices, visibility, vertex normals (opt-in, forward only) ----------------------
+ * FineNet's output is a [B,H,W,1] plane and the coarse decode a [B,3,N] vertex tensor; the reference leaves them unjoined
+ * (nets/network.py:451-453, "how to inversely convert predicted fine depth into new vertices?") and keeps the coarse vertices.  The
+ * map between the two is the rasteriser's tri_ind.  Three entry points, none with a backward:
+ *   vertex [B,3,vertex_pitch] (vertex_pitch >= nver, as in the interpolated depth);  tri [3,ntri], float-stored ids;  tri_ind,
+ *   fine_depth, coarse_depth dense [B,H,W] (a trailing channel of 1 is the caller's);  visible, state uint8 [B,nver];  vertex_out,
+ *   normal [B,3,out_pitch] (out_pitch >= nver; the columns from nver on are not written).  x is the column, y the row.
+ * NAMES.  The stream parameter is called `stream`, as in the sections above; tests/test_fine_mesh_cpu.py holds the return codes.
+ * ARITHMETIC.  Float64 on the widened fp32 inputs, every operation rounded on its own (no contraction), IEEE division and square root:
+ * numpy reproduces every output bit (tests/ref_mesh.py).  Every output element is written on every call.  No float atomics.
+ * VISIBLE.  visible[b][v] = 1 iff at least one OK pixel of face b -- OK exactly as in the interpolated depth above: tri_ind names
+ * t in [0, ntri) and all three ids of t lie in [0, nver); NaN, -1, a value >= ntri or a bad id is not OK -- names v among the three
+ * ids of its triangle; else 0.  The call zeroes the plane itself (a memset on `stream`), then one pass over the pixels stores the
+ * byte 1: the only race is several lanes storing the same value, so the result is a function of the inputs alone.  ntri == 0 or an
+ * empty image gives all zeros.
+ * LIFT.  Rows x and y of vertex_out are copies of vertex's, bit for bit.  Per (face, vertex), with (x, y, z) its position:
+ *   visible == 0:                      state = 0, z copied
+ *   x or y not finite, or ntri == 0:   state = 2, z copied
+ *   else  c0 = floor(x), r0 = floor(y), fx = x - c0, fy = y - r0; the corners (r0, c0), (r0, c0 + 1), (r0 + 1, c0), (r0 + 1, c0 + 1)
+ *         in this order, with the weights (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy, fx fy  ((1 - fx) and (1 - fy) formed once).
+ *         A corner COUNTS when it lies inside the image, its tri_ind converts (the x86 conversion of the render backwards) to a
+ *         t in [0, ntri), and its weight is not 0; a corner that does not count is neither read in the depth maps nor multiplied.
+ *         For a counting corner d_k = (double)fine - (double)coarse; num and den are the chains, from +0.0 in corner order, of
+ *         w_k d_k and of w_k.
+ *   no counting corner:                state = 2, z copied
+ *   else                               state = 1, z' = fl32((double)z + num / den)
+ * The DIFFERENCE is sampled, not fine_depth: the flat coarse depth is a staircase per triangle, and the difference leaves it out of
+ * the mesh.  A non-finite depth reaches only the vertices whose stencil reads it.  x and y do not move.
+ * VERTEX NORMALS.  A gather over a vertex -> triangle adjacency in CSR form, built once per mesh on the host: adj_start int32
+ * [nver + 1], adj_tri int32 [3 ntri] (utils/mesh_io.vertex_adjacency; device arrays, shared by the faces).  Per (face, vertex) the
+ * triangles adj_tri[adj_start[v] .. adj_start[v + 1]) are walked in table order; each contributes (P2 - P1) x (P3 - P1), the render's
+ * orientation, area-weighted: with a = P2 - P1, b = P3 - P1 in float64, (ay bz - az by, az bx - ax bz, ax by - ay bx).  The three sums
+ * are float64 chains from +0.0 in table order; s = sqrt((nx nx + ny ny) + nz nz); normal = fl32(n / s) per component, or (+0, +0, +0)
+ * where s is 0 or not finite.  A triangle with an id outside [0, nver) contributes nothing.  The TABLE is checked on the host side of
+ * the binding (rendering_layer/ops.py::MeshAdjacency: adj_start starts at 0, never decreases and ends at most at 3 ntri -- at 3 ntri unless a
+ * triangle names a vertex twice, which lists it once, or names an id outside the mesh -- and ids in range); the kernel skips an entry
+ * outside [0, ntri) and clamps a row to the table, so a bad table gives wrong normals, not a fault.
+ * Checks, all before any HIP call, in this order: (1) a negative size, or a pitch below nver, is FR_ERR_INVALID_ARG; (2) B == 0 or
+ * nver == 0 is FR_OK with nothing launched and nothing written; (3) a NULL vertex, visible, vertex_out, state, normal -- or, where
+ * triangles (and, for the first two, pixels) exist, a NULL tri, tri_ind, fine_depth, coarse_depth, adj_start, adj_tri -- is
+ * FR_ERR_INVALID_ARG; (4) ntri >= 2^24, more than 2^31 - 1 pixels per face, or more than 2^31 - 1 workgroups of 256 lanes (pixels for
+ * the first, vertices for the other two; the grid is one-dimensional, so the 65,535 limit of the other grid axes does not arise) is
+ * FR_ERR_UNSUPPORTED.  Nothing is allocated or synchronised; each call is one launch (fr_mesh_visible: a memset and a launch), can be
+ * captured in a graph and is reentrant under the rules at the top of this file.
+ * Kernels (csrc/fr_mesh.hip): fr_mesh_visible one lane per pixel in 256-pixel blocks, as the interpolated depth's forward; the other
+ * two one lane per (face, vertex), consecutive lanes on consecutive vertices.  No LDS, no workspace.
+ * Time: tools/fine_mesh_probe.py (profiles/fine_mesh.json) measures the three at 32 and 64 faces of the full mesh at 200 x 200 beside
+ * the bytes each must move, a 512 MiB copy and the same operators from stock torch ops. */
+int fr_mesh_visible(const float* tri, const float* tri_ind, int B, int nver, int ntri, int H, int W, unsigned char* visible,
+                    void* stream);
+int fr_mesh_lift(const float* vertex, int vertex_pitch, const float* tri_ind, const unsigned char* visible, const float* fine_depth,
+                 const float* coarse_depth, int B, int nver, int ntri, int H, int W, float* vertex_out, int out_pitch,
+                 unsigned char* state, void* stream);
+int fr_mesh_vertex_normals(const float* vertex, int vertex_pitch, const float* tri, const int* adj_start, const int* adj_tri, int B,
+                           int nver, int ntri, float* normal, int out_pitch, void* stream);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
