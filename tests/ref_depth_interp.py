@@ -109,20 +109,7 @@ def model(depth_grad, vertex, tri, tri_ind, H, W):
     R.shift, R.nver, R.faces = RN.shift_of(npix), nver, []
     for b in range(B):
         ids, _, T32 = terms(g[b], vertex[b], tri, tind[b], nver, W)
-        F = RN.Face()
-        flat = (np.arange(3)[None, None, :] * nver + ids.T[:, :, None]).ravel()      # [n, vertex k, row c] -> c * nver + id
-        t = T32.ravel()
-        fin = np.isfinite(t)
-        F.bad = bool((~fin).any())
-        F.elem, slot = np.unique(flat, return_inverse=True)
-        k = len(F.elem)
-        tf = np.where(fin, t, np.float32(0))
-        F.S = RN._exact_sums(slot, k, tf)
-        F.A = RN._exact_sums(slot, k, np.abs(tf))
-        F.n = np.bincount(slot, minlength=k).astype(np.int64)
-        F.nonfinite = np.bincount(slot, weights=~fin, minlength=k) > 0
-        F.M = RN.to_units(np.abs(tf).max()) if tf.size else 0
-        R.faces.append(F)
+        R.faces.append(RN.face_of(ids, T32, nver))
     return R
 
 

@@ -139,21 +139,61 @@ def model(normal_grad, vertex, tri, tri_ind, H, W, mode):
     for b in range(B):
         ids, _, T32, mag32 = terms(g[b], vertex[b], tri, tind[b], nver, mode)
         R.mag32.append(mag32)
-        F = Face()
-        flat = (np.arange(3)[None, None, :] * nver + ids.T[:, :, None]).ravel()      # [n, vertex k, row c] -> c * nver + id
-        t = T32.ravel()
-        fin = np.isfinite(t)
-        F.bad = bool((~fin).any())
-        F.elem, slot = np.unique(flat, return_inverse=True)
-        k = len(F.elem)
-        tf = np.where(fin, t, np.float32(0))
-        F.S = _exact_sums(slot, k, tf)
-        F.A = _exact_sums(slot, k, np.abs(tf))
-        F.n = np.bincount(slot, minlength=k).astype(np.int64)
-        F.nonfinite = np.bincount(slot, weights=~fin, minlength=k) > 0
-        F.M = to_units(np.abs(tf).max()) if tf.size else 0
-        R.faces.append(F)
+        R.faces.append(face_of(ids, T32, nver))
     return R
+
+
+FINITE, POS_INF, NEG_INF, NAN = 0, 1, 2, 3
+
+
+def face_of(ids, T32, nver):
+    """The Face of one face's terms (ids [3,n], T32 [n,3,3] fp32: axis 1 the vertex of the triangle, axis 2 the row).  Beside the
+    fields the class names: cls [k], what the header's rule for a face with a non-finite term makes of the element -- NAN where a
+    NaN term or Inf terms of both signs arrive, POS_INF / NEG_INF where Inf terms of that one sign arrive, else FINITE."""
+    F = Face()
+    flat = (np.arange(3)[None, None, :] * nver + ids.T[:, :, None]).ravel()          # [n, vertex k, row c] -> c * nver + id
+    t = T32.ravel()
+    fin = np.isfinite(t)
+    F.bad = bool((~fin).any())
+    F.elem, slot = np.unique(flat, return_inverse=True)
+    slot = slot.reshape(-1)
+    k = len(F.elem)
+    tf = np.where(fin, t, np.float32(0))
+    F.S = _exact_sums(slot, k, tf)
+    F.A = _exact_sums(slot, k, np.abs(tf))
+    F.n = np.bincount(slot, minlength=k).astype(np.int64)
+    F.nonfinite = np.bincount(slot, weights=~fin, minlength=k) > 0
+    F.M = to_units(np.abs(tf).max()) if tf.size else 0
+    has = lambda sel: np.bincount(slot, weights=sel, minlength=k) > 0                 # noqa: E731
+    nan, pinf, ninf = has(np.isnan(t)), has(t == np.inf), has(t == -np.inf)
+    F.cls = np.full(k, FINITE, np.int8)
+    F.cls[pinf] = POS_INF
+    F.cls[ninf] = NEG_INF
+    F.cls[nan | (pinf & ninf)] = NAN
+    return F
+
+
+def check_bad_faces(got, R):
+    """The header's rule on every face of R with a non-finite term (the faces check_bound leaves out; it names what the float-atomic
+    route guarantees, not bits): an element that receives a non-finite term comes out non-finite -- NaN where a NaN term or Infs of
+    both signs arrive, the Inf otherwise; every other element of the face is finite; an element with no term is +0.
+    Returns the number of such faces."""
+    got = np.ascontiguousarray(got, np.float32)
+    count = 0
+    for b, F in enumerate(R.faces):
+        if not F.bad:
+            continue
+        count += 1
+        flat = got[b].reshape(-1)
+        none = np.ones(flat.size, bool)
+        none[F.elem] = False
+        assert np.all(flat[none].view(np.uint32) == 0), "face %d: an element without terms is not +0" % b
+        z = flat[F.elem]
+        cls = np.where(np.isnan(z), NAN, np.where(z == np.inf, POS_INF, np.where(z == -np.inf, NEG_INF, FINITE)))
+        wrong = np.flatnonzero(cls != F.cls)
+        assert wrong.size == 0, "face %d: %d elements of the wrong class, first (row %d, vertex %d): got %r, the terms say class %d" % (
+            b, wrong.size, int(F.elem[wrong[0]]) // R.nver, int(F.elem[wrong[0]]) % R.nver, float(z[wrong[0]]), int(F.cls[wrong[0]]))
+    return count
 
 
 def to_units(x32):

@@ -201,12 +201,23 @@ def hand_planes(B, H, W, seed, nan=False):
     return tex, nrm, ti, light, target, weight
 
 
-def reaches_every_branch(tex, nrm, ti, light):
+BRANCHES = ("flipped", "not flipped", "unit", "not unit", "unlit", "lit", "tex clamped", "tex kept")
+
+
+def branches(tex, nrm, ti, light):
+    """which side of each clamp and of the lit / unlit branch the covered pixels of these planes reach -> dict over BRANCHES"""
     st = shade_terms(tex, nrm, ti, light)
     cov = st["covered"]
-    return bool((cov & st["flipped"]).any() and (cov & ~st["flipped"]).any() and (cov & st["unit"]).any() and
-                (cov & ~st["unit"]).any() and (cov & (st["s"] < 0)).any() and (cov & (st["s"] > 0)).any() and
-                (cov & (tex < EPS).any(-1)).any() and (~cov[:, 1:-1, 1:-1]).any() and not cov[:, 0].any() and not cov[:, :, -1].any())
+    low = np.asarray(tex, F) < EPS
+    sides = ((cov & st["flipped"]), (cov & ~st["flipped"]), (cov & st["unit"]), (cov & ~st["unit"]), (cov & (st["s"] < 0)),
+             (cov & (st["s"] > 0)), (cov & low.any(-1)), (cov & ~low.all(-1)))
+    return {name: bool(side.any()) for name, side in zip(BRANCHES, sides)}
+
+
+def reaches_every_branch(tex, nrm, ti, light):
+    cov = np.asarray(ti, F).reshape(np.shape(tex)[:3]) >= 0
+    return bool(all(branches(tex, nrm, ti, light).values()) and
+                (~cov[:, 1:-1, 1:-1]).any() and not cov[:, 0].any() and not cov[:, :, -1].any())
 
 
 def smooth_case(B=2, H=6, W=7, seed=3):

@@ -20,6 +20,7 @@ import ref_depth_interp as RD
 import ref_normal_backward as RN
 from conftest import pkg
 from gpu_util import ops, net_mod, assert_bits_equal
+from raw_calls import dbwd, dfwd
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -49,34 +50,6 @@ def geom(B, nver, H, W):
     out = (ctypes.c_int * 6)()
     _h().lib().fr_debug_depth_interp_bwd_geom(B, nver, H, W, out)
     return dict(zip(("splits", "range", "shift", "chunks", "lds", "xcd"), out))
-
-
-def dfwd(V, tri, ti, H, W, pitch=None, stream=None):
-    """fr_depth_interp_forward (device tensors; not synchronised) -> depth [B,H,W,1], pre-filled with NaN.
-    pitch = (floats per vertex row, nver)"""
-    h, L = _h(), _h().lib()
-    B = int(V.shape[0])
-    nver = int(V.shape[2]) if pitch is None else pitch[1]
-    out = torch.full((B, H, W, 1), float("nan"), device=DEV)
-    rc = L.fr_depth_interp_forward(h.ptr(V), nver if pitch is None else pitch[0], h.ptr(tri), h.ptr(ti), B, nver, int(tri.shape[1]),
-                                   H, W, h.ptr(out), _stream(stream))
-    assert rc == 0, rc
-    return out
-
-
-def dbwd(g, V, tri, ti, H, W, out=None, accumulate=0, pitch=None, stream=None):
-    """fr_depth_interp_backward with a workspace of its own -> vertex_grad, pre-filled with NaN unless `out` is given"""
-    h, L = _h(), _h().lib()
-    B = int(V.shape[0])
-    nver = int(V.shape[2]) if pitch is None else pitch[1]
-    nws = L.fr_depth_interp_backward_workspace_bytes(B, nver, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
-    if out is None:
-        out = torch.full((B, 3, nver), float("nan"), device=DEV)
-    rc = L.fr_depth_interp_backward(h.ptr(g), h.ptr(V), nver if pitch is None else pitch[0], h.ptr(tri), h.ptr(ti), h.ptr(out), B,
-                                    nver, int(tri.shape[1]), H, W, accumulate, h.ptr(ws), nws, _stream(stream))
-    assert rc == 0, rc
-    return out
 
 
 # ---- scenes: the synthetic mesh placed on an H x W screen, a pose per face ---------------------------------------------------------

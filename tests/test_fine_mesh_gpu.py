@@ -14,10 +14,10 @@ import torch
 
 import ref_mesh as RM
 from conftest import ROOT, pkg
+from raw_calls import SENT, raw_lift, raw_normals, raw_visible
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SENT = 0x7FC12345   # a NaN no kernel produces
 
 
 def _h():
@@ -42,42 +42,6 @@ def _sp():
 
 def _u32(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _sentinel(shape):
-    return torch.full(shape, SENT, dtype=torch.int32, device=DEV).view(torch.float32)
-
-
-def raw_visible(tri, tind, nver):
-    h, L = _h(), _h().lib()
-    B, H, W = tind.shape
-    out = torch.full((B, nver), 7, dtype=torch.uint8, device=DEV)
-    rc = L.fr_mesh_visible(h.ptr(tri) if tri.numel() else None, h.ptr(tind), B, nver, int(tri.shape[1]), H, W, h.ptr(out), _sp())
-    assert rc == 0, rc
-    return out
-
-
-def raw_lift(vertex, nver, tind, vis, fine, coarse, ntri, out_pitch):
-    """vertex [B,3,pitch] -> (vertex_out [B,3,out_pitch] pre-filled with the sentinel, state pre-filled with 7)"""
-    h, L = _h(), _h().lib()
-    B, H, W = tind.shape
-    out = _sentinel((B, 3, out_pitch))
-    state = torch.full((B, nver), 7, dtype=torch.uint8, device=DEV)
-    rc = L.fr_mesh_lift(h.ptr(vertex), int(vertex.shape[2]), h.ptr(tind), h.ptr(vis), h.ptr(fine), h.ptr(coarse), B, nver, ntri, H,
-                        W, h.ptr(out), out_pitch, h.ptr(state), _sp())
-    assert rc == 0, rc
-    return out, state
-
-
-def raw_normals(vertex, nver, tri, adj, out_pitch):
-    h, L = _h(), _h().lib()
-    B = int(vertex.shape[0])
-    out = _sentinel((B, 3, out_pitch))
-    a0, a1 = _t(adj[0], np.int32), _t(adj[1], np.int32)
-    rc = L.fr_mesh_vertex_normals(h.ptr(vertex), int(vertex.shape[2]), h.ptr(tri) if tri.numel() else None, h.ptr(a0),
-                                  h.ptr(a1) if a1.numel() else None, B, nver, int(tri.shape[1]), h.ptr(out), out_pitch, _sp())
-    assert rc == 0, rc
-    return out
 
 
 def _check_padded(out, want, nver):

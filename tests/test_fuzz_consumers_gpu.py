@@ -1,0 +1,224 @@
+"""Seeded differential fuzzing of every consumer of the rasteriser's tri_ind plane -- the normal backward (raw and post mode), the
+texture backward (shared and per-face texture), the interpolated depth (forward and backward), mesh_visible / mesh_lift, and
+synth_shade / photo_loss -- on the scenes of the rasteriser fuzz (tests/fuzz_scenes.py: jittered sub-pixel grids, triangle soup,
+small-triangle soup, integer coordinates with ties, and the specials: duplicated and degenerate triangles, NaN / Inf / 3e9 /
+subnormal / -0.0 coordinates, triangle ids of -1, nver, NaN and 0.75), cut down to at most 8 faces and 200,000 pixels.
+
+A case renders its scene once and holds the planes to the CPU oracle; every consumer and its numpy model (tests/ref_*.py) is then
+handed the ORACLE's tri_ind and normal planes, so a consumer's failure is not a forward failure in disguise.  No bound here is new
+or measured: each is the one include/fr_hotpath.h states for the kernel and the model already implements -- bits where the header
+says bit for bit, the integer bound of ref_normal_backward.check_bound for the owner-scatter sums, the header's class rule
+(ref_normal_backward.check_bad_faces, ref_texture_backward.assert_bad_scope) for a face or scope with a non-finite term.
+A second pass hands the consumers what no rendered scene holds (fuzz_scenes.ConsumerCase.altered): bad ids in triangles that do win
+pixels, and NaN / ntri / fractional / -0.0 entries in the plane.  Without it an `ok` test that ignores an id, or a NaN tri_ind taken as
+covered, passes every case.  tests/test_fuzz_scenes_cpu.py holds the seed set to reaching every class of input this file exists
+for, and names the seed base."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import fuzz_scenes as FS
+import ref_depth_interp as RD
+import ref_mesh as RM
+import ref_normal_backward as RN
+import ref_photo_loss as RP
+import ref_synth_batch as RS
+import ref_texture_backward as RT
+from gpu_util import assert_bits_equal, assert_render_equal, ops, render_gpu
+from raw_calls import (GAIN, OFFSET, SENT, PhotoCall, assert_f64_bits_equal, dbwd, dfwd, nbwd, raw_lift, raw_visible, tbwd)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+N_RENDER = int(os.environ.get("FR_FUZZ_CASES", "160"))
+N_CASES = max(1, N_RENDER * 3 // 10)
+
+
+def _t(a, dtype=np.float32):
+    return torch.as_tensor(np.ascontiguousarray(a, dtype), device=DEV)
+
+
+def _finite_faces(*models):
+    return np.array([not any(R.faces[b].bad for R in models) for b in range(len(models[0].faces))])
+
+
+def _twice(call, R, what, post=False):
+    """two launches of an owner-scatter backward -> the first result: bit-equal on the finite faces, and each within the model:
+    the integer bound there, the header's class rule on the faces with a non-finite term"""
+    first, second = call().cpu().numpy(), call().cpu().numpy()
+    fin = _finite_faces(R)
+    assert_bits_equal(first[fin], second[fin], what + ": two launches")
+    assert RN.check_bound(first, R, post=post) <= 1.0, what
+    for out in (first, second):
+        RN.check_bad_faces(out, R)
+    return first
+
+
+def check_normal_backward(c, ti, what, profiles=(0, 1)):
+    """-> (the raw-mode result and its model on the first gradient profile)"""
+    V, tri, tind = _t(c.ver), _t(c.tri), _t(ti)
+    keep = None
+    for mode in (0, 1):
+        for k in profiles:
+            g = c.g_normal[k]
+            R = RN.model(g, c.ver, c.tri, ti, c.H, c.W, mode)
+            gt = _t(g)
+            got = _twice(lambda: nbwd(gt, V, tri, tind, c.H, c.W, mode), R,
+                         "%s: normal backward, profile %d, %s" % (what, k, "post" if mode else "raw"), post=mode == 1)
+            if k == profiles[0] and mode == c.seed % 2:                       # once per case: accumulate onto a finite tensor
+                acc = nbwd(gt, V, tri, tind, c.H, c.W, mode, out=_t(c.old), accumulate=1).cpu().numpy()
+                fin = _finite_faces(R)
+                assert_bits_equal(acc[fin], (c.old + got)[fin], what + ": normal backward, accumulate")
+            if k == 0 and mode == 0:
+                keep = (got, R)
+    return keep
+
+
+def check_depth_interp(c, ti, what, profiles=(0, 1)):
+    V, tri, tind = _t(c.ver), _t(c.tri), _t(ti)
+    want = RD.forward(c.ver, c.tri, ti, c.H, c.W)
+    assert_bits_equal(dfwd(V, tri, tind, c.H, c.W).cpu().numpy(), want, what + ": interpolated depth")
+    keep = None
+    for k in profiles:
+        g = c.g_depth[k]
+        R = RD.model(g, c.ver, c.tri, ti, c.H, c.W)
+        gt = _t(g)
+        got = _twice(lambda: dbwd(gt, V, tri, tind, c.H, c.W), R, "%s: interpolated depth backward, profile %d" % (what, k))
+        if k == 0:
+            keep = (got, R)
+    return keep
+
+
+def check_texture_backward(c, ti, what, profiles=(0, 1)):
+    tri, tind = _t(c.tri), _t(ti)
+    keep = None
+    for k in profiles:
+        g = c.g_tex[k]
+        M = RT.model(g, c.tri, ti, c.nver, c.H, c.W, c.tex_batch)
+        got = tbwd(_t(g), tri, tind, c.nver, c.H, c.W, c.tex_batch).cpu().numpy()
+        for s in range(c.tex_batch):
+            if M.bad[s]:
+                RT.assert_bad_scope(got[s], M, s)
+            else:
+                assert_bits_equal(got[s], M.value()[s], "%s: texture backward, profile %d, scope %d of %d" % (what, k, s, c.tex_batch))
+        if k == 0:
+            keep = (got, M)
+    return keep
+
+
+def check_mesh(c, planes, what):
+    ntri = c.tri.shape[1]
+    tind = planes[3].reshape(c.B, c.H, c.W)
+    coarse = planes[0].reshape(c.B, c.H, c.W)
+    fine = c.with_noise(RM.fine_of(coarse))
+    m_vis = RM.visible(c.tri, tind, c.nver)
+    m_out, m_state = RM.lift(c.ver, tind, m_vis, fine, coarse, ntri)
+    g_vis = raw_visible(_t(c.tri), _t(tind), c.nver)
+    g_out, g_state = raw_lift(_t(c.ver), c.nver, _t(tind), g_vis, _t(fine), _t(coarse), ntri, c.nver + 3)
+    assert np.array_equal(g_vis.cpu().numpy(), m_vis), what + ": mesh_visible"
+    assert np.array_equal(g_state.cpu().numpy(), m_state), what + ": mesh_lift state"
+    g_out = g_out.cpu().numpy()
+    assert_bits_equal(g_out[:, :, :c.nver], m_out, what + ": mesh_lift")
+    assert (g_out[:, :, c.nver:].view(np.uint32) == SENT).all(), what + ": mesh_lift wrote a pad column"
+
+
+def check_shade_and_photo_loss(c, planes, what):
+    tex_img, normal, ti = planes[1], planes[2], planes[3]
+    weighted = c.weight is not None
+    im, mask = ops().synth_shade(_t(tex_img), _t(normal), _t(ti), _t(c.light), gain=GAIN, offset=OFFSET)
+    want_im, want_mask = RS.shade(tex_img, normal, ti, c.light, None, GAIN, OFFSET)
+    assert_bits_equal(im.cpu().numpy(), want_im, what + ": synth_shade im_gray")
+    assert_bits_equal(mask.cpu().numpy(), want_mask, what + ": synth_shade mask")
+
+    def run(nrm):
+        call = PhotoCall((tex_img, nrm, ti, c.light, c.target, c.weight), weighted)
+        sums = call.forward()
+        grads = call.backward(sums, c.grad_sse)
+        return sums.cpu().numpy(), [g.cpu().numpy() for g in grads]
+    sums, (gt, gn, gl) = run(normal)
+    want = RP.forward(tex_img, normal, ti, c.light, c.target, c.weight, GAIN, OFFSET)
+    assert_f64_bits_equal(sums, want, what + ": photo_loss sums")
+    gt_w, gn_w, gl_w, A = RP.backward(tex_img, normal, ti, c.light, c.target, c.grad_sse, c.weight, GAIN, OFFSET, sums=want)
+    assert_bits_equal(gt, gt_w, what + ": photo_loss grad_tex_img")
+    assert_bits_equal(gl, gl_w, what + ": photo_loss grad_light")
+    # grad_normal: the header's bound where the model is finite; where it is not, the same NaN or the same Inf
+    fin = np.isfinite(gn_w)
+    assert np.array_equal(np.isnan(gn), np.isnan(gn_w)), what + ": photo_loss grad_normal NaNs"
+    assert np.array_equal(gn[~fin & ~np.isnan(gn_w)], gn_w[~fin & ~np.isnan(gn_w)]), what + ": photo_loss grad_normal Infs"
+    bound = 2.0 ** -24 * np.abs(gn_w.astype(np.float64)) + 2.0 ** -40 * np.broadcast_to(A[..., None], gn_w.shape)
+    with np.errstate(invalid="ignore"):
+        err = np.abs(gn.astype(np.float64) - gn_w.astype(np.float64))
+        assert (err[fin] <= bound[fin]).all(), (what + ": photo_loss grad_normal", float(np.nanmax(err[fin] / bound[fin])))
+    covered = ti[..., 0] >= 0
+    assert not gt[~covered].view(np.uint32).any() and not gn[~covered].view(np.uint32).any()
+    # a NaN normal reaches its own pixel and its own face's sums, and nothing else changes by a bit: the same call with those
+    # normals replaced by finite ones
+    sick = covered & np.isnan(normal).any(-1)
+    if sick.any():
+        clean_sums, (gt2, gn2, gl2) = run(np.where(sick[..., None], np.float32(0.5), normal))
+        well = ~sick.reshape(c.B, -1).any(1)
+        assert_f64_bits_equal(sums[well], clean_sums[well], what + ": photo_loss, the faces without a NaN normal")
+        assert_f64_bits_equal(sums[:, 1], clean_sums[:, 1], what + ": photo_loss cnt")
+        assert_bits_equal(gl[well], gl2[well], what + ": photo_loss grad_light, the faces without a NaN normal")
+        assert_bits_equal(gt[~sick], gt2[~sick], what + ": photo_loss grad_tex_img, the pixels without a NaN normal")
+        assert_bits_equal(gn[~sick], gn2[~sick], what + ": photo_loss grad_normal, the pixels without a NaN normal")
+        assert np.isnan(sums[~well, 0]).all() and np.isfinite(clean_sums[:, 1]).all()
+
+
+def check_operator_surface(c, normal_part, depth_part, tex_part, what):
+    """the wiring, not the arithmetic: render_depth with the three flags and all three gradients arriving in one backward"""
+    B, H, W = c.B, c.H, c.W
+    v = _t(c.ver).requires_grad_(True)
+    tx = _t(c.tex).requires_grad_(True)
+    tri = _t(c.tri)
+    outs = ops().render_depth(v, tri, tx, torch.zeros((B, H, W, 3), device=DEV), normal_grad=True, texture_grad=True,
+                              depth_interp=True)
+    gd, gt, gn = _t(c.g_depth[0].reshape(B, H, W, 1)), _t(c.g_tex[0].reshape(B, H, W, 3)), _t(c.g_normal[0].reshape(B, H, W, 3))
+    torch.autograd.backward([outs[0], outs[1], outs[2]], [gd, gt, gn])
+    ti = outs[3].detach()
+    raw = dbwd(gd, v.detach(), tri, ti, H, W)
+    nbwd(gn, v.detach(), tri, ti, H, W, 0, out=raw, accumulate=1)
+    fin = _finite_faces(normal_part[1], depth_part[1])
+    assert_bits_equal(v.grad.cpu().numpy()[fin], raw.cpu().numpy()[fin], what + ": ver.grad through render_depth")
+    with np.errstate(invalid="ignore"):                                        # (a face with Inf terms of both signs is not in `fin`)
+        want = (depth_part[0] + normal_part[0])[fin]                           # the same two results, one fp32 add per element
+    assert_bits_equal(v.grad.cpu().numpy()[fin], want, what + ": ver.grad against the raw calls on the oracle's planes")
+    good = ~tex_part[1].bad                                                    # (a scope with a non-finite term has no bits to repeat)
+    assert tuple(tx.grad.shape) == tuple(c.tex.shape)
+    assert_bits_equal(tx.grad.cpu().numpy()[good], tex_part[0][good], what + ": texture.grad through render_depth")
+
+
+def run_case(c, oracle, what):
+    want = oracle.render_depth(c.ver, c.tri, c.tex, c.H, c.W)
+    assert_render_equal(render_gpu(c.ver, c.tri, c.tex, c.H, c.W), want, what)
+    ti = want[3].reshape(c.B, c.H * c.W)
+    normal_part = check_normal_backward(c, ti, what)
+    depth_part = check_depth_interp(c, ti, what)
+    tex_part = check_texture_backward(c, ti, what)
+    check_mesh(c, want, what)
+    check_shade_and_photo_loss(c, want, what)
+    check_operator_surface(c, normal_part, depth_part, tex_part, what)
+    # a second pass on what the rasteriser never emits (fuzz_scenes.ConsumerCase.altered): bad ids in triangles that DO win pixels,
+    # and NaN / ntri / fractional / -0.0 entries in the plane -- the pixels on which the consumers' two rules part.  Every consumer
+    # must treat them as its header paragraph and its model do; one gradient profile, by the seed's parity
+    a, ti2 = c.altered(ti)
+    what, one = what + ", altered table and plane", (c.seed % 2,)
+    planes2 = (want[0], want[1], want[2], ti2.reshape(want[3].shape))
+    check_normal_backward(a, ti2, what, one)
+    check_depth_interp(a, ti2, what, one)
+    check_texture_backward(a, ti2, what, one)
+    check_mesh(a, planes2, what)
+    check_shade_and_photo_loss(a, planes2, what)
+
+
+@pytest.mark.parametrize("seed", range(N_CASES))
+def test_consumers_of_tri_ind(oracle, seed):
+    c = FS.ConsumerCase(seed)
+    run_case(c, oracle, "consumer fuzz %d (scene %d, %s)" % (seed, c.drawn_from, FS.KINDS[c.kind]))
+
+
+def test_consumers_on_the_texture_clamp_scene(oracle):
+    """the class no seed reaches (tests/test_fuzz_scenes_cpu.py): tex_img below the shader's clamp under covered pixels"""
+    run_case(FS.clamp_scene(), oracle, "the texture clamp scene")

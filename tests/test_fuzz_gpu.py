@@ -10,6 +10,7 @@ import torch
 
 import ref_render_bwd_model as bwd_model
 from conftest import pkg
+from fuzz_scenes import _scene
 from gpu_util import assert_render_equal, net_mod, ops, render_gpu
 
 pytestmark = pytest.mark.gpu
@@ -17,65 +18,6 @@ pytestmark = pytest.mark.gpu
 # FR_FUZZ_CASES=3000 widens the sweep (a couple of minutes); the default keeps the suite short
 N_RENDER = int(os.environ.get("FR_FUZZ_CASES", "160"))
 N_DECODE = max(1, N_RENDER * 3 // 10)
-
-
-def _scene(seed):
-    rs = np.random.RandomState(seed)
-    B = int(rs.choice([1, 1, 2, 3, 5, 8, 17, 64, 70]))
-    H = int(rs.choice([1, 2, 3, 5, 9, 16, 31, 40, 64, 100, 200, 257]))
-    W = int(rs.choice([1, 2, 4, 7, 8, 9, 33, 64, 100, 200, 300]))
-    if B * H * W > 3_000_000:
-        B = max(1, 3_000_000 // (H * W))
-    kind = int(rs.randint(0, 5))
-    if kind == 0:      # jittered sub-pixel grid (the 3DMM regime), random triangle order
-        nu, nv = max(2, int(H * rs.uniform(0.8, 1.6))), max(2, int(W * rs.uniform(0.8, 1.6)))
-        gx, gy = np.meshgrid(np.linspace(-2.0, W + 1.0, nv), np.linspace(-2.0, H + 1.0, nu))
-        nver = nu * nv
-        ver = np.empty((B, 3, nver), np.float32)
-        j = rs.uniform(0.0, 0.6)
-        for b in range(B):
-            ver[b, 0] = (gx + rs.uniform(-j, j, gx.shape)).reshape(-1)
-            ver[b, 1] = (gy + rs.uniform(-j, j, gy.shape)).reshape(-1)
-            ver[b, 2] = rs.uniform(-5, 5, nver)
-        iu, iv = np.meshgrid(np.arange(nu - 1), np.arange(nv - 1), indexing="ij")
-        v00 = (iu * nv + iv).reshape(-1)
-        tri = np.concatenate([np.stack([v00, v00 + nv, v00 + 1]), np.stack([v00 + 1, v00 + nv, v00 + nv + 1])], 1)
-        tri = tri[:, rs.permutation(tri.shape[1])]
-    else:
-        nver = int(rs.randint(3, 3000))
-        ntri = int(rs.randint(1, 6000))
-        ver = np.empty((B, 3, nver), np.float32)
-        ver[:, 0] = rs.uniform(-0.2 * W - 1, 1.2 * W + 1, (B, nver))
-        ver[:, 1] = rs.uniform(-0.2 * H - 1, 1.2 * H + 1, (B, nver))
-        ver[:, 2] = rs.uniform(-50, 50, (B, nver))
-        tri = rs.randint(0, nver, (3, ntri))
-        if kind >= 2:   # most triangles small: two vertices near the first
-            scale = float(rs.choice([0.3, 1.0, 3.0, 12.0]))
-            k = min(ntri, nver // 3)
-            idx = rs.permutation(nver)[:3 * k].reshape(-1, 3)
-            for b in range(B):
-                c = ver[b, :2][:, idx[:, 0]]
-                ver[b, :2][:, idx[:, 1]] = c + rs.uniform(-scale, scale, c.shape).astype(np.float32)
-                ver[b, :2][:, idx[:, 2]] = c + rs.uniform(-scale, scale, c.shape).astype(np.float32)
-            tri[:, :k] = idx.T
-        if kind == 3:   # integer coordinates: pixel centres on edges and vertices, equal depths (ties)
-            ver[:, :2] = np.round(ver[:, :2])
-            ver[:, 2] = np.round(ver[:, 2] / 10)
-        if kind == 4:   # duplicates, degenerate triangles and special values
-            tri[:, ::7] = tri[:, ::7][:, ::-1] if tri[:, ::7].shape[1] > 1 else tri[:, ::7]
-            tri[1, ::11] = tri[0, ::11]
-            flat = ver.reshape(-1)
-            for val in (np.nan, np.inf, -np.inf, 3e9, -3e9, 1e-40, -0.0):
-                flat[rs.randint(0, flat.size, 3)] = val
-    tri = tri.astype(np.float32)
-    if kind == 4:
-        tri[rs.randint(0, 3), rs.randint(0, tri.shape[1])] = -1.0
-        tri[rs.randint(0, 3), rs.randint(0, tri.shape[1])] = float(nver)
-        tri[rs.randint(0, 3), rs.randint(0, tri.shape[1])] = np.nan
-        tri[rs.randint(0, 3), rs.randint(0, tri.shape[1])] = 0.75
-    tex_b = B if rs.rand() < 0.5 else 1
-    tex = rs.uniform(0, 1, (tex_b, 3, nver)).astype(np.float32)
-    return ver, tri, tex, H, W
 
 
 @pytest.mark.parametrize("seed", range(N_RENDER))

@@ -16,6 +16,7 @@ import torch
 import ref_normal_backward as RN
 from conftest import pkg
 from gpu_util import ops, net_mod
+from raw_calls import nbwd
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -41,24 +42,6 @@ def geom(B, nver, H, W):
     out = (ctypes.c_int * 6)()
     _h().lib().fr_debug_render_normal_bwd_geom(B, nver, H, W, out)
     return dict(zip(("splits", "range", "shift", "chunks", "lds", "xcd"), out))
-
-
-def nbwd(g, V, tri, ti, H, W, mode, out=None, accumulate=0, stride=3, offset=0, pitch=None):
-    """fr_render_normal_backward on torch's current stream (device tensors; not synchronised) -> vertex_grad, pre-filled with
-    NaN unless `out` is given"""
-    h, L = _h(), _h().lib()
-    B = int(V.shape[0])
-    nver = int(V.shape[2]) if pitch is None else pitch[1]                     # pitch = (floats per vertex row, nver)
-    ntri = int(tri.shape[1])
-    nws = L.fr_render_normal_backward_workspace_bytes(B, nver, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
-    if out is None:
-        out = torch.full((B, 3, nver), float("nan"), device=DEV)
-    rc = L.fr_render_normal_backward(ctypes.c_void_p(g.data_ptr() + 4 * offset), stride, h.ptr(V),
-                                     nver if pitch is None else pitch[0], h.ptr(tri), h.ptr(ti), h.ptr(out), B, nver, ntri, H, W,
-                                     mode, accumulate, h.ptr(ws), nws, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, rc
-    return out
 
 
 # ---- scenes: a handful of large triangles over chosen vertex ids of a mesh of any size -----------------------------------------

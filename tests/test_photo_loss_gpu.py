@@ -18,10 +18,10 @@ import torch
 from conftest import ROOT, pkg
 from gpu_util import assert_bits_equal, net_mod, ops
 import ref_photo_loss as RP
+from raw_calls import GAIN, OFFSET, PhotoCall as Call, assert_f64_bits_equal
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-GAIN, OFFSET = 1.75, -0.125
 # one partial tile; two full tiles plus 49 pixels; sixteen full tiles; 257 tiles: one more than the finish workgroup's 256 threads, so
 # thread 0 chains two partials
 SHAPES = [(1, 5, 6), (3, 33, 17), (2, 64, 64), (1, 257, 256)]
@@ -42,52 +42,6 @@ def _t(a):
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def assert_f64_bits_equal(got, want, what=""):
-    got, want = np.ascontiguousarray(got, np.float64), np.ascontiguousarray(want, np.float64)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = (got.view(np.uint64) != want.view(np.uint64)) & ~(np.isnan(got) & np.isnan(want))
-    assert not bad.any(), "%s: %d of %d float64 differ, first at %s: got %r want %r" % (
-        what, bad.sum(), got.size, tuple(np.argwhere(bad)[0]), got[tuple(np.argwhere(bad)[0])], want[tuple(np.argwhere(bad)[0])])
-
-
-class Call:
-    """the two entry points called directly, with buffers of the call's own (state, sums, gradients) on a given stream"""
-
-    def __init__(self, planes, weighted, gain=GAIN, offset=OFFSET):
-        tex, nrm, ti, light, target, weight = planes
-        self.B, self.H, self.W = ti.shape[:3]
-        self.t = [_t(tex), _t(nrm), _t(ti), _t(light), _t(target), _t(weight) if weighted else None]
-        self.gain, self.offset = gain, offset
-        self.L = pkg("_lib").lib()
-
-    def forward(self, stream=None):
-        dev = _dev()
-        st = torch.cuda.current_stream(dev) if stream is None else stream
-        nst = self.L.fr_photo_loss_state_bytes(self.B, self.H, self.W)
-        with torch.cuda.stream(st):
-            state = torch.full((nst,), 0xA5, dtype=torch.uint8, device=dev)       # (needs nothing cleared)
-            sums = torch.full((self.B, 6), float("nan"), dtype=torch.float64, device=dev)
-            rc = self.L.fr_photo_loss_forward(*[_p(x) for x in self.t], self.B, self.H, self.W, self.gain, self.offset, _p(sums),
-                                              _p(state), nst, ctypes.c_void_p(st.cuda_stream))
-        assert rc == 0
-        self.keep = state
-        return sums
-
-    def backward(self, sums, g, want=(True, True, True), stream=None):
-        dev = _dev()
-        st = torch.cuda.current_stream(dev) if stream is None else stream
-        with torch.cuda.stream(st):
-            nan = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=dev)   # noqa: E731
-            out = [nan(self.B, self.H, self.W, 3), nan(self.B, self.H, self.W, 3), nan(self.B, 4)]
-            g_t = torch.as_tensor(np.asarray(g, np.float64), device=dev)
-            rc = self.L.fr_photo_loss_backward(_p(g_t), _p(sums), *[_p(x) for x in self.t], self.B, self.H, self.W, self.gain,
-                                               self.offset, *[_p(o) if w else None for o, w in zip(out, want)],
-                                               ctypes.c_void_p(st.cuda_stream))
-        assert rc == 0
-        self.keep_g = g_t
-        return out
 
 
 def _grad_up(B):

@@ -17,6 +17,7 @@ import torch
 import ref_texture_backward as RT
 from conftest import pkg, ROOT
 from gpu_util import ops, net_mod, assert_bits_equal
+from raw_calls import tbwd
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -43,23 +44,6 @@ def geom(B, nver, H, W, tb):
     out = (ctypes.c_int * 7)()
     _h().lib().fr_debug_render_texture_bwd_geom(B, nver, H, W, tb, out)
     return dict(zip(GEOM, out))
-
-
-def tbwd(g, tri, ti, nver, H, W, tb, out=None, accumulate=0, stride=3, offset=0):
-    """fr_render_texture_backward on torch's current stream (device tensors; not synchronised) -> texture_grad [tb,3,nver],
-    pre-filled with NaN unless `out` is given"""
-    h, L = _h(), _h().lib()
-    B = int(ti.shape[0])
-    ntri = int(tri.shape[1])
-    nws = L.fr_render_texture_backward_workspace_bytes(B, nver, H, W, tb)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
-    if out is None:
-        out = torch.full((tb, 3, nver), float("nan"), device=DEV)
-    rc = L.fr_render_texture_backward(ctypes.c_void_p(g.data_ptr() + 4 * offset), stride, h.ptr(tri), h.ptr(ti), h.ptr(out), B, nver,
-                                      ntri, H, W, tb, accumulate, h.ptr(ws), nws,
-                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, rc
-    return out
 
 
 # ---- scenes: a handful of large triangles over chosen vertex ids of a mesh of any size -----------------------------------------
