@@ -261,8 +261,114 @@ def lib():
 DECODE_ARITH_Q30, DECODE_ARITH_F32 = 0, 1
 # This file is loaded under two module names (the package's `3dfacerecon_amd._lib`, and by path from the reference-style
 # flat modules rendering_layer/ops.py, nets/network.py, pipeline.py): process-wide choices live in ONE shared namespace.
-_STATE = sys.modules.setdefault("_fr_hotpath_state", types.SimpleNamespace(decode_arith=None, q30_levels=7, option_epoch=0))
+_STATE = sys.modules.setdefault("_fr_hotpath_state", types.SimpleNamespace(decode_arith=None, q30_levels=7, option_epoch=0,
+                                                                           pools={}))
 _ARITH_ENV = {"q30": 7, "q30l7": 7, "q30l5": 5, "q30l4": 4}
+
+
+def _torch_stream_key(dev):
+    import torch
+    return (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream,
+            torch.cuda.is_current_stream_capturing())
+
+
+class StreamBuffers:
+    """Device buffers that live from call to call, one per (kind, device, stream): a bounded pool.  What is kept in one is dead
+    once the call that wrote it has been enqueued -- the render forward writes every part of its workspace (hit records, bucket
+    offsets, tables: ~330 MB at 64 faces) that it later reads and its backward needs none of it; a loss's partial sums are
+    consumed by its own finish launch -- and launches on one stream are ordered, so consecutive calls on a stream share a buffer
+    where the reference cudaMallocs / cudaFrees six per call (render_depth_op.cu.cc:272-277, 335-340).  The rules:
+
+      R1  A pooled buffer is handed out only inside a hold -- `with pool.hold(kind, dev, nbytes) as ent:` -- and the entry's lock
+          is held until the with-block is left, i.e. until the C call that launches on `ent.buf` has returned.  Threads that share
+          a stream (every thread that sets none shares torch's default stream) share its entries, and one call's kernels must not
+          land between another call's launches on the same buffer.  The launches are asynchronous: the lock is held for
+          microseconds.  `ent.note` is the holder's own slot, read and written under the same lock (the render path keeps there
+          which triangle list the table in its workspace was packed from).
+      R2  A request larger than the entry replaces the entry: a new buffer, a new lock, an empty note.  A thread still inside a
+          hold on the old entry keeps the old buffer alive until it lets go.
+      R3  While the current stream is being captured into a hipGraph the hold yields a fresh entry that is never inserted, and
+          the pool is left exactly as it was: a captured launch must not point at a buffer the pool may later replace, so the
+          capture gets one of its own from the graph's memory pool.
+      R4  Lock order: an entry's lock, then the pool's dict lock.  The dict lock is a leaf -- taken for the lookup alone and
+          released before the entry's lock is waited for.  Holds nest in one place, render workspace -> "hand"
+          (rendering_layer/ops.py, _DecodeRenderingLayer.forward), and always in that order.
+      R5  Process-wide: the named pools (stream_buffers()) live in the namespace both loads of this file share, so every module
+          name this package is loaded under finds the same buffers.
+      Bounded: at most `bound` entries, the least recently used dropped first (a caller that cycles streams does not accumulate a
+      buffer per stream handle it ever used); clear() drops them all.  No buffer is smaller than `floor` bytes.
+
+    `alloc(nbytes, dev)` and `stream_key(dev)` -> (device index, stream handle, whether the stream is being captured) default to
+    torch's; a test without a GPU passes its own.  An entry carries the handle it was taken on as `stream`: a host-bound holder
+    launches on it without asking torch a second time."""
+
+    class Entry:
+        __slots__ = ("buf", "nbytes", "stream", "lock", "note", "pooled")
+
+        def __init__(self, buf, nbytes, stream, pooled):
+            self.buf, self.nbytes, self.stream, self.pooled = buf, nbytes, stream, pooled
+            self.lock = threading.Lock()
+            self.note = None
+
+    class _Hold:
+        __slots__ = ("ent", "asked")
+
+        def __init__(self, ent, asked):
+            self.ent, self.asked = ent, asked
+
+        def __enter__(self):
+            self.ent.lock.acquire()
+            return self.ent if self.asked is None else (self.asked, self.ent.buf)
+
+        def __exit__(self, *exc):
+            self.ent.lock.release()
+            return False
+
+    def __init__(self, bound, floor, alloc=None, stream_key=None):
+        self.bound, self.floor = bound, floor
+        self._alloc = alloc if alloc is not None else byte_buffer
+        self._stream_key = stream_key if stream_key is not None else _torch_stream_key
+        self._entries = {}   # (insertion order = least recently used first)
+        self._lock = threading.Lock()
+
+    def __len__(self):
+        return len(self._entries)
+
+    def clear(self):
+        with self._lock:
+            self._entries.clear()
+
+    def snapshot(self):
+        """{(kind, device index, stream handle): entry}, least recently used first"""
+        with self._lock:
+            return dict(self._entries)
+
+    def hold(self, kind, dev, nbytes, sized=False):
+        """The context manager of R1: entering it takes the entry's lock and gives the entry (`buf`: at least nbytes bytes) --
+        sized=True: the pair (nbytes, buf) instead, for a caller that hands exactly these two to its C call."""
+        asked = nbytes if sized else None
+        index, stream, capturing = self._stream_key(dev)
+        if capturing:
+            n = max(nbytes, self.floor)
+            return self._Hold(self.Entry(self._alloc(n, dev), n, stream, False), asked)
+        key = (kind, index, stream)
+        with self._lock:
+            ent = self._entries.pop(key, None)
+            if ent is None or ent.nbytes < nbytes:
+                n = max(nbytes, self.floor)
+                ent = self.Entry(self._alloc(n, dev), n, stream, True)
+            self._entries[key] = ent   # (re-inserted last: most recently used)
+            while len(self._entries) > self.bound:
+                del self._entries[next(iter(self._entries))]
+        return self._Hold(ent, asked)
+
+
+def stream_buffers(name, bound, floor):
+    """The process-wide pool of that name (R5), created at the first request."""
+    pool = _STATE.pools.get(name)
+    if pool is None:
+        pool = _STATE.pools.setdefault(name, StreamBuffers(bound, floor))
+    return pool
 
 
 def decode_arith():
@@ -351,6 +457,12 @@ def require_gpu_f32(t, name):
     if t.dtype != torch.float32:
         raise TypeError("%s must be float32 (got %s)" % (name, t.dtype))
     return t.contiguous()
+
+
+def byte_buffer(nbytes, dev, floor=16):
+    """A fresh device buffer of nbytes bytes, never smaller than `floor` (a size query may answer 0; a pointer must exist)."""
+    import torch
+    return torch.empty((max(nbytes, floor),), dtype=torch.uint8, device=dev)
 
 
 def stream_ptr(device):

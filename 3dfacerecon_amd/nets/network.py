@@ -73,8 +73,7 @@ class PackedBasis:
         self.q30_ws_bytes = L.fr_decode_q30_workspace_bytes(ndim_shape, ndim_exp)
         self._packed_ok = None
         self.backward_from_mu = False   # True: the autograd node's backward does not keep the forward's output (see _Decode3DMM)
-        self._bwd_ws = {}      # decode-backward workspaces by (device, stream, bytes): backward_workspace()
-        self._bwd_ws_lock = threading.Lock()   # threads on other streams take backwards through one basis at once
+        self._bwd_ws = _host().StreamBuffers(4, 16)   # decode-backward workspaces, the byte count as the kind: backward_workspace()
 
     def image_t(self):
         """The basis packed for the decode backward (fr_decode_backward_pack_basis), built on first use: callers that never
@@ -105,24 +104,12 @@ class PackedBasis:
         return self._packed_ok
 
     def backward_workspace(self, B, dev):
-        """(bytes, buffer) of the decode backward's workspace for B faces on torch's current stream of `dev`.  The buffer is kept
-        per (stream, size) -- launches on one stream are ordered, so consecutive backwards may share it; at most four are held
-        (least recently used dropped); under graph capture a fresh one is taken (a captured launch must not point at a buffer
-        the cache may later replace).  The size query and the allocation used to be paid per call: with the kernels at ~70 us
-        the autograd route was host-bound below 64 faces (profiles/round4_bwd_probe.log)."""
-        L = _host().lib()
-        nws = L.fr_decode_backward_workspace_bytes(B, self.nvert, self.ndim_shape, self.ndim_exp)
-        if torch.cuda.is_current_stream_capturing():
-            return nws, torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
-        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, nws)
-        with self._bwd_ws_lock:
-            buf = self._bwd_ws.pop(key, None)
-            if buf is None:
-                buf = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
-            self._bwd_ws[key] = buf               # (re-inserted last: most recently used)
-            while len(self._bwd_ws) > 4:
-                self._bwd_ws.pop(next(iter(self._bwd_ws)))
-        return nws, buf
+        """`with basis.backward_workspace(B, dev) as (bytes, buffer):` -- a hold (_lib.StreamBuffers) on the decode backward's
+        workspace for B faces on torch's current stream of `dev`, in this basis's own pool of four: kept per (stream, size), so
+        alternating batch sizes keep a buffer each.  The size query and the allocation used to be paid per call: with the
+        kernels at ~70 us the autograd route was host-bound below 64 faces (profiles/round4_bwd_probe.log)."""
+        nws = _host().lib().fr_decode_backward_workspace_bytes(B, self.nvert, self.ndim_shape, self.ndim_exp)
+        return self._bwd_ws.hold(nws, dev, nws, sized=True)
 
     def use_q30(self):
         """True when the Q30 entry point serves this call: selected AND the shape is covered (else the f32 chain)."""
@@ -207,22 +194,23 @@ class _Decode3DMM(torch.autograd.Function):
         L = h.lib()
         dev = params.device
         with torch.cuda.device(dev):
-            nws, ws = basis.backward_workspace(B, dev)
             Rp = h.ptr(R) if ctx.has_R else None
-            if ctx.from_mu:
-                rc = L.fr_decode_3dmm_backward_packed_mu(h.ptr(g), h.ptr(params), h.ptr(basis.mu), h.ptr(basis.image_t()), Rp, B,
-                                                         net.nvert, net.ndim_shape, net.ndim_exp, ctx.im_size, h.ptr(gp),
-                                                         h.ptr(ws), nws, h.stream_ptr(dev))
-            elif ctx.packed:
-                # (the fused kernel streams the packed image: built once per basis, at the first backward)
-                rc = L.fr_decode_3dmm_backward_packed(h.ptr(g), h.ptr(params), h.ptr(ctx.saved_tensors[2]), h.ptr(basis.image_t()),
-                                                      Rp, B, net.nvert, net.ndim_shape, net.ndim_exp, ctx.im_size, h.ptr(gp),
-                                                      h.ptr(ws), nws, h.stream_ptr(dev))
-            else:   # more than 256 coefficients or fewer than 16 vertices (not the model's): reference-layout entry point
-                out = ctx.saved_tensors[2]
-                rc = L.fr_decode_3dmm_backward(h.ptr(g), h.ptr(params), h.ptr(out), h.ptr(basis.pc_shape),
-                                               h.ptr(basis.pc_exp), Rp, B, net.nvert, net.ndim_shape, net.ndim_exp,
-                                               ctx.im_size, h.ptr(gp), h.ptr(ws), nws, h.stream_ptr(dev))
+            # (the fused kernels stream the packed image: built once per basis, at the first backward -- before the hold)
+            image_t = basis.image_t() if ctx.packed else None
+            with basis.backward_workspace(B, dev) as (nws, ws):
+                if ctx.from_mu:
+                    rc = L.fr_decode_3dmm_backward_packed_mu(h.ptr(g), h.ptr(params), h.ptr(basis.mu), h.ptr(image_t), Rp, B,
+                                                             net.nvert, net.ndim_shape, net.ndim_exp, ctx.im_size, h.ptr(gp),
+                                                             h.ptr(ws), nws, h.stream_ptr(dev))
+                elif ctx.packed:
+                    rc = L.fr_decode_3dmm_backward_packed(h.ptr(g), h.ptr(params), h.ptr(ctx.saved_tensors[2]), h.ptr(image_t),
+                                                          Rp, B, net.nvert, net.ndim_shape, net.ndim_exp, ctx.im_size, h.ptr(gp),
+                                                          h.ptr(ws), nws, h.stream_ptr(dev))
+                else:   # more than 256 coefficients or fewer than 16 vertices (not the model's): reference-layout entry point
+                    out = ctx.saved_tensors[2]
+                    rc = L.fr_decode_3dmm_backward(h.ptr(g), h.ptr(params), h.ptr(out), h.ptr(basis.pc_shape),
+                                                   h.ptr(basis.pc_exp), Rp, B, net.nvert, net.ndim_shape, net.ndim_exp,
+                                                   ctx.im_size, h.ptr(gp), h.ptr(ws), nws, h.stream_ptr(dev))
             h.check(rc, "fr_decode_3dmm_backward")
             gR = None
             if ctx.pose_grad:
@@ -231,7 +219,7 @@ class _Decode3DMM(torch.autograd.Function):
                     gR = torch.empty_like(R)
                 if gR is not None or not ctx.has_R:
                     pws_bytes = L.fr_decode_pose_backward_workspace_bytes(B, net.nvert)
-                    pws = torch.empty((max(pws_bytes, 16),), dtype=torch.uint8, device=dev)
+                    pws = h.byte_buffer(pws_bytes, dev)
                     rc = L.fr_decode_pose_backward(h.ptr(g), h.ptr(ctx.saved_tensors[2]), h.ptr(params), Rp, B, net.nvert,
                                                    net.ndim_shape, net.ndim_exp, ctx.im_size, h.ptr(gp), h.ptr(gR), h.ptr(pws),
                                                    pws_bytes, h.stream_ptr(dev))
@@ -463,9 +451,10 @@ class FaceRecNet:
     def gram_state(self, B, dev, stream):
         """(key, bytes, buffer): a state buffer of the Gram-form loss for B faces on `stream` (torch's current stream of `dev`, as
         its address), the caller's until it hands it back through gram_state_done(key, buffer).  Free buffers are kept per
-        (stream, size), like PackedBasis.backward_workspace -- launches on one stream are ordered, so the next call may reuse
-        what the last one's backward has read -- at most four in all; a buffer that never comes back (a forward without a
-        backward) is the allocator's again when its node dies.  Under graph capture a fresh one is taken and never pooled."""
+        (stream, size) -- launches on one stream are ordered, so the next call may reuse what the last one's backward has read --
+        at most four in all; a buffer that never comes back (a forward without a backward) is the allocator's again when its
+        node dies.  Under graph capture a fresh one is taken and never pooled.  (Not a _lib.StreamBuffers hold: the buffer is one
+        node's from its forward to its backward, not one call's -- a free list, where that pool shares entries under a lock.)"""
         nst = self._gram_nst.get(B)
         if nst is None:
             nst = self._gram_nst[B] = _host().lib().fr_geometry_loss_state_bytes(B, self.ndim_shape, self.ndim_exp)

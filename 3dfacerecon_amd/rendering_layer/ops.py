@@ -14,12 +14,10 @@ C ABI of include/fr_hotpath.h through ctypes on torch's current HIP stream.  Lik
 module loads the native library and builds it first if the .so is missing (reference ops.py:63-72) -- but there
 is no fallback path: no library or no GPU tensor => an exception.
 """
-import collections
 import ctypes
 import importlib.util
 import os
 import sys
-import threading
 import weakref
 
 import torch
@@ -55,63 +53,29 @@ def compile(op=None):
 _host().lib()
 
 
-# Render workspace (hit records, bucket offsets, tables: ~330 MB at 64 faces) reused across calls: one buffer per
-# (device, stream), grown on demand.  The forward writes every part it later reads and nothing of it is needed by the
-# backward, so calls on one stream can share it; the reference cudaMallocs / cudaFrees six buffers per call
-# (render_depth_op.cu.cc:272-277, 335-340).
-#   * bounded: at most WS_CACHE_MAX entries, least recently used evicted first (a caller that cycles streams no longer
-#     accumulates one 330 MB buffer per stream handle it ever used); clear_workspace_cache() drops them all;
-#   * never used while the current stream is being captured into a hipGraph: a captured launch must not point at a buffer
-#     the cache may later replace, so the capture gets a buffer of its own from the graph's memory pool;
-#   * the cache itself is guarded by _WS_LOCK (autograd worker threads call the forward too), and each entry by a lock of its
-#     own, held from the choice of phases through the launch to the record of the packed table: threads that share a stream
-#     (every thread that sets none shares torch's default stream) share its entry, and one thread's pack must not land between
-#     another's choice to skip it and that thread's launch -- nor its kernels between another call's emit and resolve.  The
-#     launch is asynchronous, so the lock is held for microseconds.
-# Each entry also remembers which triangle list its pre-validated triangle table (pack_tri_kernel) was built from -- the
-# tensor OBJECT (held weakly), its torch version counter and the geometry -- so a loop that renders with the same `tri`
-# tensor every call (the reference makes it a tf.constant, network.py:178) packs it once, not once per call.  A new tensor
-# is never mistaken for an old one whose memory the caching allocator handed out again (object identity, not data_ptr);
-# the version counter sees in-place torch writes; a caller that rewrites the tensor's memory behind torch's back must call
-# clear_workspace_cache().
+# The buffers that live from call to call (_lib.StreamBuffers: its docstring has the rules).  Two pools, so that a small scratch
+# kind cycling through never evicts a 330 MB render workspace and the triangle table packed into it.
 WS_CACHE_MAX = 4
-_WS_CACHE = collections.OrderedDict()
-_WS_LOCK = threading.Lock()
-
-
-class _WsEntry:
-    __slots__ = ("buf", "tri_ref", "tri_key", "lock")
-
-    def __init__(self, buf):
-        self.buf = buf
-        self.lock = threading.Lock()   # decide phases -> launch -> record the table, as one step
-        self.tri_ref = None   # weakref to the tensor the table was packed from
-        self.tri_key = None   # (its version counter, its data_ptr) + geometry
+_RENDER_POOL = _host().stream_buffers("render", WS_CACHE_MAX, 16)
+# What the autograd nodes and fits below keep per kind and stream: the pitched vertex hand-off of the decode -> rendering-layer
+# forward ("hand"), the workspace of its backward ("bwd"), the partial sums of the losses and fits.
+_KINDS_POOL = _host().stream_buffers("scratch", 8, 256)
 
 
 def clear_workspace_cache():
-    """Releases every cached render workspace (their memory returns to torch's caching allocator)."""
-    with _WS_LOCK:
-        _WS_CACHE.clear()
-        _SCRATCH.clear()
+    """Releases every pooled render workspace and scratch buffer (their memory returns to torch's caching allocator), with the
+    record of which triangle list each workspace's table was packed from.  The pools are process-wide: this reaches what every
+    load of this file uses -- the package's, and the one nets/network.py (FaceRecNet) and nets/losses.py load by path."""
+    _RENDER_POOL.clear()
+    _KINDS_POOL.clear()
 
 
-def _workspace(dev, nbytes):
-    """-> (entry, cached): the workspace entry for torch's current stream on `dev`."""
-    if torch.cuda.is_current_stream_capturing():
-        return _WsEntry(torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)), False
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    with _WS_LOCK:
-        ent = _WS_CACHE.get(key)
-        if ent is None or ent.buf.numel() < nbytes:
-            ent = _WsEntry(torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev))
-            _WS_CACHE[key] = ent
-        _WS_CACHE.move_to_end(key)
-        while len(_WS_CACHE) > WS_CACHE_MAX:
-            _WS_CACHE.popitem(last=False)
-    return ent, True
-
-
+# A render workspace's entry remembers in `note` which triangle list its pre-validated triangle table (pack_tri_kernel) was built
+# from -- (a weak reference to the tensor OBJECT, (its torch version counter, its data_ptr, the option epoch) + the geometry) --
+# so a loop that renders with the same `tri` tensor every call (the reference makes it a tf.constant, network.py:178) packs it
+# once, not once per call.  A new tensor is never mistaken for an old one whose memory the caching allocator handed out again
+# (object identity, not data_ptr); the version counter sees in-place torch writes; a caller that rewrites the tensor's memory
+# behind torch's back must call clear_workspace_cache().
 def _render_phases(ent, cached, tri_c, geom):
     """-> (phases, pending): phases = 7 (pack + emit + resolve), or 3 when the entry's triangle table was packed from this very
     list for this geometry under the launcher options in force now; `pending` is the record _table_packed() commits once the
@@ -119,32 +83,52 @@ def _render_phases(ent, cached, tri_c, geom):
     # an inference tensor (created under torch.inference_mode()) has no version counter: in-place writes to it cannot be
     # seen, so its table is never reused -- packed every call, like a caller that passes a new tensor each time
     if tri_c.is_inference():
-        ent.tri_ref = ent.tri_key = None
+        ent.note = None
         return 7, None
     # (the option epoch: FR_RENDER_IMPL / FR_RENDER_ROWS / FR_EMIT_ORDER decide whether and how the table is written, and
     # can only change through _lib.set_option, which bumps it)
     key = (tri_c._version, tri_c.data_ptr(), _host().option_epoch()) + geom
-    if cached and ent.tri_ref is not None and ent.tri_ref() is tri_c and ent.tri_key == key:
+    if cached and ent.note is not None and ent.note[0]() is tri_c and ent.note[1] == key:
         return 3, None
-    ent.tri_ref = ent.tri_key = None   # whatever this call does, the old record no longer describes the table
+    ent.note = None   # whatever this call does, the old record no longer describes the table
     return 7, ((weakref.ref(tri_c), key) if cached else None)
 
 
 def _table_packed(ent, pending):
     if pending is not None:
-        ent.tri_ref, ent.tri_key = pending
+        ent.note = pending
 
 
 def _render_with_workspace(dev, ws_bytes, tri_c, geom, call):
-    """The step every render forward makes as one, under the entry's lock: take the stream's workspace, choose the phases, make the
-    call -- call(workspace buffer, phases) -> rc -- and, where it returned 0, record the table it packed.  -> rc"""
-    ent, cached = _workspace(dev, ws_bytes)
-    with ent.lock:
-        phases, pending = _render_phases(ent, cached, tri_c, geom)
+    """The step every render forward makes as one, inside a hold on the stream's workspace (decide the phases -> launch -> record
+    the table: one thread's pack must not land between another's choice to skip it and that thread's launch): choose the phases,
+    make the call -- call(workspace buffer, phases) -> rc -- and, where it returned 0, record the table it packed.  -> rc"""
+    with _RENDER_POOL.hold("render", dev, ws_bytes) as ent:
+        phases, pending = _render_phases(ent, ent.pooled, tri_c, geom)
         rc = call(ent.buf, phases)
         if rc == 0:
             _table_packed(ent, pending)
     return rc
+
+
+def _check_ver(ver):
+    if ver.dim() != 3 or ver.shape[1] != 3:
+        raise ValueError("The vertex is not Batch x 3 x nver")
+
+
+def _check_tri(tri):
+    if tri.dim() != 2 or tri.shape[0] != 3:
+        raise ValueError("The tri is not 3 x ntri")
+
+
+def _check_plane(op, name, t, B, H, W, c, dev=None, anchor=None, flat=False):
+    """ValueError unless `t` is a pixel plane [B,H,W,c] (flat: or [B,H,W]) and -- where `dev` is given -- on `dev`, the device of
+    the op's argument `anchor`"""
+    shapes = ((B, H, W, c), (B, H, W)) if flat else ((B, H, W, c),)
+    if tuple(t.shape) not in shapes:
+        raise ValueError("%s: %s must be %s (got %s)" % (op, name, " or ".join(str(list(s)) for s in shapes), tuple(t.shape)))
+    if dev is not None and t.device != dev:
+        raise ValueError("%s: %s is on %s, %s on %s" % (op, name, t.device, anchor, dev))
 
 
 def _check_forward_shapes(ver, tri, texture, image):
@@ -154,10 +138,8 @@ def _check_forward_shapes(ver, tri, texture, image):
     B = image.shape[0]
     if ver.shape[0] != B:
         raise ValueError("The vertex's batch is not the same as image batch")
-    if ver.shape[1] != 3:
-        raise ValueError("The vertex is not Batch x 3 x nver")
-    if tri.shape[0] != 3:
-        raise ValueError("The tri is not 3 x ntri")
+    _check_ver(ver)
+    _check_tri(tri)
     if texture.shape[-2] != 3:
         raise ValueError("The texture channel must be equal to image channel namely 3")
     if texture.shape[-1] != ver.shape[2]:
@@ -170,7 +152,7 @@ def _backward_call(h, g, tri_c, tri_ind, vertex_grad, B, nver, ntri, H, W, dev):
     """fr_render_depth_backward_ws with its workspace (one 16-byte record per pixel)."""
     L = h.lib()
     nws = L.fr_render_depth_backward_workspace_bytes(B, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
+    ws = h.byte_buffer(nws, dev)
     rc = L.fr_render_depth_backward_ws(h.ptr(g), h.ptr(tri_c), h.ptr(tri_ind), h.ptr(vertex_grad), B, nver, ntri, H, W,
                                        h.ptr(ws), nws, h.stream_ptr(dev))
     h.check(rc, "fr_render_depth_backward")
@@ -182,7 +164,7 @@ def _normal_backward_call(h, g, g_offset, g_stride, ver_c, tri_c, tri_ind, verte
     `g_stride` floats between pixels; accumulate=1 completes a vertex_grad the depth backward has written on this stream."""
     L = h.lib()
     nws = L.fr_render_normal_backward_workspace_bytes(B, nver, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
+    ws = h.byte_buffer(nws, dev)
     rc = L.fr_render_normal_backward(ctypes.c_void_p(g.data_ptr() + 4 * g_offset), g_stride, h.ptr(ver_c), nver, h.ptr(tri_c),
                                      h.ptr(tri_ind), h.ptr(vertex_grad), B, nver, ntri, H, W, mode, accumulate, h.ptr(ws), nws,
                                      h.stream_ptr(dev))
@@ -194,7 +176,7 @@ def _texture_backward_call(h, g, g_offset, g_stride, tri_c, tri_ind, texture_gra
     at `g_offset` floats into `g`, `g_stride` floats between pixels; texture_grad is dense [tex_batch,3,nver]."""
     L = h.lib()
     nws = L.fr_render_texture_backward_workspace_bytes(B, nver, H, W, tex_batch)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
+    ws = h.byte_buffer(nws, dev)
     rc = L.fr_render_texture_backward(ctypes.c_void_p(g.data_ptr() + 4 * g_offset), g_stride, h.ptr(tri_c), h.ptr(tri_ind),
                                       h.ptr(texture_grad), B, nver, ntri, H, W, tex_batch, accumulate, h.ptr(ws), nws,
                                       h.stream_ptr(dev))
@@ -218,7 +200,7 @@ def _depth_interp_backward_call(h, g, ver_c, tri_c, tri_ind, vertex_grad, B, nve
         return
     L = h.lib()
     nws = L.fr_depth_interp_backward_workspace_bytes(B, nver, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=dev)
+    ws = h.byte_buffer(nws, dev)
     rc = L.fr_depth_interp_backward(h.ptr(g), h.ptr(ver_c), nver, h.ptr(tri_c), h.ptr(tri_ind), h.ptr(vertex_grad), B, nver, ntri,
                                     H, W, accumulate, h.ptr(ws), nws, h.stream_ptr(dev))
     h.check(rc, "fr_depth_interp_backward")
@@ -397,27 +379,6 @@ class _RenderingLayerFused(torch.autograd.Function):
         return vertex_grad, None, None, None, None
 
 
-# Per-stream scratch of the decode -> rendering-layer node, kept like the render workspace (least recently used dropped, a
-# fresh buffer under graph capture): the pitched vertex hand-off of the forward and the workspace of the backward.  Launches on
-# one stream are ordered, so consecutive calls share a buffer; nothing in it outlives the call that wrote it.
-_SCRATCH = collections.OrderedDict()
-_SCRATCH_MAX = 8
-
-
-def _scratch(kind, dev, nbytes):
-    if torch.cuda.is_current_stream_capturing():
-        return torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-    key = (kind, dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    with _WS_LOCK:
-        buf = _SCRATCH.pop(key, None)
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-        _SCRATCH[key] = buf
-        while len(_SCRATCH) > _SCRATCH_MAX:
-            _SCRATCH.popitem(last=False)
-    return buf
-
-
 class _DecodeRenderingLayer(torch.autograd.Function):
     """vertices_transform -> coarse_net_input as ONE autograd node (include/fr_hotpath.h, "differentiable decode ->
     rendering-layer step"): (params, R, im_gray) -> (net_input [B,H,W,7], depth_img [B,H,W,1]).  Forward:
@@ -443,8 +404,7 @@ class _DecodeRenderingLayer(torch.autograd.Function):
         B = int(p.shape[0])
         if img_c.dim() != 4 or img_c.shape[0] != B or img_c.shape[-1] != 1:
             raise ValueError("im_gray must be [B,H,W,1]")
-        if tri_c.dim() != 2 or tri_c.shape[0] != 3:
-            raise ValueError("The tri is not 3 x ntri")
+        _check_tri(tri_c)
         if tex_c.dim() not in (2, 3) or tex_c.shape[-2] != 3 or tex_c.shape[-1] != N:
             raise ValueError("The texture is not Batch x 3 x nver")
         tex_batch = 1 if tex_c.dim() == 2 else int(tex_c.shape[0])
@@ -462,17 +422,21 @@ class _DecodeRenderingLayer(torch.autograd.Function):
         with torch.cuda.device(dev):
             ws_bytes = L.fr_render_depth_workspace_bytes(B, N, ntri, H, W)
             hand_bytes = L.fr_decode_render_vertex_bytes(B, N)
-            hand = None
+            hand = h.byte_buffer(hand_bytes, dev, 256) if pose_grad else None
 
-            def call(ws, phases):
-                # (the hand-off is taken under the entry's lock: threads that share the stream share both buffers)
-                nonlocal hand
-                hand = (torch.empty((max(hand_bytes, 256),), dtype=torch.uint8, device=dev) if pose_grad
-                        else _scratch("hand", dev, hand_bytes))
+            def launch(ws, phases, hand):
                 return L.fr_decode_rendering_layer_forward(h.ptr(p), h.ptr(basis.image), h.ptr(R), h.ptr(tri_c), h.ptr(tex_c),
                                                            h.ptr(img_c), B, N, ns, ne, ntri, H, W, tex_batch, float(im_size),
                                                            h.ptr(hand), hand_bytes, h.ptr(net_in), h.ptr(depth_img), h.ptr(depth),
                                                            h.ptr(tri_ind), h.ptr(ws), ws_bytes, h.stream_ptr(dev), 8 | phases)
+
+            def call(ws, phases):
+                if pose_grad:
+                    return launch(ws, phases, hand)
+                # (the one nested hold: the pooled hand-off is taken inside the hold on the render workspace -- threads that
+                # share the stream share both buffers)
+                with _KINDS_POOL.hold("hand", dev, hand_bytes) as ent:
+                    return launch(ws, phases, ent.buf)
             rc = _render_with_workspace(dev, ws_bytes, tri_c, (B, N, ntri, H, W), call)
         if rc == -4:
             raise NotImplementedError("decode -> rendering layer: shape only covered by the fallback rasteriser")
@@ -505,19 +469,20 @@ class _DecodeRenderingLayer(torch.autograd.Function):
                 if ctx.has_R and ctx.needs_input_grad[1]:
                     gR = torch.empty_like(R)
                 nws = L.fr_decode_render_backward_pose_workspace_bytes(B, N, ns, ne, H, W)
-                ws = _scratch("bwd", dev, nws)
-                rc = L.fr_decode_render_backward_pose(None, h.ptr(gd), h.ptr(gn), h.ptr(img), h.ptr(depth), h.ptr(ctx.tri),
-                                                      h.ptr(tri_ind), h.ptr(p), h.ptr(basis.mu), h.ptr(image_t),
-                                                      h.ptr(R) if ctx.has_R else None, B, N, ns, ne, ntri, H, W, ctx.im_size,
-                                                      h.ptr(gp), h.ptr(ws), nws, h.stream_ptr(dev), h.ptr(ctx.hand[0]),
-                                                      ctx.hand[1], h.ptr(gR))
+                with _KINDS_POOL.hold("bwd", dev, nws) as ent:
+                    rc = L.fr_decode_render_backward_pose(None, h.ptr(gd), h.ptr(gn), h.ptr(img), h.ptr(depth), h.ptr(ctx.tri),
+                                                          h.ptr(tri_ind), h.ptr(p), h.ptr(basis.mu), h.ptr(image_t),
+                                                          h.ptr(R) if ctx.has_R else None, B, N, ns, ne, ntri, H, W, ctx.im_size,
+                                                          h.ptr(gp), h.ptr(ent.buf), nws, h.stream_ptr(dev), h.ptr(ctx.hand[0]),
+                                                          ctx.hand[1], h.ptr(gR))
                 h.check(rc, "fr_decode_render_backward_pose")
                 return gp, gR, None, None, None, None, None, None
             nws = L.fr_decode_render_backward_workspace_bytes(B, N, ns, ne, H, W)
-            ws = _scratch("bwd", dev, nws)
-            rc = L.fr_decode_render_backward(None, h.ptr(gd), h.ptr(gn), h.ptr(img), h.ptr(depth), h.ptr(ctx.tri), h.ptr(tri_ind),
-                                             h.ptr(p), h.ptr(basis.mu), h.ptr(image_t), h.ptr(R) if ctx.has_R else None, B, N, ns,
-                                             ne, ntri, H, W, ctx.im_size, h.ptr(gp), h.ptr(ws), nws, h.stream_ptr(dev))
+            with _KINDS_POOL.hold("bwd", dev, nws) as ent:
+                rc = L.fr_decode_render_backward(None, h.ptr(gd), h.ptr(gn), h.ptr(img), h.ptr(depth), h.ptr(ctx.tri),
+                                                 h.ptr(tri_ind), h.ptr(p), h.ptr(basis.mu), h.ptr(image_t),
+                                                 h.ptr(R) if ctx.has_R else None, B, N, ns, ne, ntri, H, W, ctx.im_size, h.ptr(gp),
+                                                 h.ptr(ent.buf), nws, h.stream_ptr(dev))
         h.check(rc, "fr_decode_render_backward")
         return gp, None, None, None, None, None, None, None
 
@@ -551,10 +516,7 @@ def _sfs_inputs(op, h, abedo, normal, im_gray, abedo_new, normal_new, abedo_grad
         raise ValueError("%s expects normal [B,H,W,3]" % op)
     B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
     for t, name, c in ((a_c, "abedo", 1), (i_c, "im_gray", 1), (a2_c, "abedo_new", 1), (n2_c, "normal_new", 3)):
-        if tuple(t.shape) != (B, H, W, c):
-            raise ValueError("%s: %s must be [%d,%d,%d,%d] (got %s)" % (op, name, B, H, W, c, tuple(t.shape)))
-        if t.device != n_c.device:
-            raise ValueError("%s: %s is on %s, normal on %s" % (op, name, t.device, n_c.device))
+        _check_plane(op, name, t, B, H, W, c, n_c.device, "normal")
     return a_c, n_c, i_c, a2_c, n2_c, B, H, W
 
 
@@ -754,11 +716,7 @@ class _DepthNormals(torch.autograd.Function):
         m_c = None
         if mask is not None:
             m_c = h.require_gpu_f32(mask, "mask")
-            if tuple(m_c.shape) not in ((B, H, W, 1), (B, H, W)):
-                raise ValueError("depth_normals: mask must be [%d,%d,%d,1] or [%d,%d,%d] (got %s)"
-                                 % (B, H, W, B, H, W, tuple(m_c.shape)))
-            if m_c.device != d_c.device:
-                raise ValueError("depth_normals: mask is on %s, depth on %s" % (m_c.device, d_c.device))
+            _check_plane("depth_normals", "mask", m_c, B, H, W, 1, d_c.device, "depth", flat=True)
         dev = d_c.device
         normal = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
@@ -806,10 +764,8 @@ class _DepthInterpolate(torch.autograd.Function):
         ver_c = h.require_gpu_f32(ver, "ver")
         tri_c = h.require_gpu_f32(tri, "tri")
         ti_c = h.require_gpu_f32(tri_ind, "tri_ind")
-        if ver_c.dim() != 3 or ver_c.shape[1] != 3:
-            raise ValueError("The vertex is not Batch x 3 x nver")
-        if tri_c.dim() != 2 or tri_c.shape[0] != 3:
-            raise ValueError("The tri is not 3 x ntri")
+        _check_ver(ver_c)
+        _check_tri(tri_c)
         if ti_c.dim() != 4 or ti_c.shape[0] != ver_c.shape[0] or ti_c.shape[3] != 1:
             raise ValueError("depth_interpolate expects tri_ind [B,H,W,1] with the vertex's batch (got %s)" % (tuple(ti_c.shape),))
         if tri_c.device != ver_c.device or ti_c.device != ver_c.device:
@@ -852,10 +808,7 @@ def depth_interpolate(ver, tri, tri_ind):
 def _mesh_plane(h, t, name, op, B, H, W, dev):
     """a [B,H,W,1] or [B,H,W] fp32 plane on `dev`, detached and contiguous"""
     t_c = h.require_gpu_f32(t.detach() if isinstance(t, torch.Tensor) else t, name)
-    if tuple(t_c.shape) not in ((B, H, W, 1), (B, H, W)):
-        raise ValueError("%s: %s must be [%d,%d,%d,1] or [%d,%d,%d] (got %s)" % (op, name, B, H, W, B, H, W, tuple(t_c.shape)))
-    if t_c.device != dev:
-        raise ValueError("%s: %s is on %s, expected %s" % (op, name, t_c.device, dev))
+    _check_plane(op, name, t_c, B, H, W, 1, dev, "vertex", flat=True)
     return t_c
 
 
@@ -874,8 +827,7 @@ def mesh_visible(tri, tri_ind, nver):
     read as constants and the result does not require grad.  Runs on the current stream."""
     h = _host()
     tri_c = h.require_gpu_f32(tri.detach() if isinstance(tri, torch.Tensor) else tri, "tri")
-    if tri_c.dim() != 2 or tri_c.shape[0] != 3:
-        raise ValueError("The tri is not 3 x ntri")
+    _check_tri(tri_c)
     ti_c, B, H, W = _mesh_tri_ind(h, tri_ind, "mesh_visible")
     if ti_c.device != tri_c.device:
         raise ValueError("mesh_visible: tri_ind is on %s, tri on %s" % (ti_c.device, tri_c.device))
@@ -902,8 +854,7 @@ def mesh_lift(vertex, tri_ind, visible, fine_depth, coarse_depth, ntri=None):
     current stream."""
     h = _host()
     ver_c = h.require_gpu_f32(vertex.detach() if isinstance(vertex, torch.Tensor) else vertex, "vertex")
-    if ver_c.dim() != 3 or ver_c.shape[1] != 3:
-        raise ValueError("The vertex is not Batch x 3 x nver")
+    _check_ver(ver_c)
     dev = ver_c.device
     ti_c, B, H, W = _mesh_tri_ind(h, tri_ind, "mesh_lift")
     nver = int(ver_c.shape[2])
@@ -959,10 +910,8 @@ def vertex_normals(vertex, tri, adjacency):
     h = _host()
     ver_c = h.require_gpu_f32(vertex.detach() if isinstance(vertex, torch.Tensor) else vertex, "vertex")
     tri_c = h.require_gpu_f32(tri.detach() if isinstance(tri, torch.Tensor) else tri, "tri")
-    if ver_c.dim() != 3 or ver_c.shape[1] != 3:
-        raise ValueError("The vertex is not Batch x 3 x nver")
-    if tri_c.dim() != 2 or tri_c.shape[0] != 3:
-        raise ValueError("The tri is not 3 x ntri")
+    _check_ver(ver_c)
+    _check_tri(tri_c)
     dev = ver_c.device
     if tri_c.device != dev:
         raise ValueError("vertex_normals: tri is on %s, vertex on %s" % (tri_c.device, dev))
@@ -982,7 +931,6 @@ def vertex_normals(vertex, tri, adjacency):
 
 
 _LAPLACE_K = ((0.5, 1.0, 0.5), (1.0, -6.0, 1.0), (0.5, 1.0, 0.5))  # network.py:383-385
-_FL_LOCK = threading.Lock()
 
 
 def _fine_losses_planes(h, pred, coarse):
@@ -995,10 +943,7 @@ def _fine_losses_planes(h, pred, coarse):
         B, H, W = (int(v) for v in p_c.shape)
     else:
         raise ValueError("fine_depth_losses expects pred [B,H,W,1] or [B,H,W] (got %s)" % (tuple(p_c.shape),))
-    if tuple(c_c.shape) not in ((B, H, W, 1), (B, H, W)):
-        raise ValueError("fine_depth_losses: coarse must be [%d,%d,%d,1] or [%d,%d,%d] (got %s)" % (B, H, W, B, H, W, tuple(c_c.shape)))
-    if c_c.device != p_c.device:
-        raise ValueError("fine_depth_losses: coarse is on %s, pred on %s" % (c_c.device, p_c.device))
+    _check_plane("fine_depth_losses", "coarse", c_c, B, H, W, 1, p_c.device, "pred", flat=True)
     return p_c, c_c, (B, H, W)
 
 
@@ -1006,9 +951,8 @@ class _FineDepthLosses(torch.autograd.Function):
     """fr_fine_losses_forward / _backward (include/fr_hotpath.h, "fine-depth losses") as one autograd node: (pred, coarse) ->
     (fidelity, smoothness), two 0-dim fp32 tensors.  It saves pred and coarse and nothing plane-sized of its own: the backward
     recomputes the signs from pred.  The forward's state (two float64 partials per tile) is dead once the forward has run, so it
-    is the per-(stream) scratch buffer that consecutive calls share (_scratch; a fresh one under graph capture); _FL_LOCK keeps the
-    forward's two launches of one call together where host threads share a stream.  A gradient that never arrives (an output
-    nobody used) is passed as NULL and its term is not evaluated."""
+    is the pooled per-stream buffer of kind "fine_losses", held across the forward's two launches.  A gradient that never arrives
+    (an output nobody used) is passed as NULL and its term is not evaluated."""
 
     @staticmethod
     def forward(ctx, pred, coarse):
@@ -1017,11 +961,11 @@ class _FineDepthLosses(torch.autograd.Function):
         p_c, c_c, (B, H, W) = _fine_losses_planes(h, pred, coarse)
         dev = p_c.device
         out = torch.empty((2,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev), _FL_LOCK:
+        with torch.cuda.device(dev):
             nst = L.fr_fine_losses_state_bytes(B, H, W)
-            state = _scratch("fine_losses", dev, nst)
-            rc = L.fr_fine_losses_forward(p_c.data_ptr(), c_c.data_ptr(), B, H, W, out.data_ptr(), out.data_ptr() + 4,
-                                          state.data_ptr(), nst, torch.cuda.current_stream(dev).cuda_stream)
+            with _KINDS_POOL.hold("fine_losses", dev, nst) as ent:
+                rc = L.fr_fine_losses_forward(p_c.data_ptr(), c_c.data_ptr(), B, H, W, out.data_ptr(), out.data_ptr() + 4,
+                                              ent.buf.data_ptr(), nst, ent.stream)   # (the hold has asked for the stream)
         if rc:
             h.check(rc, "fr_fine_losses_forward")
         ctx.save_for_backward(p_c, c_c)
@@ -1071,8 +1015,7 @@ def albedo_basis(tri, pc_tex):
     h = _host()
     tri_c = h.require_gpu_f32(tri, "tri")
     pc_c = h.require_gpu_f32(pc_tex, "pc_tex")
-    if tri_c.dim() != 2 or tri_c.shape[0] != 3:
-        raise ValueError("The tri is not 3 x ntri")
+    _check_tri(tri_c)
     if pc_c.dim() != 2 or pc_c.shape[0] % 3 != 0:
         raise ValueError("albedo_basis expects pc_tex [3N,K] (got %s)" % (tuple(pc_c.shape),))
     if pc_c.device != tri_c.device:
@@ -1100,27 +1043,20 @@ def sfs_lighting(abedo, normal, im_gray, rcond=1e-15):
     if n_c.dim() != 4 or n_c.shape[3] != 3:
         raise ValueError("sfs_lighting expects normal [B,H,W,3]")
     B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
-    for t, name in ((a_c, "abedo"), (i_c, "im_gray")):
-        if tuple(t.shape) != (B, H, W, 1):
-            raise ValueError("sfs_lighting: %s must be [%d,%d,%d,1] (got %s)" % (name, B, H, W, tuple(t.shape)))
-        if t.device != n_c.device:
-            raise ValueError("sfs_lighting: %s is on %s, normal on %s" % (name, t.device, n_c.device))
     dev = n_c.device
+    for t, name in ((a_c, "abedo"), (i_c, "im_gray")):
+        _check_plane("sfs_lighting", name, t, B, H, W, 1, dev, "normal")
     L = h.lib()
     state = torch.empty((10, H, W), dtype=torch.float64, device=dev)
     if H * W == 0:
         return state[6:9]
     nst, nmo = L.fr_sfs_state_bytes(H, W), L.fr_sfs_moments_bytes(H, W)
-    with torch.cuda.device(dev), _AL_LOCK:
-        mom = _scratch("sfs_lighting", dev, nmo)
-        rc = L.fr_sfs_moments(h.ptr(a_c), h.ptr(n_c), h.ptr(i_c), B, H, W, h.ptr(mom), nmo, h.stream_ptr(dev))
+    with torch.cuda.device(dev), _KINDS_POOL.hold("sfs_lighting", dev, nmo) as ent:
+        rc = L.fr_sfs_moments(h.ptr(a_c), h.ptr(n_c), h.ptr(i_c), B, H, W, h.ptr(ent.buf), nmo, h.stream_ptr(dev))
         h.check(rc, "fr_sfs_moments")
-        rc = L.fr_sfs_lighting(h.ptr(mom), 1, H, W, float(rcond), h.ptr(state), nst, h.stream_ptr(dev))
+        rc = L.fr_sfs_lighting(h.ptr(ent.buf), 1, H, W, float(rcond), h.ptr(state), nst, h.stream_ptr(dev))
     h.check(rc, "fr_sfs_lighting")
     return state[6:9]
-
-
-_AL_LOCK = threading.Lock()   # keeps the launches of one call together where host threads share a stream's scratch
 
 
 def albedo_lse(basis, tri_ind, lighting, normal_new, abedo, im_gray, ridge=1e-6):
@@ -1142,8 +1078,7 @@ def albedo_lse(basis, tri_ind, lighting, normal_new, abedo, im_gray, ridge=1e-6)
     B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
     dev = n_c.device
     for t, name in ((ti_c, "tri_ind"), (a_c, "abedo"), (i_c, "im_gray")):
-        if tuple(t.shape) != (B, H, W, 1):
-            raise ValueError("albedo_lse: %s must be [%d,%d,%d,1] (got %s)" % (name, B, H, W, tuple(t.shape)))
+        _check_plane("albedo_lse", name, t, B, H, W, 1)   # (their devices are checked with the basis's and the lighting's, below)
     if not (isinstance(basis, torch.Tensor) and basis.dtype == torch.float64 and basis.dim() == 2):
         raise ValueError("albedo_lse: basis must be a float64 tensor [T,K] (albedo_basis)")
     if not (isinstance(lighting, torch.Tensor) and lighting.dtype == torch.float64 and tuple(lighting.shape) == (3, H, W)):
@@ -1159,10 +1094,9 @@ def albedo_lse(basis, tri_ind, lighting, normal_new, abedo, im_gray, ridge=1e-6)
     moments = make((B, 16, 16), dtype=torch.float64, device=dev)   # (the C call's third output; not returned)
     stats = make((B, 4), dtype=torch.float64, device=dev)
     nws = L.fr_albedo_lse_workspace_bytes(B, H, W, K)
-    with torch.cuda.device(dev), _AL_LOCK:
-        ws = _scratch("albedo_lse", dev, nws)
+    with torch.cuda.device(dev), _KINDS_POOL.hold("albedo_lse", dev, nws) as ent:
         rc = L.fr_albedo_lse_forward(h.ptr(b_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(n_c), h.ptr(a_c), h.ptr(i_c), B, T, H, W, K,
-                                     float(ridge), h.ptr(alpha), h.ptr(moments), h.ptr(stats), h.ptr(ws), ws.numel(),
+                                     float(ridge), h.ptr(alpha), h.ptr(moments), h.ptr(stats), h.ptr(ent.buf), ent.nbytes,
                                      h.stream_ptr(dev))
     h.check(rc, "fr_albedo_lse_forward")
     return alpha, stats
@@ -1266,9 +1200,9 @@ def synth_texture_backward(pc_tex, grad_tex):
                                                                                                  pc_c.device))
     L = h.lib()
     nws = L.fr_synth_texture_backward_workspace_bytes(B, N, K)
-    with torch.cuda.device(dev), _PH_LOCK:
-        ws = _scratch("synth_texture_backward", dev, nws)
-        rc = L.fr_synth_texture_backward(h.ptr(pc_c), h.ptr(g_c), B, N, K, h.ptr(grad_alpha), h.ptr(ws), ws.numel(), h.stream_ptr(dev))
+    with torch.cuda.device(dev), _KINDS_POOL.hold("synth_texture_backward", dev, nws) as ent:
+        rc = L.fr_synth_texture_backward(h.ptr(pc_c), h.ptr(g_c), B, N, K, h.ptr(grad_alpha), h.ptr(ent.buf), ent.nbytes,
+                                         h.stream_ptr(dev))
     h.check(rc, "fr_synth_texture_backward")
     return grad_alpha
 
@@ -1310,15 +1244,9 @@ def synth_texture(mu_tex, pc_tex, alpha, out=None):
     return _synth_texture_call(mu_tex, pc_tex, alpha, out)[0]
 
 
-_PH_LOCK = threading.Lock()   # keeps the launches of one call together where host threads share a stream's scratch
-
-
 def _photo_plane(h, t, name, B, H, W, dev):
     t_c = h.require_gpu_f32(t.detach(), name)
-    if tuple(t_c.shape) not in ((B, H, W, 1), (B, H, W)):
-        raise ValueError("photo_loss: %s must be [%d,%d,%d,1] or [%d,%d,%d] (got %s)" % (name, B, H, W, B, H, W, tuple(t_c.shape)))
-    if t_c.device != dev:
-        raise ValueError("photo_loss: %s is on %s, normal on %s" % (name, t_c.device, dev))
+    _check_plane("photo_loss", name, t_c, B, H, W, 1, dev, "normal", flat=True)
     return t_c
 
 
@@ -1326,9 +1254,9 @@ class _PhotoLoss(torch.autograd.Function):
     """fr_photo_loss_forward / _backward (include/fr_hotpath.h, "photometric loss") as one autograd node: (tex_img, normal, tri_ind,
     light, target, weight, gain, offset) -> (sse [B], count [B]) float64.  It saves its inputs by reference and the forward's
     sums [B,6] (the lighting gradient is linear in them); nothing plane-sized of its own.  The forward's state (six float64 partials
-    per tile) is dead once the forward has run: it is the per-stream scratch that consecutive calls share; _PH_LOCK keeps the
-    forward's two launches together where host threads share a stream.  The backward asks the kernel only for the outputs
-    needs_input_grad names; target, weight and tri_ind are constants."""
+    per tile) is dead once the forward has run: it is the pooled per-stream buffer of kind "photo_loss", held across the forward's
+    two launches.  The backward asks the kernel only for the outputs needs_input_grad names; target, weight and tri_ind are
+    constants."""
 
     @staticmethod
     def forward(ctx, tex_img, normal, tri_ind, light, target, weight, gain, offset):
@@ -1341,8 +1269,7 @@ class _PhotoLoss(torch.autograd.Function):
         dev = n_c.device
         t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
         l_c = h.require_gpu_f32(light.detach(), "light")
-        if tuple(t_c.shape) != (B, H, W, 3) or t_c.device != dev:
-            raise ValueError("photo_loss: tex_img must be [%d,%d,%d,3] on %s (got %s on %s)" % (B, H, W, dev, tuple(t_c.shape), t_c.device))
+        _check_plane("photo_loss", "tex_img", t_c, B, H, W, 3, dev, "normal")
         if tuple(l_c.shape) != (B, 4) or l_c.device != dev:
             raise ValueError("photo_loss: light must be [%d,4] on %s (got %s on %s)" % (B, dev, tuple(l_c.shape), l_c.device))
         ti_c = _photo_plane(h, tri_ind, "tri_ind", B, H, W, dev)
@@ -1351,11 +1278,10 @@ class _PhotoLoss(torch.autograd.Function):
         empty = B * H * W == 0
         sums = (torch.zeros if empty else torch.empty)((B, 6), dtype=torch.float64, device=dev)
         if not empty:
-            with torch.cuda.device(dev), _PH_LOCK:
-                nst = L.fr_photo_loss_state_bytes(B, H, W)
-                state = _scratch("photo_loss", dev, nst)
+            nst = L.fr_photo_loss_state_bytes(B, H, W)
+            with torch.cuda.device(dev), _KINDS_POOL.hold("photo_loss", dev, nst) as ent:
                 rc = L.fr_photo_loss_forward(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(tg_c), h.ptr(w_c), B, H, W,
-                                             float(gain), float(offset), h.ptr(sums), h.ptr(state), state.numel(), h.stream_ptr(dev))
+                                             float(gain), float(offset), h.ptr(sums), h.ptr(ent.buf), ent.nbytes, h.stream_ptr(dev))
             h.check(rc, "fr_photo_loss_forward")
         ctx.save_for_backward(t_c, n_c, ti_c, l_c, tg_c, sums, *(() if w_c is None else (w_c,)))
         ctx.dims = (B, H, W)
@@ -1426,9 +1352,10 @@ def synth_shade(tex_img, normal, tri_ind, light, background=None, gain=1.0, offs
         if bg_batch not in (1, B) or tuple(bg_c.shape[1:]) != (H, W, 1):
             raise ValueError("synth_shade: background must be [1,%d,%d,1] or [%d,%d,%d,1] (got %s)"
                              % (H, W, B, H, W, tuple(bg_c.shape)))
-    for t, name, shape in ((t_c, "tex_img", (B, H, W, 3)), (ti_c, "tri_ind", (B, H, W, 1)), (l_c, "light", (B, 4))):
-        if tuple(t.shape) != shape:
-            raise ValueError("synth_shade: %s must be %s (got %s)" % (name, list(shape), tuple(t.shape)))
+    _check_plane("synth_shade", "tex_img", t_c, B, H, W, 3)   # (every device is checked below, behind every shape)
+    _check_plane("synth_shade", "tri_ind", ti_c, B, H, W, 1)
+    if tuple(l_c.shape) != (B, 4):
+        raise ValueError("synth_shade: light must be [%d, 4] (got %s)" % (B, tuple(l_c.shape)))
     for t, name in ((t_c, "tex_img"), (ti_c, "tri_ind"), (l_c, "light"), (bg_c, "background")):
         if t is not None and t.device != dev:
             raise ValueError("synth_shade: %s is on %s, normal on %s" % (name, t.device, dev))
@@ -1486,12 +1413,10 @@ def render_depth_grad(depth_grad, ver, tri, depth, tri_ind, image):
     g = h.require_gpu_f32(depth_grad, "depth_grad")
     tri_c = h.require_gpu_f32(tri, "tri")
     ti = h.require_gpu_f32(tri_ind, "tri_ind")
-    if ver.dim() != 3 or ver.shape[1] != 3:
-        raise ValueError("The vertex is not Batch x 3 x nver")
+    _check_ver(ver)
     if ver.shape[0] != image.shape[0]:
         raise ValueError("The vertex's batch is not the same as image batch")
-    if tri_c.dim() != 2 or tri_c.shape[0] != 3:
-        raise ValueError("The tri is not 3 x ntri")
+    _check_tri(tri_c)
     B, H, W = int(image.shape[0]), int(image.shape[1]), int(image.shape[2])
     nver, ntri = int(ver.shape[2]), int(tri_c.shape[1])
     dev = g.device

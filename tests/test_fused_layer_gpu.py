@@ -130,8 +130,8 @@ def test_fused_layer_packs_the_triangle_list_once(full_assets, synth):
         finally:
             h.lib().fr_rendering_layer_forward_phases = real_call
         assert seen[-1][0] == 7 and seen[-1][1] is not None
-        ent = next(iter(o._WS_CACHE.values()))
-        assert ent.tri_ref is None and ent.tri_key is None
+        ent = next(iter(o._RENDER_POOL.snapshot().values()))
+        assert ent.note is None
         after = o.rendering_layer_fused(V, tri2, net.vertex_code, im)
         assert seen[-1][0] == 7
         for a, b in zip(after, back):

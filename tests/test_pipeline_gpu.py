@@ -258,7 +258,7 @@ def test_q30_plan_capture_and_replay(oracle, full_assets, synth, levels):
 
 
 def test_workspace_cache_is_bounded_and_skipped_under_capture(small_assets):
-    """ops._WS_CACHE: at most WS_CACHE_MAX entries however many streams call the op, clear_workspace_cache() empties it,
+    """The render pool (ops._RENDER_POOL): at most WS_CACHE_MAX entries however many streams call the op, clear_workspace_cache() empties it,
     and a call made while a stream is being captured does not touch it (the graph keeps its own buffer)."""
     o = ops()
     A = small_assets
@@ -272,7 +272,7 @@ def test_workspace_cache_is_bounded_and_skipped_under_capture(small_assets):
     img = torch.zeros((2, 40, 40, 3), device="cuda:0")
     ref = [t.clone() for t in o.render_depth(V, net.tri, net.vertex_code, img)]
     o.clear_workspace_cache()
-    assert len(o._WS_CACHE) == 0
+    assert len(o._RENDER_POOL) == 0
     streams = [torch.cuda.Stream() for _ in range(o.WS_CACHE_MAX + 3)]
     torch.cuda.synchronize()
     for st in streams:
@@ -282,8 +282,8 @@ def test_workspace_cache_is_bounded_and_skipped_under_capture(small_assets):
         st.synchronize()
         for a, b, c in zip(outs, outs2, ref):
             assert torch.equal(a, c) and torch.equal(b, c)
-        assert len(o._WS_CACHE) <= o.WS_CACHE_MAX
-    assert len(o._WS_CACHE) == o.WS_CACHE_MAX
+        assert len(o._RENDER_POOL) <= o.WS_CACHE_MAX
+    assert len(o._RENDER_POOL) == o.WS_CACHE_MAX
     # an in-place change of the triangle list is seen (torch's version counter), not served from the cached table
     tri2 = net.tri.clone()
     o.render_depth(V, tri2, net.vertex_code, img)
@@ -293,16 +293,16 @@ def test_workspace_cache_is_bounded_and_skipped_under_capture(small_assets):
     for a, b in zip(got2, want2):
         assert torch.equal(a, b)
     o.clear_workspace_cache()
-    n0 = len(o._WS_CACHE)
+    n0 = len(o._RENDER_POOL)
     g = torch.cuda.CUDAGraph()
     side = torch.cuda.Stream()
     with torch.cuda.stream(side):
         o.render_depth(V, net.tri, net.vertex_code, img)    # warm-up outside the capture
         side.synchronize()
-        before = dict(o._WS_CACHE)
+        before = o._RENDER_POOL.snapshot()
         with torch.cuda.graph(g, stream=side):
             cap = o.render_depth(V, net.tri, net.vertex_code, img)
-        assert dict(o._WS_CACHE) == before                  # the capture neither added nor replaced an entry
+        assert o._RENDER_POOL.snapshot() == before                  # the capture neither added nor replaced an entry
         o.clear_workspace_cache()                           # ... and survives the cache being dropped
         g.replay()
     side.synchronize()

@@ -547,8 +547,8 @@ def test_decode_backward_workspace_lru_under_six_streams(oracle, synth):
                 _, gp = run(t)
                 # the LRU itself, from six threads at once (autograd runs the backwards of one device on one thread)
                 for _ in range(4):
-                    nws, buf = basis.backward_workspace(B, DEV)
-                    assert buf.numel() >= nws
+                    with basis.backward_workspace(B, DEV) as (nws, buf):
+                        assert buf.numel() >= nws
                 streams[i].synchronize()
                 d = _diff(gp, refs[i])
                 if d:
