@@ -9,7 +9,9 @@ BASELINE.json config 4.  Stock torch ops, except where the
     (rendering_layer/ops.py::fine_depth_losses) instead of a chain of elementwise ops, a convolution and two reductions, and
   * opt-in (photo_light / photo_alpha), a photometric term compares the face rendered and shaded under a given lighting and albedo
     with the picture itself (photometric_loss: synth_texture -> render_depth -> rendering_layer/ops.py::photo_loss), with a
-    gradient to the geometry, the lighting and the albedo coefficients.
+    gradient to the geometry, the lighting and the albedo coefficients, and
+  * opt-in (silhouette_mask), a silhouette term compares the soft coverage of the rendered face with a target mask
+    (silhouette_loss: FaceRecNet.soft_mask -> rendering_layer/ops.py::soft_coverage), with a gradient to x and y of the vertices.
 
 Names and weights follow the reference: pose MSE (lambda 1e-3), geometry MSE through the basis (1e-6), spherical
 harmonics / SfS MSE (1e-3), fidelity MSE between the coarse and the fine depth map (100), Laplacian-L1 smoothness (1e-5)
@@ -231,6 +233,17 @@ def photometric_loss(face_net, vertices_proj, im_gray, light, alpha, weight=None
     return sse.sum() / count.sum().clamp_min(1)
 
 
+def silhouette_loss(face_net, vertices_proj, target_mask):
+    """The mean squared difference between the soft silhouette of the face of vertices_proj [B,3,N] (FaceRecNet.soft_mask: one
+    render for tri_ind, then rendering_layer/ops.py::soft_coverage) and target_mask ([B,H,W,1] or [B,H,W], e.g. the `mask` of
+    pipeline.SynthBatches; a constant: it gets no gradient).  The gradient reaches the x and y rows of vertices_proj -- the only
+    term that tells a fit where the face is in the picture.  Stock torch on one plane after the kernel; each rank takes the mean
+    over its own faces (no collective)."""
+    cov = face_net.soft_mask(vertices_proj)
+    target = target_mask.detach().to(cov.dtype).reshape(cov.shape)
+    return F.mse_loss(cov, target)
+
+
 def combine_losses(losses):
     """total = 1e-3 pose + 1e-6 geometry + 1e-3 SfS + 100 fidelity + 1e-5 smoothness (network.py:27-31, 373)"""
     return (LAMBDA_POSE * losses['pose_loss'] + LAMBDA_GEO * losses['geometry_loss'] +
@@ -241,6 +254,7 @@ def combine_losses(losses):
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
              gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False,
              sfs_fused_gather=False, sfs_fine=False, fine_fused=False, sfs_alpha_lse=False, sfs_alpha_ridge=1e-6,
+             silhouette_mask=None, lambda_silhouette=1.0,
              photo_light=None, photo_alpha=None, photo_weight=None, photo_gain=1.0, photo_offset=0.0, lambda_photo=1.0,
              geometry_gram=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
@@ -268,7 +282,10 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     photo_light [B,4] / photo_alpha [B,K] (default None: the term is absent, the dict and every bit are today's; one without the
     other is a ValueError): adds losses['photometric_loss'] = photometric_loss(face_net, vertices_proj, im_gray, photo_light,
     photo_alpha, photo_weight, photo_gain, photo_offset) -- the rendered and shaded face against im_gray itself -- and lambda_photo
-    times it to total_loss.  Its gradient reaches vertices_proj, and photo_light / photo_alpha where they require grad."""
+    times it to total_loss.  Its gradient reaches vertices_proj, and photo_light / photo_alpha where they require grad.
+    silhouette_mask [B,H,W,1] (default None: the term is absent, the dict and every bit are today's): adds
+    losses['silhouette_loss'] = silhouette_loss(face_net, vertices_proj, silhouette_mask) and lambda_silhouette times it to
+    total_loss.  Its gradient reaches the x and y rows of vertices_proj; the mask is a constant."""
     fn = face_net
     if (photo_light is None) != (photo_alpha is None):
         raise ValueError("photo_light and photo_alpha go together: the photometric term needs the lighting and the albedo coefficients")
@@ -309,4 +326,7 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
         losses['photometric_loss'] = photometric_loss(fn, vertices_proj, im_gray, photo_light, photo_alpha, weight=photo_weight,
                                                       gain=photo_gain, offset=photo_offset)
         losses['total_loss'] = losses['total_loss'] + (lambda_photo * losses['photometric_loss']).to(losses['total_loss'].dtype)
+    if silhouette_mask is not None:
+        losses['silhouette_loss'] = silhouette_loss(fn, vertices_proj, silhouette_mask)
+        losses['total_loss'] = losses['total_loss'] + (lambda_silhouette * losses['silhouette_loss']).to(losses['total_loss'].dtype)
     return losses

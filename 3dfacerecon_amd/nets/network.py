@@ -448,6 +448,19 @@ class FaceRecNet:
             normals = ops.vertex_normals(vertices, self.tri, self.adjacency()) if with_normals else None
         return {"vertices": vertices, "state": state, "normals": normals}
 
+    def soft_mask(self, vertices_proj):
+        """The soft silhouette [B,H,W,1] in [0, 1] of the face of vertices_proj [B,3,N]: one render for its tri_ind (the winners are
+        held fixed), then rendering_layer/ops.py::soft_coverage -- 1 inside, +0 outside, the covered share on the pixels either
+        side of the face / background border.  Its gradient reaches the x and y rows of vertices_proj, which is what tells a fit
+        where the face is in the picture; through vertices_transform(pose_grad=True) it reaches t3d, f and the angles."""
+        ops = _ops()
+        ver = vertices_proj.float()
+        B = int(ver.shape[0])
+        with torch.no_grad():
+            image = torch.zeros((B, self.im_size, self.im_size, 3), dtype=torch.float32, device=ver.device)
+            tri_ind = ops.render_depth(ver=ver.detach(), tri=self.tri, texture=self.vertex_code, image=image)[3]
+        return ops.soft_coverage(ver, self.tri, tri_ind)
+
     def gram_state(self, B, dev, stream):
         """(key, bytes, buffer): a state buffer of the Gram-form loss for B faces on `stream` (torch's current stream of `dev`, as
         its address), the caller's until it hands it back through gram_state_done(key, buffer).  Free buffers are kept per

@@ -804,6 +804,68 @@ def depth_interpolate(ver, tri, tri_ind):
     return _DepthInterpolate.apply(ver, tri, tri_ind)
 
 
+class _SoftCoverage(torch.autograd.Function):
+    """fr_coverage_forward / _backward (include/fr_hotpath.h, "soft coverage") as one autograd node."""
+
+    @staticmethod
+    def forward(ctx, ver, tri, tri_ind):
+        h = _host()
+        if isinstance(tri_ind, torch.Tensor) and tri_ind.requires_grad:
+            raise ValueError("soft_coverage: tri_ind requires grad, but the winning triangles are held fixed (detach it)")
+        ver_c = h.require_gpu_f32(ver, "ver")
+        tri_c = h.require_gpu_f32(tri, "tri")
+        ti_c = h.require_gpu_f32(tri_ind, "tri_ind")
+        _check_ver(ver_c)
+        _check_tri(tri_c)
+        if ti_c.dim() != 4 or ti_c.shape[0] != ver_c.shape[0] or ti_c.shape[3] != 1:
+            raise ValueError("soft_coverage expects tri_ind [B,H,W,1] with the vertex's batch (got %s)" % (tuple(ti_c.shape),))
+        if tri_c.device != ver_c.device or ti_c.device != ver_c.device:
+            raise ValueError("soft_coverage: ver, tri and tri_ind must be on one device")
+        B, H, W = int(ti_c.shape[0]), int(ti_c.shape[1]), int(ti_c.shape[2])
+        nver, ntri = int(ver_c.shape[2]), int(tri_c.shape[1])
+        dev = ver_c.device
+        cov = torch.empty((B, H, W, 1), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = h.lib().fr_coverage_forward(h.ptr(ver_c), nver, h.ptr(tri_c), h.ptr(ti_c), B, nver, ntri, H, W, h.ptr(cov),
+                                             h.stream_ptr(dev))
+        h.check(rc, "fr_coverage_forward")
+        ctx.save_for_backward(ver_c, tri_c, ti_c, cov)
+        ctx.dims = (B, nver, ntri, H, W)
+        return cov
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        h = _host()
+        ver_c, tri_c, ti_c, cov = ctx.saved_tensors
+        B, nver, ntri, H, W = ctx.dims
+        dev = ver_c.device
+        if B * H * W == 0 or nver == 0:   # the entry point writes nothing for an empty image
+            return torch.zeros((B, 3, nver), dtype=torch.float32, device=dev), None, None
+        vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=dev)
+        g_c = h.require_gpu_f32(g, "cov_grad")
+        L = h.lib()
+        nws = L.fr_coverage_backward_workspace_bytes(B, nver, H, W)
+        # (the workspace is dead once the two launches are enqueued: one per stream, under the pool's hold)
+        with torch.cuda.device(dev), _KINDS_POOL.hold("coverage_bwd", dev, nws) as ent:
+            rc = L.fr_coverage_backward(h.ptr(g_c), h.ptr(cov), h.ptr(ver_c), nver, h.ptr(tri_c), h.ptr(ti_c), h.ptr(vertex_grad), B,
+                                        nver, ntri, H, W, 0, h.ptr(ent.buf), ent.nbytes, h.stream_ptr(dev))
+        h.check(rc, "fr_coverage_backward")
+        return vertex_grad, None, None
+
+
+def soft_coverage(ver, tri, tri_ind):
+    """The soft silhouette [B,H,W,1] of a render's winners, in [0, 1]: 1 on a pixel whose tri_ind ([B,H,W,1], e.g. render_depth's
+    fourth output) names a triangle of `tri` [3,ntri] and whose four neighbours do too, +0 on a background pixel among background
+    pixels, and on the pixels either side of the face / background border the share of the pixel the face covers along the line
+    to its neighbour (fr_coverage_forward: float64, one pass).  Which triangle wins is not re-decided.  The gradient goes to the x
+    and y rows of `ver` [B,3,nver] (the z row is +0): moving the border's vertices moves the border (fr_coverage_backward:
+    bit-reproducible); a tri_ind that requires grad is refused.  Only the face / background border is soft -- not an occlusion edge
+    inside the face.  The node saves `ver`, `tri`, `tri_ind` and the plane itself."""
+    return _SoftCoverage.apply(ver, tri, tri_ind)
+
+
 # ---- fine mesh (include/fr_hotpath.h, "fine mesh"): forward only, outside autograd ------------------------------------------------------
 def _mesh_plane(h, t, name, op, B, H, W, dev):
     """a [B,H,W,1] or [B,H,W] fp32 plane on `dev`, detached and contiguous"""

@@ -81,9 +81,14 @@ def build_harness(args, dev, rank, world, local):
         if stream is None:
             return resident
         b = stream.next()
+        extra = {}
         if args.photo_loss:   # the batch's own lighting and albedo, and the stream's gain and offset: the image is their shading
-            return b["im_gray"], b["params"], dict(photo_light=b["light"], photo_alpha=b["alpha"], photo_gain=stream.gain,
-                                                   photo_offset=stream.offset, lambda_photo=args.photo_lambda)
+            extra.update(photo_light=b["light"], photo_alpha=b["alpha"], photo_gain=stream.gain, photo_offset=stream.offset,
+                         lambda_photo=args.photo_lambda)
+        if args.silhouette_loss:   # the batch's ground-truth mask against the soft coverage of the predicted face
+            extra.update(silhouette_mask=b["mask"], lambda_silhouette=args.silhouette_lambda)
+        if extra:
+            return b["im_gray"], b["params"], extra
         return b["im_gray"], b["params"]
 
     def forward_loss(im, lab, photo={}):
@@ -381,6 +386,12 @@ def build_parser():
                          "and lighting against the batch's image; its gradient reaches the vertices (the pose angles too with "
                          "--pose-grad); the record gains photometric_loss; off: no term compares a rendered face with the picture")
     ap.add_argument("--photo-lambda", type=float, default=1.0, help="with --photo-loss: the term's weight in total_loss")
+    ap.add_argument("--silhouette-loss", action="store_true",
+                    help="with --synth-data and --train: add the silhouette term (get_loss(silhouette_mask=); fr_coverage_forward / "
+                         "_backward) -- the soft coverage of the predicted face against the batch's ground-truth mask; its gradient "
+                         "reaches x and y of the vertices (the pose angles too with --pose-grad); the record's losses gain "
+                         "silhouette_loss; off: no term tells the fit where the face is in the picture")
+    ap.add_argument("--silhouette-lambda", type=float, default=1.0, help="with --silhouette-loss: the term's weight in total_loss")
     ap.add_argument("--small", action="store_true", help="tiny synthetic assets (smoke runs)")
     ap.add_argument("--dump-batches", default=None, metavar="FILE.npz",
                     help="--phase test: save every timed batch's parameters, vertices and planes (as its consumer saw them) for an "
@@ -404,6 +415,8 @@ def main():
     args = ap.parse_args()
     if args.photo_loss and not args.synth_data:
         ap.error("--photo-loss needs --synth-data (the term uses the batch's ground-truth lighting and albedo)")
+    if args.silhouette_loss and not args.synth_data:
+        ap.error("--silhouette-loss needs --synth-data (the term uses the batch's ground-truth mask)")
     if args.export_mesh and (args.phase != "test" or args.im_size % 4):
         ap.error("--export-mesh needs --phase test and an image size that is a multiple of 4 (FineNet pools twice)")
     # (ONE line on stdout: RCCL prints a version banner to fd 1 when its first communicator comes up -- from here on fd 1 is

@@ -6,10 +6,14 @@ HIP backward).
     python examples/photo_fit.py --small                 # tiny assets, 32 x 32, 3 faces
     python examples/photo_fit.py --batch 8 --steps 200   # the full mesh at 200 x 200
     python examples/photo_fit.py --small --fit-shape     # also fit the shape and expression coefficients (pose held at the truth)
+    python examples/photo_fit.py --small --fit-pose      # also fit t3d, f and the angles, from the truth perturbed
 
 A batch of pipeline.SynthBatches gives the picture and its ground truth (parameters, light, alpha).  The fit starts from the truth
 perturbed (light by --light-noise, alpha by --alpha-noise; with --fit-shape the coefficients from zero) and runs Adam.  By default the
-geometry is the ground truth's and stays fixed.  Prints ONE JSON record: the first and last loss and the parameter errors (RMS
+geometry is the ground truth's and stays fixed.  With --fit-pose the translation, the scale and the three angles start from the truth
+perturbed (--pose-noise) and are fitted too: the decode runs with pose_grad=True, and the silhouette term
+(nets/losses.py::silhouette_loss: the soft coverage of the rendered face against the batch's mask, --silhouette-lambda) stands beside
+the photometric one -- it is the term that tells the fit where the face is in the picture.  Prints ONE JSON record: the first and last loss and the parameter errors (RMS
 against the ground truth) before and after.
 """
 import argparse
@@ -42,6 +46,11 @@ def main():
     ap.add_argument("--light-noise", type=float, default=0.2)
     ap.add_argument("--alpha-noise", type=float, default=0.5)
     ap.add_argument("--fit-shape", action="store_true", help="also fit the shape and expression coefficients, from zero")
+    ap.add_argument("--fit-pose", action="store_true", help="also fit t3d, f and the angles, from the truth perturbed; adds the "
+                                                           "silhouette term")
+    ap.add_argument("--pose-noise", type=float, default=1.0, help="with --fit-pose: the perturbation, in units of 1.5 px of "
+                                                                  "translation, 3 %% of scale and 0.03 rad")
+    ap.add_argument("--silhouette-lambda", type=float, default=1.0)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -67,18 +76,44 @@ def main():
         scale = torch.cat([torch.full((ns,), 1e4), torch.ones(face.ndim_exp)]).to(dev)
         coef = torch.zeros_like(coef_gt, requires_grad=True)
         groups.append({"params": [coef], "lr": args.lr})
+    pose = None
+    if args.fit_pose:
+        # unit-scale unknowns again: angles in 0.03 rad, x and y in 1.5 px, f in 3 % of its value; t3d's z moves no pixel and stays
+        pose_gt = params[:, :n0]
+        pose_scale = torch.tensor([0.03] * 3 + [1.5, 1.5, 1.0], device=dev).repeat(B, 1)
+        pose_scale = torch.cat([pose_scale, 0.03 * pose_gt[:, 6:7]], dim=1)
+        kick = noise(pose_gt, args.pose_noise)
+        kick[:, 5] = 0
+        pose0 = pose_gt + kick * pose_scale
+        pose = torch.zeros_like(pose_gt, requires_grad=True)
+        groups.append({"params": [pose], "lr": args.lr})
     opt = torch.optim.Adam(groups)
 
+    def pose_now():
+        return pose0 + pose * pose_scale
+
     def vertices():
-        if coef is None:
+        if coef is None and pose is None:
             with torch.no_grad():
                 return face.vertices_transform(params)
-        return face.vertices_transform(torch.cat([params[:, :n0], coef * scale], dim=1))
+        p = torch.cat([params[:, :n0] if pose is None else pose_now(), params[:, n0:] if coef is None else coef * scale], dim=1)
+        return face.vertices_transform(p, pose_grad=True) if pose is not None else face.vertices_transform(p)
 
     def loss_of():
-        return losses.photometric_loss(face, vertices(), im, light, alpha, gain=stream.gain, offset=stream.offset)
+        ver = vertices()
+        L = losses.photometric_loss(face, ver, im, light, alpha, gain=stream.gain, offset=stream.offset)
+        if pose is not None:
+            L = L + args.silhouette_lambda * losses.silhouette_loss(face, ver, b["mask"]).double()
+        return L
+
+    def pose_errors():
+        p = pose_now().detach()
+        return {"t3d_rms": rms(p[:, 3:6], pose_gt[:, 3:6]), "f_rel_rms": rms(p[:, 6] / pose_gt[:, 6], torch.ones_like(p[:, 6])),
+                "angle_rms": rms(p[:, 0:3], pose_gt[:, 0:3])}
 
     before = {"light_rms": rms(light, light_gt), "alpha_rms": rms(alpha, alpha_gt)}
+    if pose is not None:
+        before.update(pose_errors())
     if coef is not None:
         before["coef_rms_scaled"] = rms(coef, coef_gt / scale)
     first = last = None
@@ -93,7 +128,10 @@ def main():
     after = {"light_rms": rms(light, light_gt), "alpha_rms": rms(alpha, alpha_gt)}
     if coef is not None:
         after["coef_rms_scaled"] = rms(coef, coef_gt / scale)
+    if pose is not None:
+        after.update(pose_errors())
     print(json.dumps({"program": "photo_fit", "faces": B, "im_size": S, "steps": args.steps, "lr": args.lr, "fit_shape": bool(args.fit_shape),
+                      "fit_pose": bool(args.fit_pose),
                       "first": first, "last": last, "ratio": last / first if first else None, "errors_before": before,
                       "errors_after": after, "finite": bool(torch.isfinite(light).all() and torch.isfinite(alpha).all())}))
 

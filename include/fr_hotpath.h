@@ -1186,6 +1186,80 @@ int fr_mesh_lift(const float* vertex, int vertex_pitch, const float* tri_ind, co
 int fr_mesh_vertex_normals(const float* vertex, int vertex_pitch, const float* tri, const int* adj_start, const int* adj_tri, int B,
                            int nver, int ntri, float* normal, int out_pitch, void* stream);
 
+/* ---- soft coverage: an antialiased silhouette with an x, y backward (opt-in) ---------------------------------------------------------
+ * Every gradient above holds tri_ind fixed and every plane is flat per triangle in the screen plane: when a face moves sideways or is
+ * scaled in the image, no plane changes through x and y except by the slope of the interpolated depth.  These entry points are a
+ * post-pass over a forward's tri_ind that gives the SILHOUETTE of the rendered face as a plane cov in [0, 1] -- 1 inside, +0 outside,
+ * in between on the pixels either side of the face / background border -- with an exact gradient to the x and y rows of the vertices.
+ * It is the pair construction differentiable rasterisers use for antialiasing, restricted to face-against-background.
+ *   vertex [B,3,vertex_pitch] (vertex_pitch >= nver, as in the interpolated depth);  tri [3,ntri], float-stored ids;
+ *   tri_ind, cov, cov_grad dense [B,H,W,1];  vertex_grad dense [B,3,nver].  Pixel (row j, column i) is the point X = (i, j).
+ * NAMES.  The stream parameter is called `stream`, as in the Gram-form geometry loss above and for its reason;
+ * tests/test_coverage_cpu.py holds these entry points' return codes.
+ * WHICH PIXEL.  A pixel is OK exactly as in the interpolated depth (tri_ind names t in [0, ntri) and all three ids of t lie in
+ * [0, nver)); NaN, -1, a value >= ntri or a bad id is not OK.  P_k = (x, y) of vertex[b][.][p_k].
+ * ARITHMETIC.  Float64 on the widened fp32 inputs; every difference, product, sum and quotient is rounded on its own (no
+ * contraction).  The neighbours of a pixel are visited in the order left, right, up, down; a neighbour outside the image does not
+ * exist.
+ * PAIR (c, n): c an OK pixel with triangle (P1, P2, P3), n a not-OK neighbour of c.
+ *   e(A, B, X) = (Bx - Ax)(Xy - Ay) - (By - Ay)(Xx - Ax)
+ *   area = e(P1, P2, P3); area == 0 or not finite: the pair is INERT.  Otherwise sigma = +-1 is its sign.
+ *   for edge k = 1, 2, 3 = (P1,P2), (P2,P3), (P3,P1):   Fc = sigma e(A, B, c),   Fn = sigma e(A, B, n)
+ *   edge k is a candidate iff Fn < 0 and Fc > Fn and s_k = Fc / (Fc - Fn) is finite
+ *   s = the smallest s_k, the lowest k on a tie; no candidate: the pair is inert.   s^ = min(max(s, 0), 1)
+ * s is the position along c -> n at which the segment leaves c's triangle.  The border sits at s^: the face covers s^ - 0.5 of n
+ * beyond the pixel boundary, or leaves 0.5 - s^ of c uncovered.
+ * FORWARD, from a = +0:
+ *   OK pixel c:      for each not-OK neighbour with a non-inert pair:       a = a + max(0.5 - s^, 0);   cov = fl32(max(0, 1 - a))
+ *   not-OK pixel u:  for each OK neighbour n with a non-inert pair (n, u):  a = a + max(s^ - 0.5, 0);   cov = fl32(min(1, a))
+ * A pixel whose four neighbours share its state is exactly 1.0 or +0.  (tests/ref_coverage.py is this in numpy.)
+ * BACKWARD.  tri_ind is held fixed; the fp32 roundings and the clamps count as the identity where they are inactive.  The call takes
+ * G = (double)cov_grad and the forward's cov plane.  For an OK pixel c and each not-OK neighbour n, in order, whose pair is non-inert
+ * with 0 < s < 1:
+ *   q = 0;   s < 0.5 and cov(c) > 0:  q = q + G(c);   s > 0.5 and cov(n) < 1:  q = q + G(n)
+ *   with the winning edge (A, B), D = Fc - Fn, and v one of (Ax, Ay, Bx, By):
+ *     d e(X) / d v = (By - Xy,  Xx - Bx,  Xy - Ay,  Ax - Xx)
+ *     d s / d v    = (sigma ((-Fn) d e(c)/d v + Fc d e(n)/d v)) / (D D)
+ *   slot(vertex of v, row of v) = slot + q (d s / d v)          six float64 slots per pixel, each from +0, pair after pair
+ * Each of the pixel's six x, y slots is rounded to fp32 once: these are its terms; its z terms are +0.  A pixel whose six terms are
+ * all zero contributes nothing (no record).  Each (face, row, vertex) sum of terms is formed exactly as the interpolated depth's
+ * backward forms its own (the same record planes, the same owner workgroups, csrc/fr_owner_scatter.h): 64-bit fixed point on a grid
+ * of 2^(e - 39 + shift), integer addition in LDS, one rounding to fp32; no float atomics, bit-reproducible, independent of the launch
+ * geometry; |result - exact sum| <= 2^-24 |sum| + n 2^(shift - 39) M for n terms, M the face's largest finite |term|.  A face with
+ * a non-finite term takes fp32 LDS atomics, as there.  The z row is exactly +0 (accumulate 0).
+ *   accumulate 0 / 1 and the workspace -- fr_coverage_backward_workspace_bytes(B, nver, H, W) = B H W 48 + B ceil(H W / 1024) 8
+ *   bytes, 16-byte aligned, caller-owned, per call in flight -- are those of fr_depth_interp_backward.  The forward needs none.
+ * LIMITS.  Only the face / background border is softened: an occlusion edge between two triangles of the face is not (both pixels
+ * are OK, no pair exists).  A neighbouring triangle that covers part of the segment c -> n without winning a pixel centre is
+ * ignored: the border is put where c's own triangle ends.
+ * Checks, all before any HIP call, in the order and with the codes of fr_depth_interp_*: (1) a negative size, accumulate outside
+ * {0, 1} or vertex_pitch < nver is FR_ERR_INVALID_ARG; (2) B == 0 or an empty image is FR_OK with nothing launched and nothing
+ * written (so is the backward with nver == 0); (3) a NULL tri_ind, cov or vertex_grad -- or, where triangles exist, a NULL tri,
+ * vertex, cov_grad or (backward) cov -- is FR_ERR_INVALID_ARG; ntri >= 2^24 or more than 2^31 - 1 pixels per face is
+ * FR_ERR_UNSUPPORTED; (4) a workspace that is missing, too small or misaligned is FR_ERR_WORKSPACE.  With ntri == 0 the forward
+ * writes +0 everywhere and the backward zeros (or, accumulate 1, nothing).  Nothing is allocated or synchronised; reentrant under the
+ * rules at the top of this file.
+ * Kernels (csrc/fr_coverage.hip): the forward is one lane per pixel in tiles of 32 x 8; the workgroup stages its tile of tri_ind with
+ * a one-pixel halo in LDS as "triangle if OK, else -1" (OK depends on the triangle's ids, so a covered pixel costs three id gathers
+ * there; an uncovered one none), and only a lane with a neighbour of the other state gathers vertices.  The backward is a records
+ * pass over 1,024-pixel chunks in which only border pixels evaluate pairs and write term planes, then the shared owner.
+ * Time: tools/coverage_probe.py (profiles/coverage.json) measures both at 64 and 32 faces of the full mesh at 200 x 200 beside
+ * fr_depth_interp_forward / _backward on the same inputs and a 512 MiB copy.  MI355X, medians of 6 rounds of 40 calls: forward
+ * 27.7 / 17.3 us beside the interpolated depth's 26.0 / 14.7 us, where it must move 31 / 16 MB = 5.8 / 2.9 us at the 5.3 TB/s that
+ * run's copy reached (0.21 / 0.17 of it): the staged tile binds, not memory -- on a tri_ind of -1 everywhere it takes 13.6 / 7.9 us
+ * where the interpolated depth's plain map takes 6.7 / 4.9 us; backward 92.2 / 53.6 us beside the interpolated depth's 75.1 / 42.5 us
+ * (the same owners; a records pass that decides OK for four neighbours by id gathers of its own). */
+int fr_coverage_forward(const float* vertex, int vertex_pitch, const float* tri, const float* tri_ind, int B, int nver, int ntri,
+                        int H, int W, float* cov, void* stream);
+size_t fr_coverage_backward_workspace_bytes(int B, int nver, int H, int W);
+int fr_coverage_backward(const float* cov_grad, const float* cov, const float* vertex, int vertex_pitch, const float* tri,
+                         const float* tri_ind, float* vertex_grad, int B, int nver, int ntri, int H, int W, int accumulate,
+                         void* workspace, size_t ws_bytes, void* stream);
+
+/* The soft-coverage backward's launch geometry (no GPU needed; the launcher reads the same function): out[6] as
+ * fr_debug_depth_interp_bwd_geom.  Used by tests/test_coverage_cpu.py and tests/test_coverage_gpu.py. */
+void fr_debug_coverage_bwd_geom(int B, int nver, int H, int W, int* out);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
