@@ -206,6 +206,12 @@ SIGNATURES = {
     "fr_photo_loss_forward":                          "i:ppppppiiiffppzp",
     "fr_photo_loss_backward":                         "i:ppppppppiiiffpppp",
     "fr_debug_photo_loss_geom":                       "v:iiiI",
+    "fr_synth_light_rgb":                             "i:uuippp",
+    "fr_synth_shade_rgb":                             "i:pppppiiiiffpppp",
+    "fr_photo_loss_rgb_state_bytes":                  "z:iii",
+    "fr_photo_loss_rgb_forward":                      "i:ppppppiiiffppzp",
+    "fr_photo_loss_rgb_backward":                     "i:ppppppppiiiffpppp",
+    "fr_debug_photo_loss_rgb_geom":                   "v:iiiI",
     "fr_mesh_visible":                                "i:ppiiiiipp",
     "fr_mesh_lift":                                   "i:pippppiiiiipipp",
     "fr_mesh_vertex_normals":                         "i:pipppiiipip",

@@ -637,4 +637,24 @@ int fr_synth_shade(const float* tex_img, const float* normal, const float* tri_i
                                  (hipStream_t)stream);
 }
 
+// ---- colour shading: the checks of fr_synth_params and fr_synth_shade ----------------------------------------------------------------
+int fr_synth_light_rgb(unsigned long long seed, unsigned long long first_face, int B, const float* ranges, float* light, void* stream) {
+    if (B < 1) return FR_ERR_INVALID_ARG;
+    if (B > 65535) return FR_ERR_UNSUPPORTED;
+    if (!ranges || !light) return FR_ERR_INVALID_ARG;
+    if (!synth_ranges_ok(ranges, 27)) return FR_ERR_INVALID_ARG;
+    return fr_launch_synth_light_rgb(seed, first_face, B, ranges, light, (hipStream_t)stream);
+}
+
+int fr_synth_shade_rgb(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* background,
+                       int bg_batch, int B, int H, int W, float gain, float offset, float* im_rgb, float* im_gray, float* mask,
+                       void* stream) {
+    if (B < 1 || H < 1 || W < 1) return FR_ERR_INVALID_ARG;
+    if (background ? (bg_batch != 1 && bg_batch != B) : bg_batch != 0) return FR_ERR_INVALID_ARG;
+    if (!tex_img || !normal || !tri_ind || !light || !im_rgb || !mask) return FR_ERR_INVALID_ARG;
+    if ((long long)H * W > 0x7FFFFFFFll || B > 65535) return FR_ERR_UNSUPPORTED;
+    return fr_launch_synth_shade_rgb(tex_img, normal, tri_ind, light, background, bg_batch, B, H, W, gain, offset, im_rgb, im_gray,
+                                     mask, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -242,6 +242,12 @@ int fr_launch_synth_texture(const float* mu_tex, const float* pc_tex, const floa
 int fr_launch_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light,
                           const float* background, int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray,
                           float* mask, hipStream_t stream);
+// the colour route: the lighting's sampler [B,3,9] (ranges: host [27][2]) and the shader with its gray plane (im_gray may be null)
+int fr_launch_synth_light_rgb(unsigned long long seed, unsigned long long first_face, int B, const float* ranges, float* light,
+                              hipStream_t stream);
+int fr_launch_synth_shade_rgb(const float* tex_img, const float* normal, const float* tri_ind, const float* light,
+                              const float* background, int bg_batch, int B, int H, int W, float gain, float offset, float* im_rgb,
+                              float* im_gray, float* mask, hipStream_t stream);
 // the blend's adjoint: partials [row tile][b][k] in the workspace, then the finish step
 size_t fr_synth_texture_backward_workspace_impl(int B, int N, int K);
 int fr_launch_synth_texture_backward(const float* pc_tex, const float* grad_tex, int B, int N, int K, float* grad_alpha,

@@ -192,7 +192,73 @@ __global__ __launch_bounds__(256) void synth_shade_kernel(const float* __restric
     mask[i] = 1.0f;
 }
 
+// The colour lighting's sampler: one lane per draw j = 9 c + k of face b, word j & 3 of the block with counter (j >> 2, g_lo, g_hi, 1)
+// -- the fourth word is 1 where synth_params_kernel's is 0, so the two streams are disjoint under one seed.
+struct SynthLightRgbArgs {
+    unsigned long long seed, first_face;
+    float* light;   // [B,3,9]
+    float lo[27], hi[27];
+};
+__global__ __launch_bounds__(64) void synth_light_rgb_kernel(const SynthLightRgbArgs a) {
+    const int j = (int)threadIdx.x;
+    const int b = (int)blockIdx.x;
+    if (j >= 27) return;
+    const unsigned long long g = a.first_face + (unsigned long long)b;
+    uint32_t w[4];
+    philox4x32_10((uint32_t)j >> 2, (uint32_t)g, (uint32_t)(g >> 32), 1u, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), w);
+    const uint32_t word = (j & 3) == 0 ? w[0] : (j & 3) == 1 ? w[1] : (j & 3) == 2 ? w[2] : w[3];
+    const float u = (float)(word >> 8) * 5.9604644775390625e-8f;   // 2^-24: exact, in [0,1)
+    a.light[(size_t)b * 27 + j] = a.lo[j] + (a.hi[j] - a.lo[j]) * u;
+}
+
+// one lane per pixel: the colour model of fr_shade.h, the background's three channels off the face, and the gray of the result
+__global__ __launch_bounds__(256) void synth_shade_rgb_kernel(const float* __restrict__ tex_img, const float* __restrict__ normal,
+                                                              const float* __restrict__ tri_ind, const float* __restrict__ light,
+                                                              const float* __restrict__ background, int bg_batch, int HW, float gain,
+                                                              float offset, float* __restrict__ im_rgb, float* __restrict__ im_gray,
+                                                              float* __restrict__ mask) {
+    const unsigned int pix = blockIdx.x * 256u + threadIdx.x;
+    const int b = (int)blockIdx.y;
+    if (pix >= (unsigned int)HW) return;
+    const size_t i = (size_t)b * (size_t)HW + pix;
+    float rgb[3];
+    const bool covered = tri_ind[i] >= 0.0f;
+    if (!covered) {
+        const size_t k = (bg_batch == 1 ? (size_t)0 : (size_t)b * (size_t)HW) + pix;
+#pragma unroll
+        for (int c = 0; c < 3; c++) rgb[c] = background ? background[3 * k + c] : 0.0f;
+    } else {
+        fr::ShadeRGB sh;
+        float I[3];
+        fr::shade_pixel_rgb(tex_img[3 * i], tex_img[3 * i + 1], tex_img[3 * i + 2], normal[3 * i], normal[3 * i + 1], normal[3 * i + 2],
+                            light + (size_t)b * 27, sh, I);   // (fr_shade.h: the colour loss runs it too)
+#pragma unroll
+        for (int c = 0; c < 3; c++) rgb[c] = I[c] * gain + offset;
+    }
+    im_rgb[3 * i] = rgb[0]; im_rgb[3 * i + 1] = rgb[1]; im_rgb[3 * i + 2] = rgb[2];
+    if (im_gray) im_gray[i] = fr::gray_of(rgb[0], rgb[1], rgb[2]);
+    mask[i] = covered ? 1.0f : 0.0f;
+}
+
 }  // namespace fr
+
+int fr_launch_synth_light_rgb(unsigned long long seed, unsigned long long first_face, int B, const float* ranges, float* light,
+                              hipStream_t stream) {
+    fr::SynthLightRgbArgs a{};
+    a.seed = seed; a.first_face = first_face; a.light = light;
+    for (int j = 0; j < 27; j++) { a.lo[j] = ranges[2 * j]; a.hi[j] = ranges[2 * j + 1]; }
+    hipLaunchKernelGGL(fr::synth_light_rgb_kernel, dim3((unsigned)B, 1, 1), dim3(64, 1, 1), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
+
+int fr_launch_synth_shade_rgb(const float* tex_img, const float* normal, const float* tri_ind, const float* light,
+                              const float* background, int bg_batch, int B, int H, int W, float gain, float offset, float* im_rgb,
+                              float* im_gray, float* mask, hipStream_t stream) {
+    const int HW = H * W;
+    hipLaunchKernelGGL(fr::synth_shade_rgb_kernel, dim3((unsigned)(((long long)HW + 255) / 256), (unsigned)B, 1), dim3(256, 1, 1), 0,
+                       stream, tex_img, normal, tri_ind, light, background, bg_batch, HW, gain, offset, im_rgb, im_gray, mask);
+    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
 
 int fr_launch_synth_params(unsigned long long seed, unsigned long long first_face, int B, int ns, int ne, int K, float im_size,
                            float beta, float focal, const float* light_ranges, const float* alpha_ranges, float* params,

@@ -222,13 +222,29 @@ def photometric_loss(face_net, vertices_proj, im_gray, light, alpha, weight=None
     synth_texture -> render_depth(normal_grad=True, texture_grad=True) -> photo_loss (rendering_layer/ops.py): the gradient reaches
     vertices_proj (x, y and z, through the normal map; tri_ind held fixed), light and alpha, wherever they require grad.  im_gray
     [B,H,W,1] and weight (None = 1) are constants.  -> a 0-dim float64 tensor, sse.sum() / count.sum().clamp_min(1); each rank
-    takes the mean over its own faces (no collective)."""
+    takes the mean over its own faces (no collective).
+    COLOUR (opt-in, chosen by light's shape): with light [B,3,9] -- per-channel albedo under a second-order lighting per channel, the
+    image pipeline.SynthBatches(colour=True) makes -- the picture in im_gray's place is the colour one, im_rgb [B,H,W,3] (a
+    constant), the term compares in colour through rendering_layer/ops.py::photo_loss_rgb, and is
+    sse.sum() / (3 count.sum()).clamp_min(1): the mean over the covered pixels' channels.  ValueError where the lighting and the
+    picture do not go together (a [B,3,9] lighting with a one-channel picture, a [B,4] lighting with a three-channel one).  With
+    light [B,4] every bit is the gray route's."""
     fn = face_net
     if fn.mu_tex is None or fn.pc_tex is None:
         raise ValueError("the asset dict has no texture model (mu_tex / pc_tex)")
+    colour = light.dim() == 3
+    channels = int(im_gray.shape[-1]) if im_gray.dim() == 4 else 1
+    if colour and (tuple(light.shape[1:]) != (3, 9) or channels != 3):
+        raise ValueError("the colour route (light [B,3,9]) needs the colour picture im_rgb [B,H,W,3]; got light %s and a picture %s"
+                         % (tuple(light.shape), tuple(im_gray.shape)))
+    if not colour and channels == 3:
+        raise ValueError("a colour picture im_rgb [B,H,W,3] goes with a colour lighting [B,3,9]; light is %s" % (tuple(light.shape),))
     ops = _ops()
     tex = ops.synth_texture(fn.mu_tex, fn.pc_tex, alpha)
     _, tex_img, normal, tri_ind = ops.render_depth(vertices_proj.float(), fn.tri, tex, im_gray, normal_grad=True, texture_grad=True)
+    if colour:
+        sse, count = ops.photo_loss_rgb(tex_img, normal, tri_ind.detach(), light, im_gray.detach(), weight, gain, offset)
+        return sse.sum() / (3 * count.sum()).clamp_min(1)
     sse, count = ops.photo_loss(tex_img, normal, tri_ind.detach(), light, im_gray.detach(), weight, gain, offset)
     return sse.sum() / count.sum().clamp_min(1)
 
@@ -254,7 +270,7 @@ def combine_losses(losses):
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
              gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False,
              sfs_fused_gather=False, sfs_fine=False, fine_fused=False, sfs_alpha_lse=False, sfs_alpha_ridge=1e-6,
-             silhouette_mask=None, lambda_silhouette=1.0,
+             silhouette_mask=None, lambda_silhouette=1.0, photo_target_rgb=None,
              photo_light=None, photo_alpha=None, photo_weight=None, photo_gain=1.0, photo_offset=0.0, lambda_photo=1.0,
              geometry_gram=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
@@ -283,12 +299,16 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     other is a ValueError): adds losses['photometric_loss'] = photometric_loss(face_net, vertices_proj, im_gray, photo_light,
     photo_alpha, photo_weight, photo_gain, photo_offset) -- the rendered and shaded face against im_gray itself -- and lambda_photo
     times it to total_loss.  Its gradient reaches vertices_proj, and photo_light / photo_alpha where they require grad.
+    photo_target_rgb [B,H,W,3] (default None): the colour picture; photometric_loss then gets it in im_gray's place.  It goes with a
+    colour photo_light [B,3,9] (ValueError otherwise), and the term compares in colour.
     silhouette_mask [B,H,W,1] (default None: the term is absent, the dict and every bit are today's): adds
     losses['silhouette_loss'] = silhouette_loss(face_net, vertices_proj, silhouette_mask) and lambda_silhouette times it to
     total_loss.  Its gradient reaches the x and y rows of vertices_proj; the mask is a constant."""
     fn = face_net
     if (photo_light is None) != (photo_alpha is None):
         raise ValueError("photo_light and photo_alpha go together: the photometric term needs the lighting and the albedo coefficients")
+    if photo_target_rgb is not None and photo_light is None:
+        raise ValueError("photo_target_rgb needs photo_light [B,3,9] and photo_alpha: it is the colour photometric term's picture")
     if fine_fused and pred_depth_map is None:
         raise ValueError("fine_fused=True needs pred_depth_map (the fine depth map the two terms are taken of)")
     B = pred_params.shape[0]
@@ -323,7 +343,8 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
         losses['smoothness_loss'] = filtered_depth.abs().sum()    # tf.contrib.layers.l1_regularizer(1.0), network.py:367
     losses['total_loss'] = combine_losses(losses)
     if photo_light is not None:
-        losses['photometric_loss'] = photometric_loss(fn, vertices_proj, im_gray, photo_light, photo_alpha, weight=photo_weight,
+        picture = im_gray if photo_target_rgb is None else photo_target_rgb
+        losses['photometric_loss'] = photometric_loss(fn, vertices_proj, picture, photo_light, photo_alpha, weight=photo_weight,
                                                       gain=photo_gain, offset=photo_offset)
         losses['total_loss'] = losses['total_loss'] + (lambda_photo * losses['photometric_loss']).to(losses['total_loss'].dtype)
     if silhouette_mask is not None:

@@ -360,6 +360,10 @@ class _SynthSlot:
         self.plan = DecodeRenderPlan(net, B, H, W, texture=self.tex, stream=stream)
         self.params = self.plan.params
         self.light = torch.empty((B, 4), **f32)
+        # colour: the batch's lighting is [B,3,9] and the image has three channels; the first-order draw above is still made (the
+        # sampler's other outputs do not move) and goes unused
+        self.light_rgb = torch.empty((B, 3, 9), **f32) if owner.colour else None
+        self.im_rgb = torch.empty((B, H, W, 3), **f32) if owner.colour else None
         self.alpha = torch.empty((B, owner.K), **f32)
         self.im_gray = torch.empty((B, H, W, 1), **f32)
         self.mask = torch.empty((B, H, W, 1), **f32)
@@ -367,8 +371,11 @@ class _SynthSlot:
         self.first_face = None
 
     def batch(self):
-        return {"im_gray": self.im_gray, "params": self.params, "depth": self.depth, "mask": self.mask,
-                "tri_ind": self.plan.tri_ind, "light": self.light, "alpha": self.alpha}
+        out = {"im_gray": self.im_gray, "params": self.params, "depth": self.depth, "mask": self.mask,
+               "tri_ind": self.plan.tri_ind, "light": self.light, "alpha": self.alpha}
+        if self.im_rgb is not None:
+            out.update(im_rgb=self.im_rgb, light=self.light_rgb)
+        return out
 
 
 class SynthBatches:
@@ -387,10 +394,15 @@ class SynthBatches:
     Faces are numbered globally: call n draws faces first_face + n stride .. + batch (stride: default `batch`).  A rank of a
     sharded loop passes first_face = synth_face_range(0, rank, world, batch)[0] and stride = world batch; the ranks' streams
     together are then the single-process stream, face for face.  Two streams with different seeds are independent.
-    The launches go out eagerly: first_face travels in the sampler's launch arguments, which a captured graph would freeze."""
+    The launches go out eagerly: first_face travels in the sampler's launch arguments, which a captured graph would freeze.
+    colour=True (default False: every bit is the gray stream's): the face is shaded in colour -- per-channel albedo under a
+    second-order lighting per channel (synth_light_rgb -> synth_shade_rgb).  A batch then also carries "im_rgb" [B,H,W,3], its
+    "light" is [B,3,9] (light_ranges: 27 pairs, default ops.SYNTH_LIGHT_RANGES_RGB), "im_gray" is the gray of that image
+    (0.3 R + 0.59 G + 0.11 B: what the nets take) and a background is [1,H,W,3] or [B,H,W,3].  params, alpha, depth, mask and
+    tri_ind are those of the gray stream with the same seed: the colour lighting is drawn on a sampler stream of its own."""
 
     def __init__(self, net, batch, seed, slots=2, first_face=0, stride=None, light_ranges=None, alpha_ranges=1.0, background=None,
-                 gain=1.0, offset=0.0, beta=0.7, focal=1e-3, height=None, width=None):
+                 gain=1.0, offset=0.0, beta=0.7, focal=1e-3, height=None, width=None, colour=False):
         if int(slots) < 1:
             raise ValueError("slots must be >= 1")
         if net.mu_tex is None:
@@ -406,7 +418,9 @@ class SynthBatches:
         self.seed = int(seed)
         self.first_face = int(first_face)
         self.stride = self.B if stride is None else int(stride)
-        self.light_ranges = ops.SYNTH_LIGHT_RANGES if light_ranges is None else light_ranges
+        self.colour = bool(colour)
+        self.light_ranges = ops.SYNTH_LIGHT_RANGES if light_ranges is None or self.colour else light_ranges
+        self.light_ranges_rgb = (ops.SYNTH_LIGHT_RANGES_RGB if light_ranges is None else light_ranges) if self.colour else None
         self.alpha_ranges = alpha_ranges
         self.gain, self.offset, self.beta, self.focal = float(gain), float(offset), float(beta), float(focal)
         self.background = None
@@ -433,8 +447,13 @@ class SynthBatches:
                              out=(sl.params, sl.light, sl.alpha))
             ops.synth_texture(net.mu_tex, net.pc_tex, sl.alpha, out=sl.tex)
             sl.plan.step()
-            ops.synth_shade(sl.plan.texture_image, sl.plan.normal, sl.plan.tri_ind, sl.light, background=self.background,
-                            gain=self.gain, offset=self.offset, out=(sl.im_gray, sl.mask))
+            if self.colour:
+                ops.synth_light_rgb(self.seed, sl.first_face, self.B, ranges=self.light_ranges_rgb, out=sl.light_rgb)
+                ops.synth_shade_rgb(sl.plan.texture_image, sl.plan.normal, sl.plan.tri_ind, sl.light_rgb, background=self.background,
+                                    gain=self.gain, offset=self.offset, out=(sl.im_rgb, sl.im_gray, sl.mask))
+            else:
+                ops.synth_shade(sl.plan.texture_image, sl.plan.normal, sl.plan.tri_ind, sl.light, background=self.background,
+                                gain=self.gain, offset=self.offset, out=(sl.im_gray, sl.mask))
             torch.clamp_min(sl.plan.depth, 1e-6, out=sl.depth)
             sl.event.record(sl.stream)
         self._made = n + 1

@@ -1434,6 +1434,158 @@ def synth_shade(tex_img, normal, tri_ind, light, background=None, gain=1.0, offs
     return im_gray, mask
 
 
+# ---- colour shading (opt-in): per-channel albedo under a second-order lighting per channel ---------------------------------------------
+# light[b][c][k]: the four first-order ranges above in every channel, then five second-order coefficients around 0
+SYNTH_LIGHT_RANGES_RGB = tuple(SYNTH_LIGHT_RANGES[k] if k < 4 else (-0.15, 0.15) for _c in range(3) for k in range(9))
+
+
+def synth_light_rgb(seed, first_face, batch, ranges=SYNTH_LIGHT_RANGES_RGB, device=None, out=None):
+    """`batch` faces of colour lighting drawn on the device (fr_synth_light_rgb) -> light [B,3,9], channel-major, uniform in
+    `ranges` (27 (lo, hi) pairs; a scalar s means (-s, s)).  The sampler and key of synth_params on a stream of its own (the
+    counter's fourth word is 1): under one seed no draw of synth_params moves.  out: a tensor to write instead of a fresh one.
+    Nothing requires grad.  Runs on the current stream."""
+    h = _host()
+    B = int(batch)
+    if out is None:
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise RuntimeError("synth_light_rgb draws on an MI355X only (no CPU fallback); got %s" % dev)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((B, 3, 9), dtype=torch.float32, device=dev)
+    elif h.require_gpu_f32(out, "out") is not out or tuple(out.shape) != (B, 3, 9):
+        raise ValueError("synth_light_rgb: out must be a contiguous float32 tensor [%d,3,9]" % B)
+    dev = out.device
+    rg = _synth_ranges(ranges, 27, "ranges")
+    with torch.cuda.device(dev):
+        rc = h.lib().fr_synth_light_rgb(int(seed) & (2 ** 64 - 1), int(first_face) & (2 ** 64 - 1), B, rg, h.ptr(out), h.stream_ptr(dev))
+    h.check(rc, "fr_synth_light_rgb")
+    return out
+
+
+def _rgb_light(h, op, light, B, dev):
+    l_c = h.require_gpu_f32(light.detach(), "light")
+    if tuple(l_c.shape) != (B, 3, 9) or l_c.device != dev:
+        raise ValueError("%s: light must be [%d,3,9] on %s (got %s on %s)" % (op, B, dev, tuple(l_c.shape), l_c.device))
+    return l_c
+
+
+def synth_shade_rgb(tex_img, normal, tri_ind, light, background=None, gain=1.0, offset=0.0, out=None):
+    """The colour image of a render's planes (fr_synth_shade_rgb, one lane per pixel): where tri_ind >= 0, per channel c,
+    im_rgb_c = a_c max(s_c, 0) gain + offset with a_c = clamp_min(tex_img_c, 1e-6) -- no mean over the channels -- and
+    s_c = sum over k of light[b][c][k] H_k(n^), H the nine second-order polynomials of include/fr_hotpath.h ("colour shading")
+    in the normal map of synth_shade; elsewhere the background pixel ([1,H,W,3] or [B,H,W,3]; 0 without one).  im_gray is the
+    gray of im_rgb, 0.3 R + 0.59 G + 0.11 B, background included: the plane the nets take.  tex_img, normal [B,H,W,3],
+    tri_ind [B,H,W,1], light [B,3,9].  -> (im_rgb [B,H,W,3], im_gray [B,H,W,1], mask [B,H,W,1]); out: three tensors to write
+    instead.  fp32 in a stated order, bit-exact against numpy.  Nothing requires grad.  Runs on the current stream."""
+    h = _host()
+    t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
+    n_c = h.require_gpu_f32(normal.detach(), "normal")
+    ti_c = h.require_gpu_f32(tri_ind.detach(), "tri_ind")
+    if n_c.dim() != 4 or n_c.shape[3] != 3:
+        raise ValueError("synth_shade_rgb expects normal [B,H,W,3]")
+    B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+    dev = n_c.device
+    bg_c, bg_batch = None, 0
+    if background is not None:
+        bg_c = h.require_gpu_f32(background.detach(), "background")
+        bg_batch = int(bg_c.shape[0]) if bg_c.dim() == 4 else -1
+        if bg_batch not in (1, B) or tuple(bg_c.shape[1:]) != (H, W, 3) or bg_c.device != dev:
+            raise ValueError("synth_shade_rgb: background must be [1,%d,%d,3] or [%d,%d,%d,3] on %s (got %s on %s)"
+                             % (H, W, B, H, W, dev, tuple(bg_c.shape), bg_c.device))
+    _check_plane("synth_shade_rgb", "tex_img", t_c, B, H, W, 3, dev, "normal")
+    _check_plane("synth_shade_rgb", "tri_ind", ti_c, B, H, W, 1, dev, "normal")
+    l_c = _rgb_light(h, "synth_shade_rgb", light, B, dev)
+    if out is None:
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = (torch.empty((B, H, W, 3), **f32), torch.empty((B, H, W, 1), **f32), torch.empty((B, H, W, 1), **f32))
+    im_rgb, im_gray, mask = out
+    for t, name, c in ((im_rgb, "im_rgb", 3), (im_gray, "im_gray", 1), (mask, "mask", 1)):
+        if h.require_gpu_f32(t, name) is not t or tuple(t.shape) != (B, H, W, c) or t.device != dev:
+            raise ValueError("synth_shade_rgb: out %s must be a contiguous float32 tensor [%d,%d,%d,%d] on %s" % (name, B, H, W, c, dev))
+    with torch.cuda.device(dev):
+        rc = h.lib().fr_synth_shade_rgb(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(bg_c), bg_batch, B, H, W, float(gain),
+                                        float(offset), h.ptr(im_rgb), h.ptr(im_gray), h.ptr(mask), h.stream_ptr(dev))
+    h.check(rc, "fr_synth_shade_rgb")
+    return im_rgb, im_gray, mask
+
+
+class _PhotoLossRGB(torch.autograd.Function):
+    """fr_photo_loss_rgb_forward / _backward (include/fr_hotpath.h, "colour shading") as one autograd node: (tex_img, normal,
+    tri_ind, light [B,3,9], target [B,H,W,3], weight, gain, offset) -> (sse [B], count [B]) float64.  As _PhotoLoss: it saves its
+    inputs by reference and the forward's sums [B,29]; the forward's state is the pooled per-stream buffer of kind
+    "photo_loss_rgb", held across the forward's two launches; the backward asks the kernel only for the outputs needs_input_grad
+    names."""
+
+    @staticmethod
+    def forward(ctx, tex_img, normal, tri_ind, light, target, weight, gain, offset):
+        h = _host()
+        L = h.lib()
+        n_c = h.require_gpu_f32(normal.detach(), "normal")
+        if n_c.dim() != 4 or n_c.shape[3] != 3:
+            raise ValueError("photo_loss_rgb expects normal [B,H,W,3]")
+        B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+        dev = n_c.device
+        t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
+        tg_c = h.require_gpu_f32(target.detach(), "target")
+        _check_plane("photo_loss_rgb", "tex_img", t_c, B, H, W, 3, dev, "normal")
+        _check_plane("photo_loss_rgb", "target", tg_c, B, H, W, 3, dev, "normal")
+        l_c = _rgb_light(h, "photo_loss_rgb", light, B, dev)
+        ti_c = _photo_plane(h, tri_ind, "tri_ind", B, H, W, dev)
+        w_c = _photo_plane(h, weight, "weight", B, H, W, dev) if weight is not None else None
+        empty = B * H * W == 0
+        sums = (torch.zeros if empty else torch.empty)((B, 29), dtype=torch.float64, device=dev)
+        if not empty:
+            nst = L.fr_photo_loss_rgb_state_bytes(B, H, W)
+            with torch.cuda.device(dev), _KINDS_POOL.hold("photo_loss_rgb", dev, nst) as ent:
+                rc = L.fr_photo_loss_rgb_forward(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(tg_c), h.ptr(w_c), B, H, W,
+                                                 float(gain), float(offset), h.ptr(sums), h.ptr(ent.buf), ent.nbytes, h.stream_ptr(dev))
+            h.check(rc, "fr_photo_loss_rgb_forward")
+        ctx.save_for_backward(t_c, n_c, ti_c, l_c, tg_c, sums, *(() if w_c is None else (w_c,)))
+        ctx.dims = (B, H, W)
+        ctx.scale = (float(gain), float(offset))
+        ctx.shapes = (tuple(tex_img.shape), tuple(normal.shape), tuple(light.shape))
+        ctx.set_materialize_grads(False)
+        sse, count = sums[:, 0].contiguous(), sums[:, 1].contiguous()
+        ctx.mark_non_differentiable(count)
+        return sse, count
+
+    @staticmethod
+    def backward(ctx, g_sse, g_count):
+        if g_sse is None:
+            return (None,) * 8
+        h = _host()
+        t_c, n_c, ti_c, l_c, tg_c, sums = ctx.saved_tensors[:6]
+        w_c = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
+        B, H, W = ctx.dims
+        dev = n_c.device
+        want = ctx.needs_input_grad
+        empty = B * H * W == 0
+        make = torch.zeros if empty else torch.empty
+        gt = make(ctx.shapes[0], dtype=torch.float32, device=dev) if want[0] else None
+        gn = make(ctx.shapes[1], dtype=torch.float32, device=dev) if want[1] else None
+        gl = make(ctx.shapes[2], dtype=torch.float32, device=dev) if want[3] else None
+        if not empty and (want[0] or want[1] or want[3]):
+            g = g_sse.detach().to(device=dev, dtype=torch.float64).contiguous()
+            with torch.cuda.device(dev):
+                rc = h.lib().fr_photo_loss_rgb_backward(h.ptr(g), h.ptr(sums), h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c),
+                                                        h.ptr(tg_c), h.ptr(w_c), B, H, W, ctx.scale[0], ctx.scale[1], h.ptr(gt),
+                                                        h.ptr(gn), h.ptr(gl), h.stream_ptr(dev))
+            h.check(rc, "fr_photo_loss_rgb_backward")
+        return gt, gn, None, gl, None, None, None, None
+
+
+def photo_loss_rgb(tex_img, normal, tri_ind, light, target, weight=None, gain=1.0, offset=0.0):
+    """The photometric term in colour (fr_photo_loss_rgb_forward / _backward): per face b, sse[b] = sum over the covered pixels
+    and the three channels of weight (I^_c - target_c)^2 with I^ the image synth_shade_rgb makes of the same planes, light, gain
+    and offset -- the same bits -- and count[b] = the covered pixels.  tex_img, normal, target [B,H,W,3], tri_ind, weight
+    [B,H,W,1] or [B,H,W] (weight None = 1), light [B,3,9]; -> (sse, count), float64 [B], in the association of photo_loss.  One
+    autograd node: the gradient of sse reaches tex_img (per channel), normal and light; count is not differentiable; tri_ind,
+    target and weight are constants.  A mean squared error is sse.sum() / (3 count.sum()).clamp_min(1).  Runs on the current
+    stream."""
+    return _PhotoLossRGB.apply(tex_img, normal, tri_ind, light, target, weight, gain, offset)
+
+
 def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     """One-pass rendering layer: returns (net_input [B,H,W,7] = [mask*im | pncc | normal],
     depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers.

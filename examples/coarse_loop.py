@@ -73,7 +73,7 @@ def build_harness(args, dev, rank, world, local):
         # and shaded on a side stream); train and validation draw from two streams with disjoint seeds, every rank its own faces
         pipe = pkg("pipeline")
         kw = dict(slots=2, first_face=pipe.synth_face_range(0, rank, world, B)[0], stride=world * B,
-                  focal=1e-3 * S / 200.0 if args.small else 1e-3)
+                  focal=1e-3 * S / 200.0 if args.small else 1e-3, **({"colour": True} if args.synth_colour else {}))
         train_s = pipe.SynthBatches(face, B, args.synth_seed, **kw)
         val_s = pipe.SynthBatches(face, B, args.synth_seed + 1, **kw)
 
@@ -85,6 +85,8 @@ def build_harness(args, dev, rank, world, local):
         if args.photo_loss:   # the batch's own lighting and albedo, and the stream's gain and offset: the image is their shading
             extra.update(photo_light=b["light"], photo_alpha=b["alpha"], photo_gain=stream.gain, photo_offset=stream.offset,
                          lambda_photo=args.photo_lambda)
+            if args.synth_colour:   # a colour batch: light is [B,3,9] and the term compares against the colour picture
+                extra.update(photo_target_rgb=b["im_rgb"])
         if args.silhouette_loss:   # the batch's ground-truth mask against the soft coverage of the predicted face
             extra.update(silhouette_mask=b["mask"], lambda_silhouette=args.silhouette_lambda)
         if extra:
@@ -386,6 +388,10 @@ def build_parser():
                          "and lighting against the batch's image; its gradient reaches the vertices (the pose angles too with "
                          "--pose-grad); the record gains photometric_loss; off: no term compares a rendered face with the picture")
     ap.add_argument("--photo-lambda", type=float, default=1.0, help="with --photo-loss: the term's weight in total_loss")
+    ap.add_argument("--synth-colour", action="store_true",
+                    help="with --synth-data and --train: the synthetic faces are shaded in colour (SynthBatches(colour=True): RGB albedo "
+                         "under a second-order lighting per channel; the net takes the gray of that image); with --photo-loss the "
+                         "term compares in colour (get_loss(photo_target_rgb=); fr_photo_loss_rgb_forward / _backward)")
     ap.add_argument("--silhouette-loss", action="store_true",
                     help="with --synth-data and --train: add the silhouette term (get_loss(silhouette_mask=); fr_coverage_forward / "
                          "_backward) -- the soft coverage of the predicted face against the batch's ground-truth mask; its gradient "
@@ -415,6 +421,8 @@ def main():
     args = ap.parse_args()
     if args.photo_loss and not args.synth_data:
         ap.error("--photo-loss needs --synth-data (the term uses the batch's ground-truth lighting and albedo)")
+    if args.synth_colour and not args.synth_data:
+        ap.error("--synth-colour needs --synth-data (it is the synthetic batches' shading)")
     if args.silhouette_loss and not args.synth_data:
         ap.error("--silhouette-loss needs --synth-data (the term uses the batch's ground-truth mask)")
     if args.export_mesh and (args.phase != "test" or args.im_size % 4):

@@ -7,6 +7,7 @@ HIP backward).
     python examples/photo_fit.py --batch 8 --steps 200   # the full mesh at 200 x 200
     python examples/photo_fit.py --small --fit-shape     # also fit the shape and expression coefficients (pose held at the truth)
     python examples/photo_fit.py --small --fit-pose      # also fit t3d, f and the angles, from the truth perturbed
+    python examples/photo_fit.py --small --colour        # the picture in colour: RGB albedo, second-order lighting per channel
 
 A batch of pipeline.SynthBatches gives the picture and its ground truth (parameters, light, alpha).  The fit starts from the truth
 perturbed (light by --light-noise, alpha by --alpha-noise; with --fit-shape the coefficients from zero) and runs Adam.  By default the
@@ -35,7 +36,7 @@ def rms(a, b):
     return float((a.detach().double() - b.double()).pow(2).mean().sqrt())
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--small", action="store_true", help="tiny synthetic assets at 32 x 32, 3 faces (smoke runs)")
     ap.add_argument("--batch", type=int, default=None)
@@ -51,7 +52,13 @@ def main():
     ap.add_argument("--pose-noise", type=float, default=1.0, help="with --fit-pose: the perturbation, in units of 1.5 px of "
                                                                   "translation, 3 %% of scale and 0.03 rad")
     ap.add_argument("--silhouette-lambda", type=float, default=1.0)
-    args = ap.parse_args()
+    ap.add_argument("--colour", action="store_true", help="the picture in colour: per-channel albedo under a second-order lighting per "
+                                                          "channel, light [B,3,9] (default: the gray first-order route)")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     synth, netm, pipe, losses = pkg("utils.synth"), pkg("nets.network"), pkg("pipeline"), pkg("nets.losses")
@@ -59,7 +66,7 @@ def main():
     S = args.im_size or (32 if args.small else 200)
     A = synth.make_small_assets() if args.small else synth.make_assets()
     face = netm.FaceRecNet(mesh_data=A, batch_size=B, im_size=S, device=dev)
-    stream = pipe.SynthBatches(face, B, args.seed, slots=1, focal=1e-3 * S / 200.0)
+    stream = pipe.SynthBatches(face, B, args.seed, slots=1, focal=1e-3 * S / 200.0, **({"colour": True} if args.colour else {}))
     b = {k: v.clone() for k, v in stream.next().items()}
     torch.cuda.synchronize(dev)
     im, params, light_gt, alpha_gt = b["im_gray"], b["params"], b["light"], b["alpha"]
@@ -101,7 +108,7 @@ def main():
 
     def loss_of():
         ver = vertices()
-        L = losses.photometric_loss(face, ver, im, light, alpha, gain=stream.gain, offset=stream.offset)
+        L = losses.photometric_loss(face, ver, b["im_rgb"] if args.colour else im, light, alpha, gain=stream.gain, offset=stream.offset)
         if pose is not None:
             L = L + args.silhouette_lambda * losses.silhouette_loss(face, ver, b["mask"]).double()
         return L
@@ -131,7 +138,7 @@ def main():
     if pose is not None:
         after.update(pose_errors())
     print(json.dumps({"program": "photo_fit", "faces": B, "im_size": S, "steps": args.steps, "lr": args.lr, "fit_shape": bool(args.fit_shape),
-                      "fit_pose": bool(args.fit_pose),
+                      "fit_pose": bool(args.fit_pose), "colour": bool(args.colour),
                       "first": first, "last": last, "ratio": last / first if first else None, "errors_before": before,
                       "errors_after": after, "finite": bool(torch.isfinite(light).all() and torch.isfinite(alpha).all())}))
 

@@ -1130,6 +1130,73 @@ int fr_photo_loss_backward(const double* grad_sse, const double* sums, const flo
  * All zero for an empty shape or one the launchers refuse.  Used by tests/ref_photo_loss.py for the sums' association. */
 void fr_debug_photo_loss_geom(int B, int H, int W, int* out);
 
+/* ---- colour shading: RGB second-order lighting, its sampler, the loss and its backward (opt-in) ------------------------------------
+ * The gray route above collapses tex_img's three channels into one mean and lights it to first order.  This is the same chain in
+ * colour: per-channel albedo under a nine-term lighting per channel.  The gray entry points, their arithmetic and their bits are
+ * unchanged; nothing here is reached unless it is called.  tex_img, normal [B,H,W,3] are the render's RAW planes, tri_ind [B,H,W] (a
+ * trailing channel of 1 is the caller's), light [B,3,9] channel-major (light[b][c][k]); all fp32, dense.
+ * MODEL (csrc/fr_shade.h, stated once; the shader and the loss run the same device function).  A pixel is COVERED iff tri_ind >= 0 (a
+ * NaN is uncovered).  At a covered pixel, in fp32, every operation rounded on its own (no contraction):
+ *   a_c = t_c < 1e-6f ? 1e-6f : t_c   per channel, no mean                                      (a NaN stays a NaN)
+ *   n, mag, d, n^ = (hx, hy, hz): exactly the SHADE chain above (the same helper)
+ *   H0 = 1 (never multiplied)   H1 = hx   H2 = hy   H3 = hz   H4 = hx hy   H5 = hx hz   H6 = hy hz
+ *   H7 = hx hx - hy hy          H8 = 3.0f (hz hz) - 1.0f
+ *   s_c = l_c0 + l_c1 H1, then + l_c2 H2, .. , + l_c8 H8, left to right;   I_c = a_c (s_c < 0 ? 0 : s_c);   im_rgb_c = I_c gain + offset
+ * The basis is the real spherical harmonics up to order two WITHOUT their normalisation: those constants, and the cosine lobe's, are
+ * folded into the coefficients.  im_gray = (0.3f R + 0.59f G) + 0.11f B of im_rgb (the weights of utils/data_process.py), at an
+ * uncovered pixel too, where im_rgb is the background's pixel.
+ * SAMPLER.  fr_synth_light_rgb: Philox4x32-10 with the key of fr_synth_params, counter = (j >> 2, g lo, g hi, 1), j = 9 c + k, word
+ * j & 3 -- the fourth counter word is 1 where fr_synth_params uses 0: the two streams are disjoint and no existing draw moves.
+ * u = (float)(word >> 8) * 2^-24 and light[b][c][k] = lo_j + (hi_j - lo_j) u, as there.  ranges: a HOST array [27][2] of (lo, hi)
+ * pairs, read before the call returns.  Checks, in this order: B < 1 is FR_ERR_INVALID_ARG; B > 65,535 is FR_ERR_UNSUPPORTED; a NULL
+ * ranges or light is FR_ERR_INVALID_ARG; a pair that is not finite or has lo > hi is FR_ERR_INVALID_ARG.  One launch, capturable.
+ * SHADE.  fr_synth_shade_rgb: background NULL (bg_batch 0), [1,H,W,3] (bg_batch 1) or [B,H,W,3] (bg_batch B).  An uncovered pixel
+ * gets im_rgb = its background pixel (0 without one) and mask = 0, a covered one the model's im_rgb and mask = 1; im_gray [B,H,W]
+ * may be NULL (not wanted, not written).  Checks: those of fr_synth_shade in its order, with im_rgb in im_gray's place.  One lane per
+ * pixel, one launch, capturable: 28 bytes read and 16 or 20 written per covered pixel.
+ * LOSS.  target [B,H,W,3], weight [B,H,W] or NULL (= 1).  Per covered pixel, in float64 on the widened fp32 values, every operation
+ * rounded on its own, with I^_c = im_rgb_c above (the shader's bits):
+ *   r_c = (double)I^_c - (double)target_c      t_c = ((2.0 w) r_c) (double)gain      u_c = t_c (double)a_c where s_c > 0, else +0.0
+ * FORWARD.  sums [B][29] float64 per face:
+ *   sse = sum (((w r_0) r_0 + (w r_1) r_1) + (w r_2) r_2)       cnt = sum 1.0 (exact)
+ *   L[c][k] = sum u_c (double)H_k at index 2 + 9 c + k; for k = 0 the term is u_c itself
+ * An uncovered pixel contributes +0.0 to every sum and nothing of it beyond tri_ind is read.
+ * ASSOCIATION.  The gray loss's, for every one of the 29 sums: the same 256-pixel tile, the same lane tree, the same finish chain with
+ * F = 256; a function of (H, W) alone.  The kernels share the tree and the finish step with the gray loss (templates in the number of
+ * sums).  STATE: caller-owned, 16-byte aligned, fr_photo_loss_rgb_state_bytes(B, H, W) bytes: the partials [B][tiles][29], float64, all
+ * written by the forward; the backward does not read it.
+ * BACKWARD.  One map pass, one launch; grad_sse [B] float64 is read from the DEVICE.  Each output may be NULL; every element of a
+ * non-NULL plane is written (+0 at an uncovered pixel).  With dI_c = grad_sse[b] t_c:
+ *   grad_tex_img[c] = fl32(dI_c (double)s_c) where s_c > 0 and not tex_c < 1e-6f; +0 elsewhere
+ *   grad_light[b][c][k] = fl32(grad_sse[b] L[c][k])                                       (needs sums)
+ *   grad_normal: q_c = dI_c (double)a_c where s_c > 0, else +0.0;  g~ = sum over c of q_c ds_c/dn^, the channels ascending from +0.0,
+ *                in float64 on the widened l and n^, each bracket left to right:
+ *                  ds/dhx = ((l1 + l4 hy) + l5 hz) + (2.0 l7) hx
+ *                  ds/dhy = ((l2 + l4 hx) + l6 hz) - (2.0 l7) hy
+ *                  ds/dhz = ((l3 + l5 hx) + l6 hy) + (6.0 l8) hz
+ *                then the normalisation's backward of the gray loss above, on this g~: (g~ - n c) / d where mag was kept, g~ / d where
+ *                it was replaced; negated where the forward flipped; rounded once to fp32 at the store.
+ * grad_tex_img and grad_light are fixed to the bit; grad_normal within the gray loss's bound evaluated with this g~.
+ * SPECIAL VALUES.  A NaN in a covered pixel makes its face's sse NaN, and reaches a channel's lighting sums where that channel is
+ * lit; cnt stays exact.  A NaN in a pixel, in light[b] or in grad_sse[b] changes no other face.
+ * Checks, limits and their order: the gray loss's, entry point by entry point (fr_photo_loss_rgb_state_bytes answers 0 where
+ * fr_photo_loss_state_bytes does).  Kernels (csrc/fr_photo.hip): one lane per pixel, 256 per workgroup.  The forward must move 40
+ * bytes per covered pixel (tex_img, normal, tri_ind, target; 4 more with a weight) and 4 per uncovered one, the backward the same
+ * plus the 24 it writes; tools/photo_rgb_probe.py (profiles/photo_rgb.json). */
+int fr_synth_light_rgb(unsigned long long seed, unsigned long long first_face, int B, const float* ranges, float* light, void* stream);
+int fr_synth_shade_rgb(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* background,
+                       int bg_batch, int B, int H, int W, float gain, float offset, float* im_rgb, float* im_gray, float* mask,
+                       void* stream);
+size_t fr_photo_loss_rgb_state_bytes(int B, int H, int W);
+int fr_photo_loss_rgb_forward(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* target,
+                              const float* weight, int B, int H, int W, float gain, float offset, double* sums, void* state,
+                              size_t state_bytes, void* stream);
+int fr_photo_loss_rgb_backward(const double* grad_sse, const double* sums, const float* tex_img, const float* normal,
+                               const float* tri_ind, const float* light, const float* target, const float* weight, int B, int H, int W,
+                               float gain, float offset, float* grad_tex_img, float* grad_normal, float* grad_light, void* stream);
+/* out[4] = {pixels per tile, tiles per face, threads of the finish workgroup, sums per face (29)}; all zero as above. */
+void fr_debug_photo_loss_rgb_geom(int B, int H, int W, int* out);
+
 /* ---- fine mesh: the fine depth map lifted onto the vertices, visibility, vertex normals (opt-in, forward only) ----------------------
  * FineNet's output is a [B,H,W,1] plane and the coarse decode a [B,3,N] vertex tensor; the reference leaves them unjoined
  * (nets/network.py:451-453, "how to inversely convert predicted fine depth into new vertices?") and keeps the coarse vertices.  The
