@@ -10,6 +10,9 @@ CONSUMER_FACES = 8             # a batch that is a multiple of 8 takes the owner
 CONSUMER_PIXELS = 200_000      # B*H*W a consumer case may have: the models run in a few seconds below it
 CONSUMER_STRIDE = 100_000      # the seed stride a too large scene is skipped by (as test_fused_rendering_layer skips)
 CONSUMER_BASE = 31000          # the consumers' seed base: chosen on the CPU by tests/test_fuzz_scenes_cpu.py (its docstring)
+ALBEDO_K = (1, 10, 15)         # the albedo fit's basis widths a case draws from: the smallest, the standard one and the largest served
+# the colour sampler's ranges (rendering_layer.ops.SYNTH_LIGHT_RANGES_RGB), stated here on their own as tests/ref_photo_rgb.py does
+LIGHT_RANGES_RGB = tuple(((0.3, 0.7), (-0.4, 0.4), (-0.4, 0.4), (0.2, 0.9))[k] if k < 4 else (-0.15, 0.15) for c in range(3) for k in range(9))
 
 
 def _draw(seed):
@@ -96,7 +99,8 @@ class ConsumerCase:
     """Everything a consumer case draws, from its seed alone: the scene (ver, tri, tex, H, W, kind, B, nver, tex_batch), and for the
     consumers g_normal / g_depth / g_tex (each a pair: the two gradient profiles), `old` (a finite tensor to accumulate onto),
     light, target, weight (odd seeds; else None), grad_sse and fine_noise (pixels of the fine depth map that get NaN / Inf on the
-    specials kind: (flat indices, values))."""
+    specials kind: (flat indices, values)).  The soft coverage, the colour shading and the albedo fit draw theirs from a later stream
+    (_draw_later_consumers), and the coverage has a pass of its own (vertex_altered)."""
 
     def __init__(self, index, scene=None):
         self.index, self.seed = index, CONSUMER_BASE + index
@@ -114,6 +118,107 @@ class ConsumerCase:
         self.grad_sse = rs.uniform(-2, 2, B)
         where = rs.randint(0, B * npix, 4)
         self.fine_noise = (where, np.float32([np.nan, np.inf, -np.inf, np.nan])) if self.kind == 4 else (where[:0], np.float32([]))
+        self._draw_later_consumers()
+
+    def _draw_later_consumers(self):
+        """What the soft coverage, the colour shading and the albedo fit draw, from a stream of their own (the attributes above keep
+        their bytes): g_cov (a pair, [B,npix]); light_rgb [B,3,9] uniform in LIGHT_RANGES_RGB -- the colour sampler's ranges, under
+        which a channel is unlit on some pixels of some cases and lit on most -- target_rgb [B,H,W,3] and background_rgb (None,
+        [1,H,W,3] or [B,H,W,3]: bg_kind 0, 1, 2); K in ALBEDO_K, pc_tex [3 nver,K] fp32, lighting [3,npix] float64, abedo and
+        im_gray [B,H,W,1] (on the specials kind im_gray holds a NaN and an Inf somewhere)."""
+        B, H, W, npix = self.B, self.H, self.W, self.H * self.W
+        rs = np.random.RandomState(self.seed + 700_000_000)
+        g = uniform_gradient(rs, (B, npix))
+        self.g_cov = (g, second_gradient(rs, g))
+        lo, hi = np.asarray(LIGHT_RANGES_RGB, np.float64).T
+        self.light_rgb = rs.uniform(lo, hi, (B, 27)).astype(np.float32).reshape(B, 3, 9)
+        self.target_rgb = rs.uniform(0, 1, (B, H, W, 3)).astype(np.float32)
+        self.bg_kind = int(rs.randint(0, 3))
+        bg = rs.uniform(-1, 1, (B, H, W, 3)).astype(np.float32)
+        self.background_rgb = (None, bg[:1], bg)[self.bg_kind]
+        self.K = int(rs.choice(ALBEDO_K))
+        self.pc_tex = (0.05 * rs.standard_normal((3 * self.nver, self.K))).astype(np.float32)
+        self.lighting = np.array([0.2, 0.1, 0.9])[:, None] + 0.1 * rs.standard_normal((3, npix))
+        self.abedo = rs.uniform(0.2, 0.8, (B, H, W, 1)).astype(np.float32)
+        self.im_gray = rs.uniform(0, 1, (B, H, W, 1)).astype(np.float32)
+        if self.kind == 4:
+            self.im_gray.reshape(-1)[rs.randint(0, B * npix, 2)] = (np.nan, np.inf)
+
+    def vertex_altered(self, tri_ind):
+        """The pass the soft coverage needs and no render produces: the rasteriser never lets a triangle with a non-finite area win a
+        pixel, so the coverage's exits for such a triangle (area, or s_k, not finite) are never taken on a rendered scene.  -> a copy
+        of the case in which up to four (face, triangle) of those that own an OK pixel with a not-OK 4-neighbour (OK by the case's
+        own table and `tri_ind` [B,H*W]) have the x or the y of one vertex set to NaN, +Inf, -3e38 and 1e30 in turn; the four
+        triangles differ where the scene has that many.  `poisoned` lists them as (face, triangle, vertex, row, value).  The
+        consumer is handed `tri_ind` as it is -- the plane of the UNPOISONED scene."""
+        import ref_coverage as RC
+        import ref_normal_backward as RN
+        rs = np.random.RandomState(self.seed + 800_000_000)
+        other = copy.copy(self)
+        other.ver = self.ver.copy()
+        other.poisoned = []
+        tind = np.asarray(tri_ind, np.float32).reshape(self.B, -1)
+        owners = []
+        for b in range(self.B):
+            okt, _ = RC.ok_triangles(self.tri, tind[b], self.nver)
+            border = RC._border(okt, self.H, self.W)
+            owners += [(b, int(t)) for t in np.unique(okt[border][okt[border] >= 0])]
+        order = rs.permutation(len(owners))
+        ids = RN.f2i_x86(self.tri)
+        taken = set()
+        for val in (np.nan, np.inf, -3e38, 1e30):
+            pick = [owners[i] for i in order if owners[i][1] not in taken] or [owners[i] for i in order]
+            if not pick:
+                break
+            b, t = pick[0]
+            taken.add(t)
+            v, row = int(ids[rs.randint(0, 3), t]), int(rs.randint(0, 2))
+            other.ver[b, row, v] = val
+            other.poisoned.append((b, t, v, row, float(val)))
+        return other
+
+    def vertex_on_segment(self, tri_ind):
+        """The other class no scene holds: two edges that tie on s with 0 < s < 1, where the winning edge decides which vertices the
+        backward's terms go to.  (On the lattice scenes every tie is at s = 0, a pixel centre on a vertex: no record is written and
+        the forward cannot tell the edges apart.)  It takes a vertex of the OK pixel's triangle exactly ON the segment from the
+        pixel's centre c to its not-OK neighbour's n, with c inside the triangle.  -> a copy of the case in which up to four
+        triangles that own such a pixel have one vertex moved to c + s0 (n - c), s0 = 0.25, 0.75 in turn (s < 0.5 passes the OK
+        pixel's gradient back, s > 0.5 the neighbour's), wherever the move gives an exact tie; `moved` lists them as (face,
+        triangle, vertex, pixel, neighbour, s0).  No two of the triangles share a vertex.  The consumer is handed `tri_ind` as it
+        is, as in vertex_altered."""
+        import ref_coverage as RC
+        rs = np.random.RandomState(self.seed + 900_000_000)
+        other = copy.copy(self)
+        other.ver = self.ver.copy()
+        other.moved = []
+        H, W = self.H, self.W
+        tind = np.asarray(tri_ind, np.float32).reshape(self.B, -1)
+        for b in rs.permutation(self.B):
+            okt, tid = RC.ok_triangles(self.tri, tind[b], self.nver)
+            border = RC._border(okt, H, W)
+            fixed = set()
+            for i in rs.permutation(border[okt[border] >= 0])[:64]:
+                t = int(okt[i])
+                if len(other.moved) == 4:
+                    return other
+                if fixed & set(tid[:, t].tolist()):
+                    continue
+                y, x = divmod(int(i), W)
+                s0 = (0.25, 0.75)[len(other.moved) % 2]
+                for (dx, dy), k in ((d, k) for d in RC.NEIGHBOURS for k in range(3)):
+                    nx, ny = x + dx, y + dy
+                    if nx < 0 or nx >= W or ny < 0 or ny >= H or okt[ny * W + nx] >= 0:
+                        continue
+                    v = int(tid[k, t])
+                    old = other.ver[b, :2, v].copy()
+                    other.ver[b, :2, v] = (x + s0 * dx, y + s0 * dy)
+                    sk = candidate_s(RC._tri_xy(other.ver[b], tid, t), (x, y), (nx, ny))
+                    if sk and sk.count(min(sk)) > 1 and 0.0 < min(sk) < 1.0:
+                        other.moved.append((int(b), t, v, int(i), ny * W + nx, s0))
+                        fixed |= set(tid[:, t].tolist())
+                        break
+                    other.ver[b, :2, v] = old
+        return other
 
     def altered(self, tri_ind):
         """The rasteriser skips a triangle with an id outside the mesh and writes whole triangle indices or -1, so on a rendered
@@ -160,7 +265,30 @@ def clamp_scene():
     tri[1, ::5] = tri[0, ::5]
     ver[:, 2, tri[0, ::5]] = 60.0                                              # the segments in front
     tex = rs.uniform(-0.4, 1.0, (B, 3, nver)).astype(np.float32)
-    return ConsumerCase(-1, (ver, tri.astype(np.float32), tex, H, W, 3, None))
+    case = ConsumerCase(-1, (ver, tri.astype(np.float32), tex, H, W, 3, None))
+    # colour lights of both signs in every channel (the sampler's ranges leave most pixels lit): every entry of
+    # ref_photo_rgb.BRANCHES is taken on this scene, the per-channel clamp included
+    case.light_rgb = np.random.RandomState(13).uniform(-1, 1, (B, 3, 9)).astype(np.float32)
+    return case
+
+
+def candidate_s(P, c, n):
+    """the s_k of the candidate edges of the soft coverage's pair (c, n) for the triangle P = ((x1, y1), (x2, y2), (x3, y3)), by
+    ref_coverage's edge function and the header's rule -> list (empty: the pair is inert)"""
+    import math
+
+    import ref_coverage as RC
+    area = RC.edge(P[0][0], P[0][1], P[1][0], P[1][1], P[2][0], P[2][1])
+    if area == 0 or not math.isfinite(area):
+        return []
+    sigma, out = (1.0 if area > 0 else -1.0), []
+    for k in range(3):
+        A, B = P[k], P[(k + 1) % 3]
+        fc = sigma * RC.edge(A[0], A[1], B[0], B[1], float(c[0]), float(c[1]))
+        fn = sigma * RC.edge(A[0], A[1], B[0], B[1], float(n[0]), float(n[1]))
+        if fn < 0 and fc > fn and math.isfinite(RC._div(fc, fc - fn)):
+            out.append(RC._div(fc, fc - fn))
+    return out
 
 
 def uniform_gradient(rs, shape):

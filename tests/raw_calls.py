@@ -138,7 +138,9 @@ def _tn(a):
 
 
 class PhotoCall:
-    """the two entry points called directly, with buffers of the call's own (state, sums, gradients) on a given stream"""
+    """the two entry points called directly, with buffers of the call's own (state, sums, gradients) on a given stream; every output
+    is pre-filled with NaN"""
+    ENTRY, NSUMS, LIGHT = "fr_photo_loss", 6, (4,)                          # the gray loss; PhotoRgbCall below is the colour one
 
     def __init__(self, planes, weighted, gain=GAIN, offset=OFFSET):
         tex, nrm, ti, light, target, weight = planes
@@ -150,12 +152,12 @@ class PhotoCall:
     def forward(self, stream=None):
         dev = torch.device(DEV)
         st = torch.cuda.current_stream(dev) if stream is None else stream
-        nst = self.L.fr_photo_loss_state_bytes(self.B, self.H, self.W)
+        nst = getattr(self.L, self.ENTRY + "_state_bytes")(self.B, self.H, self.W)
         with torch.cuda.stream(st):
             state = torch.full((nst,), 0xA5, dtype=torch.uint8, device=dev)       # (needs nothing cleared)
-            sums = torch.full((self.B, 6), float("nan"), dtype=torch.float64, device=dev)
-            rc = self.L.fr_photo_loss_forward(*[_p(x) for x in self.t], self.B, self.H, self.W, self.gain, self.offset, _p(sums),
-                                              _p(state), nst, ctypes.c_void_p(st.cuda_stream))
+            sums = torch.full((self.B, self.NSUMS), float("nan"), dtype=torch.float64, device=dev)
+            rc = getattr(self.L, self.ENTRY + "_forward")(*[_p(x) for x in self.t], self.B, self.H, self.W, self.gain, self.offset,
+                                                          _p(sums), _p(state), nst, ctypes.c_void_p(st.cuda_stream))
         assert rc == 0
         self.keep = state
         return sums
@@ -165,14 +167,19 @@ class PhotoCall:
         st = torch.cuda.current_stream(dev) if stream is None else stream
         with torch.cuda.stream(st):
             nan = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=dev)   # noqa: E731
-            out = [nan(self.B, self.H, self.W, 3), nan(self.B, self.H, self.W, 3), nan(self.B, 4)]
+            out = [nan(self.B, self.H, self.W, 3), nan(self.B, self.H, self.W, 3), nan(self.B, *self.LIGHT)]
             g_t = torch.as_tensor(np.asarray(g, np.float64), device=dev)
-            rc = self.L.fr_photo_loss_backward(_p(g_t), _p(sums), *[_p(x) for x in self.t], self.B, self.H, self.W, self.gain,
-                                               self.offset, *[_p(o) if w else None for o, w in zip(out, want)],
-                                               ctypes.c_void_p(st.cuda_stream))
+            rc = getattr(self.L, self.ENTRY + "_backward")(_p(g_t), _p(sums), *[_p(x) for x in self.t], self.B, self.H, self.W,
+                                                           self.gain, self.offset, *[_p(o) if w else None for o, w in zip(out, want)],
+                                                           ctypes.c_void_p(st.cuda_stream))
         assert rc == 0
         self.keep_g = g_t
         return out
+
+
+class PhotoRgbCall(PhotoCall):
+    """fr_photo_loss_rgb_forward / _backward the same way: 29 sums per face, light and grad_light [B,3,9], target [B,H,W,3]"""
+    ENTRY, NSUMS, LIGHT = "fr_photo_loss_rgb", 29, (3, 9)
 
 
 def assert_f64_bits_equal(got, want, what=""):
@@ -181,3 +188,63 @@ def assert_f64_bits_equal(got, want, what=""):
     bad = (got.view(np.uint64) != want.view(np.uint64)) & ~(np.isnan(got) & np.isnan(want))
     assert not bad.any(), "%s: %d of %d float64 differ, first at %s: got %r want %r" % (
         what, bad.sum(), got.size, tuple(np.argwhere(bad)[0]), got[tuple(np.argwhere(bad)[0])], want[tuple(np.argwhere(bad)[0])])
+
+
+# ---- fr_coverage_forward / fr_coverage_backward ----------------------------------------------------------------------------------------
+def cfwd(V, tri, ti, H, W, pitch=None):
+    """fr_coverage_forward (device tensors; not synchronised) -> cov [B,H,W,1], pre-filled with NaN.
+    pitch = (floats per vertex row, nver)"""
+    h, L = _h(), _h().lib()
+    B = int(V.shape[0])
+    nver = int(V.shape[2]) if pitch is None else pitch[1]
+    out = torch.full((B, H, W, 1), float("nan"), device=DEV)
+    rc = L.fr_coverage_forward(h.ptr(V), nver if pitch is None else pitch[0], h.ptr(tri), h.ptr(ti), B, nver, int(tri.shape[1]), H, W,
+                               h.ptr(out), _stream())
+    assert rc == 0, rc
+    return out
+
+
+def cbwd(g, cov, V, tri, ti, H, W, out=None, accumulate=0, pitch=None):
+    """fr_coverage_backward with a workspace of its own -> vertex_grad, pre-filled with NaN unless `out` is given"""
+    h, L = _h(), _h().lib()
+    B = int(V.shape[0])
+    nver = int(V.shape[2]) if pitch is None else pitch[1]
+    nws = L.fr_coverage_backward_workspace_bytes(B, nver, H, W)
+    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    if out is None:
+        out = torch.full((B, 3, nver), float("nan"), device=DEV)
+    rc = L.fr_coverage_backward(h.ptr(g), h.ptr(cov), h.ptr(V), nver if pitch is None else pitch[0], h.ptr(tri), h.ptr(ti), h.ptr(out),
+                                B, nver, int(tri.shape[1]), H, W, accumulate, h.ptr(ws), nws, _stream())
+    assert rc == 0, rc
+    return out
+
+
+# ---- fr_albedo_basis_build / fr_albedo_lse_forward -------------------------------------------------------------------------------------
+def raw_basis(tri, pc_tex, nver):
+    """fr_albedo_basis_build on a buffer of its own (tri [3,ntri], pc_tex [3 nver,K] device tensors) -> basis [ntri,K] float64,
+    pre-filled with NaN"""
+    L = _h().lib()
+    ntri, K = int(tri.shape[1]), int(pc_tex.shape[1])
+    out = torch.full((max(ntri, 1), K), float("nan"), dtype=torch.float64, device=DEV)[:ntri]
+    rc = L.fr_albedo_basis_build(_p(tri), _p(pc_tex), nver, ntri, K, _p(out), L.fr_albedo_basis_bytes(ntri, K), _stream())
+    assert rc == 0, rc
+    return out
+
+
+def raw_fit(inp, ridge):
+    """fr_albedo_lse_forward on buffers of its own, every output pre-filled with 7.0 (inp: device tensors basis [ntri,K] float64,
+    tri_ind, lighting [3,H,W] float64, normal, abedo, im_gray) -> (alpha, stats, moments) as numpy, synchronised"""
+    L = _h().lib()
+    B, H, W = inp["tri_ind"].shape[:3]
+    T, Kb = inp["basis"].shape
+    alpha = torch.full((B, Kb), 7.0, dtype=torch.float32, device=DEV)
+    moments = torch.full((B, 16, 16), 7.0, dtype=torch.float64, device=DEV)
+    stats = torch.full((B, 4), 7.0, dtype=torch.float64, device=DEV)
+    nws = L.fr_albedo_lse_workspace_bytes(B, H, W, Kb)
+    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    rc = L.fr_albedo_lse_forward(_p(inp["basis"]), _p(inp["tri_ind"]), _p(inp["lighting"]), _p(inp["normal"]), _p(inp["abedo"]),
+                                 _p(inp["im_gray"]), B, T, H, W, Kb, float(ridge), _p(alpha), _p(moments), _p(stats), _p(ws), nws,
+                                 _stream())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return alpha.cpu().numpy(), stats.cpu().numpy(), moments.cpu().numpy()

@@ -11,6 +11,7 @@ import torch
 
 from conftest import pkg
 import ref_albedo_lse as RA
+from raw_calls import raw_fit as _raw_fit
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -50,24 +51,6 @@ def _tile():
     out = (ctypes.c_int * 5)()
     _L().fr_debug_albedo_lse_geom(1, 1, 1, K, out)
     return out[0]
-
-
-def _raw_fit(inp, ridge, stream=None):
-    """the C call on buffers of its own -> (alpha, stats, moments) as numpy"""
-    L = _L()
-    B, H, W = inp["tri_ind"].shape[:3]
-    T, Kb = inp["basis"].shape
-    alpha = torch.full((B, Kb), 7.0, dtype=torch.float32, device=DEV)
-    moments = torch.full((B, 16, 16), 7.0, dtype=torch.float64, device=DEV)
-    stats = torch.full((B, 4), 7.0, dtype=torch.float64, device=DEV)
-    nws = L.fr_albedo_lse_workspace_bytes(B, H, W, Kb)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
-    rc = L.fr_albedo_lse_forward(_p(inp["basis"]), _p(inp["tri_ind"]), _p(inp["lighting"]), _p(inp["normal"]), _p(inp["abedo"]),
-                                 _p(inp["im_gray"]), B, T, H, W, Kb, float(ridge), _p(alpha), _p(moments), _p(stats), _p(ws), nws,
-                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, rc
-    torch.cuda.synchronize()
-    return alpha.cpu().numpy(), stats.cpu().numpy(), moments.cpu().numpy()
 
 
 def _np(inp):

@@ -23,6 +23,7 @@ import ref_coverage as RC
 import ref_normal_backward as RN
 from conftest import ROOT, pkg
 from gpu_util import ops, net_mod, assert_bits_equal
+from raw_calls import cbwd, cfwd
 from test_depth_interp_gpu import make_scene
 
 pytestmark = pytest.mark.gpu
@@ -45,41 +46,10 @@ def _same(a, b):
     return tuple(a.shape) == tuple(b.shape) and bool((_bits(a) == _bits(b)).all())
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def geom(B, nver, H, W):
     out = (ctypes.c_int * 6)()
     _h().lib().fr_debug_coverage_bwd_geom(B, nver, H, W, out)
     return dict(zip(("splits", "range", "shift", "chunks", "lds", "xcd"), out))
-
-
-# ---- the raw entry points, with buffers of the call's own, outputs pre-filled with NaN --------------------------------------------
-def cfwd(V, tri, ti, H, W, pitch=None):
-    """pitch = (floats per vertex row, nver)"""
-    h, L = _h(), _h().lib()
-    B = int(V.shape[0])
-    nver = int(V.shape[2]) if pitch is None else pitch[1]
-    out = torch.full((B, H, W, 1), float("nan"), device=DEV)
-    rc = L.fr_coverage_forward(h.ptr(V), nver if pitch is None else pitch[0], h.ptr(tri), h.ptr(ti), B, nver, int(tri.shape[1]), H, W,
-                               h.ptr(out), _stream())
-    assert rc == 0, rc
-    return out
-
-
-def cbwd(g, cov, V, tri, ti, H, W, out=None, accumulate=0, pitch=None):
-    h, L = _h(), _h().lib()
-    B = int(V.shape[0])
-    nver = int(V.shape[2]) if pitch is None else pitch[1]
-    nws = L.fr_coverage_backward_workspace_bytes(B, nver, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
-    if out is None:
-        out = torch.full((B, 3, nver), float("nan"), device=DEV)
-    rc = L.fr_coverage_backward(h.ptr(g), h.ptr(cov), h.ptr(V), nver if pitch is None else pitch[0], h.ptr(tri), h.ptr(ti), h.ptr(out),
-                                B, nver, int(tri.shape[1]), H, W, accumulate, h.ptr(ws), nws, _stream())
-    assert rc == 0, rc
-    return out
 
 
 _SCENES = {}

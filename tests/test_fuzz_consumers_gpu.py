@@ -1,6 +1,7 @@
 """Seeded differential fuzzing of every consumer of the rasteriser's tri_ind plane -- the normal backward (raw and post mode), the
-texture backward (shared and per-face texture), the interpolated depth (forward and backward), mesh_visible / mesh_lift, and
-synth_shade / photo_loss -- on the scenes of the rasteriser fuzz (tests/fuzz_scenes.py: jittered sub-pixel grids, triangle soup,
+texture backward (shared and per-face texture), the interpolated depth (forward and backward), mesh_visible / mesh_lift,
+synth_shade / photo_loss, the soft coverage (forward and backward), synth_shade_rgb / photo_loss_rgb, and the per-face albedo fit
+(basis build and moments) -- on the scenes of the rasteriser fuzz (tests/fuzz_scenes.py: jittered sub-pixel grids, triangle soup,
 small-triangle soup, integer coordinates with ties, and the specials: duplicated and degenerate triangles, NaN / Inf / 3e9 /
 subnormal / -0.0 coordinates, triangle ids of -1, nver, NaN and 0.75), cut down to at most 8 faces and 200,000 pixels.
 
@@ -11,7 +12,14 @@ says bit for bit, the integer bound of ref_normal_backward.check_bound for the o
 (ref_normal_backward.check_bad_faces, ref_texture_backward.assert_bad_scope) for a face or scope with a non-finite term.
 A second pass hands the consumers what no rendered scene holds (fuzz_scenes.ConsumerCase.altered): bad ids in triangles that do win
 pixels, and NaN / ntri / fractional / -0.0 entries in the plane.  Without it an `ok` test that ignores an id, or a NaN tri_ind taken as
-covered, passes every case.  tests/test_fuzz_scenes_cpu.py holds the seed set to reaching every class of input this file exists
+covered, passes every case.  The soft coverage has a third pass (ConsumerCase.vertex_altered): NaN, Inf and huge coordinates in
+vertices of triangles that own a border pixel, under the oracle's plane of the unpoisoned scene -- the rasteriser never lets such a
+triangle win, so no render reaches the coverage's exits for a non-finite area or quotient -- and a fourth
+(ConsumerCase.vertex_on_segment): a vertex exactly on the segment between an OK pixel's centre and its neighbour's, so that two
+edges tie on s inside (0, 1) and the "lowest k" rule shows in the backward.
+NOT covered: the owner-scatter geometry with shift > 0 (more than 2^20 pixels per face).  The numpy models cannot afford such a
+plane, and CONSUMER_PIXELS keeps every case far below it; tests/test_render_backward_exact_gpu.py reaches it for the render
+backward alone.  tests/test_fuzz_scenes_cpu.py holds the seed set to reaching every class of input this file exists
 for, and names the seed base."""
 import os
 
@@ -20,14 +28,18 @@ import pytest
 import torch
 
 import fuzz_scenes as FS
+import ref_albedo_lse as RA
+import ref_coverage as RC
 import ref_depth_interp as RD
 import ref_mesh as RM
 import ref_normal_backward as RN
 import ref_photo_loss as RP
+import ref_photo_rgb as RPR
 import ref_synth_batch as RS
 import ref_texture_backward as RT
 from gpu_util import assert_bits_equal, assert_render_equal, ops, render_gpu
-from raw_calls import (GAIN, OFFSET, SENT, PhotoCall, assert_f64_bits_equal, dbwd, dfwd, nbwd, raw_lift, raw_visible, tbwd)
+from raw_calls import (GAIN, OFFSET, SENT, PhotoCall, PhotoRgbCall, assert_f64_bits_equal, cbwd, cfwd, dbwd, dfwd, nbwd, raw_basis,
+                       raw_fit, raw_lift, raw_visible, tbwd)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -167,7 +179,141 @@ def check_shade_and_photo_loss(c, planes, what):
         assert np.isnan(sums[~well, 0]).all() and np.isfinite(clean_sums[:, 1]).all()
 
 
-def check_operator_surface(c, normal_part, depth_part, tex_part, what):
+def check_coverage(c, ti, what, profiles=(0, 1)):
+    """The soft coverage on the case's table and plane, then on poisoned vertices (ConsumerCase.vertex_altered) and on vertices moved
+    onto a segment between two centres (ConsumerCase.vertex_on_segment), both under the same plane.
+    The forward bit for bit; the backward -- handed the model's plane, which the forward's has just been held to -- through _twice;
+    the z row exactly +0 on the finite faces; once per case accumulate = 1, and both kernels on a padded vertex pitch with NaN in
+    the pad.  -> (the result and its model on the first profile, the model's plane)"""
+    H, W, nver = c.H, c.W, c.nver
+    tri, tind = _t(c.tri), _t(ti)
+
+    def run(case, label, profiles, extras):
+        V = _t(case.ver)
+        want = RC.forward(case.ver, c.tri, ti, H, W)
+        got_cov = cfwd(V, tri, tind, H, W).cpu().numpy()
+        assert_bits_equal(got_cov, want, label + ": soft coverage")
+        cov, keep = _t(want), None
+        for k in profiles:
+            R = RC.model(case.g_cov[k], want, case.ver, c.tri, ti, H, W)
+            gt = _t(case.g_cov[k])
+            got = _twice(lambda: cbwd(gt, cov, V, tri, tind, H, W), R, "%s: soft coverage backward, profile %d" % (label, k))
+            fin = _finite_faces(R)
+            assert not got[fin][:, 2].view(np.uint32).any(), label + ": soft coverage backward, the z row"
+            if extras and k == profiles[0]:
+                acc = cbwd(gt, cov, V, tri, tind, H, W, out=_t(c.old), accumulate=1).cpu().numpy()
+                assert_bits_equal(acc[fin], (c.old + got)[fin], label + ": soft coverage backward, accumulate")
+                pitch = nver + 5
+                Vp = torch.full((c.B, 3, pitch), float("nan"), device=DEV)
+                Vp[:, :, :nver] = V
+                assert_bits_equal(cfwd(Vp, tri, tind, H, W, pitch=(pitch, nver)).cpu().numpy(), want, label + ": soft coverage, padded pitch")
+                padded = cbwd(gt, cov, Vp, tri, tind, H, W, pitch=(pitch, nver)).cpu().numpy()
+                assert_bits_equal(padded[fin], got[fin], label + ": soft coverage backward, padded pitch")
+            if k == 0:
+                keep = (got, R)
+        return got_cov, keep, want
+
+    clean, keep, want = run(c, what, profiles, True)
+    v = c.vertex_altered(ti)
+    sick, _, _ = run(v, what + ", poisoned vertices", (c.seed % 2,), False)
+    # a pixel is out of the poison's reach when neither its own triangle nor a 4-neighbour's names a poisoned vertex: its bits stay
+    marked = (v.ver.view(np.uint32) != c.ver.view(np.uint32)).any(axis=1)      # [B,nver]
+    reach = np.zeros((c.B, H + 2, W + 2), bool)
+    for b in range(c.B):
+        okt, tid = RC.ok_triangles(c.tri, ti[b], nver)
+        hit = ((okt >= 0) & marked[b][np.clip(tid[:, np.maximum(okt, 0)], 0, nver - 1)].any(axis=0)).reshape(H, W)
+        for dy, dx in ((1, 1), (1, 0), (1, 2), (0, 1), (2, 1)):
+            reach[b, dy:dy + H, dx:dx + W] |= hit
+    far = ~reach[:, 1:-1, 1:-1]
+    assert_bits_equal(sick.reshape(c.B, H, W)[far], clean.reshape(c.B, H, W)[far], what + ": soft coverage away from the poisoned vertices")
+    # ... and with vertices moved onto the segment between two centres (ConsumerCase.vertex_on_segment): two edges tie on s inside
+    # (0, 1), and the lowest k decides which vertices the terms go to
+    run(c.vertex_on_segment(ti), what + ", vertices on a segment", (0, 1), False)
+    return keep, want
+
+
+def check_shade_and_photo_loss_rgb(c, planes, what):
+    """check_shade_and_photo_loss for the colour pair: the case's light_rgb, target_rgb and background_rgb, its weight and grad_sse"""
+    tex_img, normal, ti = planes[1], planes[2], planes[3]
+    weighted = c.weight is not None
+    bg = c.background_rgb
+    got = ops().synth_shade_rgb(_t(tex_img), _t(normal), _t(ti), _t(c.light_rgb), background=None if bg is None else _t(bg),
+                                gain=GAIN, offset=OFFSET)
+    for g, w, name in zip(got, RPR.shade(tex_img, normal, ti, c.light_rgb, bg, GAIN, OFFSET), ("im_rgb", "im_gray", "mask")):
+        assert_bits_equal(g.cpu().numpy(), w, "%s: synth_shade_rgb %s" % (what, name))
+
+    def run(nrm):
+        call = PhotoRgbCall((tex_img, nrm, ti, c.light_rgb, c.target_rgb, c.weight), weighted)
+        sums = call.forward()
+        grads = call.backward(sums, c.grad_sse)
+        return sums.cpu().numpy(), [g.cpu().numpy() for g in grads]
+    sums, (gt, gn, gl) = run(normal)
+    want = RPR.forward(tex_img, normal, ti, c.light_rgb, c.target_rgb, c.weight, GAIN, OFFSET)
+    assert_f64_bits_equal(sums, want, what + ": photo_loss_rgb sums")
+    gt_w, gn_w, gl_w, A = RPR.backward(tex_img, normal, ti, c.light_rgb, c.target_rgb, c.grad_sse, c.weight, GAIN, OFFSET, sums=want)
+    assert_bits_equal(gt, gt_w, what + ": photo_loss_rgb grad_tex_img")
+    assert_bits_equal(gl, gl_w, what + ": photo_loss_rgb grad_light")
+    # grad_normal: the gray header's bound with the colour g~ where the model is finite; where it is not, the same NaN or the same Inf
+    fin = np.isfinite(gn_w)
+    assert np.array_equal(np.isnan(gn), np.isnan(gn_w)), what + ": photo_loss_rgb grad_normal NaNs"
+    assert np.array_equal(gn[~fin & ~np.isnan(gn_w)], gn_w[~fin & ~np.isnan(gn_w)]), what + ": photo_loss_rgb grad_normal Infs"
+    bound = 2.0 ** -24 * np.abs(gn_w.astype(np.float64)) + 2.0 ** -40 * np.broadcast_to(A[..., None], gn_w.shape)
+    with np.errstate(invalid="ignore"):
+        err = np.abs(gn.astype(np.float64) - gn_w.astype(np.float64))
+        assert (err[fin] <= bound[fin]).all(), (what + ": photo_loss_rgb grad_normal", float(np.nanmax(err[fin] / bound[fin])))
+    covered = ti[..., 0] >= 0
+    assert not gt[~covered].view(np.uint32).any() and not gn[~covered].view(np.uint32).any()
+    # a NaN normal reaches its own pixel and its own face's sums, and nothing else changes by a bit (as in the gray check)
+    sick = covered & np.isnan(normal).any(-1)
+    if sick.any():
+        clean_sums, (gt2, gn2, gl2) = run(np.where(sick[..., None], np.float32(0.5), normal))
+        well = ~sick.reshape(c.B, -1).any(1)
+        assert_f64_bits_equal(sums[well], clean_sums[well], what + ": photo_loss_rgb, the faces without a NaN normal")
+        assert_f64_bits_equal(sums[:, 1], clean_sums[:, 1], what + ": photo_loss_rgb cnt")
+        assert_bits_equal(gl[well], gl2[well], what + ": photo_loss_rgb grad_light, the faces without a NaN normal")
+        assert_bits_equal(gt[~sick], gt2[~sick], what + ": photo_loss_rgb grad_tex_img, the pixels without a NaN normal")
+        assert_bits_equal(gn[~sick], gn2[~sick], what + ": photo_loss_rgb grad_normal, the pixels without a NaN normal")
+        assert np.isnan(sums[~well, 0]).all() and np.isfinite(clean_sums[:, 1]).all()
+
+
+def check_albedo_fit(c, planes, what):
+    """The per-face albedo fit on the case's table (bad ids: +0 basis rows) and plane (counted iff 0 <= (int)tri_ind < ntri), with the
+    oracle's normal as it comes.  The basis bit for bit; the count exact; every moment the model (fsum of the rounded products) has
+    finite within gamma(H W) sum |x_i x_j| of it -- tests/test_albedo_lse_gpu.py::test_moments_and_solve's bound.  A non-finite x
+    stays in its face (test_poisoned_face's rule): where the model's moment is not finite the kernel's is the same NaN or the same Inf
+    -- a sum of products holding a NaN, or Infs of both signs, is NaN in any order, and one holding Infs of one sign is that Inf --
+    the count is unchanged and the face fails.  The moments are symmetric and repeat on a second launch.  alpha is not asserted
+    (most scenes are rank-deficient by construction; the solve has its own tests), the failure flag is: on a face whose moments are
+    all finite it is ref_albedo_lse.solve_ref's on the kernel's own moments.  The ridge is 0 on even seeds, 1e-6 on odd ones."""
+    B, H, W, K = c.B, c.H, c.W, c.K
+    tind, normal = planes[3].reshape(B, H, W, 1), planes[2]
+    basis_w = RA.basis_ref(c.tri, c.pc_tex)
+    basis = raw_basis(_t(c.tri), _t(c.pc_tex), c.nver)
+    assert_f64_bits_equal(basis.cpu().numpy(), basis_w, what + ": albedo basis")
+    inp = dict(basis=basis, tri_ind=_t(tind), lighting=_t(c.lighting.reshape(3, H, W), np.float64), normal=_t(normal),
+               abedo=_t(c.abedo), im_gray=_t(c.im_gray))
+    ridge = (0.0, 1e-6)[c.seed % 2]
+    alpha, stats, M = raw_fit(inp, ridge)
+    x, counted = RA.pixel_x(basis_w, tind, c.lighting, normal, c.abedo, c.im_gray)
+    with np.errstate(invalid="ignore"):                                       # (Infs of both signs in one sum)
+        RM, RS_ = RA.moments_fsum(x)
+    assert np.array_equal(stats[:, 0], counted.sum(1).astype(np.float64)), what + ": albedo fit count"
+    fin = np.isfinite(RM)
+    with np.errstate(invalid="ignore"):
+        err = np.abs(M - RM)
+    assert (err[fin] <= (RA.gamma(H * W) * RS_)[fin]).all(), what + ": albedo fit moments"
+    assert np.array_equal(np.isnan(M), np.isnan(RM)), what + ": albedo fit, the NaN moments"
+    assert np.array_equal(M[~fin & ~np.isnan(RM)], RM[~fin & ~np.isnan(RM)]), what + ": albedo fit, the Inf moments"
+    assert_f64_bits_equal(M, np.transpose(M, (0, 2, 1)), what + ": albedo fit, symmetry")
+    assert_f64_bits_equal(raw_fit(inp, ridge)[2], M, what + ": albedo fit, two launches")
+    for b in range(B):
+        if fin[b].all():
+            assert stats[b, 3] == RA.solve_ref(M[b], K, ridge, stats[b, 0])[3], "%s: albedo fit, face %d's failure flag" % (what, b)
+        else:
+            assert stats[b, 3] == 0.0 and not alpha[b].view(np.uint32).any(), "%s: albedo fit, poisoned face %d" % (what, b)
+
+
+def check_operator_surface(c, normal_part, depth_part, tex_part, cov_part, what):
     """the wiring, not the arithmetic: render_depth with the three flags and all three gradients arriving in one backward"""
     B, H, W = c.B, c.H, c.W
     v = _t(c.ver).requires_grad_(True)
@@ -188,6 +334,13 @@ def check_operator_surface(c, normal_part, depth_part, tex_part, what):
     good = ~tex_part[1].bad                                                    # (a scope with a non-finite term has no bits to repeat)
     assert tuple(tx.grad.shape) == tuple(c.tex.shape)
     assert_bits_equal(tx.grad.cpu().numpy()[good], tex_part[0][good], what + ": texture.grad through render_depth")
+    # ops.soft_coverage under autograd on the rendered tri_ind: the model's plane, and the raw backward's bits on the finite faces
+    (got, R), want = cov_part
+    v2 = _t(c.ver).requires_grad_(True)
+    cov = ops().soft_coverage(v2, tri, ti)
+    assert_bits_equal(cov.detach().cpu().numpy(), want, what + ": ops.soft_coverage")
+    cov.backward(_t(c.g_cov[0].reshape(B, H, W, 1)))
+    assert_bits_equal(v2.grad.cpu().numpy()[_finite_faces(R)], got[_finite_faces(R)], what + ": ver.grad through ops.soft_coverage")
 
 
 def run_case(c, oracle, what):
@@ -199,7 +352,10 @@ def run_case(c, oracle, what):
     tex_part = check_texture_backward(c, ti, what)
     check_mesh(c, want, what)
     check_shade_and_photo_loss(c, want, what)
-    check_operator_surface(c, normal_part, depth_part, tex_part, what)
+    cov_part = check_coverage(c, ti, what)
+    check_shade_and_photo_loss_rgb(c, want, what)
+    check_albedo_fit(c, want, what)
+    check_operator_surface(c, normal_part, depth_part, tex_part, cov_part, what)
     # a second pass on what the rasteriser never emits (fuzz_scenes.ConsumerCase.altered): bad ids in triangles that DO win pixels,
     # and NaN / ntri / fractional / -0.0 entries in the plane -- the pixels on which the consumers' two rules part.  Every consumer
     # must treat them as its header paragraph and its model do; one gradient profile, by the seed's parity
@@ -211,6 +367,9 @@ def run_case(c, oracle, what):
     check_texture_backward(a, ti2, what, one)
     check_mesh(a, planes2, what)
     check_shade_and_photo_loss(a, planes2, what)
+    check_coverage(a, ti2, what, one)
+    check_shade_and_photo_loss_rgb(a, planes2, what)
+    check_albedo_fit(a, planes2, what)
 
 
 @pytest.mark.parametrize("seed", range(N_CASES))

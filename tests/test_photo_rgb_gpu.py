@@ -18,7 +18,7 @@ import torch
 from conftest import ROOT, pkg
 from gpu_util import assert_bits_equal, net_mod, ops
 import ref_photo_rgb as RC
-from raw_calls import GAIN, OFFSET, assert_f64_bits_equal
+from raw_calls import GAIN, OFFSET, PhotoRgbCall as Call, assert_f64_bits_equal
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -45,45 +45,6 @@ def _p(t):
 
 def _grad_up(B):
     return np.array([1.0, -0.75, 2.5])[:B]
-
-
-class Call:
-    """the two entry points called directly, with buffers of the call's own (state, sums, gradients) on a given stream; every output
-    is pre-filled with NaN"""
-
-    def __init__(self, planes, weighted, gain=GAIN, offset=OFFSET):
-        tex, nrm, ti, light, target, weight = planes
-        self.B, self.H, self.W = ti.shape[:3]
-        self.t = [_t(tex), _t(nrm), _t(ti), _t(light), _t(target), _t(weight) if weighted else None]
-        self.gain, self.offset = gain, offset
-        self.L = pkg("_lib").lib()
-
-    def forward(self, stream=None):
-        dev = _dev()
-        st = torch.cuda.current_stream(dev) if stream is None else stream
-        nst = self.L.fr_photo_loss_rgb_state_bytes(self.B, self.H, self.W)
-        with torch.cuda.stream(st):
-            state = torch.full((nst,), 0xA5, dtype=torch.uint8, device=dev)       # (needs nothing cleared)
-            sums = torch.full((self.B, 29), float("nan"), dtype=torch.float64, device=dev)
-            rc = self.L.fr_photo_loss_rgb_forward(*[_p(x) for x in self.t], self.B, self.H, self.W, self.gain, self.offset, _p(sums),
-                                                  _p(state), nst, ctypes.c_void_p(st.cuda_stream))
-        assert rc == 0
-        self.keep = state
-        return sums
-
-    def backward(self, sums, g, want=(True, True, True), stream=None):
-        dev = _dev()
-        st = torch.cuda.current_stream(dev) if stream is None else stream
-        with torch.cuda.stream(st):
-            nan = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=dev)   # noqa: E731
-            out = [nan(self.B, self.H, self.W, 3), nan(self.B, self.H, self.W, 3), nan(self.B, 3, 9)]
-            g_t = torch.as_tensor(np.asarray(g, np.float64), device=dev)
-            rc = self.L.fr_photo_loss_rgb_backward(_p(g_t), _p(sums), *[_p(x) for x in self.t], self.B, self.H, self.W, self.gain,
-                                                   self.offset, *[_p(o) if w else None for o, w in zip(out, want)],
-                                                   ctypes.c_void_p(st.cuda_stream))
-        assert rc == 0
-        self.keep_g = g_t
-        return out
 
 
 @pytest.fixture(scope="module")
