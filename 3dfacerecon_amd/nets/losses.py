@@ -260,6 +260,26 @@ def silhouette_loss(face_net, vertices_proj, target_mask):
     return F.mse_loss(cov, target)
 
 
+def landmark_loss(face_net, pred_params, idx, target, weight=None, pose_grad=True):
+    """The landmark term: the mean over faces of sse_b / max(sum_k w_k, 1), with sse_b the weighted squared pixel distance between
+    the projections of the vertices `idx` under pred_params ((B,d) or (B,1,1,d)) and target [B,K,2] (x, y; a constant).  weight:
+    None (= 1), [K] or [B,K] (e.g. the `landmark_visible` of pipeline.SynthBatches); a landmark of weight 0 is skipped entirely and
+    may carry a NaN target.  FaceRecNet.landmark_basis(idx) -> rendering_layer/ops.py::landmark_sse: the dense basis is not read and
+    no [B,3,N] tensor exists; one launch each way.  The gradient reaches pred_params -- the angles too unless pose_grad=False.
+    -> a 0-dim float64 tensor; each rank takes the mean over its own faces (no collective)."""
+    fn = face_net
+    B = pred_params.shape[0]
+    pred = pred_params.reshape(B, fn.ndim)
+    lb = fn.landmark_basis(idx)
+    sse = _ops().landmark_sse(pred, lb, target, weight=weight, im_size=fn.im_size, pose_grad=pose_grad)
+    if weight is None:
+        wsum = torch.full((B,), float(lb.K), dtype=torch.float64, device=sse.device)
+    else:
+        w = weight.detach().to(device=sse.device, dtype=torch.float64)
+        wsum = w.sum().expand(B) if w.dim() == 1 else w.sum(dim=1)
+    return (sse / wsum.clamp_min(1.0)).mean()
+
+
 def combine_losses(losses):
     """total = 1e-3 pose + 1e-6 geometry + 1e-3 SfS + 100 fidelity + 1e-5 smoothness (network.py:27-31, 373)"""
     return (LAMBDA_POSE * losses['pose_loss'] + LAMBDA_GEO * losses['geometry_loss'] +
@@ -270,7 +290,8 @@ def combine_losses(losses):
 def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse_depth_map, pred_depth_map,
              gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False,
              sfs_fused_gather=False, sfs_fine=False, fine_fused=False, sfs_alpha_lse=False, sfs_alpha_ridge=1e-6,
-             silhouette_mask=None, lambda_silhouette=1.0, photo_target_rgb=None,
+             silhouette_mask=None, lambda_silhouette=1.0,
+             landmark_target=None, landmark_idx=None, landmark_weight=None, lambda_landmark=1.0, photo_target_rgb=None,
              photo_light=None, photo_alpha=None, photo_weight=None, photo_gain=1.0, photo_offset=0.0, lambda_photo=1.0,
              geometry_gram=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
@@ -303,8 +324,14 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     colour photo_light [B,3,9] (ValueError otherwise), and the term compares in colour.
     silhouette_mask [B,H,W,1] (default None: the term is absent, the dict and every bit are today's): adds
     losses['silhouette_loss'] = silhouette_loss(face_net, vertices_proj, silhouette_mask) and lambda_silhouette times it to
-    total_loss.  Its gradient reaches the x and y rows of vertices_proj; the mask is a constant."""
+    total_loss.  Its gradient reaches the x and y rows of vertices_proj; the mask is a constant.
+    landmark_target [B,K,2] with landmark_idx (K vertex ids) (default None: the term is absent, the dict and every bit are today's;
+    one without the other is a ValueError): adds losses['landmark_loss'] = landmark_loss(face_net, pred_params, landmark_idx,
+    landmark_target, landmark_weight) and lambda_landmark times it to total_loss.  Its gradient reaches pred_params directly, the
+    angles included; it does not go through vertices_proj."""
     fn = face_net
+    if (landmark_target is None) != (landmark_idx is None):
+        raise ValueError("landmark_target and landmark_idx go together: the 2D points and the vertices they belong to")
     if (photo_light is None) != (photo_alpha is None):
         raise ValueError("photo_light and photo_alpha go together: the photometric term needs the lighting and the albedo coefficients")
     if photo_target_rgb is not None and photo_light is None:
@@ -350,4 +377,7 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     if silhouette_mask is not None:
         losses['silhouette_loss'] = silhouette_loss(fn, vertices_proj, silhouette_mask)
         losses['total_loss'] = losses['total_loss'] + (lambda_silhouette * losses['silhouette_loss']).to(losses['total_loss'].dtype)
+    if landmark_target is not None:
+        losses['landmark_loss'] = landmark_loss(fn, pred_params, landmark_idx, landmark_target, weight=landmark_weight)
+        losses['total_loss'] = losses['total_loss'] + (lambda_landmark * losses['landmark_loss']).to(losses['total_loss'].dtype)
     return losses

@@ -327,6 +327,7 @@ class FaceRecNet:
         self._gram_lock = threading.Lock()
         self._albedo_basis = None   # the texture basis per triangle in float64 (fr_albedo_basis_build), built on first use
         self._adjacency = None      # the vertex -> triangle CSR table on the device (utils/mesh_io.vertex_adjacency), on first use
+        self._landmark_bases = {}   # compact basis images of chosen vertices by id tuple (fr_landmark_basis_build): landmark_basis()
 
         # initial parameters (network.py:57-62)
         geo = torch.zeros((batch_size, self.ndim_shape + self.ndim_exp), **f32)
@@ -428,6 +429,37 @@ class FaceRecNet:
                 adj_start, adj_tri = mesh_io.vertex_adjacency(self.tri.cpu().numpy(), self.nvert)
                 self._adjacency = _ops().MeshAdjacency(adj_start, adj_tri, self.nvert, int(self.tri.shape[1]), self.device)
             return self._adjacency
+
+    def landmark_basis(self, idx):
+        """The compact image of the basis rows of the vertices `idx` (a sequence or tensor of ids in [0, N); duplicates are legal)
+        as a rendering_layer/ops.py::LandmarkBasis, built on first use per id tuple and cached under the lock gram() uses: 187 KB
+        twice over at 68 landmarks of the full model.  ValueError for an id outside [0, N)."""
+        ids = tuple(int(i) for i in (idx.reshape(-1).tolist() if hasattr(idx, "reshape") else idx))
+        with self._gram_lock:
+            lb = self._landmark_bases.get(ids)
+            if lb is None:
+                bad = [i for i in ids if not 0 <= i < self.nvert]
+                if bad:
+                    raise ValueError("landmark id %d is outside [0, %d)" % (bad[0], self.nvert))
+                with torch.cuda.device(self.device):
+                    lb = _ops().landmark_basis(self.mu, self.pc_shape, self.pc_exp, ids)
+                _publish(self.device)
+                self._landmark_bases[ids] = lb
+            return lb
+
+    def landmarks(self, pred_params, idx, R=None, pose_grad=False):
+        """(B,1,1,d) or (B,d) parameters -> the projections [B,3,K] of the vertices `idx`: what vertices_transform(pred_params)
+        [:, :, idx] holds, to the rounding of an fp32 chain, from the compact image of landmark_basis(idx) alone -- float64
+        arithmetic rounded once, no pass over the dense basis and no [B,3,N] tensor (rendering_layer/ops.py::landmarks).  R and
+        pose_grad as in vertices_transform."""
+        p = pred_params
+        if p.dim() == 4:
+            p = p.reshape(p.shape[0], p.shape[-1])
+        if p.dim() != 2 or p.shape[1] != self.ndim:
+            raise ValueError("pred_params must be (B,1,1,%d) or (B,%d)" % (self.ndim, self.ndim))
+        if R is not None and not isinstance(R, torch.Tensor):
+            R = torch.as_tensor(R, dtype=torch.float32, device=p.device)
+        return _ops().landmarks(p, self.landmark_basis(idx), R=R, im_size=self.im_size, pose_grad=pose_grad)
 
     def fine_mesh(self, vertices_proj, pred_depth_map, coarse_depth_map, with_normals=True):
         """The fine depth map taken back to the mesh: {"vertices": [B,3,N] fp32, "state": uint8 [B,N], "normals": [B,3,N] fp32 or

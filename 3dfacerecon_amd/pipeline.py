@@ -368,6 +368,10 @@ class _SynthSlot:
         self.im_gray = torch.empty((B, H, W, 1), **f32)
         self.mask = torch.empty((B, H, W, 1), **f32)
         self.depth = torch.empty((B, H, W, 1), **f32)
+        self.landmarks = self.landmark_visible = None
+        if owner.landmark_basis is not None:
+            self.landmarks = torch.empty((B, owner.landmark_basis.K, 2), **f32)
+            self.landmark_visible = torch.empty((B, owner.landmark_basis.K), **f32)
         self.first_face = None
 
     def batch(self):
@@ -375,6 +379,8 @@ class _SynthSlot:
                "tri_ind": self.plan.tri_ind, "light": self.light, "alpha": self.alpha}
         if self.im_rgb is not None:
             out.update(im_rgb=self.im_rgb, light=self.light_rgb)
+        if self.landmarks is not None:
+            out.update(landmarks=self.landmarks, landmark_visible=self.landmark_visible)
         return out
 
 
@@ -399,10 +405,14 @@ class SynthBatches:
     second-order lighting per channel (synth_light_rgb -> synth_shade_rgb).  A batch then also carries "im_rgb" [B,H,W,3], its
     "light" is [B,3,9] (light_ranges: 27 pairs, default ops.SYNTH_LIGHT_RANGES_RGB), "im_gray" is the gray of that image
     (0.3 R + 0.59 G + 0.11 B: what the nets take) and a background is [1,H,W,3] or [B,H,W,3].  params, alpha, depth, mask and
-    tri_ind are those of the gray stream with the same seed: the colour lighting is drawn on a sampler stream of its own."""
+    tri_ind are those of the gray stream with the same seed: the colour lighting is drawn on a sampler stream of its own.
+    landmarks=idx (default None: every bit is today's stream): K vertex ids.  A batch then also carries, made on the slot's stream,
+    "landmarks" [B,K,2] -- x and y of the sparse forward of its own parameters (FaceRecNet.landmarks: the compact image, not the
+    dense decode) -- and "landmark_visible" [B,K] fp32, 1.0 where rendering_layer/ops.py::mesh_visible of the batch's render marks
+    the vertex, else 0.0: ready to be the weight of nets/losses.py::landmark_loss."""
 
     def __init__(self, net, batch, seed, slots=2, first_face=0, stride=None, light_ranges=None, alpha_ranges=1.0, background=None,
-                 gain=1.0, offset=0.0, beta=0.7, focal=1e-3, height=None, width=None, colour=False):
+                 gain=1.0, offset=0.0, beta=0.7, focal=1e-3, height=None, width=None, landmarks=None, colour=False):
         if int(slots) < 1:
             raise ValueError("slots must be >= 1")
         if net.mu_tex is None:
@@ -427,6 +437,10 @@ class SynthBatches:
         if background is not None:
             self.background = _host().require_gpu_f32(background, "background")
         self.lifetime = int(slots)
+        self.landmark_basis = self._landmark_idx = None
+        if landmarks is not None:
+            self.landmark_basis = net.landmark_basis(landmarks)
+            self._landmark_idx = torch.tensor(self.landmark_basis.idx, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             self.slots = [_SynthSlot(self, torch.cuda.Stream(device=self.device)) for _ in range(int(slots) + 1)]
             torch.cuda.synchronize(self.device)   # every slot's triangle table is packed before anything else touches the slots
@@ -455,6 +469,12 @@ class SynthBatches:
                 ops.synth_shade(sl.plan.texture_image, sl.plan.normal, sl.plan.tri_ind, sl.light, background=self.background,
                                 gain=self.gain, offset=self.offset, out=(sl.im_gray, sl.mask))
             torch.clamp_min(sl.plan.depth, 1e-6, out=sl.depth)
+            if self.landmark_basis is not None:
+                with torch.no_grad():
+                    points = ops.landmarks(sl.params, self.landmark_basis, im_size=net.im_size)
+                    sl.landmarks.copy_(points[:, 0:2].transpose(1, 2))
+                    visible = ops.mesh_visible(net.tri, sl.plan.tri_ind, net.nvert)
+                    sl.landmark_visible.copy_(visible.index_select(1, self._landmark_idx))
             sl.event.record(sl.stream)
         self._made = n + 1
 

@@ -1586,6 +1586,153 @@ def photo_loss_rgb(tex_img, normal, tri_ind, light, target, weight=None, gain=1.
     return _PhotoLossRGB.apply(tex_img, normal, tri_ind, light, target, weight, gain, offset)
 
 
+class LandmarkBasis:
+    """The compact image of K chosen vertices' basis rows (fr_landmark_basis_build; include/fr_hotpath.h, "landmarks"): `image`
+    (uint8, on the device), K, n_shape, n_exp and `idx` (the ids as a tuple of ints).  Built once by landmark_basis()."""
+
+    def __init__(self, image, K, n_shape, n_exp, idx):
+        self.image, self.K, self.n_shape, self.n_exp, self.idx = image, int(K), int(n_shape), int(n_exp), tuple(idx)
+        self.device = image.device
+
+    @property
+    def nbytes(self):
+        return int(self.image.numel())
+
+
+def landmark_basis(mu, pc_shape, pc_exp, idx):
+    """Gathers the mean and the basis rows of the vertices `idx` (ints in [0, N); duplicates are legal) out of mu [3N], pc_shape
+    [3N,n_shape], pc_exp [3N,n_exp] (blocked rows) into a LandmarkBasis: one launch on the current stream, never repeated per step.
+    ValueError for an id outside [0, N), K outside 1 .. 1024 or more than 256 coefficients."""
+    h = _host()
+    L = h.lib()
+    mu_c = h.require_gpu_f32(mu.detach().reshape(-1), "mu")
+    ps_c = h.require_gpu_f32(pc_shape.detach(), "pc_shape")
+    pe_c = h.require_gpu_f32(pc_exp.detach(), "pc_exp")
+    N = int(mu_c.numel() // 3)
+    if mu_c.numel() != 3 * N or ps_c.dim() != 2 or pe_c.dim() != 2 or ps_c.shape[0] != 3 * N or pe_c.shape[0] != 3 * N:
+        raise ValueError("landmark_basis: mu must be [3N], pc_shape [3N,n_shape], pc_exp [3N,n_exp]")
+    ids = [int(i) for i in (idx.reshape(-1).tolist() if hasattr(idx, "reshape") else list(idx))]
+    bad = [i for i in ids if not 0 <= i < N]
+    if bad:
+        raise ValueError("landmark_basis: vertex id %d is outside [0, %d)" % (bad[0], N))
+    K, ns, ne = len(ids), int(ps_c.shape[1]), int(pe_c.shape[1])
+    nbytes = L.fr_landmark_basis_bytes(K, ns, ne)
+    if nbytes == 0:
+        raise ValueError("landmark_basis: needs 1 <= K <= 1024 and n_shape + n_exp <= 256 (got K = %d, %d + %d)" % (K, ns, ne))
+    dev = mu_c.device
+    idx_t = torch.tensor(ids, dtype=torch.int32, device=dev)
+    image = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.fr_landmark_basis_build(h.ptr(mu_c), h.ptr(ps_c), h.ptr(pe_c), h.ptr(idx_t), N, ns, ne, K, h.ptr(image), nbytes,
+                                       h.stream_ptr(dev))
+    h.check(rc, "fr_landmark_basis_build")
+    return LandmarkBasis(image, K, ns, ne, ids)
+
+
+class _Landmark(torch.autograd.Function):
+    """fr_landmark_forward / _backward as one autograd node: (params, R, lbasis, target, weight, im_size, pose_grad) -> (points
+    [B,3,K] fp32, sse [B] float64 -- zeros without a target).  One launch each way.  It saves its inputs by reference and nothing of
+    its own: the backward recomputes the landmarks from params.  Gradient to params, and to R where R requires grad and pose_grad is
+    set; target and weight are constants."""
+
+    @staticmethod
+    def forward(ctx, params, R, lbasis, target, weight, im_size, pose_grad):
+        h = _host()
+        p_c = h.require_gpu_f32(params.detach(), "params")
+        K, nd = lbasis.K, 7 + lbasis.n_shape + lbasis.n_exp
+        if p_c.dim() != 2 or p_c.shape[1] != nd:
+            raise ValueError("landmarks: params must be [B,%d] (got %s)" % (nd, tuple(p_c.shape)))
+        B, dev = int(p_c.shape[0]), p_c.device
+        if lbasis.device != dev:
+            raise ValueError("landmarks: the basis image is on %s, params on %s" % (lbasis.device, dev))
+        R_c = None
+        if R is not None:
+            R_c = h.require_gpu_f32(R.detach(), "R")
+            if tuple(R_c.shape) != (B, 3, 3) or R_c.device != dev:
+                raise ValueError("landmarks: R must be [%d,3,3] on %s" % (B, dev))
+        t_c = w_c = None
+        wb = 0
+        if target is not None:
+            t_c = h.require_gpu_f32(target.detach(), "target")
+            if tuple(t_c.shape) != (B, K, 2) or t_c.device != dev:
+                raise ValueError("landmark_sse: target must be [%d,%d,2] on %s (got %s)" % (B, K, dev, tuple(t_c.shape)))
+            if weight is not None:
+                w_c = h.require_gpu_f32(weight.detach(), "weight")
+                if tuple(w_c.shape) not in ((K,), (B, K)) or w_c.device != dev:
+                    raise ValueError("landmark_sse: weight must be [%d] or [%d,%d] on %s" % (K, B, K, dev))
+                wb = 1 if w_c.dim() == 2 else 0
+        points = torch.empty((B, 3, K), dtype=torch.float32, device=dev)
+        sse = (torch.empty if t_c is not None and B else torch.zeros)((B,), dtype=torch.float64, device=dev)
+        if B:
+            with torch.cuda.device(dev):
+                rc = h.lib().fr_landmark_forward(h.ptr(p_c), h.ptr(lbasis.image), lbasis.nbytes, h.ptr(R_c), h.ptr(t_c), h.ptr(w_c), wb,
+                                                 B, K, lbasis.n_shape, lbasis.n_exp, float(im_size), h.ptr(points), h.ptr(sse),
+                                                 h.stream_ptr(dev))
+            h.check(rc, "fr_landmark_forward")
+        ctx.save_for_backward(p_c, *[t for t in (R_c, t_c, w_c) if t is not None])
+        ctx.have = (R_c is not None, t_c is not None, w_c is not None)
+        ctx.lbasis, ctx.wb, ctx.im_size, ctx.pose_grad = lbasis, wb, float(im_size), bool(pose_grad)
+        ctx.set_materialize_grads(False)
+        if t_c is None:
+            ctx.mark_non_differentiable(sse)
+        return points, sse
+
+    @staticmethod
+    def backward(ctx, g_points, g_sse):
+        if (g_points is None and g_sse is None) or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 7
+        h = _host()
+        saved = list(ctx.saved_tensors)
+        p_c = saved.pop(0)
+        R_c, t_c, w_c = [saved.pop(0) if have else None for have in ctx.have]
+        lb = ctx.lbasis
+        B, dev = int(p_c.shape[0]), p_c.device
+        grad_params = (torch.empty if B else torch.zeros)(tuple(p_c.shape), dtype=torch.float32, device=dev)
+        grad_R = torch.empty((B, 3, 3), dtype=torch.float32, device=dev) if R_c is not None and ctx.pose_grad else None
+        if B:
+            gp = h.require_gpu_f32(g_points.detach(), "grad_points") if g_points is not None else None
+            gs = g_sse.detach().to(device=dev, dtype=torch.float64).contiguous() if g_sse is not None and t_c is not None else None
+            if gp is None and gs is None:
+                return (None,) * 7
+            with torch.cuda.device(dev):
+                rc = h.lib().fr_landmark_backward(h.ptr(gp), h.ptr(gs), h.ptr(p_c), h.ptr(lb.image), lb.nbytes, h.ptr(R_c), h.ptr(t_c),
+                                                  h.ptr(w_c), ctx.wb, B, lb.K, lb.n_shape, lb.n_exp, ctx.im_size, h.ptr(grad_params),
+                                                  h.ptr(grad_R), int(ctx.pose_grad), h.stream_ptr(dev))
+            h.check(rc, "fr_landmark_backward")
+        return grad_params, (grad_R if ctx.needs_input_grad[1] else None), None, None, None, None, None
+
+
+def _landmark_args(op, lbasis, target, weight):
+    # (by its fields, not its class: this file is loaded under two module names -- the package's, and FaceRecNet's by path)
+    if not all(hasattr(lbasis, k) for k in ("image", "K", "n_shape", "n_exp", "idx")):
+        raise TypeError("%s: lbasis must be a LandmarkBasis (landmark_basis())" % op)
+    for name, t in (("target", target), ("weight", weight)):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError("%s: %s is a constant of the term and must not require grad" % (op, name))
+
+
+def landmarks(params, lbasis, R=None, im_size=200, pose_grad=False):
+    """The projected landmarks [B,3,K] (x, y, z in the picture's frame, as vertices_transform gives them) of params [B, 7 + n_shape
+    + n_exp], decoded from the compact image alone (fr_landmark_forward): float64 arithmetic on the fp32 inputs, rounded to fp32
+    once.  R: optional [B,3,3] rotation (else the rotation of the angles, evaluated in the kernel).  An autograd node: the gradient
+    reaches params -- the angle columns only with pose_grad=True, the project's default being 0 there -- and, with pose_grad=True,
+    R where it requires grad.  Runs on the current stream."""
+    _landmark_args("landmarks", lbasis, None, None)
+    return _Landmark.apply(params, R, lbasis, None, None, im_size, bool(pose_grad))[0]
+
+
+def landmark_sse(params, lbasis, target, weight=None, R=None, im_size=200, pose_grad=False):
+    """The landmark term: per face b, sse[b] = sum_k w_k ((x_k - tx_k)^2 + (y_k - ty_k)^2) with (x, y) the projections of
+    landmarks() BEFORE their rounding to fp32 -> float64 [B].  target [B,K,2] (x, y in pixels), weight None (= 1), [K] or [B,K]; a
+    landmark of weight 0 is skipped entirely, so a missing landmark may carry any target, NaN included.  One launch each way: the
+    backward recomputes the landmarks.  Gradient to params (angles with pose_grad=True) and, with pose_grad=True, to R; a target or
+    weight that requires grad is refused.  Runs on the current stream."""
+    _landmark_args("landmark_sse", lbasis, target, weight)
+    if target is None:
+        raise ValueError("landmark_sse: target is required")
+    return _Landmark.apply(params, R, lbasis, target, weight, im_size, bool(pose_grad))[1]
+
+
 def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     """One-pass rendering layer: returns (net_input [B,H,W,7] = [mask*im | pncc | normal],
     depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers.

@@ -56,6 +56,18 @@ def read_3dmm_model(model_path, tri_base=None):
             'ndim_pose': 7}
 
 
+def read_keypoints(model_path, base=1):
+    """The `keypoints` field of Model_Shape.mat -- the landmark vertices some 3DMM distributions store beside the model (MATLAB
+    ids) -- as a 1-D int64 array of 0-based ids (`base` is subtracted), or None where the file has no such field.
+    read_3dmm_model and its dict do not change."""
+    shapefile = os.path.join(model_path, 'Model_Shape.mat')
+    assert os.path.exists(shapefile), 'File %s does not exist!' % (shapefile)
+    data = sio.loadmat(shapefile, variable_names=['keypoints'])
+    if 'keypoints' not in data:
+        return None
+    return np.asarray(data['keypoints']).reshape(-1).astype(np.int64) - int(base)
+
+
 def write_3dmm_model(model_path, model_params, tri_base=0):
     """Stores a model dict as the three .mat files read_3dmm_model expects.  `tri_base` is added to the triangle ids
     (use 1 to write MATLAB-style lists).  mu is stored as mu_shape with a zero mu_exp."""

@@ -118,6 +118,17 @@ def make_small_assets(grid_u=20, grid_v=24, n_shape=9, n_exp=5, scale_px=None, s
     return make_assets(grid_u, grid_v, n_shape, n_exp, patch=(3, 4, 2, 3), seed_basis=seed_basis)
 
 
+def landmark_ids(assets, K=68, seed=4567):
+    """K distinct vertex ids of an asset dict, ascending: a seeded draw without replacement over [0, N) -- deterministic, a function
+    of (N, K, seed) alone.  The stand-in for a keypoint list, which the synthetic assets (and this repository) do not have; real
+    BFM files may carry one (utils/parser_3dmm.py::read_keypoints)."""
+    N = int(np.asarray(assets["mu"]).size // 3)
+    K = int(K)
+    if not 1 <= K <= N:
+        raise ValueError("landmark_ids: need 1 <= K <= %d vertices (got %d)" % (N, K))
+    return np.sort(np.random.RandomState(int(seed)).permutation(N)[:K]).astype(np.int64)
+
+
 def get_random_params(im_size, num_shape_param, num_exp_param, beta=1.0, rand=None):
     """The reference sampler (rendering_layer/sample_test.py:23-38 == prepare_data/get_random_params.m:1-11):
     phi in U[-75,45] deg, gamma in U[-90,90] deg, theta in U[-30,30] deg (radians), f in U[0,1e-3],

@@ -74,6 +74,9 @@ def build_harness(args, dev, rank, world, local):
         pipe = pkg("pipeline")
         kw = dict(slots=2, first_face=pipe.synth_face_range(0, rank, world, B)[0], stride=world * B,
                   focal=1e-3 * S / 200.0 if args.small else 1e-3, **({"colour": True} if args.synth_colour else {}))
+        if args.landmark_loss:   # the batches also carry the projections of 68 vertices and whether the render shows them
+            lm_idx = synth.landmark_ids(A, min(68, face.nvert))
+            kw["landmarks"] = lm_idx
         train_s = pipe.SynthBatches(face, B, args.synth_seed, **kw)
         val_s = pipe.SynthBatches(face, B, args.synth_seed + 1, **kw)
 
@@ -89,6 +92,9 @@ def build_harness(args, dev, rank, world, local):
                 extra.update(photo_target_rgb=b["im_rgb"])
         if args.silhouette_loss:   # the batch's ground-truth mask against the soft coverage of the predicted face
             extra.update(silhouette_mask=b["mask"], lambda_silhouette=args.silhouette_lambda)
+        if args.landmark_loss:   # the predicted parameters' projections of the same vertices against the batch's, where visible
+            extra.update(landmark_target=b["landmarks"], landmark_idx=lm_idx, landmark_weight=b["landmark_visible"],
+                         lambda_landmark=args.landmark_lambda)
         if extra:
             return b["im_gray"], b["params"], extra
         return b["im_gray"], b["params"]
@@ -398,6 +404,13 @@ def build_parser():
                          "reaches x and y of the vertices (the pose angles too with --pose-grad); the record's losses gain "
                          "silhouette_loss; off: no term tells the fit where the face is in the picture")
     ap.add_argument("--silhouette-lambda", type=float, default=1.0, help="with --silhouette-loss: the term's weight in total_loss")
+    ap.add_argument("--landmark-loss", action="store_true",
+                    help="with --synth-data and --train: add the landmark term (get_loss(landmark_target=); fr_landmark_forward / "
+                         "_backward) -- the projections of 68 vertices (utils/synth.landmark_ids) under the predicted parameters "
+                         "against the batch's own, weighted by their visibility; decoded from a compact image of those vertices' "
+                         "basis rows, its gradient reaches the predicted parameters directly, the angles included; the record's "
+                         "losses gain landmark_loss")
+    ap.add_argument("--landmark-lambda", type=float, default=1.0, help="with --landmark-loss: the term's weight in total_loss")
     ap.add_argument("--small", action="store_true", help="tiny synthetic assets (smoke runs)")
     ap.add_argument("--dump-batches", default=None, metavar="FILE.npz",
                     help="--phase test: save every timed batch's parameters, vertices and planes (as its consumer saw them) for an "
@@ -425,6 +438,8 @@ def main():
         ap.error("--synth-colour needs --synth-data (it is the synthetic batches' shading)")
     if args.silhouette_loss and not args.synth_data:
         ap.error("--silhouette-loss needs --synth-data (the term uses the batch's ground-truth mask)")
+    if args.landmark_loss and not args.synth_data:
+        ap.error("--landmark-loss needs --synth-data (the term uses the batch's ground-truth landmarks)")
     if args.export_mesh and (args.phase != "test" or args.im_size % 4):
         ap.error("--export-mesh needs --phase test and an image size that is a multiple of 4 (FineNet pools twice)")
     # (ONE line on stdout: RCCL prints a version banner to fd 1 when its first communicator comes up -- from here on fd 1 is

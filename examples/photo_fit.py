@@ -8,14 +8,20 @@ HIP backward).
     python examples/photo_fit.py --small --fit-shape     # also fit the shape and expression coefficients (pose held at the truth)
     python examples/photo_fit.py --small --fit-pose      # also fit t3d, f and the angles, from the truth perturbed
     python examples/photo_fit.py --small --colour        # the picture in colour: RGB albedo, second-order lighting per channel
+    python examples/photo_fit.py --small --fit-pose --landmarks 68                    # ... with the landmark term beside the two
+    python examples/photo_fit.py --small --fit-pose --landmarks 68 --landmarks-only   # pose from the landmarks alone: no render
 
 A batch of pipeline.SynthBatches gives the picture and its ground truth (parameters, light, alpha).  The fit starts from the truth
 perturbed (light by --light-noise, alpha by --alpha-noise; with --fit-shape the coefficients from zero) and runs Adam.  By default the
 geometry is the ground truth's and stays fixed.  With --fit-pose the translation, the scale and the three angles start from the truth
 perturbed (--pose-noise) and are fitted too: the decode runs with pose_grad=True, and the silhouette term
 (nets/losses.py::silhouette_loss: the soft coverage of the rendered face against the batch's mask, --silhouette-lambda) stands beside
-the photometric one -- it is the term that tells the fit where the face is in the picture.  Prints ONE JSON record: the first and last loss and the parameter errors (RMS
-against the ground truth) before and after.
+the photometric one -- it is the term that tells the fit where the face is in the picture.  With --landmarks K the batch also carries
+the projections of K vertices (utils/synth.py::landmark_ids; pipeline.SynthBatches(landmarks=)) and the landmark term
+(nets/losses.py::landmark_loss, --landmark-lambda) holds the fit's own projections of those vertices to them: it reads a compact image
+of their basis rows, not the dense basis.  --landmarks-only fits the pose (and with --fit-shape the coefficients) to that term alone
+-- the usual first stage of a fit to a real picture -- with no render and no dense decode in the loop; light and alpha then stay where
+they start.  Prints ONE JSON record: the first and last loss and the parameter errors (RMS against the ground truth) before and after.
 """
 import argparse
 import importlib
@@ -54,7 +60,41 @@ def build_parser():
     ap.add_argument("--silhouette-lambda", type=float, default=1.0)
     ap.add_argument("--colour", action="store_true", help="the picture in colour: per-channel albedo under a second-order lighting per "
                                                           "channel, light [B,3,9] (default: the gray first-order route)")
+    ap.add_argument("--landmarks", type=int, default=0, help="K > 0: add the landmark term over K vertices (utils/synth.landmark_ids)")
+    ap.add_argument("--landmark-lambda", type=float, default=1.0)
+    ap.add_argument("--landmarks-only", action="store_true", help="fit to the landmark term alone (needs --landmarks and --fit-pose or "
+                                                                  "--fit-shape): no render in the loop")
     return ap
+
+
+def make_noise(seed, dev):
+    """uniform noise in [-s, s] of a tensor's shape, from one seeded CPU generator: the draws follow the order of the calls"""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return lambda t, s: (torch.rand(t.shape, generator=g) * 2 - 1).to(device=dev, dtype=t.dtype) * s
+
+
+def pose_start(pose_gt, noise, pose_noise):
+    """-> (pose0, pose_scale): the truth perturbed, and the unit of each unknown -- angles in 0.03 rad, x and y in 1.5 px, f in 3 %
+    of its value; t3d's z moves no pixel and stays"""
+    B, dev = pose_gt.shape[0], pose_gt.device
+    pose_scale = torch.tensor([0.03] * 3 + [1.5, 1.5, 1.0], device=dev, dtype=pose_gt.dtype).repeat(B, 1)
+    pose_scale = torch.cat([pose_scale, 0.03 * pose_gt[:, 6:7]], dim=1)
+    kick = noise(pose_gt, pose_noise)
+    kick[:, 5] = 0
+    return pose_gt + kick * pose_scale, pose_scale
+
+
+def descend(opt, loss_of, steps):
+    """`steps` optimiser steps on loss_of() -> (the first loss, the loss after the last step)"""
+    first = None
+    for _ in range(steps):
+        opt.zero_grad(set_to_none=True)
+        L = loss_of()
+        L.backward()
+        opt.step()
+        first = float(L.detach()) if first is None else first
+    with torch.no_grad():
+        return first, float(loss_of())
 
 
 def main():
@@ -66,12 +106,19 @@ def main():
     S = args.im_size or (32 if args.small else 200)
     A = synth.make_small_assets() if args.small else synth.make_assets()
     face = netm.FaceRecNet(mesh_data=A, batch_size=B, im_size=S, device=dev)
-    stream = pipe.SynthBatches(face, B, args.seed, slots=1, focal=1e-3 * S / 200.0, **({"colour": True} if args.colour else {}))
+    if args.landmarks_only and not (args.landmarks > 0 and (args.fit_pose or args.fit_shape)):
+        raise SystemExit("--landmarks-only needs --landmarks K and something to fit: --fit-pose or --fit-shape")
+    if args.landmarks > 0 and not (args.fit_pose or args.fit_shape):
+        raise SystemExit("--landmarks needs --fit-pose or --fit-shape: with the geometry fixed the term is a constant")
+    lm_idx = synth.landmark_ids(A, args.landmarks) if args.landmarks > 0 else None
+    kw = {"colour": True} if args.colour else {}
+    if lm_idx is not None:
+        kw["landmarks"] = lm_idx
+    stream = pipe.SynthBatches(face, B, args.seed, slots=1, focal=1e-3 * S / 200.0, **kw)
     b = {k: v.clone() for k, v in stream.next().items()}
     torch.cuda.synchronize(dev)
     im, params, light_gt, alpha_gt = b["im_gray"], b["params"], b["light"], b["alpha"]
-    g = torch.Generator(device="cpu").manual_seed(args.seed)
-    noise = lambda t, s: (torch.rand(t.shape, generator=g) * 2 - 1).to(dev) * s   # noqa: E731
+    noise = make_noise(args.seed, dev)
     light = (light_gt + noise(light_gt, args.light_noise)).requires_grad_(True)
     alpha = (alpha_gt + noise(alpha_gt, args.alpha_noise)).requires_grad_(True)
     groups = [{"params": [light, alpha], "lr": args.lr}]
@@ -85,13 +132,8 @@ def main():
         groups.append({"params": [coef], "lr": args.lr})
     pose = None
     if args.fit_pose:
-        # unit-scale unknowns again: angles in 0.03 rad, x and y in 1.5 px, f in 3 % of its value; t3d's z moves no pixel and stays
         pose_gt = params[:, :n0]
-        pose_scale = torch.tensor([0.03] * 3 + [1.5, 1.5, 1.0], device=dev).repeat(B, 1)
-        pose_scale = torch.cat([pose_scale, 0.03 * pose_gt[:, 6:7]], dim=1)
-        kick = noise(pose_gt, args.pose_noise)
-        kick[:, 5] = 0
-        pose0 = pose_gt + kick * pose_scale
+        pose0, pose_scale = pose_start(pose_gt, noise, args.pose_noise)
         pose = torch.zeros_like(pose_gt, requires_grad=True)
         groups.append({"params": [pose], "lr": args.lr})
     opt = torch.optim.Adam(groups)
@@ -99,18 +141,28 @@ def main():
     def pose_now():
         return pose0 + pose * pose_scale
 
-    def vertices():
+    def params_now():
+        return torch.cat([params[:, :n0] if pose is None else pose_now(), params[:, n0:] if coef is None else coef * scale], dim=1)
+
+    def vertices(p):
         if coef is None and pose is None:
             with torch.no_grad():
                 return face.vertices_transform(params)
-        p = torch.cat([params[:, :n0] if pose is None else pose_now(), params[:, n0:] if coef is None else coef * scale], dim=1)
         return face.vertices_transform(p, pose_grad=True) if pose is not None else face.vertices_transform(p)
 
+    def landmark_term(p):
+        return losses.landmark_loss(face, p, lm_idx, b["landmarks"], pose_grad=pose is not None)
+
     def loss_of():
-        ver = vertices()
+        p = params_now()
+        if args.landmarks_only:
+            return args.landmark_lambda * landmark_term(p)
+        ver = vertices(p)
         L = losses.photometric_loss(face, ver, b["im_rgb"] if args.colour else im, light, alpha, gain=stream.gain, offset=stream.offset)
         if pose is not None:
             L = L + args.silhouette_lambda * losses.silhouette_loss(face, ver, b["mask"]).double()
+        if lm_idx is not None:
+            L = L + args.landmark_lambda * landmark_term(p)
         return L
 
     def pose_errors():
@@ -123,22 +175,15 @@ def main():
         before.update(pose_errors())
     if coef is not None:
         before["coef_rms_scaled"] = rms(coef, coef_gt / scale)
-    first = last = None
-    for _ in range(args.steps):
-        opt.zero_grad(set_to_none=True)
-        L = loss_of()
-        L.backward()
-        opt.step()
-        first = float(L.detach()) if first is None else first
-    with torch.no_grad():
-        last = float(loss_of())
+    first, last = descend(opt, loss_of, args.steps)
     after = {"light_rms": rms(light, light_gt), "alpha_rms": rms(alpha, alpha_gt)}
     if coef is not None:
         after["coef_rms_scaled"] = rms(coef, coef_gt / scale)
     if pose is not None:
         after.update(pose_errors())
     print(json.dumps({"program": "photo_fit", "faces": B, "im_size": S, "steps": args.steps, "lr": args.lr, "fit_shape": bool(args.fit_shape),
-                      "fit_pose": bool(args.fit_pose), "colour": bool(args.colour),
+                      "fit_pose": bool(args.fit_pose), "colour": bool(args.colour), "landmarks": int(args.landmarks),
+                      "landmarks_only": bool(args.landmarks_only),
                       "first": first, "last": last, "ratio": last / first if first else None, "errors_before": before,
                       "errors_after": after, "finite": bool(torch.isfinite(light).all() and torch.isfinite(alpha).all())}))
 

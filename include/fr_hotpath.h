@@ -1327,6 +1327,73 @@ int fr_coverage_backward(const float* cov_grad, const float* cov, const float* v
  * fr_debug_depth_interp_bwd_geom.  Used by tests/test_coverage_cpu.py and tests/test_coverage_gpu.py. */
 void fr_debug_coverage_bwd_geom(int B, int nver, int H, int W, int* out);
 
+/* ---- landmarks ----------------------------------------------------------------------------------------------
+ * The projections of K chosen vertices, their squared distance to 2D points of the picture, and the gradient of both with respect to
+ * the parameters -- without the dense decode: the landmarks' basis rows are gathered once into a compact image, then one launch each
+ * way per step (csrc/fr_landmark.hip).  Opt-in; no reference counterpart.
+ *
+ * Image (fr_landmark_basis_build; fr_landmark_basis_bytes bytes, 16-byte aligned; 0 for sizes that are not served).  fp32, with
+ * Kt = n_shape + n_exp, R3 = 3 K and row r = 3 k + c = coordinate c of landmark k:
+ *     part A  [Kt + 1][R3]  plane 0 = mu[c N + idx[k]], plane 1 + j = coefficient j of that row (shape first, then expression)
+ *     part B  [R3][Kt]      the same coefficients row-major, directly behind part A
+ * (the data twice: the forward's lane r walks the planes of A, the backward's lane j the rows of B, both coalesced).  mu [3N],
+ * pc_shape [3N,n_shape], pc_exp [3N,n_exp] and idx [K] (int) are device pointers, the basis in the reference's blocked row order
+ * (row c N + p = coordinate c of vertex p).  An id outside [0, N) gives a landmark whose mean and rows are all +0; duplicate ids
+ * are legal.  A pure gather: bit-exact.
+ *
+ * Forward.  params [B, 7 + Kt] fp32; R_override NULL or [B,3,3] fp32; target NULL or [B,K,2] fp32; weight NULL (all 1), [K]
+ * (weight_batch 0) or [B,K] (weight_batch 1); points [B,3,K] fp32; sse [B] float64, required when target is given, else ignored.
+ * All arithmetic is float64 on the widened fp32 inputs, every product and every sum rounded on its own (no contraction):
+ *     v_c  = mu_c, then + a_j U[c][j] for j ascending over the shape coefficients, then over the expression coefficients;
+ *     R    = the fp32 matrix the dense decode uses (rotation_from_sincos of csrc/fr_decode_shared.h on the float64 sincos of the
+ *            widened angles, rounded to fp32) or the override; widened;
+ *     q_i  = f ((R_i0 v_0 + R_i1 v_1) + R_i2 v_2) + t_i;      x = q_0,  y = (im_size - q_1) - 1,  z = q_2;
+ *     points = (x, y, z), each rounded to fp32 once;
+ *     sse_b = sum over k ascending, from +0, of  w_k ((x - tx)(x - tx) + (y - ty)(y - ty))   with x, y BEFORE the fp32 rounding.
+ * A landmark with w_k == 0 is skipped entirely (its target is not read: a NaN target under weight 0 changes nothing).
+ *
+ * Backward.  grad_points NULL or [B,3,K] fp32; grad_sse NULL or [B] float64 (read from the device; it needs target); at least one
+ * of the two.  It saves nothing: v is recomputed from params in the forward's chain, with the same bits.
+ *     g    = grad_points (or 0);  where w_k != 0:  s = grad_sse_b (2 w_k),  g_x = g_x + s (x - tx),  g_y = g_y + s (y - ty);
+ *     dq   = (g_x, -g_y, g_z);    Rv_i = (R_i0 v_0 + R_i1 v_1) + R_i2 v_2;    (R^T dq)_c = (R_0c dq_0 + R_1c dq_1) + R_2c dq_2;
+ *     grad t3d_i = sum_k dq_i;    grad f = sum_k ((dq_0 Rv_0 + dq_1 Rv_1) + dq_2 Rv_2);    G_ij = f sum_k dq_i v_j;
+ *     grad a_j   = f sum over (k, c) ascending of (R^T dq)_c[k] U[k][c][j];
+ *     angle a (pose_grad 1, no override):  sum over (i, j) row-major of G_ij dR_a[i][j], where dR_phi = (dR_pitch R_yaw) R_roll,
+ *     dR_gamma = (R_pitch dR_yaw) R_roll, dR_theta = (R_pitch R_yaw) dR_roll in float64 with the 3-term dots of mat3_mul and the
+ *     matrices of tests/ref_pose_backward.py::rotation_f64 (the sincos are the forward's float64 ones, not rounded to fp32).
+ * Every sum is sequential from +0 in ascending order, in float64; each output is rounded to fp32 once.  grad_params [B, 7 + Kt]:
+ * every element is written; with pose_grad 0 (the project's default) the angle columns are +0 and grad_R is untouched; under an
+ * override with pose_grad 1, grad_R [B,3,3] = G (required then) and the angle columns are +0.  No workspace, no atomics:
+ * bit-reproducible.
+ *
+ * Limits: n_shape + n_exp <= 256 and 1 <= K <= 1024.  Checks, all before any HIP call, in the order and with the codes of
+ * fr_coverage_*: (1) a negative size, or weight_batch / pose_grad outside {0, 1}, is FR_ERR_INVALID_ARG; (2) B == 0 or K == 0 is
+ * FR_OK with nothing launched; (3) a NULL params, points, grad_params or idx, a NULL basis matrix that has elements, a target without
+ * sse, both gradients NULL, grad_sse without target, or pose_grad 1 under an override without grad_R is FR_ERR_INVALID_ARG; (4) a
+ * size outside the limits is FR_ERR_UNSUPPORTED; (5) an image that is missing, too small or not 16-byte aligned is
+ * FR_ERR_WORKSPACE.  Nothing is allocated or synchronised; reentrant under the rules at the top of this file.
+ * Kernels: one workgroup per face; the landmarks go through LDS in chunks of 256 in ascending order.  The forward gives a lane to
+ * each (k, c) for the Kt-long chain, then one to each landmark for the projection and its sse term, and lane 0 adds the terms.  The
+ * backward recomputes v the same way, forms dq, dq . Rv and R^T dq per landmark, and then gives one lane to each coefficient
+ * (walking part B) and one to each of the 13 pose sums; a lane carries its sum from chunk to chunk.
+ * Time: tools/landmark_probe.py (profiles/landmark.json) measures both at 64 and 32 faces of the full model (199 + 29 coefficients,
+ * K = 68; a 373 KB image) beside the dense route to the same 68 points in the same run.  MI355X, medians of 6 rounds of 40 calls:
+ * forward 10.1 / 10.1 us, backward 17.0 / 17.0 us -- the same at either batch: one workgroup per face, latency of the 228-long
+ * float64 chain and of the launch, not bytes.  The autograd operator forward + backward (nets/losses.py::landmark_loss) takes 208 /
+ * 136 us of mostly host time (133 us in the quiet rounds at 64 faces) where vertices_transform(pose_grad=True) -> index_select ->
+ * the same loss -> backward takes 338 / 294 us, and holds 62 / 32 KB at its peak where the dense route holds 109 / 55 MB beside the
+ * 154 MB basis image. */
+size_t fr_landmark_basis_bytes(int K, int n_shape, int n_exp);
+int fr_landmark_basis_build(const float* mu, const float* pc_shape, const float* pc_exp, const int* idx, int N, int n_shape,
+                            int n_exp, int K, void* lbasis, size_t bytes, void* stream);
+int fr_landmark_forward(const float* params, const void* lbasis, size_t lbasis_bytes, const float* R_override, const float* target,
+                        const float* weight, int weight_batch, int B, int K, int n_shape, int n_exp, float im_size, float* points,
+                        double* sse, void* stream);
+int fr_landmark_backward(const float* grad_points, const double* grad_sse, const float* params, const void* lbasis,
+                         size_t lbasis_bytes, const float* R_override, const float* target, const float* weight, int weight_batch,
+                         int B, int K, int n_shape, int n_exp, float im_size, float* grad_params, float* grad_R, int pose_grad,
+                         void* stream);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
