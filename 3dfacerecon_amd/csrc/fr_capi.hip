@@ -4,6 +4,7 @@
 #include <mutex>
 
 #include "fr_common.h"
+#include "fr_landmark_shared.h"
 
 // ---- option table: environment read once, fr_set_option afterwards ------------------------------------------------------
 namespace {
@@ -655,6 +656,28 @@ int fr_synth_shade_rgb(const float* tex_img, const float* normal, const float* t
     if ((long long)H * W > 0x7FFFFFFFll || B > 65535) return FR_ERR_UNSUPPORTED;
     return fr_launch_synth_shade_rgb(tex_img, normal, tri_ind, light, background, bg_batch, B, H, W, gain, offset, im_rgb, im_gray,
                                      mask, (hipStream_t)stream);
+}
+
+// ---- landmark solver: the checks of fr_landmark_forward, then its own -----------------------------------------------------------------
+size_t fr_landmark_solve_workspace_bytes(int B, int n_shape, int n_exp) { return fr_landmark_solve_workspace_impl(B, n_shape, n_exp); }
+
+int fr_landmark_solve_step(const float* params, const void* lbasis, size_t lbasis_bytes, const float* target, const float* weight,
+                           int weight_batch, const float* ridge, const float* center, const double* damp, int pose_mask, int fit_coef,
+                           int B, int K, int n_shape, int n_exp, float im_size, double* delta, double* cost, int* ok, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    using namespace fr;
+    if (B < 0 || K < 0 || n_shape < 0 || n_exp < 0 || (weight_batch != 0 && weight_batch != 1)) return FR_ERR_INVALID_ARG;
+    if ((fit_coef != 0 && fit_coef != 1) || (pose_mask & ~0x5F)) return FR_ERR_INVALID_ARG;   // bit 5, tz: its column is zero
+    const bool coef = fit_coef && (long long)n_shape + n_exp > 0;
+    if (pose_mask == 0 && !coef) return FR_ERR_INVALID_ARG;                                   // nothing to fit
+    if (B == 0 || K == 0) return FR_OK;
+    if (!params || !target || !delta || !cost || !ok) return FR_ERR_INVALID_ARG;
+    if (!lm_sizes_ok(K, n_shape, n_exp)) return FR_ERR_UNSUPPORTED;
+    if (!ws_ok(lbasis, lbasis_bytes, lm_basis_floats(K, n_shape + n_exp) * sizeof(float), 16)) return FR_ERR_WORKSPACE;
+    if (coef && !ws_ok(workspace, workspace_bytes, fr_landmark_solve_workspace_impl(B, n_shape, n_exp), 16)) return FR_ERR_WORKSPACE;
+    return fr_launch_landmark_solve(params, reinterpret_cast<const float*>(lbasis), target, weight, weight_batch, ridge, center, damp,
+                                    pose_mask, coef ? 1 : 0, B, K, n_shape, n_exp, im_size, delta, cost, ok, workspace,
+                                    (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -252,3 +252,9 @@ int fr_launch_synth_shade_rgb(const float* tex_img, const float* normal, const f
 size_t fr_synth_texture_backward_workspace_impl(int B, int N, int K);
 int fr_launch_synth_texture_backward(const float* pc_tex, const float* grad_tex, int B, int N, int K, float* grad_alpha,
                                      void* workspace, hipStream_t stream);
+// the landmark solver (fr_landmark_solve.hip): the workspace of a fit_coef call (0 for sizes not served) and the one launch
+size_t fr_landmark_solve_workspace_impl(int B, int n_shape, int n_exp);
+int fr_launch_landmark_solve(const float* params, const float* lbasis, const float* target, const float* weight, int weight_batch,
+                             const float* ridge, const float* center, const double* damp, int pose_mask, int fit_coef, int B, int K,
+                             int n_shape, int n_exp, float im_size, double* delta, double* cost, int* ok, void* workspace,
+                             hipStream_t stream);

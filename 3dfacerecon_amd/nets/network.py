@@ -461,6 +461,20 @@ class FaceRecNet:
             R = torch.as_tensor(R, dtype=torch.float32, device=p.device)
         return _ops().landmarks(p, self.landmark_basis(idx), R=R, im_size=self.im_size, pose_grad=pose_grad)
 
+    def landmark_fit(self, pred_params, idx_or_lbasis, target, weight=None, ridge=None, center=None, iters=10, damp0=1e-3,
+                     fit_pose=True, fit_coef=False):
+        """(B,1,1,d) or (B,d) parameters -> (the parameters [B,d] after `iters` Levenberg-Marquardt iterations on the landmark
+        term, info): rendering_layer/ops.py::landmark_fit at this model's im_size, over the cached landmark_basis(idx) -- or over a
+        LandmarkBasis handed in as it is.  target [B,K,2], weight, ridge, center, fit_pose and fit_coef as there."""
+        p = pred_params
+        if p.dim() == 4:
+            p = p.reshape(p.shape[0], p.shape[-1])
+        if p.dim() != 2 or p.shape[1] != self.ndim:
+            raise ValueError("pred_params must be (B,1,1,%d) or (B,%d)" % (self.ndim, self.ndim))
+        lb = idx_or_lbasis if hasattr(idx_or_lbasis, "image") else self.landmark_basis(idx_or_lbasis)
+        return _ops().landmark_fit(p, lb, target, weight=weight, ridge=ridge, center=center, iters=iters, damp0=damp0,
+                                   fit_pose=fit_pose, fit_coef=fit_coef, im_size=self.im_size)
+
     def fine_mesh(self, vertices_proj, pred_depth_map, coarse_depth_map, with_normals=True):
         """The fine depth map taken back to the mesh: {"vertices": [B,3,N] fp32, "state": uint8 [B,N], "normals": [B,3,N] fp32 or
         None}.  `vertices_proj` is rendered once for its tri_ind -- the same winners, bit for bit, that produced

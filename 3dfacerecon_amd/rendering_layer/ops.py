@@ -1733,6 +1733,149 @@ def landmark_sse(params, lbasis, target, weight=None, R=None, im_size=200, pose_
     return _Landmark.apply(params, R, lbasis, target, weight, im_size, bool(pose_grad))[1]
 
 
+LANDMARK_POSE_BITS = {"phi": 0, "gamma": 1, "theta": 2, "tx": 3, "ty": 4, "f": 6}   # (tz, bit 5, has no column: its Jacobian is zero)
+
+
+def _landmark_pose_mask(op, fit_pose):
+    if fit_pose is True:
+        return 0x5F
+    if fit_pose is False or fit_pose is None:
+        return 0
+    if isinstance(fit_pose, str):
+        fit_pose = (fit_pose,)
+    mask = 0
+    for name in fit_pose:
+        if name not in LANDMARK_POSE_BITS:
+            raise ValueError("%s: fit_pose names come out of %s (got %r)" % (op, " ".join(LANDMARK_POSE_BITS), name))
+        mask |= 1 << LANDMARK_POSE_BITS[name]
+    return mask
+
+
+def _landmark_solve_args(op, params, lbasis, target, weight, ridge, center, damp, fit_pose, fit_coef):
+    """the checked, contiguous arguments of one solver call -> (p_c, t_c, w_c, wb, r_c, c_c, d_c, mask, coef)"""
+    h = _host()
+    _landmark_args(op, lbasis, target, weight)
+    if target is None:
+        raise ValueError("%s: target is required" % op)
+    p_c = h.require_gpu_f32(params.detach(), "params")
+    K, Kt = lbasis.K, lbasis.n_shape + lbasis.n_exp
+    if p_c.dim() != 2 or p_c.shape[1] != 7 + Kt:
+        raise ValueError("%s: params must be [B,%d] (got %s)" % (op, 7 + Kt, tuple(p_c.shape)))
+    B, dev = int(p_c.shape[0]), p_c.device
+    if lbasis.device != dev:
+        raise ValueError("%s: the basis image is on %s, params on %s" % (op, lbasis.device, dev))
+    t_c = h.require_gpu_f32(target.detach(), "target")
+    if tuple(t_c.shape) != (B, K, 2) or t_c.device != dev:
+        raise ValueError("%s: target must be [%d,%d,2] on %s (got %s)" % (op, B, K, dev, tuple(t_c.shape)))
+    w_c, wb = None, 0
+    if weight is not None:
+        w_c = h.require_gpu_f32(weight.detach(), "weight")
+        if tuple(w_c.shape) not in ((K,), (B, K)) or w_c.device != dev:
+            raise ValueError("%s: weight must be [%d] or [%d,%d] on %s" % (op, K, B, K, dev))
+        wb = 1 if w_c.dim() == 2 else 0
+    vec = []
+    for name, t in (("ridge", ridge), ("center", center)):
+        if t is not None:
+            t = h.require_gpu_f32(t.detach(), name)
+            if tuple(t.shape) != (Kt,) or t.device != dev:
+                raise ValueError("%s: %s must be [%d] on %s (got %s)" % (op, name, Kt, dev, tuple(t.shape)))
+        vec.append(t)
+    d_c = None
+    if damp is not None:
+        if not isinstance(damp, torch.Tensor) or damp.dtype != torch.float64 or tuple(damp.shape) != (B,) or damp.device != dev:
+            raise ValueError("%s: damp must be a float64 tensor [%d] on %s" % (op, B, dev))
+        d_c = damp.detach().contiguous()
+    mask = _landmark_pose_mask(op, fit_pose)
+    coef = bool(fit_coef) and Kt > 0
+    if mask == 0 and not coef:
+        raise ValueError("%s: nothing to fit (fit_pose is empty and fit_coef is off or the model has no coefficients)" % op)
+    return p_c, t_c, w_c, wb, vec[0], vec[1], d_c, mask, coef
+
+
+def _landmark_solve_call(args, lbasis, im_size):
+    h = _host()
+    L = h.lib()
+    p_c, t_c, w_c, wb, r_c, c_c, d_c, mask, coef = args
+    B, dev = int(p_c.shape[0]), p_c.device
+    make = torch.empty if B else torch.zeros
+    delta = make(tuple(p_c.shape), dtype=torch.float64, device=dev)
+    cost = make((B, 2), dtype=torch.float64, device=dev)
+    ok = make((B,), dtype=torch.int32, device=dev)
+    if B:
+        nws = L.fr_landmark_solve_workspace_bytes(B, lbasis.n_shape, lbasis.n_exp) if coef else 0
+        # (the workspace is dead once the one launch is enqueued: one per stream, under the pool's hold)
+        with torch.cuda.device(dev), _KINDS_POOL.hold("landmark_solve", dev, nws) as ent:
+            rc = L.fr_landmark_solve_step(h.ptr(p_c), h.ptr(lbasis.image), lbasis.nbytes, h.ptr(t_c), h.ptr(w_c), wb, h.ptr(r_c),
+                                          h.ptr(c_c), h.ptr(d_c), mask, int(coef), B, lbasis.K, lbasis.n_shape, lbasis.n_exp,
+                                          float(im_size), h.ptr(delta), h.ptr(cost), h.ptr(ok), h.ptr(ent.buf), ent.nbytes,
+                                          h.stream_ptr(dev))
+        h.check(rc, "fr_landmark_solve_step")
+    return delta, cost, ok
+
+
+def landmark_solve_step(params, lbasis, target, weight=None, ridge=None, center=None, damp=None, fit_pose=True, fit_coef=False,
+                        im_size=200):
+    """One damped Gauss-Newton step of the landmark term per face (fr_landmark_solve_step; include/fr_hotpath.h, "landmark
+    solver"): with r the residuals of landmark_sse, J their Jacobian in the fitted columns, H = J^T W J + diag(ridge), g = J^T W r +
+    ridge (a - center) and D = diag(J^T W J), it solves (H + damp_b D) delta = -g by Cholesky, in float64, in one launch.
+    -> (delta [B, 7 + Kt] float64, +0 in the columns that are not fitted; cost [B,2] float64 = (F at params, the quadratic model's
+    prediction at params + delta) with F = sse + [fit_coef] sum ridge (a - center)^2; ok [B] int32).  A face whose system is not
+    positive definite or not finite (f = 0 with an angle fitted, no landmark of weight > 0, a non-finite input) reports ok = 0, a
+    zero step and cost[b,1] = cost[b,0], and changes no other face.
+    target [B,K,2], weight None / [K] / [B,K] as in landmark_sse; ridge, center None or fp32 [Kt] (the coefficients' prior);
+    damp None or float64 [B]; fit_pose True (the six columns phi gamma theta tx ty f -- tz has no column), False, or an iterable
+    of those names; fit_coef: fit the Kt coefficients as well.  ValueError for a shape, device or name that does not fit, and when
+    nothing is fitted.  Runs outside autograd, on the current stream; the workspace of a fit_coef call comes from the stream's pool."""
+    args = _landmark_solve_args("landmark_solve_step", params, lbasis, target, weight, ridge, center, damp, fit_pose, fit_coef)
+    with torch.no_grad():
+        return _landmark_solve_call(args, lbasis, im_size)
+
+
+def landmark_fit(params, lbasis, target, weight=None, ridge=None, center=None, iters=10, damp0=1e-3, fit_pose=True, fit_coef=False,
+                 im_size=200):
+    """Levenberg-Marquardt on the landmark term from `params`: `iters` times landmark_solve_step, the candidate
+    fl32(params.double() + delta), its F from landmark_sse plus the prior in float64, and per face: where ok and F_new < F_old the
+    candidate is taken and damp divided by 3 (floor 1e-9), else the face stays and damp is multiplied by 4 (cap 1e9).  Everything
+    stays on the device (torch.where; no host synchronisation).  -> (params_fitted [B, 7 + Kt] fp32, info) with info["cost"]
+    [iters + 1, B] float64 (F before the first step, then after each iteration: non-increasing), info["accepted"] [iters, B] bool
+    and info["damp"] [B] float64 (the damping the next step would use).  Arguments as landmark_solve_step; damp0 > 0 is the
+    initial damping of every face.  Runs outside autograd, on the current stream."""
+    iters = int(iters)
+    if iters < 0 or not float(damp0) >= 0.0:
+        raise ValueError("landmark_fit: iters and damp0 must not be negative")
+    args = _landmark_solve_args("landmark_fit", params, lbasis, target, weight, ridge, center, None, fit_pose, fit_coef)
+    p_c, t_c, w_c, wb, r_c, c_c, _, mask, coef = args
+    B, dev = int(p_c.shape[0]), p_c.device
+    with torch.no_grad():
+        r64 = r_c.double() if coef and r_c is not None else None
+        c64 = c_c.double() if r64 is not None and c_c is not None else None
+
+        def F_of(p):
+            F = landmark_sse(p, lbasis, t_c, w_c, im_size=im_size)
+            if r64 is not None:
+                d = p[:, 7:].double() if c64 is None else p[:, 7:].double() - c64
+                F = F + (r64 * d * d).sum(dim=1)
+            return F
+        cur = p_c.clone()
+        damp = torch.full((B,), float(damp0), dtype=torch.float64, device=dev)
+        three = torch.full((B,), 3.0, dtype=torch.float64, device=dev)   # (a tensor: torch divides by a Python scalar through its reciprocal)
+        F = F_of(cur)
+        costs, accepted = [F], []
+        for _ in range(iters):
+            delta, _, ok = _landmark_solve_call((cur, t_c, w_c, wb, r_c, c_c, damp, mask, coef), lbasis, im_size)
+            cand = (cur.double() + delta).float()
+            F_new = F_of(cand)
+            acc = (ok != 0) & (F_new < F)
+            cur = torch.where(acc[:, None], cand, cur)
+            F = torch.where(acc, F_new, F)
+            damp = torch.where(acc, (damp / three).clamp_min(1e-9), (damp * 4.0).clamp_max(1e9))
+            costs.append(F)
+            accepted.append(acc)
+        info = {"cost": torch.stack(costs), "damp": damp,
+                "accepted": torch.stack(accepted) if accepted else torch.zeros((0, B), dtype=torch.bool, device=dev)}
+    return cur, info
+
+
 def rendering_layer_fused(ver, tri, texture, im_gray, normal_grad=False):
     """One-pass rendering layer: returns (net_input [B,H,W,7] = [mask*im | pncc | normal],
     depth_img, raw depth, tri_ind).  Raises NotImplementedError for shapes only the fallback rasteriser covers.

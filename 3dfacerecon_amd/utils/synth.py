@@ -129,6 +129,17 @@ def landmark_ids(assets, K=68, seed=4567):
     return np.sort(np.random.RandomState(int(seed)).permutation(N)[:K]).astype(np.int64)
 
 
+def coefficient_prior(n_shape, n_exp, sigma_px=1.0):
+    """(ridge, center), fp32 [n_shape + n_exp]: get_random_params' coefficient distributions as the quadratic prior of a
+    least-squares term whose residuals have the standard deviation sigma_px -- ridge_j = sigma_px^2 / var_j around the mean, with
+    shape in U[0, 1e4] (mean 5e3, variance 1e8 / 12) and expression in U[-1.5, 1.5] (mean 0, variance 0.75).  What
+    rendering_layer/ops.py::landmark_fit takes as ridge and center."""
+    s2 = float(sigma_px) ** 2
+    ridge = np.concatenate([np.full(n_shape, s2 * 12.0 / 1e8), np.full(n_exp, s2 / 0.75)]).astype(np.float32)
+    center = np.concatenate([np.full(n_shape, 5e3), np.zeros(n_exp)]).astype(np.float32)
+    return ridge, center
+
+
 def get_random_params(im_size, num_shape_param, num_exp_param, beta=1.0, rand=None):
     """The reference sampler (rendering_layer/sample_test.py:23-38 == prepare_data/get_random_params.m:1-11):
     phi in U[-75,45] deg, gamma in U[-90,90] deg, theta in U[-30,30] deg (radians), f in U[0,1e-3],

@@ -10,6 +10,7 @@ HIP backward).
     python examples/photo_fit.py --small --colour        # the picture in colour: RGB albedo, second-order lighting per channel
     python examples/photo_fit.py --small --fit-pose --landmarks 68                    # ... with the landmark term beside the two
     python examples/photo_fit.py --small --fit-pose --landmarks 68 --landmarks-only   # pose from the landmarks alone: no render
+    python examples/photo_fit.py --small --fit-pose --landmarks 68 --landmarks-only --landmark-init 6 --steps 0   # ... by the solver
 
 A batch of pipeline.SynthBatches gives the picture and its ground truth (parameters, light, alpha).  The fit starts from the truth
 perturbed (light by --light-noise, alpha by --alpha-noise; with --fit-shape the coefficients from zero) and runs Adam.  By default the
@@ -21,7 +22,10 @@ the projections of K vertices (utils/synth.py::landmark_ids; pipeline.SynthBatch
 (nets/losses.py::landmark_loss, --landmark-lambda) holds the fit's own projections of those vertices to them: it reads a compact image
 of their basis rows, not the dense basis.  --landmarks-only fits the pose (and with --fit-shape the coefficients) to that term alone
 -- the usual first stage of a fit to a real picture -- with no render and no dense decode in the loop; light and alpha then stay where
-they start.  Prints ONE JSON record: the first and last loss and the parameter errors (RMS against the ground truth) before and after.
+they start.  --landmark-init [ITERS] first runs the landmark solver (rendering_layer/ops.py::landmark_fit: damped Gauss-Newton
+steps, scale-free, a handful of iterations) from the perturbed start, and Adam goes on from where it ends; with --fit-shape the
+solver also fits the coefficients under the sampler's own prior (utils/synth.py::coefficient_prior).  --steps 0 gives the solver
+alone.  Prints ONE JSON record: the first and last loss and the parameter errors (RMS against the ground truth) before and after.
 """
 import argparse
 import importlib
@@ -64,6 +68,11 @@ def build_parser():
     ap.add_argument("--landmark-lambda", type=float, default=1.0)
     ap.add_argument("--landmarks-only", action="store_true", help="fit to the landmark term alone (needs --landmarks and --fit-pose or "
                                                                   "--fit-shape): no render in the loop")
+    ap.add_argument("--landmark-init", type=int, nargs="?", const=10, default=0, metavar="ITERS",
+                    help="run ITERS (default 10) Levenberg-Marquardt iterations on the landmark term before the Adam loop (needs "
+                         "--landmarks and --fit-pose or --fit-shape)")
+    ap.add_argument("--landmark-sigma", type=float, default=0.5, help="with --landmark-init and --fit-shape: the landmark noise, in "
+                                                                      "pixels, that scales the coefficients' prior")
     return ap
 
 
@@ -110,6 +119,8 @@ def main():
         raise SystemExit("--landmarks-only needs --landmarks K and something to fit: --fit-pose or --fit-shape")
     if args.landmarks > 0 and not (args.fit_pose or args.fit_shape):
         raise SystemExit("--landmarks needs --fit-pose or --fit-shape: with the geometry fixed the term is a constant")
+    if args.landmark_init and not (args.landmarks > 0 and (args.fit_pose or args.fit_shape)):
+        raise SystemExit("--landmark-init needs --landmarks K and something to fit: --fit-pose or --fit-shape")
     lm_idx = synth.landmark_ids(A, args.landmarks) if args.landmarks > 0 else None
     kw = {"colour": True} if args.colour else {}
     if lm_idx is not None:
@@ -175,6 +186,24 @@ def main():
         before.update(pose_errors())
     if coef is not None:
         before["coef_rms_scaled"] = rms(coef, coef_gt / scale)
+    init = None
+    if args.landmark_init:
+        ridge = center = None
+        if coef is not None:
+            ridge, center = (torch.as_tensor(t, device=dev) for t in synth.coefficient_prior(ns, face.ndim_exp, args.landmark_sigma))
+        with torch.no_grad():
+            fitted, info = face.landmark_fit(params_now(), lm_idx, b["landmarks"], ridge=ridge, center=center, iters=args.landmark_init,
+                                             fit_pose=pose is not None, fit_coef=coef is not None)
+            if pose is not None:
+                pose0 = fitted[:, :n0].clone()      # (pose stays 0: Adam goes on from the solver's pose, in the same units)
+            if coef is not None:
+                coef.copy_(fitted[:, n0:] / scale)
+        init = {"iters": int(args.landmark_init), "cost_first": float(info["cost"][0].sum()), "cost_last": float(info["cost"][-1].sum()),
+                "accepted": int(info["accepted"].sum())}
+        if pose is not None:
+            init.update(pose_errors())
+        if coef is not None:
+            init["coef_rms_scaled"] = rms(coef, coef_gt / scale)
     first, last = descend(opt, loss_of, args.steps)
     after = {"light_rms": rms(light, light_gt), "alpha_rms": rms(alpha, alpha_gt)}
     if coef is not None:
@@ -183,7 +212,7 @@ def main():
         after.update(pose_errors())
     print(json.dumps({"program": "photo_fit", "faces": B, "im_size": S, "steps": args.steps, "lr": args.lr, "fit_shape": bool(args.fit_shape),
                       "fit_pose": bool(args.fit_pose), "colour": bool(args.colour), "landmarks": int(args.landmarks),
-                      "landmarks_only": bool(args.landmarks_only),
+                      "landmarks_only": bool(args.landmarks_only), "landmark_init": init,
                       "first": first, "last": last, "ratio": last / first if first else None, "errors_before": before,
                       "errors_after": after, "finite": bool(torch.isfinite(light).all() and torch.isfinite(alpha).all())}))
 

@@ -1394,6 +1394,71 @@ int fr_landmark_backward(const float* grad_points, const double* grad_sse, const
                          int B, int K, int n_shape, int n_exp, float im_size, float* grad_params, float* grad_R, int pose_grad,
                          void* stream);
 
+/* ---- landmark solver ----------------------------------------------------------------------------------------
+ * One damped Gauss-Newton (Levenberg-Marquardt) step of the landmark term per face, in one launch (csrc/fr_landmark_solve.hip): the
+ * term is a small nonlinear least-squares problem -- 2 K residuals, at most 6 + Kt unknowns -- whose parameters live on scales from
+ * 1e-3 (f) to 1e4 (shape), which a scale-free second-order step covers in a handful of iterations.  Opt-in; no reference counterpart.
+ *
+ * Inputs per face b.  params [B, 7 + Kt] fp32 in the layout [phi, gamma, theta, tx, ty, tz, f | shape | exp]; the image of
+ * fr_landmark_basis_build; target [B,K,2] fp32; weight NULL, [K] or [B,K] as in fr_landmark_forward (a landmark of weight 0 is
+ * skipped entirely and its target is never read: it may be NaN); ridge [Kt] fp32 >= 0 or NULL (= 0); center [Kt] fp32 or NULL (= 0);
+ * damp [B] float64 >= 0 or NULL (= 0), read from the device; pose_mask: bit i set = pose column i is fitted (bit 5, tz, is refused:
+ * its column is identically zero; tz is not read); fit_coef 0 or 1: the Kt coefficients are fitted.  At least one column is fitted.
+ * The unknowns, P of them, are the fitted pose columns in parameter order, then the coefficients.
+ *
+ * The mathematics, in float64 on the widened fp32 inputs, every product and every sum rounded on its own (no contraction):
+ *     v, R, Rv_i, x, y  exactly the forward's (above): x = f Rv_0 + tx, y = (im_size - (f Rv_1 + ty)) - 1, before any fp32 rounding;
+ *     residual rows     row 2 k:  r = x - target_x;   row 2 k + 1:  r = y - target_y;
+ *     F                 = sse + [fit_coef] prior;  sse the forward's sum, bit for bit;  prior = sum over j ascending, from +0, of
+ *                         ridge_j ((a_j - center_j) (a_j - center_j));
+ *     J                 coefficient j: (f (R_0 . U_kj), -(f (R_1 . U_kj))), R_i . U = (R_i0 U_0 + R_i1 U_1) + R_i2 U_2;
+ *                       tx: (1, 0);  ty: (0, -1);  f: (Rv_0, -Rv_1);
+ *                       angle a: (f (dR_a v)_0, -(f (dR_a v)_1)) with the dR_a of the backward (above) and the same 3-term dots;
+ *                       a landmark of weight 0 has rows and residuals of exact +0;
+ *     H = J^T W J + diag(ridge) (the ridge on the coefficient block only);   g = J^T W r + ridge (a - center);   D = diag(J^T W J);
+ *     (H + damp_b D) delta = -g  by Cholesky.
+ * Summation orders.  Every sum that touches a pose column, g and D are sequential float64 sums from +0 over the rows ascending: the
+ * term of (J^T W J)_ij, i >= j in the order of the unknowns, is (w J[row][i]) J[row][j]; that of (J^T W r)_i is (w J[row][i]) r[row];
+ * g_j = that sum + ridge_j (a_j - center_j).  The coefficient-coefficient block is formed on v_mfma_f64_16x16x4_f64, lower triangle
+ * only, operand A = J[row][i], operand B = w J[row][j]: 16 rows (8 landmarks) at a time ascending, four rows per instruction ascending,
+ * accumulated in registers from +0 -- its bits are a function of (K, Kt) and the inputs, not of B or the device; how the instruction
+ * rounds inside its four products is the hardware's.  H_jj = (J^T W J)_jj + ridge_j;  A_ii = H_ii + damp D_ii.
+ * Cholesky, on the packed lower triangle with -g as an extra row P: for c ascending, the pivot d = A_cc must be positive and finite;
+ * l = sqrt(d); A_ic = A_ic / l for i = c + 1 .. P; A_ij = A_ij - A_ic A_jc for c < j <= i <= P (no (P, P)).  Row P ends as
+ * y = L^-1 (-g).  Then for c descending: delta_c = y_c / l_c;  y_j = y_j - L_cj delta_c for j < c.
+ * Prediction: q_i = sum over j ascending of H_ij delta_j;  e_i = delta_i (2 g_i + q_i);  cost_1 = F + (sum over i ascending of e_i).
+ *
+ * Outputs, every element written on every call that launches: delta [B, 7 + Kt] float64 (columns that are not fitted are +0);
+ * cost [B,2] float64 = (F at params, the quadratic model's prediction F + 2 g.delta + delta.H delta); ok [B] int32.  A face whose
+ * factorisation meets a pivot that is not positive and finite, or whose F, prediction or delta is not finite, reports ok = 0,
+ * delta = +0 and cost[b][1] = cost[b][0]; no other face changes by a bit.  That covers f = 0 with an angle fitted, all weights 0 with
+ * a pose column fitted, and any non-finite input that is read.  A face's outputs are a function of that face's inputs and of
+ * (K, n_shape, n_exp, pose_mask, fit_coef) alone: not of B, of its place in the batch or of the device.  No atomics.
+ *
+ * Workspace: fit_coef calls only (with Kt > 0; fr_landmark_solve_workspace_bytes, 16-byte aligned; 0 for sizes not served: B < 1, a
+ * negative count, Kt > 256).  Per face, with Pm = 6 + Kt, (2 (Pm (Pm + 1) / 2) + Pm) float64 rounded up to even: the augmented
+ * triangle, element (i, j) at i (i + 1) / 2 + j, rows 0 .. P, then at offset Pm (Pm + 1) / 2 + Pm the packed copy of H that the
+ * prediction reads (220 KB + 220 KB at P = 234: more than the 160 KB of LDS, so the factorisation runs in the caller's memory, from the
+ * face's one workgroup, with block barriers between dependent column steps).  A pose-only call forms and solves its system of at most
+ * 6 x 6 in LDS and takes no workspace (NULL is fine).
+ *
+ * Checks, all before any HIP call, in the order of fr_landmark_forward: (1) a negative size, weight_batch or fit_coef outside {0, 1},
+ * a pose_mask with bit 5 or a bit above 6, or nothing to fit (an empty mask without fit_coef, or with Kt == 0) is
+ * FR_ERR_INVALID_ARG; (2) B == 0 or K == 0 is FR_OK with nothing launched and nothing written; (3) a NULL params, target, delta, cost
+ * or ok is FR_ERR_INVALID_ARG; (4) K or Kt outside the landmark limits is FR_ERR_UNSUPPORTED; (5) a missing, short or misaligned
+ * image, then -- for a fit_coef call -- workspace, is FR_ERR_WORKSPACE.  Nothing is allocated or synchronised.
+ * Time: tools/landmark_solve_probe.py (profiles/landmark_solve.json) measures a step at 64 and 32 faces of the full model (199 + 29
+ * coefficients, K = 68) beside the same step in stock torch float64 (einsum Jacobian and normal matrix, linalg.cholesky,
+ * cholesky_solve) in the same run.  MI355X, medians of 6 rounds of 20 calls: the pose-only step about 23 us at either batch against
+ * about 810 us; the step with the coefficients (P = 234) about 1.5 ms against 1.6 - 1.7 ms -- only a tenth faster: it is the latency
+ * of 234 dependent column steps through memory, two block barriers each, not arithmetic (the matrix-core block is a few percent of
+ * it); a panel-blocked factorisation is the next step. */
+size_t fr_landmark_solve_workspace_bytes(int B, int n_shape, int n_exp);
+int fr_landmark_solve_step(const float* params, const void* lbasis, size_t lbasis_bytes, const float* target, const float* weight,
+                           int weight_batch, const float* ridge, const float* center, const double* damp, int pose_mask, int fit_coef,
+                           int B, int K, int n_shape, int n_exp, float im_size, double* delta, double* cost, int* ok, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
