@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libfr_hotpath.so")
 SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_bwd.hip", "fr_render_nbwd.hip",
            "fr_render_tbwd.hip", "fr_sfs.hip", "fr_depth_normals.hip", "fr_geometry.hip", "fr_fine_losses.hip", "fr_depth_interp.hip",
            "fr_albedo_lse.hip", "fr_synth.hip", "fr_photo.hip", "fr_mesh.hip", "fr_coverage.hip", "fr_landmark.hip",
-           "fr_landmark_solve.hip"]
+           "fr_landmark_solve.hip", "fr_landmark_contour.hip"]
 HEADERS = [os.path.join(_CSRC, "fr_common.h"), os.path.join(_CSRC, "fr_decode_shared.h"), os.path.join(_CSRC, "fr_sfs_pinv.h"),
            os.path.join(_CSRC, "fr_owner_scatter.h"), os.path.join(_CSRC, "fr_shade.h"), os.path.join(_CSRC, "fr_landmark_shared.h"),
            os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
@@ -227,6 +227,7 @@ SIGNATURES = {
     "fr_landmark_backward":                           "i:ppppzpppiiiiifppip",
     "fr_landmark_solve_workspace_bytes":              "z:iii",
     "fr_landmark_solve_step":                         "i:ppzppipppiiiiiifppppzp",
+    "fr_landmark_contour_select":                     "i:ppzpppippipiiiiiiifppppp",
     "fr_debug_render_geom":                           "v:iiiiiI",
     "fr_debug_decode_bwd_geom":                       "v:iiiiI",
     "fr_debug_decode_geom":                           "i:iiiiiI",

@@ -260,16 +260,35 @@ def silhouette_loss(face_net, vertices_proj, target_mask):
     return F.mse_loss(cov, target)
 
 
-def landmark_loss(face_net, pred_params, idx, target, weight=None, pose_grad=True):
+def landmark_loss(face_net, pred_params, idx, target, weight=None, pose_grad=True, lines=None, line_target=None, line_weight=None):
     """The landmark term: the mean over faces of sse_b / max(sum_k w_k, 1), with sse_b the weighted squared pixel distance between
     the projections of the vertices `idx` under pred_params ((B,d) or (B,1,1,d)) and target [B,K,2] (x, y; a constant).  weight:
     None (= 1), [K] or [B,K] (e.g. the `landmark_visible` of pipeline.SynthBatches); a landmark of weight 0 is skipped entirely and
     may carry a NaN target.  FaceRecNet.landmark_basis(idx) -> rendering_layer/ops.py::landmark_sse: the dense basis is not read and
     no [B,3,N] tensor exists; one launch each way.  The gradient reaches pred_params -- the angles too unless pose_grad=False.
-    -> a 0-dim float64 tensor; each rank takes the mean over its own faces (no collective)."""
+    -> a 0-dim float64 tensor; each rank takes the mean over its own faces (no collective).
+    lines [C,M] with line_target [B,C,2] (default None: the code path and every bit are today's; one without the other is a
+    ValueError) and line_weight (None = 1, [C] or [B,C]): contour landmarks that slide.  Each line of candidate vertex ids is held to
+    its 2D point through the candidate that projects nearest to it under pred_params (FaceRecNet.landmark_contour_basis(idx, lines)
+    -> rendering_layer/ops.py::landmark_contour_sse); the selection is a constant of the step.  idx, target and weight then belong
+    to the fixed landmarks (idx may be empty with target None), and the divisor is the sum of both kinds' weights."""
     fn = face_net
     B = pred_params.shape[0]
     pred = pred_params.reshape(B, fn.ndim)
+    if (lines is None) != (line_target is None) or (lines is None and line_weight is not None):
+        raise ValueError("lines and line_target go together: the candidate vertices of every contour point and the 2D points")
+
+    def weight_sum(w, count, dev):
+        if w is None:
+            return torch.full((B,), float(count), dtype=torch.float64, device=dev)
+        w = w.detach().to(device=dev, dtype=torch.float64)
+        return w.sum().expand(B) if w.dim() == 1 else w.sum(dim=1)
+    if lines is not None:
+        lb = fn.landmark_contour_basis(idx, lines)
+        sse = _ops().landmark_contour_sse(pred, lb, line_target, line_weight=line_weight, fixed_target=target, fixed_weight=weight,
+                                          im_size=fn.im_size, pose_grad=pose_grad)
+        wsum = weight_sum(weight, lb.n_fixed, sse.device) + weight_sum(line_weight, lb.C, sse.device)
+        return (sse / wsum.clamp_min(1.0)).mean()
     lb = fn.landmark_basis(idx)
     sse = _ops().landmark_sse(pred, lb, target, weight=weight, im_size=fn.im_size, pose_grad=pose_grad)
     if weight is None:
@@ -291,7 +310,8 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
              gather_sfs=False, sfs_normal_grad=False, sfs_fused=False, sfs_rcond=1e-15, sfs_tex_grad=False,
              sfs_fused_gather=False, sfs_fine=False, fine_fused=False, sfs_alpha_lse=False, sfs_alpha_ridge=1e-6,
              silhouette_mask=None, lambda_silhouette=1.0,
-             landmark_target=None, landmark_idx=None, landmark_weight=None, lambda_landmark=1.0, photo_target_rgb=None,
+             landmark_target=None, landmark_idx=None, landmark_weight=None, lambda_landmark=1.0, landmark_lines=None,
+             landmark_line_target=None, landmark_line_weight=None, photo_target_rgb=None,
              photo_light=None, photo_alpha=None, photo_weight=None, photo_gain=1.0, photo_offset=0.0, lambda_photo=1.0,
              geometry_gram=False):
     """dict of the reference's six scalars (network.py:336-378).  pred_params / params_label: (B,d) or (B,1,1,d).
@@ -328,10 +348,15 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     landmark_target [B,K,2] with landmark_idx (K vertex ids) (default None: the term is absent, the dict and every bit are today's;
     one without the other is a ValueError): adds losses['landmark_loss'] = landmark_loss(face_net, pred_params, landmark_idx,
     landmark_target, landmark_weight) and lambda_landmark times it to total_loss.  Its gradient reaches pred_params directly, the
-    angles included; it does not go through vertices_proj."""
+    angles included; it does not go through vertices_proj.
+    landmark_lines [C,M] with landmark_line_target [B,C,2] and landmark_line_weight (default None: absent; one of the first two
+    without the other is a ValueError): the lines / line_target / line_weight of landmark_loss -- contour landmarks that slide, with
+    or without fixed ones beside them."""
     fn = face_net
     if (landmark_target is None) != (landmark_idx is None):
         raise ValueError("landmark_target and landmark_idx go together: the 2D points and the vertices they belong to")
+    if (landmark_lines is None) != (landmark_line_target is None) or (landmark_lines is None and landmark_line_weight is not None):
+        raise ValueError("landmark_lines and landmark_line_target go together: the candidate vertices and the 2D points")
     if (photo_light is None) != (photo_alpha is None):
         raise ValueError("photo_light and photo_alpha go together: the photometric term needs the lighting and the albedo coefficients")
     if photo_target_rgb is not None and photo_light is None:
@@ -377,7 +402,12 @@ def get_loss(face_net, pred_params, params_label, im_gray, vertices_proj, coarse
     if silhouette_mask is not None:
         losses['silhouette_loss'] = silhouette_loss(fn, vertices_proj, silhouette_mask)
         losses['total_loss'] = losses['total_loss'] + (lambda_silhouette * losses['silhouette_loss']).to(losses['total_loss'].dtype)
-    if landmark_target is not None:
+    if landmark_lines is not None:
+        losses['landmark_loss'] = landmark_loss(fn, pred_params, landmark_idx, landmark_target, weight=landmark_weight,
+                                                lines=landmark_lines, line_target=landmark_line_target,
+                                                line_weight=landmark_line_weight)
+        losses['total_loss'] = losses['total_loss'] + (lambda_landmark * losses['landmark_loss']).to(losses['total_loss'].dtype)
+    elif landmark_target is not None:
         losses['landmark_loss'] = landmark_loss(fn, pred_params, landmark_idx, landmark_target, weight=landmark_weight)
         losses['total_loss'] = losses['total_loss'] + (lambda_landmark * losses['landmark_loss']).to(losses['total_loss'].dtype)
     return losses

@@ -447,6 +447,23 @@ class FaceRecNet:
                 self._landmark_bases[ids] = lb
             return lb
 
+    def landmark_contour_basis(self, fixed_idx, lines):
+        """The compact image over the fixed ids `fixed_idx` (may be empty or None) followed by the candidate lines `lines` [C,M]
+        (rendering_layer/ops.py::landmark_contour_basis: a LandmarkBasis that also carries n_fixed, C, M), built on first use per
+        (ids, lines) and cached beside landmark_basis()'s.  ValueError as there."""
+        fixed = () if fixed_idx is None else tuple(int(i) for i in (fixed_idx.reshape(-1).tolist() if hasattr(fixed_idx, "reshape")
+                                                                    else fixed_idx))
+        rows = lines.tolist() if hasattr(lines, "tolist") else [list(r) if hasattr(r, "__iter__") else r for r in lines]
+        key = ("contour", fixed, tuple(tuple(r) if isinstance(r, list) else r for r in rows))
+        with self._gram_lock:
+            lb = self._landmark_bases.get(key)
+            if lb is None:
+                with torch.cuda.device(self.device):
+                    lb = _ops().landmark_contour_basis(self.mu, self.pc_shape, self.pc_exp, list(fixed), rows)
+                _publish(self.device)
+                self._landmark_bases[key] = lb
+            return lb
+
     def landmarks(self, pred_params, idx, R=None, pose_grad=False):
         """(B,1,1,d) or (B,d) parameters -> the projections [B,3,K] of the vertices `idx`: what vertices_transform(pred_params)
         [:, :, idx] holds, to the rounding of an fp32 chain, from the compact image of landmark_basis(idx) alone -- float64
@@ -462,10 +479,12 @@ class FaceRecNet:
         return _ops().landmarks(p, self.landmark_basis(idx), R=R, im_size=self.im_size, pose_grad=pose_grad)
 
     def landmark_fit(self, pred_params, idx_or_lbasis, target, weight=None, ridge=None, center=None, iters=10, damp0=1e-3,
-                     fit_pose=True, fit_coef=False):
+                     fit_pose=True, fit_coef=False, line_target=None, line_weight=None, rule="nearest", line_dir=None):
         """(B,1,1,d) or (B,d) parameters -> (the parameters [B,d] after `iters` Levenberg-Marquardt iterations on the landmark
         term, info): rendering_layer/ops.py::landmark_fit at this model's im_size, over the cached landmark_basis(idx) -- or over a
-        LandmarkBasis handed in as it is.  target [B,K,2], weight, ridge, center, fit_pose and fit_coef as there."""
+        LandmarkBasis handed in as it is.  target [B,K,2], weight, ridge, center, fit_pose and fit_coef as there.  line_target,
+        line_weight, rule and line_dir (default: absent, today's path) go with a landmark_contour_basis(): contour landmarks that
+        are re-selected at every iteration, as there."""
         p = pred_params
         if p.dim() == 4:
             p = p.reshape(p.shape[0], p.shape[-1])
@@ -473,7 +492,8 @@ class FaceRecNet:
             raise ValueError("pred_params must be (B,1,1,%d) or (B,%d)" % (self.ndim, self.ndim))
         lb = idx_or_lbasis if hasattr(idx_or_lbasis, "image") else self.landmark_basis(idx_or_lbasis)
         return _ops().landmark_fit(p, lb, target, weight=weight, ridge=ridge, center=center, iters=iters, damp0=damp0,
-                                   fit_pose=fit_pose, fit_coef=fit_coef, im_size=self.im_size)
+                                   fit_pose=fit_pose, fit_coef=fit_coef, im_size=self.im_size, line_target=line_target,
+                                   line_weight=line_weight, rule=rule, line_dir=line_dir)
 
     def fine_mesh(self, vertices_proj, pred_depth_map, coarse_depth_map, with_normals=True):
         """The fine depth map taken back to the mesh: {"vertices": [B,3,N] fp32, "state": uint8 [B,N], "normals": [B,3,N] fp32 or

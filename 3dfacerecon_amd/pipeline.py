@@ -372,6 +372,10 @@ class _SynthSlot:
         if owner.landmark_basis is not None:
             self.landmarks = torch.empty((B, owner.landmark_basis.K, 2), **f32)
             self.landmark_visible = torch.empty((B, owner.landmark_basis.K), **f32)
+        self.contour_landmarks = self.contour_sel = None
+        if owner.contour_basis is not None:
+            self.contour_landmarks = torch.empty((B, owner.contour_basis.C, 2), **f32)
+            self.contour_sel = torch.empty((B, owner.contour_basis.C), dtype=torch.int32, device=owner.device)
         self.first_face = None
 
     def batch(self):
@@ -381,6 +385,8 @@ class _SynthSlot:
             out.update(im_rgb=self.im_rgb, light=self.light_rgb)
         if self.landmarks is not None:
             out.update(landmarks=self.landmarks, landmark_visible=self.landmark_visible)
+        if self.contour_landmarks is not None:
+            out.update(contour_landmarks=self.contour_landmarks, contour_sel=self.contour_sel)
         return out
 
 
@@ -409,10 +415,15 @@ class SynthBatches:
     landmarks=idx (default None: every bit is today's stream): K vertex ids.  A batch then also carries, made on the slot's stream,
     "landmarks" [B,K,2] -- x and y of the sparse forward of its own parameters (FaceRecNet.landmarks: the compact image, not the
     dense decode) -- and "landmark_visible" [B,K] fp32, 1.0 where rendering_layer/ops.py::mesh_visible of the batch's render marks
-    the vertex, else 0.0: ready to be the weight of nets/losses.py::landmark_loss."""
+    the vertex, else 0.0: ready to be the weight of nets/losses.py::landmark_loss.
+    contour_lines=(lines [C,M], line_dir [C,2]) (default None: every existing key keeps its bits), e.g. utils/synth.py::contour_lines:
+    a batch then also carries, made on the slot's stream, "contour_landmarks" [B,C,2] -- per line, x and y of the candidate that is
+    extreme along the line's direction at the batch's own parameters: the face's occluding contour on that line -- and "contour_sel"
+    [B,C] int32, that candidate's position in its line (rendering_layer/ops.py::landmark_contour_select, rule "extreme")."""
 
     def __init__(self, net, batch, seed, slots=2, first_face=0, stride=None, light_ranges=None, alpha_ranges=1.0, background=None,
-                 gain=1.0, offset=0.0, beta=0.7, focal=1e-3, height=None, width=None, landmarks=None, colour=False):
+                 gain=1.0, offset=0.0, beta=0.7, focal=1e-3, height=None, width=None, landmarks=None,
+                 contour_lines=None, colour=False):
         if int(slots) < 1:
             raise ValueError("slots must be >= 1")
         if net.mu_tex is None:
@@ -441,6 +452,11 @@ class SynthBatches:
         if landmarks is not None:
             self.landmark_basis = net.landmark_basis(landmarks)
             self._landmark_idx = torch.tensor(self.landmark_basis.idx, dtype=torch.int64, device=self.device)
+        self.contour_basis = self._contour_dir = None
+        if contour_lines is not None:
+            lines, line_dir = contour_lines
+            self.contour_basis = net.landmark_contour_basis(None, lines)
+            self._contour_dir = torch.as_tensor(line_dir, dtype=torch.float32).to(self.device).contiguous()
         with torch.cuda.device(self.device):
             self.slots = [_SynthSlot(self, torch.cuda.Stream(device=self.device)) for _ in range(int(slots) + 1)]
             torch.cuda.synchronize(self.device)   # every slot's triangle table is packed before anything else touches the slots
@@ -475,6 +491,11 @@ class SynthBatches:
                     sl.landmarks.copy_(points[:, 0:2].transpose(1, 2))
                     visible = ops.mesh_visible(net.tri, sl.plan.tri_ind, net.nvert)
                     sl.landmark_visible.copy_(visible.index_select(1, self._landmark_idx))
+            if self.contour_basis is not None:
+                sel, points, _, _ = ops.landmark_contour_select(sl.params, self.contour_basis, rule="extreme", line_dir=self._contour_dir,
+                                                                im_size=net.im_size)
+                sl.contour_sel.copy_(sel)
+                sl.contour_landmarks.copy_(points)
             sl.event.record(sl.stream)
         self._made = n + 1
 

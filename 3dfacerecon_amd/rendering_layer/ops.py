@@ -1588,11 +1588,14 @@ def photo_loss_rgb(tex_img, normal, tri_ind, light, target, weight=None, gain=1.
 
 class LandmarkBasis:
     """The compact image of K chosen vertices' basis rows (fr_landmark_basis_build; include/fr_hotpath.h, "landmarks"): `image`
-    (uint8, on the device), K, n_shape, n_exp and `idx` (the ids as a tuple of ints).  Built once by landmark_basis()."""
+    (uint8, on the device), K, n_shape, n_exp and `idx` (the ids as a tuple of ints).  Built once by landmark_basis().  An image of
+    landmark_contour_basis() also says how its K ids are laid out: `n_fixed` fixed ids, then `C` lines of `M` candidates (K = n_fixed
+    + C M); a plain image has n_fixed = K and no lines."""
 
-    def __init__(self, image, K, n_shape, n_exp, idx):
+    def __init__(self, image, K, n_shape, n_exp, idx, n_fixed=None, C=0, M=0):
         self.image, self.K, self.n_shape, self.n_exp, self.idx = image, int(K), int(n_shape), int(n_exp), tuple(idx)
         self.device = image.device
+        self.n_fixed, self.C, self.M = int(K) if n_fixed is None else int(n_fixed), int(C), int(M)
 
     @property
     def nbytes(self):
@@ -1733,6 +1736,127 @@ def landmark_sse(params, lbasis, target, weight=None, R=None, im_size=200, pose_
     return _Landmark.apply(params, R, lbasis, target, weight, im_size, bool(pose_grad))[1]
 
 
+LANDMARK_CONTOUR_RULES = {"nearest": 0, "extreme": 1}
+
+
+def landmark_contour_basis(mu, pc_shape, pc_exp, fixed_idx, lines):
+    """landmark_basis() over the ids `fixed_idx` (Kf of them, may be empty) followed by the lines `lines` [C,M] (ints, rectangular;
+    pad a short line by repeating its last id: a repeat can never beat its original): candidate (c, m) is landmark Kf + c M + m.
+    -> a LandmarkBasis that also carries n_fixed, C and M, for landmark_contour_select / _sse and landmark_fit(line_target=).
+    ValueError for lines that are not [C,M] with C, M >= 1, more than 256 lines, an id outside [0, N) or K = Kf + C M over 1024."""
+    fixed = [] if fixed_idx is None else [int(i) for i in (fixed_idx.reshape(-1).tolist() if hasattr(fixed_idx, "reshape")
+                                                            else list(fixed_idx))]
+    rows = lines.tolist() if hasattr(lines, "tolist") else [list(r) if hasattr(r, "__iter__") else r for r in lines]
+    if not rows or any(not isinstance(r, list) or not r or len(r) != len(rows[0]) or any(isinstance(i, list) for i in r) for r in rows):
+        raise ValueError("landmark_contour_basis: lines must be [C,M] vertex ids with C >= 1 and M >= 1, every line of the same length")
+    C, M = len(rows), len(rows[0])
+    if C > 256 or len(fixed) + C * M > 1024:
+        raise ValueError("landmark_contour_basis: needs C <= 256 and Kf + C M <= 1024 (got %d + %d x %d)" % (len(fixed), C, M))
+    ids = fixed + [int(i) for r in rows for i in r]
+    N = int(mu.numel() // 3)
+    bad = [i for i in ids if not 0 <= i < N]
+    if bad:
+        raise ValueError("landmark_contour_basis: vertex id %d is outside [0, %d)" % (bad[0], N))
+    lb = landmark_basis(mu, pc_shape, pc_exp, ids)
+    return LandmarkBasis(lb.image, lb.K, lb.n_shape, lb.n_exp, lb.idx, n_fixed=len(fixed), C=C, M=M)
+
+
+def _landmark_contour_args(op, params, cbasis, line_target, line_weight, fixed_target, fixed_weight, rule, line_dir, R):
+    """the checked, contiguous arguments of one select call -> (p_c, R_c, ft_c, fw_c, fwb, lt_c, lw_c, lwb, ld_c, rule number)"""
+    h = _host()
+    _landmark_args(op, cbasis, None, None)
+    if not all(hasattr(cbasis, k) for k in ("n_fixed", "C", "M")) or cbasis.C < 1:
+        raise ValueError("%s: the basis carries no lines (landmark_contour_basis())" % op)
+    if rule not in LANDMARK_CONTOUR_RULES:
+        raise ValueError("%s: rule is one of %s (got %r)" % (op, " ".join(LANDMARK_CONTOUR_RULES), rule))
+    for name, t in (("line_target", line_target), ("line_weight", line_weight), ("fixed_target", fixed_target),
+                    ("fixed_weight", fixed_weight), ("line_dir", line_dir)):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError("%s: %s is a constant of the term and must not require grad" % (op, name))
+    p_c = h.require_gpu_f32(params.detach(), "params")
+    Kf, C, nd = cbasis.n_fixed, cbasis.C, 7 + cbasis.n_shape + cbasis.n_exp
+    if p_c.dim() != 2 or p_c.shape[1] != nd:
+        raise ValueError("%s: params must be [B,%d] (got %s)" % (op, nd, tuple(p_c.shape)))
+    B, dev = int(p_c.shape[0]), p_c.device
+    if cbasis.device != dev:
+        raise ValueError("%s: the basis image is on %s, params on %s" % (op, cbasis.device, dev))
+
+    def take(t, name, shapes):
+        if t is None:
+            return None
+        t = h.require_gpu_f32(t.detach(), name)
+        if tuple(t.shape) not in shapes or t.device != dev:
+            raise ValueError("%s: %s must be %s on %s (got %s)" % (op, name, " or ".join(str(list(s)) for s in shapes), dev,
+                                                                     tuple(t.shape)))
+        return t
+    R_c = take(R, "R", ((B, 3, 3),))
+    lt_c = take(line_target, "line_target", ((B, C, 2),))
+    lw_c = take(line_weight, "line_weight", ((C,), (B, C)))
+    ft_c = take(fixed_target, "fixed_target", ((B, Kf, 2),))
+    fw_c = take(fixed_weight, "fixed_weight", ((Kf,), (B, Kf)))
+    ld_c = take(line_dir, "line_dir", ((C, 2),))
+    if rule == "nearest" and lt_c is None:
+        raise ValueError("%s: the nearest rule needs line_target [%d,%d,2]" % (op, B, C))
+    if rule == "extreme" and ld_c is None:
+        raise ValueError("%s: the extreme rule needs line_dir [%d,2]" % (op, C))
+    return (p_c, R_c, ft_c, fw_c, 1 if fw_c is not None and fw_c.dim() == 2 else 0, lt_c, lw_c,
+            1 if lw_c is not None and lw_c.dim() == 2 else 0, ld_c, LANDMARK_CONTOUR_RULES[rule])
+
+
+def _landmark_contour_call(args, cbasis, im_size):
+    """-> (sel, line_points, target or None, weight): target only where the call can fill it (line_target, and fixed_target if
+    the basis has fixed ids)"""
+    h = _host()
+    p_c, R_c, ft_c, fw_c, fwb, lt_c, lw_c, lwb, ld_c, rule = args
+    B, dev = int(p_c.shape[0]), p_c.device
+    Kf, C, M, K = cbasis.n_fixed, cbasis.C, cbasis.M, cbasis.K
+    make = torch.empty if B else torch.zeros
+    sel = make((B, C), dtype=torch.int32, device=dev)
+    line_points = make((B, C, 2), dtype=torch.float32, device=dev)
+    target = make((B, K, 2), dtype=torch.float32, device=dev) if lt_c is not None and (Kf == 0 or ft_c is not None) else None
+    weight = make((B, K), dtype=torch.float32, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            rc = h.lib().fr_landmark_contour_select(h.ptr(p_c), h.ptr(cbasis.image), cbasis.nbytes, h.ptr(R_c), h.ptr(ft_c), h.ptr(fw_c),
+                                                    fwb, h.ptr(lt_c), h.ptr(lw_c), lwb, h.ptr(ld_c), rule, B, Kf, C, M, cbasis.n_shape,
+                                                    cbasis.n_exp, float(im_size), h.ptr(sel), h.ptr(line_points), h.ptr(target),
+                                                    h.ptr(weight), h.stream_ptr(dev))
+        h.check(rc, "fr_landmark_contour_select")
+    return sel, line_points, target, weight
+
+
+def landmark_contour_select(params, cbasis, line_target=None, line_weight=None, fixed_target=None, fixed_weight=None, rule="nearest",
+                            line_dir=None, R=None, im_size=200):
+    """Picks one candidate per line and face (fr_landmark_contour_select; include/fr_hotpath.h, "contour landmarks") at params
+    [B, 7 + Kt] over a landmark_contour_basis(): rule "nearest" -- the candidate whose projection lies nearest line_target [B,C,2]
+    -- or "extreme" -- the one furthest along line_dir [C,2], the model's own occluding contour along the line.  Ties go to the
+    lowest m; a line of weight 0 is not looked at and a line without a winner (a NaN face) has sel = -1.
+    -> (sel [B,C] int32, line_points [B,C,2] fp32 the winners' (x, y), target [B,K,2] or None, weight [B,K]): target and weight are
+    what landmark_sse / landmark_solve_step take over the K = Kf + C M landmarks -- fixed_target [B,Kf,2] and fixed_weight (None,
+    [Kf] or [B,Kf]) copied, every candidate of a line carrying the line's target, line_weight (None = 1, [C] or [B,C]) on the winner
+    and +0 on the losers.  target is None where it cannot be filled (no line_target, or fixed ids without fixed_target).  Outside
+    autograd: the selection is a constant.  ValueError for shapes that do not fit, an input that requires grad or an unknown rule.
+    Runs on the current stream."""
+    args = _landmark_contour_args("landmark_contour_select", params, cbasis, line_target, line_weight, fixed_target, fixed_weight,
+                                  rule, line_dir, R)
+    with torch.no_grad():
+        return _landmark_contour_call(args, cbasis, im_size)
+
+
+def landmark_contour_sse(params, cbasis, line_target, line_weight=None, fixed_target=None, fixed_weight=None, rule="nearest",
+                         line_dir=None, R=None, im_size=200, pose_grad=False):
+    """The landmark term with sliding contour correspondences: landmark_contour_select at params, then landmark_sse over its target
+    and weight -> sse [B] float64.  Gradients as in landmark_sse; the selection is a constant, as tri_ind is elsewhere.  line_target
+    is required, and fixed_target where the basis has fixed ids."""
+    op = "landmark_contour_sse"
+    args = _landmark_contour_args(op, params, cbasis, line_target, line_weight, fixed_target, fixed_weight, rule, line_dir, R)
+    if line_target is None or (cbasis.n_fixed > 0 and fixed_target is None):
+        raise ValueError("%s: line_target is required, and fixed_target for a basis with fixed ids" % op)
+    with torch.no_grad():
+        _, _, target, weight = _landmark_contour_call(args, cbasis, im_size)
+    return _Landmark.apply(params, R, cbasis, target, weight, im_size, bool(pose_grad))[1]
+
+
 LANDMARK_POSE_BITS = {"phi": 0, "gamma": 1, "theta": 2, "tx": 3, "ty": 4, "f": 6}   # (tz, bit 5, has no column: its Jacobian is zero)
 
 
@@ -1773,6 +1897,12 @@ def _landmark_solve_args(op, params, lbasis, target, weight, ridge, center, damp
         if tuple(w_c.shape) not in ((K,), (B, K)) or w_c.device != dev:
             raise ValueError("%s: weight must be [%d] or [%d,%d] on %s" % (op, K, B, K, dev))
         wb = 1 if w_c.dim() == 2 else 0
+    return (p_c, t_c, w_c, wb) + _landmark_solve_extras(op, Kt, B, dev, ridge, center, damp, fit_pose, fit_coef)
+
+
+def _landmark_solve_extras(op, Kt, B, dev, ridge, center, damp, fit_pose, fit_coef):
+    """the solver's arguments beside the term's own, checked -> (r_c, c_c, d_c, mask, coef)"""
+    h = _host()
     vec = []
     for name, t in (("ridge", ridge), ("center", center)):
         if t is not None:
@@ -1789,7 +1919,7 @@ def _landmark_solve_args(op, params, lbasis, target, weight, ridge, center, damp
     coef = bool(fit_coef) and Kt > 0
     if mask == 0 and not coef:
         raise ValueError("%s: nothing to fit (fit_pose is empty and fit_coef is off or the model has no coefficients)" % op)
-    return p_c, t_c, w_c, wb, vec[0], vec[1], d_c, mask, coef
+    return vec[0], vec[1], d_c, mask, coef
 
 
 def _landmark_solve_call(args, lbasis, im_size):
@@ -1832,17 +1962,27 @@ def landmark_solve_step(params, lbasis, target, weight=None, ridge=None, center=
 
 
 def landmark_fit(params, lbasis, target, weight=None, ridge=None, center=None, iters=10, damp0=1e-3, fit_pose=True, fit_coef=False,
-                 im_size=200):
+                 im_size=200, line_target=None, line_weight=None, rule="nearest", line_dir=None):
     """Levenberg-Marquardt on the landmark term from `params`: `iters` times landmark_solve_step, the candidate
     fl32(params.double() + delta), its F from landmark_sse plus the prior in float64, and per face: where ok and F_new < F_old the
     candidate is taken and damp divided by 3 (floor 1e-9), else the face stays and damp is multiplied by 4 (cap 1e9).  Everything
     stays on the device (torch.where; no host synchronisation).  -> (params_fitted [B, 7 + Kt] fp32, info) with info["cost"]
     [iters + 1, B] float64 (F before the first step, then after each iteration: non-increasing), info["accepted"] [iters, B] bool
     and info["damp"] [B] float64 (the damping the next step would use).  Arguments as landmark_solve_step; damp0 > 0 is the
-    initial damping of every face.  Runs outside autograd, on the current stream."""
+    initial damping of every face.  Runs outside autograd, on the current stream.
+    line_target [B,C,2] (default None: the code path and every bit are today's) over a landmark_contour_basis(): contour landmarks
+    that slide.  `target` and `weight` then belong to the basis's fixed ids ([B,Kf,2]; None, [Kf] or [B,Kf]; target may be None
+    when there are none), line_weight is None, [C] or [B,C], rule and line_dir as in landmark_contour_select.  At the top of every
+    iteration the candidates are re-selected at the current parameters; F before and after the step is taken under that one
+    selection, then the step is accepted or rejected as above.  info["cost"][0] is F under the first selection and info gains "sel"
+    [iters + 1, B, C] int32: the selection of every iteration, then the one at the fitted parameters.  Under the nearest rule a
+    re-selection can only lower a term, so the cost stays non-increasing.  Still no host synchronisation."""
     iters = int(iters)
     if iters < 0 or not float(damp0) >= 0.0:
         raise ValueError("landmark_fit: iters and damp0 must not be negative")
+    if line_target is not None or line_weight is not None or line_dir is not None or rule != "nearest":
+        return _landmark_fit_contour(params, lbasis, target, weight, ridge, center, iters, damp0, fit_pose, fit_coef, im_size,
+                                     line_target, line_weight, rule, line_dir)
     args = _landmark_solve_args("landmark_fit", params, lbasis, target, weight, ridge, center, None, fit_pose, fit_coef)
     p_c, t_c, w_c, wb, r_c, c_c, _, mask, coef = args
     B, dev = int(p_c.shape[0]), p_c.device
@@ -1872,6 +2012,53 @@ def landmark_fit(params, lbasis, target, weight=None, ridge=None, center=None, i
             costs.append(F)
             accepted.append(acc)
         info = {"cost": torch.stack(costs), "damp": damp,
+                "accepted": torch.stack(accepted) if accepted else torch.zeros((0, B), dtype=torch.bool, device=dev)}
+    return cur, info
+
+
+def _landmark_fit_contour(params, cbasis, target, weight, ridge, center, iters, damp0, fit_pose, fit_coef, im_size, line_target,
+                          line_weight, rule, line_dir):
+    """landmark_fit with sliding contour landmarks: the same loop, with one selection per iteration"""
+    op = "landmark_fit"
+    sargs = _landmark_contour_args(op, params, cbasis, line_target, line_weight, target, weight, rule, line_dir, None)
+    if line_target is None or (cbasis.n_fixed > 0 and target is None):
+        raise ValueError("%s: line_target is required, and target [B,Kf,2] for a basis with fixed ids" % op)
+    p_c = sargs[0]
+    B, dev = int(p_c.shape[0]), p_c.device
+    r_c, c_c, _, mask, coef = _landmark_solve_extras(op, cbasis.n_shape + cbasis.n_exp, B, dev, ridge, center, None, fit_pose, fit_coef)
+    with torch.no_grad():
+        r64 = r_c.double() if coef and r_c is not None else None
+        c64 = c_c.double() if r64 is not None and c_c is not None else None
+
+        def F_of(p, t, w):
+            F = landmark_sse(p, cbasis, t, w, im_size=im_size)
+            if r64 is not None:
+                d = p[:, 7:].double() if c64 is None else p[:, 7:].double() - c64
+                F = F + (r64 * d * d).sum(dim=1)
+            return F
+        cur = p_c.clone()
+        damp = torch.full((B,), float(damp0), dtype=torch.float64, device=dev)
+        three = torch.full((B,), 3.0, dtype=torch.float64, device=dev)
+        costs, accepted, sels = [], [], []
+        for _ in range(iters):
+            sel, _, t_k, w_k = _landmark_contour_call((cur,) + sargs[1:], cbasis, im_size)
+            F = F_of(cur, t_k, w_k)
+            if not costs:
+                costs.append(F)
+            delta, _, ok = _landmark_solve_call((cur, t_k, w_k, 1, r_c, c_c, damp, mask, coef), cbasis, im_size)
+            cand = (cur.double() + delta).float()
+            F_new = F_of(cand, t_k, w_k)
+            acc = (ok != 0) & (F_new < F)
+            cur = torch.where(acc[:, None], cand, cur)
+            damp = torch.where(acc, (damp / three).clamp_min(1e-9), (damp * 4.0).clamp_max(1e9))
+            costs.append(torch.where(acc, F_new, F))
+            accepted.append(acc)
+            sels.append(sel)
+        sel, _, t_k, w_k = _landmark_contour_call((cur,) + sargs[1:], cbasis, im_size)
+        sels.append(sel)
+        if not costs:
+            costs.append(F_of(cur, t_k, w_k))
+        info = {"cost": torch.stack(costs), "damp": damp, "sel": torch.stack(sels),
                 "accepted": torch.stack(accepted) if accepted else torch.zeros((0, B), dtype=torch.bool, device=dev)}
     return cur, info
 

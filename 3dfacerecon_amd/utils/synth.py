@@ -129,6 +129,27 @@ def landmark_ids(assets, K=68, seed=4567):
     return np.sort(np.random.RandomState(int(seed)).permutation(N)[:K]).astype(np.int64)
 
 
+def contour_lines(grid_u, grid_v, per_side, M, stride=1):
+    """Candidate lines for contour landmarks on the UV-grid mesh of make_assets(grid_u, grid_v): -> (lines [2 per_side, M] int64,
+    line_dir [2 per_side, 2] fp32).  The lines are the grid rows iu = round((i + 1) (grid_u - 1) / (per_side + 1)), i = 0 ..
+    per_side - 1 -- evenly spaced, never the first or last row, whose every vertex is rim -- first the per_side left lines, then the
+    right ones in the same row order.  A line's candidates run from the rim inwards every `stride` columns: iv = m stride on the
+    left, grid_v - 1 - m stride on the right, so position 0 is the rim vertex.  line_dir is the picture direction in which the
+    line's occluding contour is extreme: (-1, 0) for left lines, (+1, 0) for right ones.  A function of its arguments alone.  The
+    full mesh needs stride > 1: at a yaw of 0.5 its contour lies more than 32 columns in.  The stand-in for the jaw points of a
+    68-point annotation, which the synthetic assets do not have."""
+    grid_u, grid_v, per_side, M, stride = int(grid_u), int(grid_v), int(per_side), int(M), int(stride)
+    if per_side < 1 or M < 1 or stride < 1 or grid_u < per_side + 2 or 2 * ((M - 1) * stride + 1) > grid_v:
+        raise ValueError("contour_lines: need per_side, M, stride >= 1, grid_u >= per_side + 2 and the two sides' candidates apart "
+                         "(2 ((M - 1) stride + 1) <= grid_v)")
+    rows = [int(round((i + 1) * (grid_u - 1) / (per_side + 1.0))) for i in range(per_side)]
+    cols = np.arange(M, dtype=np.int64) * stride
+    left = np.stack([iu * grid_v + cols for iu in rows])
+    right = np.stack([iu * grid_v + (grid_v - 1 - cols) for iu in rows])
+    line_dir = np.array([[-1.0, 0.0]] * per_side + [[1.0, 0.0]] * per_side, np.float32)
+    return np.concatenate([left, right]).astype(np.int64), line_dir
+
+
 def coefficient_prior(n_shape, n_exp, sigma_px=1.0):
     """(ridge, center), fp32 [n_shape + n_exp]: get_random_params' coefficient distributions as the quadratic prior of a
     least-squares term whose residuals have the standard deviation sigma_px -- ridge_j = sigma_px^2 / var_j around the mean, with

@@ -11,6 +11,8 @@ HIP backward).
     python examples/photo_fit.py --small --fit-pose --landmarks 68                    # ... with the landmark term beside the two
     python examples/photo_fit.py --small --fit-pose --landmarks 68 --landmarks-only   # pose from the landmarks alone: no render
     python examples/photo_fit.py --small --fit-pose --landmarks 68 --landmarks-only --landmark-init 6 --steps 0   # ... by the solver
+    python examples/photo_fit.py --small --fit-pose --landmarks 20 --contour 4 --landmarks-only --landmark-init 10 --steps 0 --yaw 0.5
+                                                         # ... with 4 contour points a side that slide (--contour-fixed: that do not)
 
 A batch of pipeline.SynthBatches gives the picture and its ground truth (parameters, light, alpha).  The fit starts from the truth
 perturbed (light by --light-noise, alpha by --alpha-noise; with --fit-shape the coefficients from zero) and runs Adam.  By default the
@@ -25,7 +27,11 @@ of their basis rows, not the dense basis.  --landmarks-only fits the pose (and w
 they start.  --landmark-init [ITERS] first runs the landmark solver (rendering_layer/ops.py::landmark_fit: damped Gauss-Newton
 steps, scale-free, a handful of iterations) from the perturbed start, and Adam goes on from where it ends; with --fit-shape the
 solver also fits the coefficients under the sampler's own prior (utils/synth.py::coefficient_prior).  --steps 0 gives the solver
-alone.  Prints ONE JSON record: the first and last loss and the parameter errors (RMS against the ground truth) before and after.
+alone.  --contour PER_SIDE adds PER_SIDE contour landmarks a side (utils/synth.py::contour_lines): each is a line of candidate vertices
+from the rim inwards, the batch carries the face's occluding contour on every line, and the term and the solver hold each point to
+the candidate that lies nearest under the current parameters -- the correspondence slides with the pose, as the jaw points of a
+68-point annotation do.  --contour-fixed keeps the rim vertex instead, for the comparison; --yaw sets the truth's yaw.  Prints ONE
+JSON record: the first and last loss and the parameter errors (RMS against the ground truth) before and after.
 """
 import argparse
 import importlib
@@ -73,6 +79,15 @@ def build_parser():
                          "--landmarks and --fit-pose or --fit-shape)")
     ap.add_argument("--landmark-sigma", type=float, default=0.5, help="with --landmark-init and --fit-shape: the landmark noise, in "
                                                                       "pixels, that scales the coefficients' prior")
+    ap.add_argument("--contour", type=int, default=0, metavar="PER_SIDE",
+                    help="PER_SIDE > 0: add PER_SIDE contour landmarks a side that slide along the silhouette (utils/synth.contour_lines; "
+                         "needs --landmarks)")
+    ap.add_argument("--contour-depth", type=int, default=None, metavar="M",
+                    help="candidates per contour line, from the rim inwards (default 8 with --small, else 24 every 4th column)")
+    ap.add_argument("--contour-fixed", action="store_true", help="hold each contour landmark to its line's rim vertex (a fixed "
+                                                                 "correspondence), for the comparison")
+    ap.add_argument("--yaw", type=float, default=None, help="with --landmarks-only: set the truth's yaw (radians) on every face; the "
+                                                            "landmarks are then taken at that truth")
     return ap
 
 
@@ -125,9 +140,30 @@ def main():
     kw = {"colour": True} if args.colour else {}
     if lm_idx is not None:
         kw["landmarks"] = lm_idx
+    if args.contour > 0 and lm_idx is None:
+        raise SystemExit("--contour needs --landmarks K: the contour points stand beside the fixed landmarks")
+    if args.yaw is not None and not args.landmarks_only:
+        raise SystemExit("--yaw needs --landmarks-only: the batch's picture shows the sampled pose")
+    lines = line_dir = None
+    if args.contour > 0:
+        depth = args.contour_depth or (8 if args.small else 24)
+        lines, line_dir = synth.contour_lines(20 if args.small else synth.GRID_U, 24 if args.small else synth.GRID_V, args.contour, depth,
+                                              stride=1 if args.small else 4)
+        kw["contour_lines"] = (lines, line_dir)
     stream = pipe.SynthBatches(face, B, args.seed, slots=1, focal=1e-3 * S / 200.0, **kw)
     b = {k: v.clone() for k, v in stream.next().items()}
     torch.cuda.synchronize(dev)
+    if args.yaw is not None:
+        ops = pkg("rendering_layer.ops")
+        with torch.no_grad():
+            b["params"][:, 1] = args.yaw
+            b["landmarks"] = face.landmarks(b["params"], lm_idx)[:, 0:2].transpose(1, 2).contiguous()
+            if lines is not None:
+                b["contour_sel"], b["contour_landmarks"], _, _ = ops.landmark_contour_select(
+                    b["params"], face.landmark_contour_basis(None, lines), rule="extreme",
+                    line_dir=torch.as_tensor(line_dir, device=dev), im_size=S)
+    # --contour-fixed: every line keeps its rim vertex alone, so the correspondence cannot slide
+    fit_lines = None if lines is None else (lines[:, :1] if args.contour_fixed else lines)
     im, params, light_gt, alpha_gt = b["im_gray"], b["params"], b["light"], b["alpha"]
     noise = make_noise(args.seed, dev)
     light = (light_gt + noise(light_gt, args.light_noise)).requires_grad_(True)
@@ -162,6 +198,9 @@ def main():
         return face.vertices_transform(p, pose_grad=True) if pose is not None else face.vertices_transform(p)
 
     def landmark_term(p):
+        if fit_lines is not None:
+            return losses.landmark_loss(face, p, lm_idx, b["landmarks"], pose_grad=pose is not None, lines=fit_lines,
+                                        line_target=b["contour_landmarks"])
         return losses.landmark_loss(face, p, lm_idx, b["landmarks"], pose_grad=pose is not None)
 
     def loss_of():
@@ -186,14 +225,23 @@ def main():
         before.update(pose_errors())
     if coef is not None:
         before["coef_rms_scaled"] = rms(coef, coef_gt / scale)
-    init = None
+    init = contour = None
+    if lines is not None:
+        contour = {"per_side": int(args.contour), "depth": int(lines.shape[1]), "fixed": bool(args.contour_fixed),
+                   "sel_truth": b["contour_sel"].tolist(), "sel_fitted": None}
     if args.landmark_init:
         ridge = center = None
         if coef is not None:
             ridge, center = (torch.as_tensor(t, device=dev) for t in synth.coefficient_prior(ns, face.ndim_exp, args.landmark_sigma))
         with torch.no_grad():
-            fitted, info = face.landmark_fit(params_now(), lm_idx, b["landmarks"], ridge=ridge, center=center, iters=args.landmark_init,
-                                             fit_pose=pose is not None, fit_coef=coef is not None)
+            if fit_lines is not None:
+                fitted, info = face.landmark_fit(params_now(), face.landmark_contour_basis(lm_idx, fit_lines), b["landmarks"], ridge=ridge,
+                                                 center=center, iters=args.landmark_init, fit_pose=pose is not None,
+                                                 fit_coef=coef is not None, line_target=b["contour_landmarks"])
+                contour["sel_fitted"] = info["sel"][-1].tolist()
+            else:
+                fitted, info = face.landmark_fit(params_now(), lm_idx, b["landmarks"], ridge=ridge, center=center,
+                                                 iters=args.landmark_init, fit_pose=pose is not None, fit_coef=coef is not None)
             if pose is not None:
                 pose0 = fitted[:, :n0].clone()      # (pose stays 0: Adam goes on from the solver's pose, in the same units)
             if coef is not None:
@@ -212,7 +260,7 @@ def main():
         after.update(pose_errors())
     print(json.dumps({"program": "photo_fit", "faces": B, "im_size": S, "steps": args.steps, "lr": args.lr, "fit_shape": bool(args.fit_shape),
                       "fit_pose": bool(args.fit_pose), "colour": bool(args.colour), "landmarks": int(args.landmarks),
-                      "landmarks_only": bool(args.landmarks_only), "landmark_init": init,
+                      "landmarks_only": bool(args.landmarks_only), "landmark_init": init, "contour": contour, "yaw": args.yaw,
                       "first": first, "last": last, "ratio": last / first if first else None, "errors_before": before,
                       "errors_after": after, "finite": bool(torch.isfinite(light).all() and torch.isfinite(alpha).all())}))
 

@@ -1459,6 +1459,57 @@ int fr_landmark_solve_step(const float* params, const void* lbasis, size_t lbasi
                            int B, int K, int n_shape, int n_exp, float im_size, double* delta, double* cost, int* ok, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- contour landmarks --------------------------------------------------------------------------------------
+ * Sliding correspondences for the landmarks that mark the face's visible outline: which vertex lies under such a 2D point depends on
+ * the pose, so the point is given a LINE of M candidate vertices and, per face, one candidate is picked (csrc/fr_landmark_contour.hip).
+ * Opt-in; no reference counterpart.  No other kernel changes: the compact image is fr_landmark_basis_build's, over Kf fixed ids
+ * followed by C lines of M candidate ids, K = Kf + C M; candidate (c, m) is landmark k = Kf + c M + m.  This call writes a per-face
+ * weight [B,K] and target [B,K,2] -- the line's weight on its winner, +0 on the losers -- and fr_landmark_forward / _backward /
+ * fr_landmark_solve_step then run over K with weight_batch = 1: they skip a landmark of weight 0 entirely.  The selection is held
+ * fixed in every derivative, as tri_ind is elsewhere.
+ *
+ * Inputs.  params [B, 7 + Kt], the image and R_override as in fr_landmark_forward.  fixed_target NULL or [B,Kf,2]; fixed_weight NULL
+ * (all 1), [Kf] (fixed_weight_batch 0) or [B,Kf] (1); line_target NULL or [B,C,2]; line_weight NULL (all 1), [C] (line_weight_batch 0)
+ * or [B,C] (1); line_dir NULL or [C,2]; all fp32.  rule 0 (nearest) needs line_target, rule 1 (extreme) line_dir.
+ *
+ * Decode.  x and y of every candidate are the forward's float64 values BEFORE the fp32 rounding: the same prologue, chain and
+ * expressions (csrc/fr_landmark_shared.h), so v and R carry the forward's bits by construction.  Float64 on the widened fp32 inputs,
+ * every product and every sum rounded on its own.
+ *     rule 0 (nearest):  d = (x - tx)(x - tx) + (y - ty)(y - ty) against the line's target; for m ascending a candidate wins if
+ *                        d < best, best starting at +inf: ties go to the lowest m, and a NaN or +inf d never wins;
+ *     rule 1 (extreme):  s = dir_x x + dir_y y (two products, one sum); a candidate wins if s > best, best starting at -inf.  This is
+ *                        the model's own occluding contour along the line: it makes synthetic ground truth, and serves as a
+ *                        "landmark marching" rule.
+ * A line whose weight is 0 is not looked at (its target may be NaN) and has no winner.  A line with no winner gives sel = -1,
+ * line_points = +0 and weight +0 on all its candidates.
+ *
+ * Outputs, every element written on every call that launches: sel [B,C] int32 the winning m; line_points [B,C,2] fp32 the winner's
+ * (x, y), each rounded to fp32 once; target [B,K,2] or NULL: its fixed part a bit copy of fixed_target, every candidate of a line
+ * carrying that line's target (bit copies); weight [B,K] or NULL: the fixed part fixed_weight broadcast (1 when NULL), the line's
+ * weight on its winner (1 when NULL), +0 elsewhere.  A face's outputs are a function of that face's inputs and of (Kf, C, M, n_shape,
+ * n_exp, rule) alone.  No atomics, no workspace: bit-reproducible.
+ *
+ * Kernel: one workgroup per face; the landmarks go through LDS in the forward's chunks of 256 (boundaries at multiples of 256 of k;
+ * what lies below Kf is not decoded).  A lane per (k, c) runs the chain, a lane per candidate projects and scores, and lane c walks
+ * line c's candidates of the chunk in ascending m, carrying (best, m, x, y) from chunk to chunk -- a line may straddle a boundary.
+ *
+ * Limits: the landmark limits (n_shape + n_exp <= 256, 1 <= K <= 1024), M >= 1 and C <= 256.  Checks, all before any HIP call, in the
+ * order and with the codes of fr_landmark_forward: (1) a negative size, rule outside {0, 1} or a *_batch flag outside {0, 1} is
+ * FR_ERR_INVALID_ARG; (2) B == 0 or C == 0 is FR_OK with nothing launched; (3) a NULL params, sel or line_points, rule 0 without
+ * line_target, rule 1 without line_dir, a target output without line_target, or a target output with Kf > 0 and no fixed_target is
+ * FR_ERR_INVALID_ARG; (4) a size outside the limits is FR_ERR_UNSUPPORTED; (5) an image that is missing, too small or not 16-byte
+ * aligned is FR_ERR_WORKSPACE.  Nothing is allocated or synchronised.
+ * Time: tools/landmark_contour_probe.py (profiles/landmark_contour.json) measures the call at 64 and 32 faces of the full model
+ * with Kf = 52 and 16 lines of 24 candidates (K = 436).  MI355X, medians of 6 rounds of 20 calls: 27.0 / 27.0 us, beside
+ * fr_landmark_forward at 25.8 / 25.5 us over the same K and 10.2 / 10.1 us over K = 68 -- one workgroup per face and the latency of
+ * two chunks of the 228-long chain, flat in the batch.  The solver over the masked K: 68 us (pose only) and 2.2 ms (with the
+ * coefficients) against 22 us and 1.5 ms over K = 68. */
+int fr_landmark_contour_select(const float* params, const void* lbasis, size_t lbasis_bytes, const float* R_override,
+                               const float* fixed_target, const float* fixed_weight, int fixed_weight_batch, const float* line_target,
+                               const float* line_weight, int line_weight_batch, const float* line_dir, int rule, int B, int Kf, int C,
+                               int M, int n_shape, int n_exp, float im_size, int* sel, float* line_points, float* target, float* weight,
+                               void* stream);
+
 /* ---- test hook ---------------------------------------------------------------------------------------------
  * The screen-bin geometry the forward launcher chooses for a shape (no GPU needed): out = {rows per strip, strips,
  * triangle segments, 1 if the binned path covers the shape else 0 (the strip-scan fallback runs)}.  rows_override > 0
