@@ -628,12 +628,20 @@ int fr_synth_texture_backward(const float* pc_tex, const float* grad_tex, int B,
     return fr_launch_synth_texture_backward(pc_tex, grad_tex, B, N, K, grad_alpha, workspace, (hipStream_t)stream);
 }
 
-int fr_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* background,
-                   int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray, float* mask, void* stream) {
+// both shaders' checks, in their order; image: the model's own plane (im_gray of the gray shader, im_rgb of the colour one)
+static int synth_shade_check(const float* tex_img, const float* normal, const float* tri_ind, const float* light,
+                             const float* background, int bg_batch, int B, int H, int W, const float* image, const float* mask) {
     if (B < 1 || H < 1 || W < 1) return FR_ERR_INVALID_ARG;
     if (background ? (bg_batch != 1 && bg_batch != B) : bg_batch != 0) return FR_ERR_INVALID_ARG;
-    if (!tex_img || !normal || !tri_ind || !light || !im_gray || !mask) return FR_ERR_INVALID_ARG;
+    if (!tex_img || !normal || !tri_ind || !light || !image || !mask) return FR_ERR_INVALID_ARG;
     if ((long long)H * W > 0x7FFFFFFFll || B > 65535) return FR_ERR_UNSUPPORTED;
+    return FR_OK;
+}
+
+int fr_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* background,
+                   int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray, float* mask, void* stream) {
+    const int rc = synth_shade_check(tex_img, normal, tri_ind, light, background, bg_batch, B, H, W, im_gray, mask);
+    if (rc != FR_OK) return rc;
     return fr_launch_synth_shade(tex_img, normal, tri_ind, light, background, bg_batch, B, H, W, gain, offset, im_gray, mask,
                                  (hipStream_t)stream);
 }
@@ -650,10 +658,8 @@ int fr_synth_light_rgb(unsigned long long seed, unsigned long long first_face, i
 int fr_synth_shade_rgb(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* background,
                        int bg_batch, int B, int H, int W, float gain, float offset, float* im_rgb, float* im_gray, float* mask,
                        void* stream) {
-    if (B < 1 || H < 1 || W < 1) return FR_ERR_INVALID_ARG;
-    if (background ? (bg_batch != 1 && bg_batch != B) : bg_batch != 0) return FR_ERR_INVALID_ARG;
-    if (!tex_img || !normal || !tri_ind || !light || !im_rgb || !mask) return FR_ERR_INVALID_ARG;
-    if ((long long)H * W > 0x7FFFFFFFll || B > 65535) return FR_ERR_UNSUPPORTED;
+    const int rc = synth_shade_check(tex_img, normal, tri_ind, light, background, bg_batch, B, H, W, im_rgb, mask);   // (im_gray may be NULL)
+    if (rc != FR_OK) return rc;
     return fr_launch_synth_shade_rgb(tex_img, normal, tri_ind, light, background, bg_batch, B, H, W, gain, offset, im_rgb, im_gray,
                                      mask, (hipStream_t)stream);
 }

@@ -1,63 +1,71 @@
 // Photometric loss (opt-in; include/fr_hotpath.h, "photometric loss"): the shader's image compared with a target picture, per face, in
 // ONE streaming pass, and its gradients with respect to the render's planes and the lighting in one more.
 //
-//   photo_loss_forward_kernel   a workgroup owns PH_TILE = 256 consecutive pixels of one face, one lane per pixel, as the shader does.
-//                               A covered lane runs the shader's own device function (fr_shade.h) and forms, in float64, the six terms
-//                               of the header; the 256 x 6 values meet in a fixed tree: inside a wave by lane exchanges (strides
+//   photo_loss[_rgb]_forward_kernel   a workgroup owns PH_TILE = 256 consecutive pixels of one face, one lane per pixel, as the shader
+//                               does.  A covered lane runs the shader's own device function (fr_shade.h) and forms, in float64, the NS
+//                               terms of the header; the 256 x NS values meet in a fixed tree: inside a wave by lane exchanges (strides
 //                               32 .. 1, all the sums packed into one pass: ph_pack_level), then the four wave sums as
-//                               (w0 + w2) + (w1 + w3).  Six float64 partials per tile.
-//   photo_loss_finish_kernel    one workgroup of PH_FIN = 256 threads per face: thread i chains that face's partials i, i + 256, ..
-//                               from +0.0 (one addition at 200 x 200: 157 tiles), then the same tree.  Writes sums[b][0 .. 6).
-//                               CHOICE: the four lighting sums are taken HERE, in the forward: they are linear in the upstream
+//                               (w0 + w2) + (w1 + w3).  NS float64 partials per tile.
+//   photo_loss_finish_kernel<NS>  one workgroup of PH_FIN = 256 threads per face: thread i chains that face's partials i, i + 256, ..
+//                               from +0.0 (one addition at 200 x 200: 157 tiles), then the same tree.  Writes sums[b][0 .. NS).
+//                               CHOICE: the lighting sums are taken HERE, in the forward: they are linear in the upstream
 //                               gradient, so the backward is a pure map -- no reduction, no second launch -- and the forward is
 //                               memory-bound with or without them.
-//   photo_loss_backward_kernel  the same lane-per-pixel map: recomputes the shading (the same device function, the same bits), writes
-//                               every element of the planes that were asked for (zeros off the face), and the four lighting
+//   photo_loss[_rgb]_backward_kernel  the same lane-per-pixel map: recomputes the shading (the same device function, the same bits),
+//                               writes every element of the planes that were asked for (zeros off the face), and the lighting
 //                               gradients from sums.  grad_sse is read from the device.
-// The colour loss (include/fr_hotpath.h, "colour shading") is the same three kernels over the colour model of fr_shade.h: 29 sums per
-// face (sse, cnt, and nine lighting sums per channel) instead of six, in the SAME association -- the tile tree and the finish kernel
-// are templates in the number of sums, stated once.
+// ONE programme for both losses: every body below is a template in the model M of fr_shade.h (GrayModel: NC = 1 channel, NK = 4
+// lighting terms; ColourModel, include/fr_hotpath.h "colour shading": NC = 3, NK = 9) or in its number of sums NS = 2 + NC NK per face
+// (sse, cnt and NK lighting sums per channel: 6 or 29), in the SAME association.  The four pass kernels keep their names as wrappers
+// over the templated bodies (profiles, DESIGN.md and the resource test name them).  Where the two models' arithmetic is not the same
+// expression, the model owns the piece (fr_shade.h: tex_gradient, chain_gradient); nothing here branches on the model.
 // Float64 products and sums each rounded on their own (-ffp-contract=off).  No atomics.
 #include "fr_common.h"
 #include "fr_shade.h"
 
 namespace fr {
 
-constexpr int PH_TILE = 256, PH_WAVES = PH_TILE / 64, PH_FIN = 256, PH_SUMS = 6, PH_SUMS_RGB = 2 + 3 * 9;
+constexpr int PH_TILE = 256, PH_WAVES = PH_TILE / 64, PH_FIN = 256;
+template <class M>
+constexpr int PH_SUMS = 2 + M::NC * M::NK;
 
-struct PhArgs {
+struct PhArgs {             // NC, NK, NS: the model's
     const float* tex_img;   // [B,H,W,3]
     const float* normal;    // [B,H,W,3]
     const float* tri_ind;   // [B,H,W]
-    const float* light;     // [B,4]
-    const float* target;    // [B,H,W]
+    const float* light;     // [B,NC,NK]
+    const float* target;    // [B,H,W,NC]
     const float* weight;    // [B,H,W] or null
-    const double* sums;     // [B,6]                      (backward, for grad_light)
+    const double* sums;     // [B,NS]                     (backward, for grad_light)
     const double* grad_sse; // [B]                        (backward)
-    double* part;           // [B][tiles][6]              (forward)
+    double* part;           // [B][tiles][NS]             (forward)
     float* g_tex;           // [B,H,W,3] or null          (backward)
     float* g_normal;        // [B,H,W,3] or null          (backward)
-    float* g_light;         // [B,4] or null              (backward)
+    float* g_light;         // [B,NC,NK] or null          (backward)
     int HW, tiles;
     float gain, offset;
 };
 
-// what both directions need of a covered pixel: the shading, and t = ((2 w) r) gain in float64
+// what both directions need of a covered pixel: the shading, and per channel t = ((2 w) r) gain in float64
+template <class M>
 struct PhPixel {
-    Shade sh;
-    double r, w, t;
+    typename M::State sh;
+    double w, r[M::NC], t[M::NC];
 };
-__device__ __forceinline__ void ph_pixel(const PhArgs& a, int b, size_t i, PhPixel& p) {
-    const float I = shade_pixel(a.tex_img[3 * i], a.tex_img[3 * i + 1], a.tex_img[3 * i + 2], a.normal[3 * i], a.normal[3 * i + 1],
-                                a.normal[3 * i + 2], a.light + (size_t)b * 4, p.sh);
-    const float im = I * a.gain + a.offset;
+template <class M>
+__device__ __forceinline__ void ph_pixel(const PhArgs& a, int b, size_t i, PhPixel<M>& p) {
+    float I[M::NC];
+    M::shade(a.tex_img + 3 * i, a.normal + 3 * i, a.light + (size_t)b * (M::NC * M::NK), p.sh, I);
     p.w = a.weight ? (double)a.weight[i] : 1.0;
-    p.r = (double)im - (double)a.target[i];
-    p.t = ((2.0 * p.w) * p.r) * (double)a.gain;
+#pragma unroll
+    for (int c = 0; c < M::NC; c++) {
+        const float im = I[c] * a.gain + a.offset;
+        p.r[c] = (double)im - (double)a.target[M::NC * i + c];
+        p.t[c] = ((2.0 * p.w) * p.r[c]) * (double)a.gain;
+    }
 }
 
-// the tree over a workgroup's 256 slots, for NS values at once (six: the gray loss; 29: the colour one); thread 0 ends with the NS
-// sums in v
+// the tree over a workgroup's 256 slots, for NS values at once; thread 0 ends with the NS sums in v
 //
 // The lane tree of the header -- v[i] = v[i] + v[i + k] for i < k, k = 32 .. 1 -- leaves 64 - k lanes idle at every step, once per sum.
 // ph_pack_level runs the SAME additions for all the sums together and fills the idle lanes: at distance K two registers a, b share one
@@ -131,30 +139,39 @@ __device__ __forceinline__ void ph_normal_backward(const ShadeNormal& sh, double
     gn[0] = (float)ox; gn[1] = (float)oy; gn[2] = (float)oz;
 }
 
-__global__ __launch_bounds__(PH_TILE) void photo_loss_forward_kernel(const PhArgs a) {
-    __shared__ double ws[PH_SUMS][PH_WAVES];
+template <class M>
+__device__ __forceinline__ void photo_loss_forward_body(const PhArgs& a) {
+    constexpr int NC = M::NC, NK = M::NK, NS = PH_SUMS<M>;
+    __shared__ double ws[NS][PH_WAVES];
     const unsigned int pix = blockIdx.x * (unsigned)PH_TILE + threadIdx.x;
     const int b = (int)blockIdx.y;
-    double v[PH_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // a slot outside the image or off the face: +0.0
+    double v[NS];   // a slot outside the image or off the face: +0.0
+#pragma unroll
+    for (int j = 0; j < NS; j++) v[j] = 0.0;
     if (pix < (unsigned int)a.HW) {
         const size_t i = (size_t)b * (size_t)a.HW + pix;
         if (a.tri_ind[i] >= 0.0f) {
-            PhPixel p;
+            PhPixel<M> p;
             ph_pixel(a, b, i, p);
-            const double u = p.sh.s > 0.0f ? p.t * (double)p.sh.a : 0.0;
-            v[0] = (p.w * p.r) * p.r;
+            double e = (p.w * p.r[0]) * p.r[0];   // the first channel, then the others in ascending order
+#pragma unroll
+            for (int c = 1; c < NC; c++) e = e + (p.w * p.r[c]) * p.r[c];
+            v[0] = e;
             v[1] = 1.0;
-            v[2] = u;
-            v[3] = u * (double)p.sh.hx;
-            v[4] = u * (double)p.sh.hy;
-            v[5] = u * (double)p.sh.hz;
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                const double u = M::chain(p.sh, c) > 0.0f ? p.t[c] * (double)M::albedo(p.sh, c) : 0.0;
+                v[2 + NK * c] = u;   // (H0 = 1 is not multiplied)
+#pragma unroll
+                for (int k = 1; k < NK; k++) v[2 + NK * c + k] = u * (double)M::basis(p.sh, k);
+            }
         }
     }
     ph_block_tree(v, ws);
     if (threadIdx.x == 0) {
-        double* out = a.part + ((size_t)b * a.tiles + blockIdx.x) * PH_SUMS;
+        double* out = a.part + ((size_t)b * a.tiles + blockIdx.x) * NS;
 #pragma unroll
-        for (int j = 0; j < PH_SUMS; j++) out[j] = v[j];
+        for (int j = 0; j < NS; j++) out[j] = v[j];
     }
 }
 
@@ -177,140 +194,43 @@ __global__ __launch_bounds__(PH_FIN) void photo_loss_finish_kernel(const double*
     }
 }
 
-__global__ __launch_bounds__(PH_TILE) void photo_loss_backward_kernel(const PhArgs a) {
+template <class M>
+__device__ __forceinline__ void photo_loss_backward_body(const PhArgs& a) {
+    constexpr int NC = M::NC, NK = M::NK;
     const unsigned int pix = blockIdx.x * (unsigned)PH_TILE + threadIdx.x;
     const int b = (int)blockIdx.y;
     const double g = a.grad_sse[b];
-    if (a.g_light && blockIdx.x == 0 && threadIdx.x < 4)
-        a.g_light[(size_t)b * 4 + threadIdx.x] = (float)(g * a.sums[(size_t)b * PH_SUMS + 2 + threadIdx.x]);
+    if (a.g_light && blockIdx.x == 0 && threadIdx.x < NC * NK)
+        a.g_light[(size_t)b * (NC * NK) + threadIdx.x] = (float)(g * a.sums[(size_t)b * PH_SUMS<M> + 2 + threadIdx.x]);
     if (pix >= (unsigned int)a.HW) return;
     const size_t i = (size_t)b * (size_t)a.HW + pix;
     float gt[3] = {0.0f, 0.0f, 0.0f}, gn[3] = {0.0f, 0.0f, 0.0f};
     if (a.tri_ind[i] >= 0.0f) {
-        PhPixel p;
+        PhPixel<M> p;
         ph_pixel(a, b, i, p);
-        const Shade& sh = p.sh;
-        const double dI = g * p.t;
-        const bool lit = sh.s > 0.0f;
-        if (a.g_tex) {
-            const float gc = (float)((dI * (double)sh.s) * (1.0 / 3.0));
+        double gx = 0.0, gy = 0.0, gz = 0.0;   // g~; what a channel does to it is the model's (fr_shade.h, chain_gradient)
 #pragma unroll
-            for (int c = 0; c < 3; c++) gt[c] = (lit && !(a.tex_img[3 * i + c] < 1e-6f)) ? gc : 0.0f;
-        }
-        if (a.g_normal) {
-            const float* l = a.light + (size_t)b * 4;
-            const double q = lit ? dI * (double)sh.a : 0.0;
-            const double gx = q * (double)l[1], gy = q * (double)l[2], gz = q * (double)l[3];
-            ph_normal_backward(sh, gx, gy, gz, gn);
-        }
-    }
-    if (a.g_tex) { a.g_tex[3 * i] = gt[0]; a.g_tex[3 * i + 1] = gt[1]; a.g_tex[3 * i + 2] = gt[2]; }
-    if (a.g_normal) { a.g_normal[3 * i] = gn[0]; a.g_normal[3 * i + 1] = gn[1]; a.g_normal[3 * i + 2] = gn[2]; }
-}
-
-// ---- the colour loss ---------------------------------------------------------------------------------------------------------------
-struct PhRgbArgs {
-    const float* tex_img;   // [B,H,W,3]
-    const float* normal;    // [B,H,W,3]
-    const float* tri_ind;   // [B,H,W]
-    const float* light;     // [B,3,9]
-    const float* target;    // [B,H,W,3]
-    const float* weight;    // [B,H,W] or null
-    const double* sums;     // [B,29]                     (backward, for grad_light)
-    const double* grad_sse; // [B]                        (backward)
-    double* part;           // [B][tiles][29]             (forward)
-    float* g_tex;           // [B,H,W,3] or null          (backward)
-    float* g_normal;        // [B,H,W,3] or null          (backward)
-    float* g_light;         // [B,3,9] or null            (backward)
-    int HW, tiles;
-    float gain, offset;
-};
-
-// what both directions need of a covered pixel: the shading, and per channel t = ((2 w) r) gain in float64
-struct PhRgbPixel {
-    ShadeRGB sh;
-    double w, r[3], t[3];
-};
-__device__ __forceinline__ void ph_pixel_rgb(const PhRgbArgs& a, int b, size_t i, PhRgbPixel& p) {
-    float I[3];
-    shade_pixel_rgb(a.tex_img[3 * i], a.tex_img[3 * i + 1], a.tex_img[3 * i + 2], a.normal[3 * i], a.normal[3 * i + 1],
-                    a.normal[3 * i + 2], a.light + (size_t)b * 27, p.sh, I);
-    p.w = a.weight ? (double)a.weight[i] : 1.0;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float im = I[c] * a.gain + a.offset;
-        p.r[c] = (double)im - (double)a.target[3 * i + c];
-        p.t[c] = ((2.0 * p.w) * p.r[c]) * (double)a.gain;
-    }
-}
-
-__global__ __launch_bounds__(PH_TILE) void photo_loss_rgb_forward_kernel(const PhRgbArgs a) {
-    __shared__ double ws[PH_SUMS_RGB][PH_WAVES];
-    const unsigned int pix = blockIdx.x * (unsigned)PH_TILE + threadIdx.x;
-    const int b = (int)blockIdx.y;
-    double v[PH_SUMS_RGB];   // a slot outside the image or off the face: +0.0
-#pragma unroll
-    for (int j = 0; j < PH_SUMS_RGB; j++) v[j] = 0.0;
-    if (pix < (unsigned int)a.HW) {
-        const size_t i = (size_t)b * (size_t)a.HW + pix;
-        if (a.tri_ind[i] >= 0.0f) {
-            PhRgbPixel p;
-            ph_pixel_rgb(a, b, i, p);
-            v[0] = ((p.w * p.r[0]) * p.r[0] + (p.w * p.r[1]) * p.r[1]) + (p.w * p.r[2]) * p.r[2];
-            v[1] = 1.0;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const double u = p.sh.s[c] > 0.0f ? p.t[c] * (double)p.sh.a[c] : 0.0;
-                v[2 + 9 * c] = u;
-#pragma unroll
-                for (int k = 1; k < 9; k++) v[2 + 9 * c + k] = u * (double)p.sh.h[k];
-            }
-        }
-    }
-    ph_block_tree(v, ws);
-    if (threadIdx.x == 0) {
-        double* out = a.part + ((size_t)b * a.tiles + blockIdx.x) * PH_SUMS_RGB;
-#pragma unroll
-        for (int j = 0; j < PH_SUMS_RGB; j++) out[j] = v[j];
-    }
-}
-
-__global__ __launch_bounds__(PH_TILE) void photo_loss_rgb_backward_kernel(const PhRgbArgs a) {
-    const unsigned int pix = blockIdx.x * (unsigned)PH_TILE + threadIdx.x;
-    const int b = (int)blockIdx.y;
-    const double g = a.grad_sse[b];
-    if (a.g_light && blockIdx.x == 0 && threadIdx.x < 27)
-        a.g_light[(size_t)b * 27 + threadIdx.x] = (float)(g * a.sums[(size_t)b * PH_SUMS_RGB + 2 + threadIdx.x]);
-    if (pix >= (unsigned int)a.HW) return;
-    const size_t i = (size_t)b * (size_t)a.HW + pix;
-    float gt[3] = {0.0f, 0.0f, 0.0f}, gn[3] = {0.0f, 0.0f, 0.0f};
-    if (a.tri_ind[i] >= 0.0f) {
-        PhRgbPixel p;
-        ph_pixel_rgb(a, b, i, p);
-        const ShadeRGB& sh = p.sh;
-        const double hx = (double)sh.hx, hy = (double)sh.hy, hz = (double)sh.hz;
-        double gx = 0.0, gy = 0.0, gz = 0.0;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
+        for (int c = 0; c < NC; c++) {
             const double dI = g * p.t[c];
-            const bool lit = sh.s[c] > 0.0f;
-            if (a.g_tex) gt[c] = (lit && !(a.tex_img[3 * i + c] < 1e-6f)) ? (float)(dI * (double)sh.s[c]) : 0.0f;
+            const bool lit = M::chain(p.sh, c) > 0.0f;
+            if (a.g_tex) M::tex_gradient(p.sh, c, dI, lit, a.tex_img + 3 * i, gt);
             if (a.g_normal) {
-                const float* l = a.light + (size_t)b * 27 + 9 * c;
-                const double q = lit ? dI * (double)sh.a[c] : 0.0;
-                const double l1 = (double)l[1], l2 = (double)l[2], l3 = (double)l[3], l4 = (double)l[4], l5 = (double)l[5],
-                             l6 = (double)l[6], l7 = (double)l[7], l8 = (double)l[8];
-                const double dx = ((l1 + l4 * hy) + l5 * hz) + (2.0 * l7) * hx;
-                const double dy = ((l2 + l4 * hx) + l6 * hz) - (2.0 * l7) * hy;
-                const double dz = ((l3 + l5 * hx) + l6 * hy) + (6.0 * l8) * hz;
-                gx = gx + q * dx; gy = gy + q * dy; gz = gz + q * dz;
+                const double q = lit ? dI * (double)M::albedo(p.sh, c) : 0.0;
+                M::chain_gradient(p.sh, a.light + (size_t)b * (NC * NK) + NK * c, q, gx, gy, gz);
             }
         }
-        if (a.g_normal) ph_normal_backward(sh, gx, gy, gz, gn);
+        if (a.g_normal) ph_normal_backward(p.sh, gx, gy, gz, gn);
     }
     if (a.g_tex) { a.g_tex[3 * i] = gt[0]; a.g_tex[3 * i + 1] = gt[1]; a.g_tex[3 * i + 2] = gt[2]; }
     if (a.g_normal) { a.g_normal[3 * i] = gn[0]; a.g_normal[3 * i + 1] = gn[1]; a.g_normal[3 * i + 2] = gn[2]; }
 }
+
+// the four pass kernels under their own names (not instantiations of one __global__ template: the names are what profiles, DESIGN.md
+// and tests/test_photo_rgb_cpu.py know them by)
+__global__ __launch_bounds__(PH_TILE) void photo_loss_forward_kernel(const PhArgs a) { photo_loss_forward_body<GrayModel>(a); }
+__global__ __launch_bounds__(PH_TILE) void photo_loss_backward_kernel(const PhArgs a) { photo_loss_backward_body<GrayModel>(a); }
+__global__ __launch_bounds__(PH_TILE) void photo_loss_rgb_forward_kernel(const PhArgs a) { photo_loss_forward_body<ColourModel>(a); }
+__global__ __launch_bounds__(PH_TILE) void photo_loss_rgb_backward_kernel(const PhArgs a) { photo_loss_backward_body<ColourModel>(a); }
 
 }  // namespace fr
 
@@ -319,11 +239,16 @@ namespace {
 // more than 2^31 - 1 pixels per face (the pixel index is a 32-bit word), or more faces than the grid's y takes
 bool ph_size_ok(int B, int H, int W) { return (long long)H * W <= 0x7FFFFFFFll && B <= 65535; }
 int ph_tiles(int H, int W) { return (int)(((long long)H * W + fr::PH_TILE - 1) / fr::PH_TILE); }
-// state: the tile partials [B][tiles][sums], float64 (six sums: the gray loss; 29: the colour one).  0 for an empty shape or one the
-// launchers refuse.
-size_t ph_state_bytes(int B, int H, int W, int sums = fr::PH_SUMS) {
+// state: the tile partials [B][tiles][sums], float64.  0 for an empty shape or one the launchers refuse.
+size_t ph_state_bytes(int B, int H, int W, int sums) {
     if (B <= 0 || H <= 0 || W <= 0 || !ph_size_ok(B, H, W)) return 0;
     return (size_t)B * (size_t)ph_tiles(H, W) * (size_t)sums * sizeof(double);
+}
+// test hook: out = {pixels per tile, tiles per face, threads of the finish workgroup, sums per face}
+void ph_geom(int B, int H, int W, int sums, int* out) {
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    if (B <= 0 || H <= 0 || W <= 0 || !ph_size_ok(B, H, W)) return;
+    out[0] = fr::PH_TILE; out[1] = ph_tiles(H, W); out[2] = fr::PH_FIN; out[3] = sums;
 }
 // the order both entry points answer in: a negative size, an empty shape (FR_OK, nothing launched), the entry point's own pointers,
 // its state, a shape beyond one grid.  FR_OK with *go = true: launch.
@@ -337,39 +262,31 @@ int ph_check(int B, int H, int W, bool pointers_ok, bool state_ok, bool* go) {
     *go = true;
     return FR_OK;
 }
-}  // namespace
 
-extern "C" {
-
-size_t fr_photo_loss_state_bytes(int B, int H, int W) { return ph_state_bytes(B, H, W); }
-
-// test hook: out = {pixels per tile, tiles per face, threads of the finish workgroup, sums per face}
-void fr_debug_photo_loss_geom(int B, int H, int W, int* out) {
-    for (int i = 0; i < 4; i++) out[i] = 0;
-    if (B <= 0 || H <= 0 || W <= 0 || !ph_size_ok(B, H, W)) return;
-    out[0] = fr::PH_TILE; out[1] = ph_tiles(H, W); out[2] = fr::PH_FIN; out[3] = fr::PH_SUMS;
-}
-
-int fr_photo_loss_forward(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* target,
-                          const float* weight, int B, int H, int W, float gain, float offset, double* sums, void* state,
-                          size_t state_bytes, void* stream) {
+// the two launchers, handed a model's pass kernel (the kernels are named, not instantiated: see there); the forward's state and finish
+// step need the model's number of sums as well
+using PhKernel = void (*)(const fr::PhArgs);
+template <class M>
+int ph_forward(PhKernel pass, const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* target,
+               const float* weight, int B, int H, int W, float gain, float offset, double* sums, void* state, size_t state_bytes,
+               void* stream) {
+    constexpr int NS = fr::PH_SUMS<M>;
     bool go;
     const int rc = ph_check(B, H, W, tex_img && normal && tri_ind && light && target && sums,
-                            ws_ok(state, state_bytes, ph_state_bytes(B, H, W), 16), &go);
+                            ws_ok(state, state_bytes, ph_state_bytes(B, H, W, NS), 16), &go);
     if (!go) return rc;
     fr::PhArgs a{};
     a.tex_img = tex_img; a.normal = normal; a.tri_ind = tri_ind; a.light = light; a.target = target; a.weight = weight;
     a.part = (double*)state; a.HW = H * W; a.tiles = ph_tiles(H, W); a.gain = gain; a.offset = offset;
-    hipLaunchKernelGGL(fr::photo_loss_forward_kernel, dim3((unsigned)a.tiles, (unsigned)B, 1), dim3(fr::PH_TILE, 1, 1), 0,
-                       (hipStream_t)stream, a);
-    hipLaunchKernelGGL(fr::photo_loss_finish_kernel<fr::PH_SUMS>, dim3((unsigned)B, 1, 1), dim3(fr::PH_FIN, 1, 1), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(pass, dim3((unsigned)a.tiles, (unsigned)B, 1), dim3(fr::PH_TILE, 1, 1), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(fr::photo_loss_finish_kernel<NS>, dim3((unsigned)B, 1, 1), dim3(fr::PH_FIN, 1, 1), 0, (hipStream_t)stream,
                        (const double*)a.part, a.tiles, sums);
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }
 
-int fr_photo_loss_backward(const double* grad_sse, const double* sums, const float* tex_img, const float* normal, const float* tri_ind,
-                           const float* light, const float* target, const float* weight, int B, int H, int W, float gain,
-                           float offset, float* grad_tex_img, float* grad_normal, float* grad_light, void* stream) {
+int ph_backward(PhKernel pass, const double* grad_sse, const double* sums, const float* tex_img, const float* normal,
+                const float* tri_ind, const float* light, const float* target, const float* weight, int B, int H, int W, float gain,
+                float offset, float* grad_tex_img, float* grad_normal, float* grad_light, void* stream) {
     bool go;
     const int rc = ph_check(B, H, W, grad_sse && tex_img && normal && tri_ind && light && target && (sums || !grad_light), true, &go);
     if (!go) return rc;
@@ -378,51 +295,45 @@ int fr_photo_loss_backward(const double* grad_sse, const double* sums, const flo
     a.tex_img = tex_img; a.normal = normal; a.tri_ind = tri_ind; a.light = light; a.target = target; a.weight = weight;
     a.sums = sums; a.grad_sse = grad_sse; a.g_tex = grad_tex_img; a.g_normal = grad_normal; a.g_light = grad_light;
     a.HW = H * W; a.tiles = ph_tiles(H, W); a.gain = gain; a.offset = offset;
-    hipLaunchKernelGGL(fr::photo_loss_backward_kernel, dim3((unsigned)a.tiles, (unsigned)B, 1), dim3(fr::PH_TILE, 1, 1), 0,
-                       (hipStream_t)stream, a);
+    hipLaunchKernelGGL(pass, dim3((unsigned)a.tiles, (unsigned)B, 1), dim3(fr::PH_TILE, 1, 1), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }
+}  // namespace
 
-// ---- the colour loss: the gray loss's checks, geometry and launches over 29 sums ---------------------------------------------------
-size_t fr_photo_loss_rgb_state_bytes(int B, int H, int W) { return ph_state_bytes(B, H, W, fr::PH_SUMS_RGB); }
+extern "C" {
 
-void fr_debug_photo_loss_rgb_geom(int B, int H, int W, int* out) {
-    for (int i = 0; i < 4; i++) out[i] = 0;
-    if (B <= 0 || H <= 0 || W <= 0 || !ph_size_ok(B, H, W)) return;
-    out[0] = fr::PH_TILE; out[1] = ph_tiles(H, W); out[2] = fr::PH_FIN; out[3] = fr::PH_SUMS_RGB;
+size_t fr_photo_loss_state_bytes(int B, int H, int W) { return ph_state_bytes(B, H, W, fr::PH_SUMS<fr::GrayModel>); }
+size_t fr_photo_loss_rgb_state_bytes(int B, int H, int W) { return ph_state_bytes(B, H, W, fr::PH_SUMS<fr::ColourModel>); }
+
+void fr_debug_photo_loss_geom(int B, int H, int W, int* out) { ph_geom(B, H, W, fr::PH_SUMS<fr::GrayModel>, out); }
+void fr_debug_photo_loss_rgb_geom(int B, int H, int W, int* out) { ph_geom(B, H, W, fr::PH_SUMS<fr::ColourModel>, out); }
+
+int fr_photo_loss_forward(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* target,
+                          const float* weight, int B, int H, int W, float gain, float offset, double* sums, void* state,
+                          size_t state_bytes, void* stream) {
+    return ph_forward<fr::GrayModel>(fr::photo_loss_forward_kernel, tex_img, normal, tri_ind, light, target, weight, B, H, W, gain,
+                                     offset, sums, state, state_bytes, stream);
 }
 
 int fr_photo_loss_rgb_forward(const float* tex_img, const float* normal, const float* tri_ind, const float* light, const float* target,
                               const float* weight, int B, int H, int W, float gain, float offset, double* sums, void* state,
                               size_t state_bytes, void* stream) {
-    bool go;
-    const int rc = ph_check(B, H, W, tex_img && normal && tri_ind && light && target && sums,
-                            ws_ok(state, state_bytes, ph_state_bytes(B, H, W, fr::PH_SUMS_RGB), 16), &go);
-    if (!go) return rc;
-    fr::PhRgbArgs a{};
-    a.tex_img = tex_img; a.normal = normal; a.tri_ind = tri_ind; a.light = light; a.target = target; a.weight = weight;
-    a.part = (double*)state; a.HW = H * W; a.tiles = ph_tiles(H, W); a.gain = gain; a.offset = offset;
-    hipLaunchKernelGGL(fr::photo_loss_rgb_forward_kernel, dim3((unsigned)a.tiles, (unsigned)B, 1), dim3(fr::PH_TILE, 1, 1), 0,
-                       (hipStream_t)stream, a);
-    hipLaunchKernelGGL(fr::photo_loss_finish_kernel<fr::PH_SUMS_RGB>, dim3((unsigned)B, 1, 1), dim3(fr::PH_FIN, 1, 1), 0,
-                       (hipStream_t)stream, (const double*)a.part, a.tiles, sums);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    return ph_forward<fr::ColourModel>(fr::photo_loss_rgb_forward_kernel, tex_img, normal, tri_ind, light, target, weight, B, H, W,
+                                       gain, offset, sums, state, state_bytes, stream);
+}
+
+int fr_photo_loss_backward(const double* grad_sse, const double* sums, const float* tex_img, const float* normal, const float* tri_ind,
+                           const float* light, const float* target, const float* weight, int B, int H, int W, float gain,
+                           float offset, float* grad_tex_img, float* grad_normal, float* grad_light, void* stream) {
+    return ph_backward(fr::photo_loss_backward_kernel, grad_sse, sums, tex_img, normal, tri_ind, light, target, weight, B, H, W, gain,
+                       offset, grad_tex_img, grad_normal, grad_light, stream);
 }
 
 int fr_photo_loss_rgb_backward(const double* grad_sse, const double* sums, const float* tex_img, const float* normal,
                                const float* tri_ind, const float* light, const float* target, const float* weight, int B, int H, int W,
                                float gain, float offset, float* grad_tex_img, float* grad_normal, float* grad_light, void* stream) {
-    bool go;
-    const int rc = ph_check(B, H, W, grad_sse && tex_img && normal && tri_ind && light && target && (sums || !grad_light), true, &go);
-    if (!go) return rc;
-    if (!grad_tex_img && !grad_normal && !grad_light) return FR_OK;   // nothing is wanted
-    fr::PhRgbArgs a{};
-    a.tex_img = tex_img; a.normal = normal; a.tri_ind = tri_ind; a.light = light; a.target = target; a.weight = weight;
-    a.sums = sums; a.grad_sse = grad_sse; a.g_tex = grad_tex_img; a.g_normal = grad_normal; a.g_light = grad_light;
-    a.HW = H * W; a.tiles = ph_tiles(H, W); a.gain = gain; a.offset = offset;
-    hipLaunchKernelGGL(fr::photo_loss_rgb_backward_kernel, dim3((unsigned)a.tiles, (unsigned)B, 1), dim3(fr::PH_TILE, 1, 1), 0,
-                       (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    return ph_backward(fr::photo_loss_rgb_backward_kernel, grad_sse, sums, tex_img, normal, tri_ind, light, target, weight, B, H, W,
+                       gain, offset, grad_tex_img, grad_normal, grad_light, stream);
 }
 
 }  // extern "C"

@@ -2,6 +2,8 @@
 // ("colour shading", MODEL).  The shaders (fr_synth.hip) and the photometric losses (fr_photo.hip) run these functions, so the image a
 // loss compares is its shader's image bit for bit.  fp32, every operation rounded on its own (-ffp-contract=off), IEEE division and
 // square root.  Both models share the normal's part (shade_normal).
+// A model is a TYPE (GrayModel, ColourModel, at the end): its sizes, its state, its arithmetic and the two pieces of the loss's
+// backward that are not the same expression in both.  The shader and the loss are written once, over that type.
 #pragma once
 #include "fr_common.h"
 
@@ -74,5 +76,59 @@ __device__ __forceinline__ void shade_pixel_rgb(float t0, float t1, float t2, fl
 
 // the gray of an RGB pixel (the weights of utils/data_process.py)
 __device__ __forceinline__ float gray_of(float r, float g, float b) { return (0.3f * r + 0.59f * g) + 0.11f * b; }
+
+// ---- a model as a type ----------------------------------------------------------------------------------------------------------------
+// NC image channels, NK lighting terms per channel (light[b] is [NC][NK], a pixel of the image [NC]); State, what shade() leaves of
+// a covered pixel; albedo / chain: a_c and s_c; basis: H_k, k >= 1 (H_0 = 1 is never multiplied).  The backward's two pieces, in
+// float64 on the widened values, of image channel c with dI = d sse / d I_c and lit = s_c > 0:
+//   tex_gradient    writes the elements of gt that channel c reaches.  NOT one expression: the gray image reads all three texture
+//                   channels through their mean -- ONE value (dI s) (1 / 3), gated by each channel's own clamp -- the colour image's
+//                   channel c reads texture channel c alone: dI s_c.
+//   chain_gradient  q = lit ? dI a_c : 0 times the derivative of s_c with respect to n^, into g~.  NOT one accumulation: the gray
+//                   model ASSIGNS its one product, the colour model ADDS each channel's to g~, which starts at +0.0.  On an unlit
+//                   pixel q = 0.0 and a negative coefficient makes the product -0.0: assigned it stays -0.0, added to +0.0 it becomes
+//                   +0.0, and ph_normal_backward carries the sign into grad_normal.  Either model written the other's way moves bits.
+struct GrayModel {
+    static constexpr int NC = 1, NK = 4;
+    using State = Shade;
+    static __device__ __forceinline__ void shade(const float* t, const float* n, const float* l, State& o, float (&I)[NC]) {
+        I[0] = shade_pixel(t[0], t[1], t[2], n[0], n[1], n[2], l, o);
+    }
+    static __device__ __forceinline__ float albedo(const State& o, int) { return o.a; }
+    static __device__ __forceinline__ float chain(const State& o, int) { return o.s; }
+    static __device__ __forceinline__ float basis(const State& o, int k) { return k == 1 ? o.hx : k == 2 ? o.hy : o.hz; }
+    static __device__ __forceinline__ void tex_gradient(const State& o, int, double dI, bool lit, const float* t, float (&gt)[3]) {
+        const float gc = (float)((dI * (double)o.s) * (1.0 / 3.0));
+#pragma unroll
+        for (int k = 0; k < 3; k++) gt[k] = (lit && !(t[k] < 1e-6f)) ? gc : 0.0f;
+    }
+    static __device__ __forceinline__ void chain_gradient(const State&, const float* l, double q, double& gx, double& gy, double& gz) {
+        gx = q * (double)l[1]; gy = q * (double)l[2]; gz = q * (double)l[3];
+    }
+};
+
+struct ColourModel {
+    static constexpr int NC = 3, NK = 9;
+    using State = ShadeRGB;
+    static __device__ __forceinline__ void shade(const float* t, const float* n, const float* l, State& o, float (&I)[NC]) {
+        shade_pixel_rgb(t[0], t[1], t[2], n[0], n[1], n[2], l, o, I);
+    }
+    static __device__ __forceinline__ float albedo(const State& o, int c) { return o.a[c]; }
+    static __device__ __forceinline__ float chain(const State& o, int c) { return o.s[c]; }
+    static __device__ __forceinline__ float basis(const State& o, int k) { return o.h[k]; }
+    static __device__ __forceinline__ void tex_gradient(const State& o, int c, double dI, bool lit, const float* t, float (&gt)[3]) {
+        gt[c] = (lit && !(t[c] < 1e-6f)) ? (float)(dI * (double)o.s[c]) : 0.0f;
+    }
+    // l = light[b][c]
+    static __device__ __forceinline__ void chain_gradient(const State& o, const float* l, double q, double& gx, double& gy, double& gz) {
+        const double hx = (double)o.hx, hy = (double)o.hy, hz = (double)o.hz;
+        const double l1 = (double)l[1], l2 = (double)l[2], l3 = (double)l[3], l4 = (double)l[4], l5 = (double)l[5], l6 = (double)l[6],
+                     l7 = (double)l[7], l8 = (double)l[8];
+        const double dx = ((l1 + l4 * hy) + l5 * hz) + (2.0 * l7) * hx;
+        const double dy = ((l2 + l4 * hx) + l6 * hz) - (2.0 * l7) * hy;
+        const double dz = ((l3 + l5 * hx) + l6 * hy) + (6.0 * l8) * hz;
+        gx = gx + q * dx; gy = gy + q * dy; gz = gz + q * dz;
+    }
+};
 
 }  // namespace fr

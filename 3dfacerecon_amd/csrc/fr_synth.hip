@@ -2,7 +2,8 @@
 // albedo blend and the shading / compositing post-pass over a render's planes.  All three are streaming or tiny: one lane per
 // element, coalesced, no atomics; LDS only to turn the texture basis' row-major reads into coalesced ones.  fp32 in the header's
 // stated order, one rounding per operation (-ffp-contract=off).  The blend has an adjoint (synth_texture_bwd_kernel and its finish
-// step): float64 sums of exact products in an association that is a function of (N, K) alone.
+// step): float64 sums of exact products in an association that is a function of (N, K) alone.  The shader is written once, over the
+// shading model of fr_shade.h (synth_shade_body<M>): synth_shade_kernel is the gray model's, synth_shade_rgb_kernel the colour one's.
 #include "fr_common.h"
 #include "fr_shade.h"
 
@@ -171,25 +172,52 @@ __global__ __launch_bounds__(64) void synth_texture_bwd_finish_kernel(const doub
     if (threadIdx.x == 0) grad_alpha[blockIdx.x] = (float)acc;
 }
 
-// one lane per pixel
-__global__ __launch_bounds__(256) void synth_shade_kernel(const float* __restrict__ tex_img, const float* __restrict__ normal,
-                                                          const float* __restrict__ tri_ind, const float* __restrict__ light,
-                                                          const float* __restrict__ background, int bg_batch, int HW, float gain,
-                                                          float offset, float* __restrict__ im_gray, float* __restrict__ mask) {
+// The shader, one lane per pixel, for the model M of fr_shade.h (the photometric loss runs the same M::shade): im [B,H,W,NC] is the
+// model's image where the face covers the pixel and the background's NC channels elsewhere (0 without one).  The colour model also
+// writes the gray of the result, background included, where im_gray is wanted.
+template <class M>
+__device__ __forceinline__ void synth_shade_body(const float* __restrict__ tex_img, const float* __restrict__ normal,
+                                                 const float* __restrict__ tri_ind, const float* __restrict__ light,
+                                                 const float* __restrict__ background, int bg_batch, int HW, float gain, float offset,
+                                                 float* __restrict__ im, float* __restrict__ im_gray, float* __restrict__ mask) {
+    constexpr int NC = M::NC;
     const unsigned int pix = blockIdx.x * 256u + threadIdx.x;
     const int b = (int)blockIdx.y;
     if (pix >= (unsigned int)HW) return;
     const size_t i = (size_t)b * (size_t)HW + pix;
-    if (!(tri_ind[i] >= 0.0f)) {
-        im_gray[i] = background ? background[(bg_batch == 1 ? (size_t)0 : (size_t)b * (size_t)HW) + pix] : 0.0f;
-        mask[i] = 0.0f;
-        return;
+    float v[NC];
+    const bool covered = tri_ind[i] >= 0.0f;
+    if (!covered) {
+        const size_t k = (bg_batch == 1 ? (size_t)0 : (size_t)b * (size_t)HW) + pix;
+#pragma unroll
+        for (int c = 0; c < NC; c++) v[c] = background ? background[NC * k + c] : 0.0f;
+    } else {
+        typename M::State sh;
+        float I[NC];
+        M::shade(tex_img + 3 * i, normal + 3 * i, light + (size_t)b * (NC * M::NK), sh, I);
+#pragma unroll
+        for (int c = 0; c < NC; c++) v[c] = I[c] * gain + offset;
     }
-    fr::Shade sh;
-    const float I = fr::shade_pixel(tex_img[3 * i], tex_img[3 * i + 1], tex_img[3 * i + 2], normal[3 * i], normal[3 * i + 1],
-                                    normal[3 * i + 2], light + (size_t)b * 4, sh);   // (fr_shade.h: the photometric loss runs it too)
-    im_gray[i] = I * gain + offset;
-    mask[i] = 1.0f;
+#pragma unroll
+    for (int c = 0; c < NC; c++) im[NC * i + c] = v[c];
+    if constexpr (NC == 3) {
+        if (im_gray) im_gray[i] = fr::gray_of(v[0], v[1], v[2]);
+    }
+    mask[i] = covered ? 1.0f : 0.0f;
+}
+// (two named kernels, not instantiations of one: profiles and tests/test_photo_rgb_cpu.py know them by these names)
+__global__ __launch_bounds__(256) void synth_shade_kernel(const float* __restrict__ tex_img, const float* __restrict__ normal,
+                                                          const float* __restrict__ tri_ind, const float* __restrict__ light,
+                                                          const float* __restrict__ background, int bg_batch, int HW, float gain,
+                                                          float offset, float* __restrict__ im_gray, float* __restrict__ mask) {
+    synth_shade_body<GrayModel>(tex_img, normal, tri_ind, light, background, bg_batch, HW, gain, offset, im_gray, nullptr, mask);
+}
+__global__ __launch_bounds__(256) void synth_shade_rgb_kernel(const float* __restrict__ tex_img, const float* __restrict__ normal,
+                                                              const float* __restrict__ tri_ind, const float* __restrict__ light,
+                                                              const float* __restrict__ background, int bg_batch, int HW, float gain,
+                                                              float offset, float* __restrict__ im_rgb, float* __restrict__ im_gray,
+                                                              float* __restrict__ mask) {
+    synth_shade_body<ColourModel>(tex_img, normal, tri_ind, light, background, bg_batch, HW, gain, offset, im_rgb, im_gray, mask);
 }
 
 // The colour lighting's sampler: one lane per draw j = 9 c + k of face b, word j & 3 of the block with counter (j >> 2, g_lo, g_hi, 1)
@@ -211,35 +239,6 @@ __global__ __launch_bounds__(64) void synth_light_rgb_kernel(const SynthLightRgb
     a.light[(size_t)b * 27 + j] = a.lo[j] + (a.hi[j] - a.lo[j]) * u;
 }
 
-// one lane per pixel: the colour model of fr_shade.h, the background's three channels off the face, and the gray of the result
-__global__ __launch_bounds__(256) void synth_shade_rgb_kernel(const float* __restrict__ tex_img, const float* __restrict__ normal,
-                                                              const float* __restrict__ tri_ind, const float* __restrict__ light,
-                                                              const float* __restrict__ background, int bg_batch, int HW, float gain,
-                                                              float offset, float* __restrict__ im_rgb, float* __restrict__ im_gray,
-                                                              float* __restrict__ mask) {
-    const unsigned int pix = blockIdx.x * 256u + threadIdx.x;
-    const int b = (int)blockIdx.y;
-    if (pix >= (unsigned int)HW) return;
-    const size_t i = (size_t)b * (size_t)HW + pix;
-    float rgb[3];
-    const bool covered = tri_ind[i] >= 0.0f;
-    if (!covered) {
-        const size_t k = (bg_batch == 1 ? (size_t)0 : (size_t)b * (size_t)HW) + pix;
-#pragma unroll
-        for (int c = 0; c < 3; c++) rgb[c] = background ? background[3 * k + c] : 0.0f;
-    } else {
-        fr::ShadeRGB sh;
-        float I[3];
-        fr::shade_pixel_rgb(tex_img[3 * i], tex_img[3 * i + 1], tex_img[3 * i + 2], normal[3 * i], normal[3 * i + 1], normal[3 * i + 2],
-                            light + (size_t)b * 27, sh, I);   // (fr_shade.h: the colour loss runs it too)
-#pragma unroll
-        for (int c = 0; c < 3; c++) rgb[c] = I[c] * gain + offset;
-    }
-    im_rgb[3 * i] = rgb[0]; im_rgb[3 * i + 1] = rgb[1]; im_rgb[3 * i + 2] = rgb[2];
-    if (im_gray) im_gray[i] = fr::gray_of(rgb[0], rgb[1], rgb[2]);
-    mask[i] = covered ? 1.0f : 0.0f;
-}
-
 }  // namespace fr
 
 int fr_launch_synth_light_rgb(unsigned long long seed, unsigned long long first_face, int B, const float* ranges, float* light,
@@ -248,15 +247,6 @@ int fr_launch_synth_light_rgb(unsigned long long seed, unsigned long long first_
     a.seed = seed; a.first_face = first_face; a.light = light;
     for (int j = 0; j < 27; j++) { a.lo[j] = ranges[2 * j]; a.hi[j] = ranges[2 * j + 1]; }
     hipLaunchKernelGGL(fr::synth_light_rgb_kernel, dim3((unsigned)B, 1, 1), dim3(64, 1, 1), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
-}
-
-int fr_launch_synth_shade_rgb(const float* tex_img, const float* normal, const float* tri_ind, const float* light,
-                              const float* background, int bg_batch, int B, int H, int W, float gain, float offset, float* im_rgb,
-                              float* im_gray, float* mask, hipStream_t stream) {
-    const int HW = H * W;
-    hipLaunchKernelGGL(fr::synth_shade_rgb_kernel, dim3((unsigned)(((long long)HW + 255) / 256), (unsigned)B, 1), dim3(256, 1, 1), 0,
-                       stream, tex_img, normal, tri_ind, light, background, bg_batch, HW, gain, offset, im_rgb, im_gray, mask);
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }
 
@@ -281,13 +271,29 @@ int fr_launch_synth_texture(const float* mu_tex, const float* pc_tex, const floa
     return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
 }
 
+// the shaders' launch: out = the kernel's output planes, in its order
+template <class Kernel, class... Out>
+static int synth_shade_launch(Kernel kernel, const float* tex_img, const float* normal, const float* tri_ind, const float* light,
+                              const float* background, int bg_batch, int B, int H, int W, float gain, float offset, hipStream_t stream,
+                              Out*... out) {
+    const int HW = H * W;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(((long long)HW + 255) / 256), (unsigned)B, 1), dim3(256, 1, 1), 0, stream, tex_img, normal,
+                       tri_ind, light, background, bg_batch, HW, gain, offset, out...);
+    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+}
+
 int fr_launch_synth_shade(const float* tex_img, const float* normal, const float* tri_ind, const float* light,
                           const float* background, int bg_batch, int B, int H, int W, float gain, float offset, float* im_gray,
                           float* mask, hipStream_t stream) {
-    const int HW = H * W;
-    hipLaunchKernelGGL(fr::synth_shade_kernel, dim3((unsigned)(((long long)HW + 255) / 256), (unsigned)B, 1), dim3(256, 1, 1), 0, stream,
-                       tex_img, normal, tri_ind, light, background, bg_batch, HW, gain, offset, im_gray, mask);
-    return hipGetLastError() == hipSuccess ? FR_OK : FR_ERR_LAUNCH;
+    return synth_shade_launch(fr::synth_shade_kernel, tex_img, normal, tri_ind, light, background, bg_batch, B, H, W, gain, offset,
+                              stream, im_gray, mask);
+}
+
+int fr_launch_synth_shade_rgb(const float* tex_img, const float* normal, const float* tri_ind, const float* light,
+                              const float* background, int bg_batch, int B, int H, int W, float gain, float offset, float* im_rgb,
+                              float* im_gray, float* mask, hipStream_t stream) {
+    return synth_shade_launch(fr::synth_shade_rgb_kernel, tex_img, normal, tri_ind, light, background, bg_batch, B, H, W, gain, offset,
+                              stream, im_rgb, im_gray, mask);
 }
 
 size_t fr_synth_texture_backward_workspace_impl(int B, int N, int K) {

@@ -14,6 +14,7 @@ C ABI of include/fr_hotpath.h through ctypes on torch's current HIP stream.  Lik
 module loads the native library and builds it first if the .so is missing (reference ops.py:63-72) -- but there
 is no fallback path: no library or no GPU tensor => an exception.
 """
+import collections
 import ctypes
 import importlib.util
 import os
@@ -1306,77 +1307,118 @@ def synth_texture(mu_tex, pc_tex, alpha, out=None):
     return _synth_texture_call(mu_tex, pc_tex, alpha, out)[0]
 
 
-def _photo_plane(h, t, name, B, H, W, dev):
+# ---- the shading models (csrc/fr_shade.h) as this file sees them: the gray one and the colour one are the same calls over other sizes ----
+# loss: the photometric op, "fr_" + loss its entry points' prefix; kind: the pool kind of its forward's state; shader: the shading op
+# and "fr_" + shader its entry point; light: a face's lighting; channels: of the image, the target and the background; sums: float64
+# sums per face, 2 + the lighting's size; planes: the shader's outputs (name, channels), in the entry point's order
+_ShadeModel = collections.namedtuple("_ShadeModel", "loss kind shader light channels sums planes")
+_GRAY = _ShadeModel("photo_loss", "photo_loss", "synth_shade", (4,), 1, 6, (("im_gray", 1), ("mask", 1)))
+_RGB = _ShadeModel("photo_loss_rgb", "photo_loss_rgb", "synth_shade_rgb", (3, 9), 3, 29, (("im_rgb", 3), ("im_gray", 1), ("mask", 1)))
+
+
+def _model_light(h, m, op, light, B, dev):
+    l_c = h.require_gpu_f32(light.detach(), "light")
+    if tuple(l_c.shape) != (B,) + m.light or l_c.device != dev:
+        raise ValueError("%s: light must be %s on %s (got %s on %s)" % (op, list((B,) + m.light), dev, tuple(l_c.shape), l_c.device))
+    return l_c
+
+
+def _photo_plane(h, op, t, name, B, H, W, dev):
     t_c = h.require_gpu_f32(t.detach(), name)
-    _check_plane("photo_loss", name, t_c, B, H, W, 1, dev, "normal", flat=True)
+    _check_plane(op, name, t_c, B, H, W, 1, dev, "normal", flat=True)
     return t_c
+
+
+def _photo_forward(m, ctx, tex_img, normal, tri_ind, light, target, weight, gain, offset):
+    """The forward of both photometric nodes, for the model m: it saves its inputs by reference and the forward's sums [B, m.sums]
+    (the lighting gradient is linear in them); nothing plane-sized of its own.  The forward's state (m.sums float64 partials per
+    tile) is dead once the forward has run: it is the pooled per-stream buffer of kind m.kind, held across the forward's two
+    launches."""
+    h = _host()
+    L = h.lib()
+    op = m.loss
+    n_c = h.require_gpu_f32(normal.detach(), "normal")
+    if n_c.dim() != 4 or n_c.shape[3] != 3:
+        raise ValueError("%s expects normal [B,H,W,3]" % op)
+    B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+    dev = n_c.device
+    t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
+    tg_c = h.require_gpu_f32(target.detach(), "target")
+    _check_plane(op, "tex_img", t_c, B, H, W, 3, dev, "normal")
+    _check_plane(op, "target", tg_c, B, H, W, m.channels, dev, "normal", flat=m.channels == 1)
+    l_c = _model_light(h, m, op, light, B, dev)
+    ti_c = _photo_plane(h, op, tri_ind, "tri_ind", B, H, W, dev)
+    w_c = _photo_plane(h, op, weight, "weight", B, H, W, dev) if weight is not None else None
+    empty = B * H * W == 0
+    sums = (torch.zeros if empty else torch.empty)((B, m.sums), dtype=torch.float64, device=dev)
+    if not empty:
+        nst = getattr(L, "fr_%s_state_bytes" % op)(B, H, W)
+        with torch.cuda.device(dev), _KINDS_POOL.hold(m.kind, dev, nst) as ent:
+            rc = getattr(L, "fr_%s_forward" % op)(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(tg_c), h.ptr(w_c), B, H, W,
+                                                  float(gain), float(offset), h.ptr(sums), h.ptr(ent.buf), ent.nbytes, h.stream_ptr(dev))
+        h.check(rc, "fr_%s_forward" % op)
+    ctx.save_for_backward(t_c, n_c, ti_c, l_c, tg_c, sums, *(() if w_c is None else (w_c,)))
+    ctx.dims = (B, H, W)
+    ctx.scale = (float(gain), float(offset))
+    ctx.shapes = (tuple(tex_img.shape), tuple(normal.shape), tuple(light.shape))
+    ctx.set_materialize_grads(False)
+    sse, count = sums[:, 0].contiguous(), sums[:, 1].contiguous()
+    ctx.mark_non_differentiable(count)
+    return sse, count
+
+
+def _photo_backward(m, ctx, g_sse):
+    """The backward of both photometric nodes: it asks the kernel only for the outputs needs_input_grad names; target, weight and
+    tri_ind are constants."""
+    if g_sse is None:
+        return (None,) * 8
+    h = _host()
+    t_c, n_c, ti_c, l_c, tg_c, sums = ctx.saved_tensors[:6]
+    w_c = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
+    B, H, W = ctx.dims
+    dev = n_c.device
+    want = ctx.needs_input_grad
+    empty = B * H * W == 0
+    make = torch.zeros if empty else torch.empty
+    gt = make(ctx.shapes[0], dtype=torch.float32, device=dev) if want[0] else None
+    gn = make(ctx.shapes[1], dtype=torch.float32, device=dev) if want[1] else None
+    gl = make(ctx.shapes[2], dtype=torch.float32, device=dev) if want[3] else None
+    if not empty and (want[0] or want[1] or want[3]):
+        g = g_sse.detach().to(device=dev, dtype=torch.float64).contiguous()
+        with torch.cuda.device(dev):
+            rc = getattr(h.lib(), "fr_%s_backward" % m.loss)(h.ptr(g), h.ptr(sums), h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c),
+                                                             h.ptr(tg_c), h.ptr(w_c), B, H, W, ctx.scale[0], ctx.scale[1], h.ptr(gt),
+                                                             h.ptr(gn), h.ptr(gl), h.stream_ptr(dev))
+        h.check(rc, "fr_%s_backward" % m.loss)
+    return gt, gn, None, gl, None, None, None, None
 
 
 class _PhotoLoss(torch.autograd.Function):
     """fr_photo_loss_forward / _backward (include/fr_hotpath.h, "photometric loss") as one autograd node: (tex_img, normal, tri_ind,
-    light, target, weight, gain, offset) -> (sse [B], count [B]) float64.  It saves its inputs by reference and the forward's
-    sums [B,6] (the lighting gradient is linear in them); nothing plane-sized of its own.  The forward's state (six float64 partials
-    per tile) is dead once the forward has run: it is the pooled per-stream buffer of kind "photo_loss", held across the forward's
-    two launches.  The backward asks the kernel only for the outputs needs_input_grad names; target, weight and tri_ind are
-    constants."""
+    light [B,4], target, weight, gain, offset) -> (sse [B], count [B]) float64: _photo_forward / _photo_backward over the gray model
+    (sums [B,6], pool kind "photo_loss")."""
 
     @staticmethod
-    def forward(ctx, tex_img, normal, tri_ind, light, target, weight, gain, offset):
-        h = _host()
-        L = h.lib()
-        n_c = h.require_gpu_f32(normal.detach(), "normal")
-        if n_c.dim() != 4 or n_c.shape[3] != 3:
-            raise ValueError("photo_loss expects normal [B,H,W,3]")
-        B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
-        dev = n_c.device
-        t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
-        l_c = h.require_gpu_f32(light.detach(), "light")
-        _check_plane("photo_loss", "tex_img", t_c, B, H, W, 3, dev, "normal")
-        if tuple(l_c.shape) != (B, 4) or l_c.device != dev:
-            raise ValueError("photo_loss: light must be [%d,4] on %s (got %s on %s)" % (B, dev, tuple(l_c.shape), l_c.device))
-        ti_c = _photo_plane(h, tri_ind, "tri_ind", B, H, W, dev)
-        tg_c = _photo_plane(h, target, "target", B, H, W, dev)
-        w_c = _photo_plane(h, weight, "weight", B, H, W, dev) if weight is not None else None
-        empty = B * H * W == 0
-        sums = (torch.zeros if empty else torch.empty)((B, 6), dtype=torch.float64, device=dev)
-        if not empty:
-            nst = L.fr_photo_loss_state_bytes(B, H, W)
-            with torch.cuda.device(dev), _KINDS_POOL.hold("photo_loss", dev, nst) as ent:
-                rc = L.fr_photo_loss_forward(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(tg_c), h.ptr(w_c), B, H, W,
-                                             float(gain), float(offset), h.ptr(sums), h.ptr(ent.buf), ent.nbytes, h.stream_ptr(dev))
-            h.check(rc, "fr_photo_loss_forward")
-        ctx.save_for_backward(t_c, n_c, ti_c, l_c, tg_c, sums, *(() if w_c is None else (w_c,)))
-        ctx.dims = (B, H, W)
-        ctx.scale = (float(gain), float(offset))
-        ctx.shapes = (tuple(tex_img.shape), tuple(normal.shape), tuple(light.shape))
-        ctx.set_materialize_grads(False)
-        sse, count = sums[:, 0].contiguous(), sums[:, 1].contiguous()
-        ctx.mark_non_differentiable(count)
-        return sse, count
+    def forward(ctx, *args):
+        return _photo_forward(_GRAY, ctx, *args)
 
     @staticmethod
     def backward(ctx, g_sse, g_count):
-        if g_sse is None:
-            return (None,) * 8
-        h = _host()
-        t_c, n_c, ti_c, l_c, tg_c, sums = ctx.saved_tensors[:6]
-        w_c = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
-        B, H, W = ctx.dims
-        dev = n_c.device
-        want = ctx.needs_input_grad
-        empty = B * H * W == 0
-        make = torch.zeros if empty else torch.empty
-        gt = make(ctx.shapes[0], dtype=torch.float32, device=dev) if want[0] else None
-        gn = make(ctx.shapes[1], dtype=torch.float32, device=dev) if want[1] else None
-        gl = make(ctx.shapes[2], dtype=torch.float32, device=dev) if want[3] else None
-        if not empty and (want[0] or want[1] or want[3]):
-            g = g_sse.detach().to(device=dev, dtype=torch.float64).contiguous()
-            with torch.cuda.device(dev):
-                rc = h.lib().fr_photo_loss_backward(h.ptr(g), h.ptr(sums), h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(tg_c),
-                                                    h.ptr(w_c), B, H, W, ctx.scale[0], ctx.scale[1], h.ptr(gt), h.ptr(gn), h.ptr(gl),
-                                                    h.stream_ptr(dev))
-            h.check(rc, "fr_photo_loss_backward")
-        return gt, gn, None, gl, None, None, None, None
+        return _photo_backward(_GRAY, ctx, g_sse)
+
+
+class _PhotoLossRGB(torch.autograd.Function):
+    """fr_photo_loss_rgb_forward / _backward (include/fr_hotpath.h, "colour shading") as one autograd node: (tex_img, normal,
+    tri_ind, light [B,3,9], target [B,H,W,3], weight, gain, offset) -> (sse [B], count [B]) float64: _photo_forward /
+    _photo_backward over the colour model (sums [B,29], pool kind "photo_loss_rgb")."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        return _photo_forward(_RGB, ctx, *args)
+
+    @staticmethod
+    def backward(ctx, g_sse, g_count):
+        return _photo_backward(_RGB, ctx, g_sse)
 
 
 def photo_loss(tex_img, normal, tri_ind, light, target, weight=None, gain=1.0, offset=0.0):
@@ -1398,40 +1440,43 @@ def synth_shade(tex_img, normal, tri_ind, light, background=None, gain=1.0, offs
     or [B,H,W,1]; 0 without one).  tex_img, normal [B,H,W,3] (the op's raw normal), tri_ind [B,H,W,1], light [B,4].
     -> (im_gray, mask) [B,H,W,1], mask = 1.0 where tri_ind >= 0 else 0.0.  fp32 in a stated order, bit-exact against numpy
     (include/fr_hotpath.h).  Nothing requires grad.  Runs on the current stream."""
+    return _synth_shade_call(_GRAY, tex_img, normal, tri_ind, light, background, gain, offset, out)
+
+
+def _synth_shade_call(m, tex_img, normal, tri_ind, light, background, gain, offset, out):
+    """synth_shade / synth_shade_rgb for the model m: the checks, the output planes m.planes and the one launch"""
     h = _host()
+    op = m.shader
     t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
     n_c = h.require_gpu_f32(normal.detach(), "normal")
     ti_c = h.require_gpu_f32(tri_ind.detach(), "tri_ind")
-    l_c = h.require_gpu_f32(light.detach(), "light")
     if n_c.dim() != 4 or n_c.shape[3] != 3:
-        raise ValueError("synth_shade expects normal [B,H,W,3]")
+        raise ValueError("%s expects normal [B,H,W,3]" % op)
     B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
     dev = n_c.device
     bg_c, bg_batch = None, 0
     if background is not None:
         bg_c = h.require_gpu_f32(background.detach(), "background")
         bg_batch = int(bg_c.shape[0]) if bg_c.dim() == 4 else -1
-        if bg_batch not in (1, B) or tuple(bg_c.shape[1:]) != (H, W, 1):
-            raise ValueError("synth_shade: background must be [1,%d,%d,1] or [%d,%d,%d,1] (got %s)"
-                             % (H, W, B, H, W, tuple(bg_c.shape)))
-    _check_plane("synth_shade", "tex_img", t_c, B, H, W, 3)   # (every device is checked below, behind every shape)
-    _check_plane("synth_shade", "tri_ind", ti_c, B, H, W, 1)
-    if tuple(l_c.shape) != (B, 4):
-        raise ValueError("synth_shade: light must be [%d, 4] (got %s)" % (B, tuple(l_c.shape)))
-    for t, name in ((t_c, "tex_img"), (ti_c, "tri_ind"), (l_c, "light"), (bg_c, "background")):
-        if t is not None and t.device != dev:
-            raise ValueError("synth_shade: %s is on %s, normal on %s" % (name, t.device, dev))
+        if bg_batch not in (1, B) or tuple(bg_c.shape[1:]) != (H, W, m.channels) or bg_c.device != dev:
+            raise ValueError("%s: background must be [1,%d,%d,%d] or [%d,%d,%d,%d] on %s (got %s on %s)"
+                             % (op, H, W, m.channels, B, H, W, m.channels, dev, tuple(bg_c.shape), bg_c.device))
+    _check_plane(op, "tex_img", t_c, B, H, W, 3, dev, "normal")
+    _check_plane(op, "tri_ind", ti_c, B, H, W, 1, dev, "normal")
+    l_c = _model_light(h, m, op, light, B, dev)
     if out is None:
-        out = (torch.empty((B, H, W, 1), dtype=torch.float32, device=dev), torch.empty((B, H, W, 1), dtype=torch.float32, device=dev))
-    im_gray, mask = out
-    for t, name in ((im_gray, "im_gray"), (mask, "mask")):
-        if h.require_gpu_f32(t, name) is not t or tuple(t.shape) != (B, H, W, 1) or t.device != dev:
-            raise ValueError("synth_shade: out %s must be a contiguous float32 tensor [%d,%d,%d,1] on %s" % (name, B, H, W, dev))
+        out = tuple(torch.empty((B, H, W, c), dtype=torch.float32, device=dev) for _name, c in m.planes)
+    out = tuple(out)
+    if len(out) != len(m.planes):
+        raise ValueError("%s: out must be the %d tensors (%s)" % (op, len(m.planes), ", ".join(name for name, _c in m.planes)))
+    for t, (name, c) in zip(out, m.planes):
+        if h.require_gpu_f32(t, name) is not t or tuple(t.shape) != (B, H, W, c) or t.device != dev:
+            raise ValueError("%s: out %s must be a contiguous float32 tensor [%d,%d,%d,%d] on %s" % (op, name, B, H, W, c, dev))
     with torch.cuda.device(dev):
-        rc = h.lib().fr_synth_shade(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(bg_c), bg_batch, B, H, W, float(gain),
-                                    float(offset), h.ptr(im_gray), h.ptr(mask), h.stream_ptr(dev))
-    h.check(rc, "fr_synth_shade")
-    return im_gray, mask
+        rc = getattr(h.lib(), "fr_" + op)(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(bg_c), bg_batch, B, H, W, float(gain),
+                                          float(offset), *[h.ptr(t) for t in out], h.stream_ptr(dev))
+    h.check(rc, "fr_" + op)
+    return out
 
 
 # ---- colour shading (opt-in): per-channel albedo under a second-order lighting per channel ---------------------------------------------
@@ -1463,13 +1508,6 @@ def synth_light_rgb(seed, first_face, batch, ranges=SYNTH_LIGHT_RANGES_RGB, devi
     return out
 
 
-def _rgb_light(h, op, light, B, dev):
-    l_c = h.require_gpu_f32(light.detach(), "light")
-    if tuple(l_c.shape) != (B, 3, 9) or l_c.device != dev:
-        raise ValueError("%s: light must be [%d,3,9] on %s (got %s on %s)" % (op, B, dev, tuple(l_c.shape), l_c.device))
-    return l_c
-
-
 def synth_shade_rgb(tex_img, normal, tri_ind, light, background=None, gain=1.0, offset=0.0, out=None):
     """The colour image of a render's planes (fr_synth_shade_rgb, one lane per pixel): where tri_ind >= 0, per channel c,
     im_rgb_c = a_c max(s_c, 0) gain + offset with a_c = clamp_min(tex_img_c, 1e-6) -- no mean over the channels -- and
@@ -1478,101 +1516,7 @@ def synth_shade_rgb(tex_img, normal, tri_ind, light, background=None, gain=1.0, 
     gray of im_rgb, 0.3 R + 0.59 G + 0.11 B, background included: the plane the nets take.  tex_img, normal [B,H,W,3],
     tri_ind [B,H,W,1], light [B,3,9].  -> (im_rgb [B,H,W,3], im_gray [B,H,W,1], mask [B,H,W,1]); out: three tensors to write
     instead.  fp32 in a stated order, bit-exact against numpy.  Nothing requires grad.  Runs on the current stream."""
-    h = _host()
-    t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
-    n_c = h.require_gpu_f32(normal.detach(), "normal")
-    ti_c = h.require_gpu_f32(tri_ind.detach(), "tri_ind")
-    if n_c.dim() != 4 or n_c.shape[3] != 3:
-        raise ValueError("synth_shade_rgb expects normal [B,H,W,3]")
-    B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
-    dev = n_c.device
-    bg_c, bg_batch = None, 0
-    if background is not None:
-        bg_c = h.require_gpu_f32(background.detach(), "background")
-        bg_batch = int(bg_c.shape[0]) if bg_c.dim() == 4 else -1
-        if bg_batch not in (1, B) or tuple(bg_c.shape[1:]) != (H, W, 3) or bg_c.device != dev:
-            raise ValueError("synth_shade_rgb: background must be [1,%d,%d,3] or [%d,%d,%d,3] on %s (got %s on %s)"
-                             % (H, W, B, H, W, dev, tuple(bg_c.shape), bg_c.device))
-    _check_plane("synth_shade_rgb", "tex_img", t_c, B, H, W, 3, dev, "normal")
-    _check_plane("synth_shade_rgb", "tri_ind", ti_c, B, H, W, 1, dev, "normal")
-    l_c = _rgb_light(h, "synth_shade_rgb", light, B, dev)
-    if out is None:
-        f32 = dict(dtype=torch.float32, device=dev)
-        out = (torch.empty((B, H, W, 3), **f32), torch.empty((B, H, W, 1), **f32), torch.empty((B, H, W, 1), **f32))
-    im_rgb, im_gray, mask = out
-    for t, name, c in ((im_rgb, "im_rgb", 3), (im_gray, "im_gray", 1), (mask, "mask", 1)):
-        if h.require_gpu_f32(t, name) is not t or tuple(t.shape) != (B, H, W, c) or t.device != dev:
-            raise ValueError("synth_shade_rgb: out %s must be a contiguous float32 tensor [%d,%d,%d,%d] on %s" % (name, B, H, W, c, dev))
-    with torch.cuda.device(dev):
-        rc = h.lib().fr_synth_shade_rgb(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(bg_c), bg_batch, B, H, W, float(gain),
-                                        float(offset), h.ptr(im_rgb), h.ptr(im_gray), h.ptr(mask), h.stream_ptr(dev))
-    h.check(rc, "fr_synth_shade_rgb")
-    return im_rgb, im_gray, mask
-
-
-class _PhotoLossRGB(torch.autograd.Function):
-    """fr_photo_loss_rgb_forward / _backward (include/fr_hotpath.h, "colour shading") as one autograd node: (tex_img, normal,
-    tri_ind, light [B,3,9], target [B,H,W,3], weight, gain, offset) -> (sse [B], count [B]) float64.  As _PhotoLoss: it saves its
-    inputs by reference and the forward's sums [B,29]; the forward's state is the pooled per-stream buffer of kind
-    "photo_loss_rgb", held across the forward's two launches; the backward asks the kernel only for the outputs needs_input_grad
-    names."""
-
-    @staticmethod
-    def forward(ctx, tex_img, normal, tri_ind, light, target, weight, gain, offset):
-        h = _host()
-        L = h.lib()
-        n_c = h.require_gpu_f32(normal.detach(), "normal")
-        if n_c.dim() != 4 or n_c.shape[3] != 3:
-            raise ValueError("photo_loss_rgb expects normal [B,H,W,3]")
-        B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
-        dev = n_c.device
-        t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
-        tg_c = h.require_gpu_f32(target.detach(), "target")
-        _check_plane("photo_loss_rgb", "tex_img", t_c, B, H, W, 3, dev, "normal")
-        _check_plane("photo_loss_rgb", "target", tg_c, B, H, W, 3, dev, "normal")
-        l_c = _rgb_light(h, "photo_loss_rgb", light, B, dev)
-        ti_c = _photo_plane(h, tri_ind, "tri_ind", B, H, W, dev)
-        w_c = _photo_plane(h, weight, "weight", B, H, W, dev) if weight is not None else None
-        empty = B * H * W == 0
-        sums = (torch.zeros if empty else torch.empty)((B, 29), dtype=torch.float64, device=dev)
-        if not empty:
-            nst = L.fr_photo_loss_rgb_state_bytes(B, H, W)
-            with torch.cuda.device(dev), _KINDS_POOL.hold("photo_loss_rgb", dev, nst) as ent:
-                rc = L.fr_photo_loss_rgb_forward(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c), h.ptr(tg_c), h.ptr(w_c), B, H, W,
-                                                 float(gain), float(offset), h.ptr(sums), h.ptr(ent.buf), ent.nbytes, h.stream_ptr(dev))
-            h.check(rc, "fr_photo_loss_rgb_forward")
-        ctx.save_for_backward(t_c, n_c, ti_c, l_c, tg_c, sums, *(() if w_c is None else (w_c,)))
-        ctx.dims = (B, H, W)
-        ctx.scale = (float(gain), float(offset))
-        ctx.shapes = (tuple(tex_img.shape), tuple(normal.shape), tuple(light.shape))
-        ctx.set_materialize_grads(False)
-        sse, count = sums[:, 0].contiguous(), sums[:, 1].contiguous()
-        ctx.mark_non_differentiable(count)
-        return sse, count
-
-    @staticmethod
-    def backward(ctx, g_sse, g_count):
-        if g_sse is None:
-            return (None,) * 8
-        h = _host()
-        t_c, n_c, ti_c, l_c, tg_c, sums = ctx.saved_tensors[:6]
-        w_c = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
-        B, H, W = ctx.dims
-        dev = n_c.device
-        want = ctx.needs_input_grad
-        empty = B * H * W == 0
-        make = torch.zeros if empty else torch.empty
-        gt = make(ctx.shapes[0], dtype=torch.float32, device=dev) if want[0] else None
-        gn = make(ctx.shapes[1], dtype=torch.float32, device=dev) if want[1] else None
-        gl = make(ctx.shapes[2], dtype=torch.float32, device=dev) if want[3] else None
-        if not empty and (want[0] or want[1] or want[3]):
-            g = g_sse.detach().to(device=dev, dtype=torch.float64).contiguous()
-            with torch.cuda.device(dev):
-                rc = h.lib().fr_photo_loss_rgb_backward(h.ptr(g), h.ptr(sums), h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(l_c),
-                                                        h.ptr(tg_c), h.ptr(w_c), B, H, W, ctx.scale[0], ctx.scale[1], h.ptr(gt),
-                                                        h.ptr(gn), h.ptr(gl), h.stream_ptr(dev))
-            h.check(rc, "fr_photo_loss_rgb_backward")
-        return gt, gn, None, gl, None, None, None, None
+    return _synth_shade_call(_RGB, tex_img, normal, tri_ind, light, background, gain, offset, out)
 
 
 def photo_loss_rgb(tex_img, normal, tri_ind, light, target, weight=None, gain=1.0, offset=0.0):

@@ -21,6 +21,7 @@ NOT covered: the owner-scatter geometry with shift > 0 (more than 2^20 pixels pe
 plane, and CONSUMER_PIXELS keeps every case far below it; tests/test_render_backward_exact_gpu.py reaches it for the render
 backward alone.  tests/test_fuzz_scenes_cpu.py holds the seed set to reaching every class of input this file exists
 for, and names the seed base."""
+import collections
 import os
 
 import numpy as np
@@ -136,33 +137,48 @@ def check_mesh(c, planes, what):
     assert (g_out[:, :, c.nver:].view(np.uint32) == SENT).all(), what + ": mesh_lift wrote a pad column"
 
 
-def check_shade_and_photo_loss(c, planes, what):
+# One shading model as check_shade_and_photo_loss sees it: the op pair (`shader`, whose outputs are `planes`, and `loss`, called raw
+# through `call`), the numpy models (`ref`: the loss's module; `shade`: the shader's function) and the names of the case's light,
+# target and background fields (background None: the case has none for this model, the shader runs without).
+ShadeModel = collections.namedtuple("ShadeModel", "shader planes loss call ref shade light target background")
+GRAY = ShadeModel("synth_shade", ("im_gray", "mask"), "photo_loss", PhotoCall, RP, RS.shade, "light", "target", None)
+RGB = ShadeModel("synth_shade_rgb", ("im_rgb", "im_gray", "mask"), "photo_loss_rgb", PhotoRgbCall, RPR, RPR.shade, "light_rgb",
+                 "target_rgb", "background_rgb")
+
+
+def check_shade_and_photo_loss(m, c, planes, what):
+    """the shader and the photometric loss of the model m (GRAY or RGB) on the case's light, target and background for that model, its
+    weight and grad_sse"""
     tex_img, normal, ti = planes[1], planes[2], planes[3]
     weighted = c.weight is not None
-    im, mask = ops().synth_shade(_t(tex_img), _t(normal), _t(ti), _t(c.light), gain=GAIN, offset=OFFSET)
-    want_im, want_mask = RS.shade(tex_img, normal, ti, c.light, None, GAIN, OFFSET)
-    assert_bits_equal(im.cpu().numpy(), want_im, what + ": synth_shade im_gray")
-    assert_bits_equal(mask.cpu().numpy(), want_mask, what + ": synth_shade mask")
+    light, target = getattr(c, m.light), getattr(c, m.target)
+    bg = getattr(c, m.background) if m.background else None
+    got = getattr(ops(), m.shader)(_t(tex_img), _t(normal), _t(ti), _t(light), background=None if bg is None else _t(bg),
+                                   gain=GAIN, offset=OFFSET)
+    for g, w, name in zip(got, m.shade(tex_img, normal, ti, light, bg, GAIN, OFFSET), m.planes):
+        assert_bits_equal(g.cpu().numpy(), w, "%s: %s %s" % (what, m.shader, name))
+    what = "%s: %s" % (what, m.loss)
 
     def run(nrm):
-        call = PhotoCall((tex_img, nrm, ti, c.light, c.target, c.weight), weighted)
+        call = m.call((tex_img, nrm, ti, light, target, c.weight), weighted)
         sums = call.forward()
         grads = call.backward(sums, c.grad_sse)
         return sums.cpu().numpy(), [g.cpu().numpy() for g in grads]
     sums, (gt, gn, gl) = run(normal)
-    want = RP.forward(tex_img, normal, ti, c.light, c.target, c.weight, GAIN, OFFSET)
-    assert_f64_bits_equal(sums, want, what + ": photo_loss sums")
-    gt_w, gn_w, gl_w, A = RP.backward(tex_img, normal, ti, c.light, c.target, c.grad_sse, c.weight, GAIN, OFFSET, sums=want)
-    assert_bits_equal(gt, gt_w, what + ": photo_loss grad_tex_img")
-    assert_bits_equal(gl, gl_w, what + ": photo_loss grad_light")
-    # grad_normal: the header's bound where the model is finite; where it is not, the same NaN or the same Inf
+    want = m.ref.forward(tex_img, normal, ti, light, target, c.weight, GAIN, OFFSET)
+    assert_f64_bits_equal(sums, want, what + " sums")
+    gt_w, gn_w, gl_w, A = m.ref.backward(tex_img, normal, ti, light, target, c.grad_sse, c.weight, GAIN, OFFSET, sums=want)
+    assert_bits_equal(gt, gt_w, what + " grad_tex_img")
+    assert_bits_equal(gl, gl_w, what + " grad_light")
+    # grad_normal: the header's bound (the gray one, with the model's own g~) where the model is finite; where it is not, the same NaN
+    # or the same Inf
     fin = np.isfinite(gn_w)
-    assert np.array_equal(np.isnan(gn), np.isnan(gn_w)), what + ": photo_loss grad_normal NaNs"
-    assert np.array_equal(gn[~fin & ~np.isnan(gn_w)], gn_w[~fin & ~np.isnan(gn_w)]), what + ": photo_loss grad_normal Infs"
+    assert np.array_equal(np.isnan(gn), np.isnan(gn_w)), what + " grad_normal NaNs"
+    assert np.array_equal(gn[~fin & ~np.isnan(gn_w)], gn_w[~fin & ~np.isnan(gn_w)]), what + " grad_normal Infs"
     bound = 2.0 ** -24 * np.abs(gn_w.astype(np.float64)) + 2.0 ** -40 * np.broadcast_to(A[..., None], gn_w.shape)
     with np.errstate(invalid="ignore"):
         err = np.abs(gn.astype(np.float64) - gn_w.astype(np.float64))
-        assert (err[fin] <= bound[fin]).all(), (what + ": photo_loss grad_normal", float(np.nanmax(err[fin] / bound[fin])))
+        assert (err[fin] <= bound[fin]).all(), (what + " grad_normal", float(np.nanmax(err[fin] / bound[fin])))
     covered = ti[..., 0] >= 0
     assert not gt[~covered].view(np.uint32).any() and not gn[~covered].view(np.uint32).any()
     # a NaN normal reaches its own pixel and its own face's sums, and nothing else changes by a bit: the same call with those
@@ -171,11 +187,11 @@ def check_shade_and_photo_loss(c, planes, what):
     if sick.any():
         clean_sums, (gt2, gn2, gl2) = run(np.where(sick[..., None], np.float32(0.5), normal))
         well = ~sick.reshape(c.B, -1).any(1)
-        assert_f64_bits_equal(sums[well], clean_sums[well], what + ": photo_loss, the faces without a NaN normal")
-        assert_f64_bits_equal(sums[:, 1], clean_sums[:, 1], what + ": photo_loss cnt")
-        assert_bits_equal(gl[well], gl2[well], what + ": photo_loss grad_light, the faces without a NaN normal")
-        assert_bits_equal(gt[~sick], gt2[~sick], what + ": photo_loss grad_tex_img, the pixels without a NaN normal")
-        assert_bits_equal(gn[~sick], gn2[~sick], what + ": photo_loss grad_normal, the pixels without a NaN normal")
+        assert_f64_bits_equal(sums[well], clean_sums[well], what + ", the faces without a NaN normal")
+        assert_f64_bits_equal(sums[:, 1], clean_sums[:, 1], what + " cnt")
+        assert_bits_equal(gl[well], gl2[well], what + " grad_light, the faces without a NaN normal")
+        assert_bits_equal(gt[~sick], gt2[~sick], what + " grad_tex_img, the pixels without a NaN normal")
+        assert_bits_equal(gn[~sick], gn2[~sick], what + " grad_normal, the pixels without a NaN normal")
         assert np.isnan(sums[~well, 0]).all() and np.isfinite(clean_sums[:, 1]).all()
 
 
@@ -230,50 +246,6 @@ def check_coverage(c, ti, what, profiles=(0, 1)):
     # (0, 1), and the lowest k decides which vertices the terms go to
     run(c.vertex_on_segment(ti), what + ", vertices on a segment", (0, 1), False)
     return keep, want
-
-
-def check_shade_and_photo_loss_rgb(c, planes, what):
-    """check_shade_and_photo_loss for the colour pair: the case's light_rgb, target_rgb and background_rgb, its weight and grad_sse"""
-    tex_img, normal, ti = planes[1], planes[2], planes[3]
-    weighted = c.weight is not None
-    bg = c.background_rgb
-    got = ops().synth_shade_rgb(_t(tex_img), _t(normal), _t(ti), _t(c.light_rgb), background=None if bg is None else _t(bg),
-                                gain=GAIN, offset=OFFSET)
-    for g, w, name in zip(got, RPR.shade(tex_img, normal, ti, c.light_rgb, bg, GAIN, OFFSET), ("im_rgb", "im_gray", "mask")):
-        assert_bits_equal(g.cpu().numpy(), w, "%s: synth_shade_rgb %s" % (what, name))
-
-    def run(nrm):
-        call = PhotoRgbCall((tex_img, nrm, ti, c.light_rgb, c.target_rgb, c.weight), weighted)
-        sums = call.forward()
-        grads = call.backward(sums, c.grad_sse)
-        return sums.cpu().numpy(), [g.cpu().numpy() for g in grads]
-    sums, (gt, gn, gl) = run(normal)
-    want = RPR.forward(tex_img, normal, ti, c.light_rgb, c.target_rgb, c.weight, GAIN, OFFSET)
-    assert_f64_bits_equal(sums, want, what + ": photo_loss_rgb sums")
-    gt_w, gn_w, gl_w, A = RPR.backward(tex_img, normal, ti, c.light_rgb, c.target_rgb, c.grad_sse, c.weight, GAIN, OFFSET, sums=want)
-    assert_bits_equal(gt, gt_w, what + ": photo_loss_rgb grad_tex_img")
-    assert_bits_equal(gl, gl_w, what + ": photo_loss_rgb grad_light")
-    # grad_normal: the gray header's bound with the colour g~ where the model is finite; where it is not, the same NaN or the same Inf
-    fin = np.isfinite(gn_w)
-    assert np.array_equal(np.isnan(gn), np.isnan(gn_w)), what + ": photo_loss_rgb grad_normal NaNs"
-    assert np.array_equal(gn[~fin & ~np.isnan(gn_w)], gn_w[~fin & ~np.isnan(gn_w)]), what + ": photo_loss_rgb grad_normal Infs"
-    bound = 2.0 ** -24 * np.abs(gn_w.astype(np.float64)) + 2.0 ** -40 * np.broadcast_to(A[..., None], gn_w.shape)
-    with np.errstate(invalid="ignore"):
-        err = np.abs(gn.astype(np.float64) - gn_w.astype(np.float64))
-        assert (err[fin] <= bound[fin]).all(), (what + ": photo_loss_rgb grad_normal", float(np.nanmax(err[fin] / bound[fin])))
-    covered = ti[..., 0] >= 0
-    assert not gt[~covered].view(np.uint32).any() and not gn[~covered].view(np.uint32).any()
-    # a NaN normal reaches its own pixel and its own face's sums, and nothing else changes by a bit (as in the gray check)
-    sick = covered & np.isnan(normal).any(-1)
-    if sick.any():
-        clean_sums, (gt2, gn2, gl2) = run(np.where(sick[..., None], np.float32(0.5), normal))
-        well = ~sick.reshape(c.B, -1).any(1)
-        assert_f64_bits_equal(sums[well], clean_sums[well], what + ": photo_loss_rgb, the faces without a NaN normal")
-        assert_f64_bits_equal(sums[:, 1], clean_sums[:, 1], what + ": photo_loss_rgb cnt")
-        assert_bits_equal(gl[well], gl2[well], what + ": photo_loss_rgb grad_light, the faces without a NaN normal")
-        assert_bits_equal(gt[~sick], gt2[~sick], what + ": photo_loss_rgb grad_tex_img, the pixels without a NaN normal")
-        assert_bits_equal(gn[~sick], gn2[~sick], what + ": photo_loss_rgb grad_normal, the pixels without a NaN normal")
-        assert np.isnan(sums[~well, 0]).all() and np.isfinite(clean_sums[:, 1]).all()
 
 
 def check_albedo_fit(c, planes, what):
@@ -351,9 +323,9 @@ def run_case(c, oracle, what):
     depth_part = check_depth_interp(c, ti, what)
     tex_part = check_texture_backward(c, ti, what)
     check_mesh(c, want, what)
-    check_shade_and_photo_loss(c, want, what)
+    check_shade_and_photo_loss(GRAY, c, want, what)
     cov_part = check_coverage(c, ti, what)
-    check_shade_and_photo_loss_rgb(c, want, what)
+    check_shade_and_photo_loss(RGB, c, want, what)
     check_albedo_fit(c, want, what)
     check_operator_surface(c, normal_part, depth_part, tex_part, cov_part, what)
     # a second pass on what the rasteriser never emits (fuzz_scenes.ConsumerCase.altered): bad ids in triangles that DO win pixels,
@@ -366,9 +338,9 @@ def run_case(c, oracle, what):
     check_depth_interp(a, ti2, what, one)
     check_texture_backward(a, ti2, what, one)
     check_mesh(a, planes2, what)
-    check_shade_and_photo_loss(a, planes2, what)
+    check_shade_and_photo_loss(GRAY, a, planes2, what)
     check_coverage(a, ti2, what, one)
-    check_shade_and_photo_loss_rgb(a, planes2, what)
+    check_shade_and_photo_loss(RGB, a, planes2, what)
     check_albedo_fit(a, planes2, what)
 
 
