@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libfr_hotpath.so")
 SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_bwd.hip", "fr_render_nbwd.hip",
            "fr_render_tbwd.hip", "fr_sfs.hip", "fr_depth_normals.hip", "fr_geometry.hip", "fr_fine_losses.hip", "fr_depth_interp.hip",
            "fr_albedo_lse.hip", "fr_synth.hip", "fr_photo.hip", "fr_mesh.hip", "fr_coverage.hip", "fr_landmark.hip",
-           "fr_landmark_solve.hip", "fr_landmark_contour.hip"]
+           "fr_landmark_solve.hip", "fr_landmark_contour.hip", "fr_photo_solve.hip"]
 HEADERS = [os.path.join(_CSRC, "fr_common.h"), os.path.join(_CSRC, "fr_decode_shared.h"), os.path.join(_CSRC, "fr_sfs_pinv.h"),
            os.path.join(_CSRC, "fr_owner_scatter.h"), os.path.join(_CSRC, "fr_shade.h"), os.path.join(_CSRC, "fr_landmark_shared.h"),
            os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
@@ -214,6 +214,13 @@ SIGNATURES = {
     "fr_photo_loss_rgb_forward":                      "i:ppppppiiiffppzp",
     "fr_photo_loss_rgb_backward":                     "i:ppppppppiiiffpppp",
     "fr_debug_photo_loss_rgb_geom":                   "v:iiiI",
+    "fr_albedo_basis_rgb_bytes":                      "z:ii",
+    "fr_albedo_basis_rgb_build":                      "i:pppiiipzp",
+    "fr_albedo_image_rgb":                            "i:pppiiiiipp",
+    "fr_photo_solve_rgb_workspace_bytes":             "z:iii",
+    "fr_photo_light_lse_rgb_forward":                 "i:ppppppiiiffdppppzp",
+    "fr_albedo_lse_rgb_forward":                      "i:ppppppiiiiiffdppppzp",
+    "fr_debug_photo_solve_rgb_geom":                  "v:iiiI",
     "fr_mesh_visible":                                "i:ppiiiiipp",
     "fr_mesh_lift":                                   "i:pippppiiiiipipp",
     "fr_mesh_vertex_normals":                         "i:pipppiiipip",

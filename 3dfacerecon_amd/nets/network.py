@@ -326,6 +326,7 @@ class FaceRecNet:
         self._gram_nst = {}      # fr_geometry_loss_state_bytes by batch
         self._gram_lock = threading.Lock()
         self._albedo_basis = None   # the texture basis per triangle in float64 (fr_albedo_basis_build), built on first use
+        self._albedo_basis_rgb = None   # the texture model per triangle and channel (fr_albedo_basis_rgb_build), built on first use
         self._adjacency = None      # the vertex -> triangle CSR table on the device (utils/mesh_io.vertex_adjacency), on first use
         self._landmark_bases = {}   # compact basis images of chosen vertices by id tuple (fr_landmark_basis_build): landmark_basis()
 
@@ -418,6 +419,24 @@ class FaceRecNet:
                     self._albedo_basis = _ops().albedo_basis(self.tri, self.pc_tex)
                 _publish(self.device)
             return self._albedo_basis
+
+    def albedo_basis_rgb(self):
+        """basis [T,3,ndim_tex+1] float64: pc_tex and mu_tex seen through the rasteriser's lookup, per triangle and channel
+        (rendering_layer/ops.py::albedo_basis_rgb), built on first use and cached under the lock albedo_basis() uses (28 MB at the
+        full mesh with ten coefficients).  ValueError without a texture model."""
+        with self._gram_lock:
+            if self._albedo_basis_rgb is None:
+                if self.pc_tex is None:
+                    raise ValueError("the asset dict has no texture model (mu_tex / pc_tex / param_tex)")
+                with torch.cuda.device(self.device):
+                    self._albedo_basis_rgb = _ops().albedo_basis_rgb(self.tri, self.mu_tex, self.pc_tex)
+                _publish(self.device)
+            return self._albedo_basis_rgb
+
+    def photo_solve_rgb(self, tri_ind, normal, target, weight=None, alpha0=None, light0=None, **kwargs):
+        """The closed-form colour fit of this mesh's texture model against `target` [B,H,W,3] on a render's planes
+        (rendering_layer/ops.py::photo_solve_rgb with albedo_basis_rgb()): -> (light [B,3,9], alpha [B,ndim_tex], tex_img, info)."""
+        return _ops().photo_solve_rgb(self.albedo_basis_rgb(), tri_ind, normal, target, weight, alpha0, light0, **kwargs)
 
     def adjacency(self):
         """The vertex -> triangle CSR table of the mesh (utils/mesh_io.vertex_adjacency) as a rendering_layer/ops.py::MeshAdjacency

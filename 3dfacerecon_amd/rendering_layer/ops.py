@@ -1530,6 +1530,165 @@ def photo_loss_rgb(tex_img, normal, tri_ind, light, target, weight=None, gain=1.
     return _PhotoLossRGB.apply(tex_img, normal, tri_ind, light, target, weight, gain, offset)
 
 
+# ---- colour photometric solve (opt-in): per-face least squares for the lighting and for alpha (include/fr_hotpath.h) -----------------
+def albedo_basis_rgb(tri, mu_tex, pc_tex):
+    """basis [T,3,K+1] float64: the texture model seen through the rasteriser's lookup, per channel -- slot k < K the mean over a
+    triangle's three vertices of pc_tex[c N + v, k], slot K the same mean of mu_tex (fr_albedo_basis_rgb_build, bit-exact against
+    numpy).  tri [3,T] float ids, mu_tex [3,N] or [3N], pc_tex [3N,K], 1 <= K <= 15.  Built once per mesh
+    (FaceRecNet.albedo_basis_rgb caches it).  Runs on the current stream."""
+    h = _host()
+    tri_c = h.require_gpu_f32(tri, "tri")
+    mu_c = h.require_gpu_f32(mu_tex.detach().reshape(-1), "mu_tex")
+    pc_c = h.require_gpu_f32(pc_tex.detach(), "pc_tex")
+    _check_tri(tri_c)
+    if pc_c.dim() != 2 or pc_c.shape[0] % 3 != 0 or mu_c.numel() != pc_c.shape[0]:
+        raise ValueError("albedo_basis_rgb expects mu_tex [3N] and pc_tex [3N,K] (got %s, %s)" % (tuple(mu_tex.shape), tuple(pc_c.shape)))
+    dev = tri_c.device
+    if pc_c.device != dev or mu_c.device != dev:
+        raise ValueError("albedo_basis_rgb: mu_tex is on %s, pc_tex on %s, tri on %s" % (mu_c.device, pc_c.device, dev))
+    T, K, nver = int(tri_c.shape[1]), int(pc_c.shape[1]), int(pc_c.shape[0]) // 3
+    L = h.lib()
+    basis = torch.empty((T, 3, K + 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.fr_albedo_basis_rgb_build(h.ptr(tri_c), h.ptr(mu_c), h.ptr(pc_c), nver, T, K, h.ptr(basis),
+                                         L.fr_albedo_basis_rgb_bytes(T, K), h.stream_ptr(dev))
+    h.check(rc, "fr_albedo_basis_rgb_build")
+    return basis
+
+
+def _solve_basis(op, basis, dev):
+    if not (isinstance(basis, torch.Tensor) and basis.dtype == torch.float64 and basis.dim() == 3 and basis.shape[1] == 3
+            and basis.shape[2] >= 2):
+        raise ValueError("%s: basis must be a float64 tensor [T,3,K+1] (albedo_basis_rgb)" % op)
+    if basis.device != dev:
+        raise ValueError("%s: basis is on %s, tri_ind on %s" % (op, basis.device, dev))
+    return basis.detach().contiguous(), int(basis.shape[0]), int(basis.shape[2]) - 1
+
+
+def albedo_image_rgb(basis, tri_ind, alpha):
+    """The albedo plane of the texture model at the coefficients alpha, without blending a [B,3,N] texture or rasterising again
+    (fr_albedo_image_rgb, one lane per pixel): tex_img[b,p,c] = m_c[t] + Phi_c[t] . alpha_b with t = tri_ind[b,p], a float64 chain
+    rounded once; +0 where no triangle of the basis is hit.  basis [T,3,K+1] (albedo_basis_rgb), tri_ind [B,H,W,1] or [B,H,W],
+    alpha [B,K]; -> tex_img [B,H,W,3] fp32, bit-exact against numpy.  Nothing requires grad.  Runs on the current stream."""
+    h = _host()
+    ti_c = h.require_gpu_f32(tri_ind.detach(), "tri_ind")
+    if ti_c.dim() not in (3, 4) or (ti_c.dim() == 4 and ti_c.shape[3] != 1):
+        raise ValueError("albedo_image_rgb expects tri_ind [B,H,W,1] or [B,H,W]")
+    B, H, W = int(ti_c.shape[0]), int(ti_c.shape[1]), int(ti_c.shape[2])
+    dev = ti_c.device
+    b_c, T, K = _solve_basis("albedo_image_rgb", basis, dev)
+    a_c = h.require_gpu_f32(alpha.detach(), "alpha")
+    if tuple(a_c.shape) != (B, K) or a_c.device != dev:
+        raise ValueError("albedo_image_rgb: alpha must be [%d,%d] on %s (got %s on %s)" % (B, K, dev, tuple(a_c.shape), a_c.device))
+    tex_img = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = h.lib().fr_albedo_image_rgb(h.ptr(b_c), h.ptr(ti_c), h.ptr(a_c), B, T, H, W, K, h.ptr(tex_img), h.stream_ptr(dev))
+    h.check(rc, "fr_albedo_image_rgb")
+    return tex_img
+
+
+def _solve_planes(h, op, normal, tri_ind, target, weight):
+    n_c = h.require_gpu_f32(normal.detach(), "normal")
+    if n_c.dim() != 4 or n_c.shape[3] != 3:
+        raise ValueError("%s expects normal [B,H,W,3]" % op)
+    B, H, W = int(n_c.shape[0]), int(n_c.shape[1]), int(n_c.shape[2])
+    dev = n_c.device
+    tg_c = h.require_gpu_f32(target.detach(), "target")
+    _check_plane(op, "target", tg_c, B, H, W, 3, dev, "normal")
+    ti_c = _photo_plane(h, op, tri_ind, "tri_ind", B, H, W, dev)
+    w_c = _photo_plane(h, op, weight, "weight", B, H, W, dev) if weight is not None else None
+    return n_c, ti_c, tg_c, w_c, B, H, W, dev
+
+
+def photo_light_lse_rgb(tex_img, normal, tri_ind, target, weight=None, gate_light=None, gain=1.0, offset=0.0, ridge=0.0,
+                        return_moments=False):
+    """The per-face, per-channel least-squares lighting of the colour model with the texture held (fr_photo_light_lse_rgb_forward):
+    light[b][c] minimises sum_p weight (target_c - offset - gain a_c sum_k light[b][c][k] H_k)^2 + lambda |light[b][c]|^2 over the
+    pixels channel c counts -- covered (tri_ind >= 0), weight > 0 and, with gate_light [B,3,9], lit under it (s_c > 0: the clamp's
+    active set) -- with a_c and H_k the bits of photo_loss_rgb, lambda = ridge x the mean diagonal of the Gram matrix.  tex_img,
+    normal, target [B,H,W,3], tri_ind, weight [B,H,W,1] or [B,H,W].  -> (light [B,3,9] fp32, stats [B,3,4] float64 = {count, E0,
+    E1, ok}[, moments [B,3,16,16]]); a (face, channel) that cannot be fitted gets gate_light's row (0 without one) and ok = 0.
+    float64 MFMA moments in a fixed association, bit-reproducible.  Nothing requires grad.  Runs on the current stream with the
+    per-stream scratch as its workspace."""
+    h = _host()
+    op = "photo_light_lse_rgb"
+    n_c, ti_c, tg_c, w_c, B, H, W, dev = _solve_planes(h, op, normal, tri_ind, target, weight)
+    t_c = h.require_gpu_f32(tex_img.detach(), "tex_img")
+    _check_plane(op, "tex_img", t_c, B, H, W, 3, dev, "normal")
+    g_c = _model_light(h, _RGB, op, gate_light, B, dev) if gate_light is not None else None
+    L = h.lib()
+    make = torch.zeros if B * H * W == 0 else torch.empty
+    light = make((B, 3, 9), dtype=torch.float32, device=dev)
+    moments = make((B, 3, 16, 16), dtype=torch.float64, device=dev)
+    stats = make((B, 3, 4), dtype=torch.float64, device=dev)
+    nws = L.fr_photo_solve_rgb_workspace_bytes(B, H, W)
+    with torch.cuda.device(dev), _KINDS_POOL.hold("photo_solve_rgb", dev, nws) as ent:
+        rc = L.fr_photo_light_lse_rgb_forward(h.ptr(t_c), h.ptr(n_c), h.ptr(ti_c), h.ptr(tg_c), h.ptr(w_c), h.ptr(g_c), B, H, W,
+                                              float(gain), float(offset), float(ridge), h.ptr(light), h.ptr(moments), h.ptr(stats),
+                                              h.ptr(ent.buf), ent.nbytes, h.stream_ptr(dev))
+    h.check(rc, "fr_photo_light_lse_rgb_forward")
+    return (light, stats, moments) if return_moments else (light, stats)
+
+
+def albedo_lse_rgb(basis, tri_ind, normal, light, target, weight=None, gain=1.0, offset=0.0, ridge=0.0, return_moments=False):
+    """The per-face least-squares albedo coefficients of the colour model with the lighting held (fr_albedo_lse_rgb_forward):
+    alpha_b minimises sum_p sum_c weight (target_c - offset - gain max(s_c, 0) (m_c[t] + Phi_c[t] . alpha))^2 + lambda |alpha|^2
+    over the pixels that hit a triangle of the basis (and have weight > 0), s_c the chain of photo_loss_rgb under light [B,3,9].
+    The albedo's clamp at 1e-6 is not in this affine model.  -> (alpha [B,K] fp32, stats [B,4] float64 = {count, E0, E1, ok}[,
+    moments [B,16,16]]); a face that cannot be fitted gets alpha = 0 and ok = 0.  Nothing requires grad.  Runs on the current stream
+    with the per-stream scratch as its workspace."""
+    h = _host()
+    op = "albedo_lse_rgb"
+    n_c, ti_c, tg_c, w_c, B, H, W, dev = _solve_planes(h, op, normal, tri_ind, target, weight)
+    b_c, T, K = _solve_basis(op, basis, dev)
+    l_c = _model_light(h, _RGB, op, light, B, dev)
+    L = h.lib()
+    make = torch.zeros if B * H * W == 0 else torch.empty
+    alpha = make((B, K), dtype=torch.float32, device=dev)
+    moments = make((B, 16, 16), dtype=torch.float64, device=dev)
+    stats = make((B, 4), dtype=torch.float64, device=dev)
+    nws = L.fr_photo_solve_rgb_workspace_bytes(B, H, W)
+    with torch.cuda.device(dev), _KINDS_POOL.hold("photo_solve_rgb", dev, nws) as ent:
+        rc = L.fr_albedo_lse_rgb_forward(h.ptr(b_c), h.ptr(ti_c), h.ptr(n_c), h.ptr(l_c), h.ptr(tg_c), h.ptr(w_c), B, T, H, W, K,
+                                         float(gain), float(offset), float(ridge), h.ptr(alpha), h.ptr(moments), h.ptr(stats),
+                                         h.ptr(ent.buf), ent.nbytes, h.stream_ptr(dev))
+    h.check(rc, "fr_albedo_lse_rgb_forward")
+    return (alpha, stats, moments) if return_moments else (alpha, stats)
+
+
+def photo_solve_rgb(basis, tri_ind, normal, target, weight=None, alpha0=None, light0=None, iters=8, gate=True, ridge_light=0.0,
+                    ridge_alpha=0.0, gain=1.0, offset=0.0):
+    """Alternating least squares for a face's colour lighting and albedo coefficients against `target` [B,H,W,3], the geometry
+    (tri_ind, normal) held: `iters` times albedo_image_rgb -> photo_light_lse_rgb -> albedo_lse_rgb.  Each half-step is the exact
+    minimiser of the model's squared error in its own unknowns (ridge 0), so the error does not rise.  alpha0 [B,K] (default 0, the
+    mean albedo) and light0 [B,3,9] (default none) start it; with gate=True the light step counts, per channel, only the pixels
+    lit under the previous lighting -- from the second iteration on, or from the first with a light0.  A (face, channel) or face
+    whose step fails (ok = 0) keeps its previous value.  -> (light [B,3,9], alpha [B,K], tex_img [B,H,W,3] at the returned alpha,
+    info) with info["E"] float64 [iters,2,B] -- the residual after the light step (summed over the channels) and after the albedo
+    step -- and info["ok"] bool [iters,2,B].  No host synchronisation: 5 launches per iteration and one for the last image.
+    Nothing requires grad."""
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError("photo_solve_rgb: iters must be >= 1")
+    B, dev = int(tri_ind.shape[0]), tri_ind.device
+    K = int(basis.shape[2]) - 1
+    alpha = torch.zeros((B, K), dtype=torch.float32, device=dev) if alpha0 is None else alpha0.detach().to(torch.float32)
+    light = None if light0 is None else light0.detach().to(torch.float32)
+    E = torch.empty((iters, 2, B), dtype=torch.float64, device=dev)
+    ok = torch.empty((iters, 2, B), dtype=torch.bool, device=dev)
+    for it in range(iters):
+        tex_img = albedo_image_rgb(basis, tri_ind, alpha)
+        new_light, st = photo_light_lse_rgb(tex_img, normal, tri_ind, target, weight, light if gate else None, gain, offset, ridge_light)
+        good = st[:, :, 3] > 0
+        light = new_light if light is None else torch.where(good[:, :, None], new_light, light)
+        E[it, 0], ok[it, 0] = st[:, :, 2].sum(1), good.all(1)
+        new_alpha, st = albedo_lse_rgb(basis, tri_ind, normal, light, target, weight, gain, offset, ridge_alpha)
+        good = st[:, 3] > 0
+        alpha = torch.where(good[:, None], new_alpha, alpha)
+        E[it, 1], ok[it, 1] = st[:, 2], good
+    return light, alpha, albedo_image_rgb(basis, tri_ind, alpha), {"E": E, "ok": ok}
+
+
 class LandmarkBasis:
     """The compact image of K chosen vertices' basis rows (fr_landmark_basis_build; include/fr_hotpath.h, "landmarks"): `image`
     (uint8, on the device), K, n_shape, n_exp and `idx` (the ids as a tuple of ints).  Built once by landmark_basis().  An image of

@@ -8,6 +8,7 @@ HIP backward).
     python examples/photo_fit.py --small --fit-shape     # also fit the shape and expression coefficients (pose held at the truth)
     python examples/photo_fit.py --small --fit-pose      # also fit t3d, f and the angles, from the truth perturbed
     python examples/photo_fit.py --small --colour        # the picture in colour: RGB albedo, second-order lighting per channel
+    python examples/photo_fit.py --small --colour --closed-form 8 --steps 0   # ... light and alpha by alternating least squares
     python examples/photo_fit.py --small --fit-pose --landmarks 68                    # ... with the landmark term beside the two
     python examples/photo_fit.py --small --fit-pose --landmarks 68 --landmarks-only   # pose from the landmarks alone: no render
     python examples/photo_fit.py --small --fit-pose --landmarks 68 --landmarks-only --landmark-init 6 --steps 0   # ... by the solver
@@ -30,7 +31,9 @@ solver also fits the coefficients under the sampler's own prior (utils/synth.py:
 alone.  --contour PER_SIDE adds PER_SIDE contour landmarks a side (utils/synth.py::contour_lines): each is a line of candidate vertices
 from the rim inwards, the batch carries the face's occluding contour on every line, and the term and the solver hold each point to
 the candidate that lies nearest under the current parameters -- the correspondence slides with the pose, as the jaw points of a
-68-point annotation do.  --contour-fixed keeps the rim vertex instead, for the comparison; --yaw sets the truth's yaw.  Prints ONE
+68-point annotation do.  --colour --closed-form [ITERS] first runs the colour photometric solve (FaceRecNet.photo_solve_rgb: the
+lighting and alpha by alternating linear least squares on the render at the current geometry, from alpha = 0 and no lighting: the
+perturbed start is not used) and Adam goes on from where it ends; --steps 0 gives the solve alone.  --contour-fixed keeps the rim vertex instead, for the comparison; --yaw sets the truth's yaw.  Prints ONE
 JSON record: the first and last loss and the parameter errors (RMS against the ground truth) before and after.
 """
 import argparse
@@ -70,6 +73,9 @@ def build_parser():
     ap.add_argument("--silhouette-lambda", type=float, default=1.0)
     ap.add_argument("--colour", action="store_true", help="the picture in colour: per-channel albedo under a second-order lighting per "
                                                           "channel, light [B,3,9] (default: the gray first-order route)")
+    ap.add_argument("--closed-form", type=int, nargs="?", const=8, default=0, metavar="ITERS",
+                    help="with --colour: first fit light and alpha by ITERS alternations of the two linear least squares "
+                         "(photo_solve_rgb); --steps 0 gives the solve alone")
     ap.add_argument("--landmarks", type=int, default=0, help="K > 0: add the landmark term over K vertices (utils/synth.landmark_ids)")
     ap.add_argument("--landmark-lambda", type=float, default=1.0)
     ap.add_argument("--landmarks-only", action="store_true", help="fit to the landmark term alone (needs --landmarks and --fit-pose or "
@@ -136,6 +142,8 @@ def main():
         raise SystemExit("--landmarks needs --fit-pose or --fit-shape: with the geometry fixed the term is a constant")
     if args.landmark_init and not (args.landmarks > 0 and (args.fit_pose or args.fit_shape)):
         raise SystemExit("--landmark-init needs --landmarks K and something to fit: --fit-pose or --fit-shape")
+    if args.closed_form and (not args.colour or args.landmarks_only):
+        raise SystemExit("--closed-form needs --colour, and a render: not --landmarks-only")
     lm_idx = synth.landmark_ids(A, args.landmarks) if args.landmarks > 0 else None
     kw = {"colour": True} if args.colour else {}
     if lm_idx is not None:
@@ -252,6 +260,20 @@ def main():
             init.update(pose_errors())
         if coef is not None:
             init["coef_rms_scaled"] = rms(coef, coef_gt / scale)
+    closed = None
+    if args.closed_form:
+        ops = pkg("rendering_layer.ops")
+        with torch.no_grad():
+            ver = vertices(params_now()).detach().float()
+            _, _, normal, tri_ind = ops.render_depth(ver, face.tri, face.mu_tex[None], b["im_rgb"])
+            l_fit, a_fit, _, info = face.photo_solve_rgb(tri_ind, normal, b["im_rgb"], iters=args.closed_form, gain=stream.gain,
+                                                         offset=stream.offset)
+            light.copy_(l_fit)
+            alpha.copy_(a_fit)
+        closed = {"iters": int(args.closed_form), "E_first": float(info["E"][0, 0].sum()), "E_last": float(info["E"][-1, 1].sum()),
+                  "ok": bool(info["ok"].all()), "light_rms": rms(light, light_gt), "alpha_rms": rms(alpha, alpha_gt)}
+        if pose is not None:
+            closed.update(pose_errors())
     first, last = descend(opt, loss_of, args.steps)
     after = {"light_rms": rms(light, light_gt), "alpha_rms": rms(alpha, alpha_gt)}
     if coef is not None:
@@ -260,7 +282,7 @@ def main():
         after.update(pose_errors())
     print(json.dumps({"program": "photo_fit", "faces": B, "im_size": S, "steps": args.steps, "lr": args.lr, "fit_shape": bool(args.fit_shape),
                       "fit_pose": bool(args.fit_pose), "colour": bool(args.colour), "landmarks": int(args.landmarks),
-                      "landmarks_only": bool(args.landmarks_only), "landmark_init": init, "contour": contour, "yaw": args.yaw,
+                      "landmarks_only": bool(args.landmarks_only), "landmark_init": init, "closed_form": closed, "contour": contour, "yaw": args.yaw,
                       "first": first, "last": last, "ratio": last / first if first else None, "errors_before": before,
                       "errors_after": after, "finite": bool(torch.isfinite(light).all() and torch.isfinite(alpha).all())}))
 

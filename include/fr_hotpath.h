@@ -1197,6 +1197,80 @@ int fr_photo_loss_rgb_backward(const double* grad_sse, const double* sums, const
 /* out[4] = {pixels per tile, tiles per face, threads of the finish workgroup, sums per face (29)}; all zero as above. */
 void fr_debug_photo_loss_rgb_geom(int B, int H, int W, int* out);
 
+/* ---- colour photometric solve: per-face least squares for the lighting and for the albedo coefficients (opt-in) ---------------------
+ * The colour model above is bilinear, I_c(p) = a_c(p) s_c(p): s_c = sum_k light[c][k] H_k(n^) is linear in the lighting, and with
+ * t = tri_ind(p) the albedo a_c(p) = m_c[t] + Phi_c[t] . alpha is affine in alpha.  With the texture held each channel's lighting is a
+ * 9-unknown linear least squares per face; with the lighting held alpha is a K-unknown one per face over the three channels.  These
+ * entry points are the two solves and the two maps that let a caller alternate them without blending [B,3,N] textures or rasterising
+ * again.  Nothing existing changes; nothing here has a backward (the results are fitted quantities).  All planes dense, fp32: tex_img,
+ * normal, target [B,H,W,3]; tri_ind, weight [B,H,W] (a trailing channel of 1 is the caller's); light, gate_light [B,3,9]; alpha [B,K].
+ * NAMES.  The stream parameter is called `stream`, as in the sections above; tests/test_photo_solve_rgb_cpu.py holds the return codes.
+ * BASIS.  fr_albedo_basis_rgb_build, once per mesh: basis [ntri][3][K+1] float64, fr_albedo_basis_rgb_bytes(ntri, K) =
+ * ntri 3 (K + 1) 8 bytes (0 for ntri <= 0 or an unserved K).  tri [3,ntri] float-stored ids, mu_tex [3 nver], pc_tex [3 nver, K]
+ * row-major, both channel-major (row c nver + v).  On the widened fp32 values, in float64:
+ *   Phi_c[t][k] = ((pc[c,v1,k] + pc[c,v2,k]) + pc[c,v3,k]) / 3.0   at slot k < K;     m_c[t] = the same expression of mu_tex at slot K
+ * A triangle with a vertex id outside [0, nver) (NaN included; x86 conversion) gets a row of +0.0.  1 <= K <= 15.  Every bit is fixed.
+ * IMAGE.  fr_albedo_image_rgb, one lane per pixel, one launch: at a pixel with 0 <= (int)tri_ind < ntri (x86 conversion)
+ *   tex_img_c = fl32( chain from m_c[t] of + Phi_c[t][k] (double)alpha_k, k ascending ),  float64, rounded once;   +0 elsewhere.
+ * Every element is written; every bit is fixed.  Against render_depth's tex_img of the texture fr_synth_texture blends from the same
+ * mu_tex, pc_tex and alpha -- an fp32 chain of K products and K sums per vertex, two sums over the vertices and a division, K + 4
+ * roundings on the largest path -- this plane differs at a pixel both cover by at most
+ *   gamma A,   gamma = n u / (1 - n u),  u = 2^-24,  n = K + 6,   A = (1/3) sum_j ( |mu_c[v_j]| + sum_k |pc_c[v_j][k]| |alpha_k| )
+ * (K + 4 roundings there, one here, one more unit for the float64 chain and the second-order terms).
+ * LIGHT FIT.  fr_photo_light_lse_rgb_forward.  A pixel is COVERED iff tri_ind >= 0, the loss's rule; nothing is gathered.  At a covered
+ * pixel a_c (clamped) and H_0 .. H_8 are the MODEL's, from the shader's own device function: the loss's bits.  Channel c COUNTS the
+ * pixel iff it is covered, weight is NULL or w > 0, and gate_light is NULL or the fp32 chain s_c of gate_light[b] is > 0 there (the
+ * active set of the clamp: an unlit pixel's model value does not depend on the lighting).  In float64 on the widened values, every
+ * operation rounded on its own:
+ *   x^c_k = ((double)a_c (double)H_k) (double)gain  for k = 1 .. 8;   x^c_0 = (double)a_c (double)gain;   x^c_9 = (double)T_c - (double)offset
+ *   x^c_k = +0.0 for 9 < k < 16, and x^c = 0 where channel c does not count the pixel, whatever the planes hold.
+ * MOMENTS.  M_bc = sum_p (w x_i) x_j with i <= j mirrored: moments [B][3][16][16] float64, symmetric bit for bit, rows and columns
+ * above 9 +0.0.  G = M[:9,:9], r = M[:9,9], E0 = M[9][9].  Without a weight the product is x_i x_j (the same register twice).
+ * ALBEDO FIT.  fr_albedo_lse_rgb_forward.  A pixel is COUNTED iff 0 <= (int)tri_ind < ntri (x86 conversion) and weight is NULL or
+ * w > 0.  With s_c the fp32 chain of light[b] at the pixel's normal (the model's function) and s+_c = s_c < 0 ? 0 : s_c, per channel:
+ *   x_k = ((double)s+_c Phi_c[t][k]) (double)gain  for k < K;   x_K = ((double)T_c - (double)offset) - ((double)s+_c m_c[t]) (double)gain
+ *   x_k = +0.0 for K < k < 16.  M_b = sum_p sum_c (w x_i) x_j, the channels ascending within a pixel group: moments [B][16][16].
+ * The albedo's clamp at 1e-6 is NOT in this affine model: E1 below is the affine model's residual, photo_loss_rgb the clamped one's;
+ * they agree where every fitted albedo is >= 1e-6.
+ * ASSOCIATION.  That of the per-face albedo fit above: tiles of T = 256 pixels (fr_debug_photo_solve_rgb_geom), within a tile
+ * consecutive groups of four pixels added in ascending order onto +0.0 accumulators by v_mfma_f64_16x16x4_f64 -- one accumulator per
+ * channel in the light fit, ONE in the albedo fit, which takes a group's channels 0, 1, 2 in turn -- the tile partials
+ * [face][tile][channel][register][lane] added in ascending tile order from +0.0.  A function of the inputs and (H, W) alone.  No
+ * atomics.  Every M_ij lies within gamma_n sum |w x_i x_j| of the exact sum of the rounded products, gamma_n = n 2^-53 / (1 - n 2^-53),
+ * n = H W for the light fit and 3 H W for the albedo fit.
+ * SOLVE.  One wave per (face, channel) of the light fit (9 unknowns, lambda = (ridge tr) / 9.0) and per face of the albedo fit (K
+ * unknowns, lambda = (ridge tr) / (double)K): the SOLVE of the per-face albedo fit above, word for word -- the trace chain, the
+ * Cholesky by columns, the two substitutions, the pivot test piv > 2^-40 G'_cc (a Gram matrix of condition 1e8 has every pivot
+ * >= 1e-8 G'_cc: admitted), the failure rules, and E1 = (E0 - 2.0 S1) + S2 on the rounded coefficients and the unridged G.
+ * OUTPUTS.  light [B,3,9] / alpha [B,K] fp32, rounded once; stats [B][3][4] / [B][4] float64 = {count, E0, E1, ok}.  A unit that
+ * FAILS (no counted pixel, a non-finite moment, a vanishing pivot, a non-finite coefficient) has ok = 0 and E1 = E0; the light fit
+ * writes gate_light's row there (+0 without a gate), the albedo fit +0.  A failure touches its (face, channel) or face alone.
+ * WORKSPACE.  fr_photo_solve_rgb_workspace_bytes(B, H, W) = B tiles 3 257 doubles serves either solve (0 for an empty or refused
+ * shape); 16-byte aligned, caller-owned, one per call in flight; written before it is read.
+ * Checks, all before any HIP call, in this order: a negative size, or a ridge that is negative or not finite, or a gain or offset that
+ * is not finite, is FR_ERR_INVALID_ARG; an empty shape (B, H or W of 0; ntri == 0 for the basis) is FR_OK with nothing launched or
+ * written; a NULL pointer (weight and gate_light may be NULL; basis only with ntri == 0; mu_tex and pc_tex only with nver == 0) is
+ * FR_ERR_INVALID_ARG; a workspace or basis that is missing, too small or misaligned is FR_ERR_WORKSPACE; K outside 1 .. 15, more than
+ * 65,535 faces, more than 2^31 - 1 pixels per face, more than 2^31 - 1 tile workgroups or ntri > 2^24 in the build is
+ * FR_ERR_UNSUPPORTED.  Nothing is allocated or synchronised; each solve makes two launches, can be captured in a graph and is reentrant
+ * with buffers per call in flight.  Kernels: csrc/fr_photo_solve.hip; time: tools/photo_solve_rgb_probe.py. */
+size_t fr_albedo_basis_rgb_bytes(int ntri, int K);
+int fr_albedo_basis_rgb_build(const float* tri, const float* mu_tex, const float* pc_tex, int nver, int ntri, int K, void* basis,
+                              size_t basis_bytes, void* stream);
+int fr_albedo_image_rgb(const void* basis, const float* tri_ind, const float* alpha, int B, int ntri, int H, int W, int K,
+                        float* tex_img, void* stream);
+size_t fr_photo_solve_rgb_workspace_bytes(int B, int H, int W);
+int fr_photo_light_lse_rgb_forward(const float* tex_img, const float* normal, const float* tri_ind, const float* target,
+                                   const float* weight, const float* gate_light, int B, int H, int W, float gain, float offset,
+                                   double ridge, float* light, void* moments, void* stats, void* workspace, size_t ws_bytes,
+                                   void* stream);
+int fr_albedo_lse_rgb_forward(const void* basis, const float* tri_ind, const float* normal, const float* light, const float* target,
+                              const float* weight, int B, int ntri, int H, int W, int K, float gain, float offset, double ridge,
+                              float* alpha, void* moments, void* stats, void* workspace, size_t ws_bytes, void* stream);
+/* out[6] = {pixels per tile, tiles per face, workgroups of a tile kernel (B ceil(tiles / 4)), workgroups of the light fit's finish
+ * kernel (3 B), of the albedo fit's (B), static LDS bytes of a finish workgroup}; all zero for an empty or refused shape. */
+void fr_debug_photo_solve_rgb_geom(int B, int H, int W, int* out);
+
 /* ---- fine mesh: the fine depth map lifted onto the vertices, visibility, vertex normals (opt-in, forward only) ----------------------
  * FineNet's output is a [B,H,W,1] plane and the coarse decode a [B,3,N] vertex tensor; the reference leaves them unjoined
  * (nets/network.py:451-453, "how to inversely convert predicted fine depth into new vertices?") and keeps the coarse vertices.  The
