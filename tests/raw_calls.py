@@ -25,12 +25,34 @@ def _stream(stream=None):
     return ctypes.c_void_p((stream if stream is not None else torch.cuda.current_stream()).cuda_stream)
 
 
+def _ws(ws, nws):
+    """the call's own workspace of nws bytes, or `ws`: a uint8 device tensor of exactly nws bytes the caller placed and filled"""
+    if ws is None:
+        return torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() == nws, (ws.numel(), nws)
+    return ws
+
+
 def _sentinel(shape):
     return torch.full(shape, SENT, dtype=torch.int32, device=DEV).view(torch.float32)
 
 
+# ---- fr_render_depth_backward_ws -------------------------------------------------------------------------------------------------------
+def rbwd(g, tri, ti, nver, H, W, ws=None):
+    """fr_render_depth_backward_ws on torch's current stream (device tensors; not synchronised) -> vertex_grad [B,3,nver], pre-filled
+    with NaN"""
+    h, L = _h(), _h().lib()
+    B, ntri = int(ti.shape[0]), int(tri.shape[1])
+    nws = L.fr_render_depth_backward_workspace_bytes(B, H, W)
+    ws = _ws(ws, nws)
+    out = torch.full((B, 3, nver), float("nan"), device=DEV)
+    rc = L.fr_render_depth_backward_ws(h.ptr(g), h.ptr(tri), h.ptr(ti), h.ptr(out), B, nver, ntri, H, W, h.ptr(ws), nws, _stream())
+    assert rc == 0, rc
+    return out
+
+
 # ---- fr_render_normal_backward ---------------------------------------------------------------------------------------------------------
-def nbwd(g, V, tri, ti, H, W, mode, out=None, accumulate=0, stride=3, offset=0, pitch=None):
+def nbwd(g, V, tri, ti, H, W, mode, out=None, accumulate=0, stride=3, offset=0, pitch=None, ws=None):
     """fr_render_normal_backward on torch's current stream (device tensors; not synchronised) -> vertex_grad, pre-filled with
     NaN unless `out` is given"""
     h, L = _h(), _h().lib()
@@ -38,7 +60,7 @@ def nbwd(g, V, tri, ti, H, W, mode, out=None, accumulate=0, stride=3, offset=0, 
     nver = int(V.shape[2]) if pitch is None else pitch[1]                     # pitch = (floats per vertex row, nver)
     ntri = int(tri.shape[1])
     nws = L.fr_render_normal_backward_workspace_bytes(B, nver, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    ws = _ws(ws, nws)
     if out is None:
         out = torch.full((B, 3, nver), float("nan"), device=DEV)
     rc = L.fr_render_normal_backward(ctypes.c_void_p(g.data_ptr() + 4 * offset), stride, h.ptr(V),
@@ -62,13 +84,13 @@ def dfwd(V, tri, ti, H, W, pitch=None, stream=None):
     return out
 
 
-def dbwd(g, V, tri, ti, H, W, out=None, accumulate=0, pitch=None, stream=None):
+def dbwd(g, V, tri, ti, H, W, out=None, accumulate=0, pitch=None, stream=None, ws=None):
     """fr_depth_interp_backward with a workspace of its own -> vertex_grad, pre-filled with NaN unless `out` is given"""
     h, L = _h(), _h().lib()
     B = int(V.shape[0])
     nver = int(V.shape[2]) if pitch is None else pitch[1]
     nws = L.fr_depth_interp_backward_workspace_bytes(B, nver, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    ws = _ws(ws, nws)
     if out is None:
         out = torch.full((B, 3, nver), float("nan"), device=DEV)
     rc = L.fr_depth_interp_backward(h.ptr(g), h.ptr(V), nver if pitch is None else pitch[0], h.ptr(tri), h.ptr(ti), h.ptr(out), B,
@@ -78,14 +100,14 @@ def dbwd(g, V, tri, ti, H, W, out=None, accumulate=0, pitch=None, stream=None):
 
 
 # ---- fr_render_texture_backward --------------------------------------------------------------------------------------------------------
-def tbwd(g, tri, ti, nver, H, W, tb, out=None, accumulate=0, stride=3, offset=0):
+def tbwd(g, tri, ti, nver, H, W, tb, out=None, accumulate=0, stride=3, offset=0, ws=None):
     """fr_render_texture_backward on torch's current stream (device tensors; not synchronised) -> texture_grad [tb,3,nver],
     pre-filled with NaN unless `out` is given"""
     h, L = _h(), _h().lib()
     B = int(ti.shape[0])
     ntri = int(tri.shape[1])
     nws = L.fr_render_texture_backward_workspace_bytes(B, nver, H, W, tb)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    ws = _ws(ws, nws)
     if out is None:
         out = torch.full((tb, 3, nver), float("nan"), device=DEV)
     rc = L.fr_render_texture_backward(ctypes.c_void_p(g.data_ptr() + 4 * offset), stride, h.ptr(tri), h.ptr(ti), h.ptr(out), B, nver,
@@ -149,12 +171,14 @@ class PhotoCall:
         self.gain, self.offset = gain, offset
         self.L = pkg("_lib").lib()
 
-    def forward(self, stream=None):
+    def forward(self, stream=None, state=None):
         dev = torch.device(DEV)
         st = torch.cuda.current_stream(dev) if stream is None else stream
         nst = getattr(self.L, self.ENTRY + "_state_bytes")(self.B, self.H, self.W)
         with torch.cuda.stream(st):
-            state = torch.full((nst,), 0xA5, dtype=torch.uint8, device=dev)       # (needs nothing cleared)
+            if state is None:
+                state = torch.full((nst,), 0xA5, dtype=torch.uint8, device=dev)   # (needs nothing cleared)
+            assert state.dtype == torch.uint8 and state.numel() == nst
             sums = torch.full((self.B, self.NSUMS), float("nan"), dtype=torch.float64, device=dev)
             rc = getattr(self.L, self.ENTRY + "_forward")(*[_p(x) for x in self.t], self.B, self.H, self.W, self.gain, self.offset,
                                                           _p(sums), _p(state), nst, ctypes.c_void_p(st.cuda_stream))
@@ -204,13 +228,13 @@ def cfwd(V, tri, ti, H, W, pitch=None):
     return out
 
 
-def cbwd(g, cov, V, tri, ti, H, W, out=None, accumulate=0, pitch=None):
+def cbwd(g, cov, V, tri, ti, H, W, out=None, accumulate=0, pitch=None, ws=None):
     """fr_coverage_backward with a workspace of its own -> vertex_grad, pre-filled with NaN unless `out` is given"""
     h, L = _h(), _h().lib()
     B = int(V.shape[0])
     nver = int(V.shape[2]) if pitch is None else pitch[1]
     nws = L.fr_coverage_backward_workspace_bytes(B, nver, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    ws = _ws(ws, nws)
     if out is None:
         out = torch.full((B, 3, nver), float("nan"), device=DEV)
     rc = L.fr_coverage_backward(h.ptr(g), h.ptr(cov), h.ptr(V), nver if pitch is None else pitch[0], h.ptr(tri), h.ptr(ti), h.ptr(out),
@@ -220,18 +244,21 @@ def cbwd(g, cov, V, tri, ti, H, W, out=None, accumulate=0, pitch=None):
 
 
 # ---- fr_albedo_basis_build / fr_albedo_lse_forward -------------------------------------------------------------------------------------
-def raw_basis(tri, pc_tex, nver):
+def raw_basis(tri, pc_tex, nver, ws=None):
     """fr_albedo_basis_build on a buffer of its own (tri [3,ntri], pc_tex [3 nver,K] device tensors) -> basis [ntri,K] float64,
-    pre-filled with NaN"""
+    pre-filled with NaN; ws: the bytes to build into instead (the result is a view of them)"""
     L = _h().lib()
     ntri, K = int(tri.shape[1]), int(pc_tex.shape[1])
-    out = torch.full((max(ntri, 1), K), float("nan"), dtype=torch.float64, device=DEV)[:ntri]
+    if ws is None:
+        out = torch.full((max(ntri, 1), K), float("nan"), dtype=torch.float64, device=DEV)[:ntri]
+    else:
+        out = _ws(ws, L.fr_albedo_basis_bytes(ntri, K)).view(torch.float64).view(ntri, K)
     rc = L.fr_albedo_basis_build(_p(tri), _p(pc_tex), nver, ntri, K, _p(out), L.fr_albedo_basis_bytes(ntri, K), _stream())
     assert rc == 0, rc
     return out
 
 
-def raw_fit(inp, ridge):
+def raw_fit(inp, ridge, ws=None):
     """fr_albedo_lse_forward on buffers of its own, every output pre-filled with 7.0 (inp: device tensors basis [ntri,K] float64,
     tri_ind, lighting [3,H,W] float64, normal, abedo, im_gray) -> (alpha, stats, moments) as numpy, synchronised"""
     L = _h().lib()
@@ -241,7 +268,7 @@ def raw_fit(inp, ridge):
     moments = torch.full((B, 16, 16), 7.0, dtype=torch.float64, device=DEV)
     stats = torch.full((B, 4), 7.0, dtype=torch.float64, device=DEV)
     nws = L.fr_albedo_lse_workspace_bytes(B, H, W, Kb)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    ws = _ws(ws, nws)
     rc = L.fr_albedo_lse_forward(_p(inp["basis"]), _p(inp["tri_ind"]), _p(inp["lighting"]), _p(inp["normal"]), _p(inp["abedo"]),
                                  _p(inp["im_gray"]), B, T, H, W, Kb, float(ridge), _p(alpha), _p(moments), _p(stats), _p(ws), nws,
                                  _stream())

@@ -257,7 +257,7 @@ class Rig:
         with torch.no_grad():
             return self.net.vertices_transform(p, R=Rt).detach()
 
-    def call(self, kind, P, G, V, R=None):
+    def call(self, kind, P, G, V, R=None, ws=None):
         h = _h()
         L = h.lib()
         B = P.shape[0]
@@ -266,7 +266,10 @@ class Rig:
         Rt = None if R is None else torch.as_tensor(np.ascontiguousarray(R, np.float32).reshape(B, 3, 3), device=DEV)
         Rp = None if Rt is None else h.ptr(Rt)
         nws = L.fr_decode_backward_workspace_bytes(B, self.N, self.ns, self.ne)
-        ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+        if ws is None:
+            ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+        else:
+            assert ws.dtype == torch.uint8 and ws.numel() == nws, (ws.numel(), nws)     # (exactly the stated bytes)
         gp = torch.full_like(p, 7.0)
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         b = self.net._basis

@@ -65,15 +65,17 @@ class Rig:
         return (torch.full((B, self.H, self.W, 7), 7.0, **o), torch.full((B, self.H, self.W, 1), 7.0, **o),
                 torch.full((B, self.H, self.W, 1), 7.0, **o), torch.full((B, self.H, self.W, 1), 7.0, **o))
 
-    def fwd_fused(self, P, im, phases=(15,), R=None, tex=None, expect=0):
+    def fwd_fused(self, P, im, phases=(15,), R=None, tex=None, expect=0, ws=None, hand=None):
+        """ws, hand: uint8 device tensors of exactly the stated sizes to use in place of the call's own"""
         h, L, n = _h(), _h().lib(), self.net
         B = int(P.shape[0])
         tex = n.vertex_code if tex is None else tex
         tb = 1 if tex.dim() == 2 else int(tex.shape[0])
         nws = L.fr_render_depth_workspace_bytes(B, self.N, self.ntri, self.H, self.W)
-        ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
         nh = L.fr_decode_render_vertex_bytes(B, self.N)
-        hand = torch.empty((nh,), dtype=torch.uint8, device=DEV)
+        assert (ws is None or ws.numel() == nws) and (hand is None or hand.numel() == nh)       # (exactly the stated bytes)
+        ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV) if ws is None else ws
+        hand = torch.empty((nh,), dtype=torch.uint8, device=DEV) if hand is None else hand
         outs = self._planes(B)
         for ph in phases:
             rc = L.fr_decode_rendering_layer_forward(h.ptr(P), h.ptr(n._basis.image), h.ptr(R), h.ptr(n.tri), h.ptr(tex), h.ptr(im),
@@ -100,12 +102,13 @@ class Rig:
         return outs
 
     # ---- backward ----
-    def bwd_fused(self, P, gd, gi, gn, im, depth, tri_ind, R=None):
+    def bwd_fused(self, P, gd, gi, gn, im, depth, tri_ind, R=None, ws=None):
         h, L, n = _h(), _h().lib(), self.net
         B = int(P.shape[0])
         nws = L.fr_decode_render_backward_workspace_bytes(B, self.N, self.ns, self.ne, self.H, self.W)
         assert nws > 0
-        ws = torch.empty((nws,), dtype=torch.uint8, device=DEV)
+        ws = torch.empty((nws,), dtype=torch.uint8, device=DEV) if ws is None else ws
+        assert ws.numel() == nws
         gp = torch.full((B, self.nd), 7.0, dtype=torch.float32, device=DEV)
         rc = L.fr_decode_render_backward(h.ptr(gd), h.ptr(gi), h.ptr(gn), h.ptr(im), h.ptr(depth), h.ptr(n.tri), h.ptr(tri_ind),
                                          h.ptr(P), h.ptr(n.mu), h.ptr(self.image_t), h.ptr(R), B, self.N, self.ns, self.ne,

@@ -97,7 +97,7 @@ class QRig(Rig):
             self.pack_into(_h().ptr(self._qimage), nbytes)
         return self._qimage
 
-    def decode(self, P, R=None, lv=7, im=IM):
+    def decode(self, P, R=None, lv=7, im=IM, ws=None, qimage=None):
         h = _h()
         L = h.lib()
         dev = torch.device("cuda:0")
@@ -105,9 +105,11 @@ class QRig(Rig):
         p = torch.as_tensor(np.ascontiguousarray(P, np.float32), device=dev)
         r = None if R is None else torch.as_tensor(np.ascontiguousarray(R, np.float32).reshape(B, 9), device=dev)
         nws = L.fr_decode_q30_workspace_bytes(self.ns, self.ne)
-        ws = torch.empty((nws,), dtype=torch.uint8, device=dev)
+        ws = torch.empty((nws,), dtype=torch.uint8, device=dev) if ws is None else ws
+        qimage = self.qimage if qimage is None else qimage
+        assert ws.numel() == nws
         out = torch.full((B, 3, self.N), SENTINEL, dtype=torch.float32, device=dev)
-        rc = L.fr_decode_3dmm_q30_lv(h.ptr(p), h.ptr(self.qimage), h.ptr(r), B, self.N, self.ns, self.ne, float(im), lv, h.ptr(out),
+        rc = L.fr_decode_3dmm_q30_lv(h.ptr(p), h.ptr(qimage), h.ptr(r), B, self.N, self.ns, self.ne, float(im), lv, h.ptr(out),
                                      h.ptr(ws), nws, h.stream_ptr(dev))
         h.check(rc, "fr_decode_3dmm_q30_lv")
         torch.cuda.synchronize()

@@ -48,7 +48,7 @@ def assert_bits64_equal(got, want, what):
         what, int(bad.sum()), got.size, np.argwhere(bad)[0], got[tuple(np.argwhere(bad)[0])], want[tuple(np.argwhere(bad)[0])])
 
 
-def raw_forward(z, c, fill=0xFF, stream=None):
+def raw_forward(z, c, fill=0xFF, stream=None, state=None):
     """fr_fine_losses_forward through the raw C ABI -> (fidelity fp32, smoothness fp32, state as float64 [2 + 2P])"""
     h = _h()
     L = h.lib()
@@ -58,7 +58,9 @@ def raw_forward(z, c, fill=0xFF, stream=None):
     nst = L.fr_fine_losses_state_bytes(B, H, W)
     g = RF.geom(B, H, W)
     assert nst == (2 + 2 * g[3] * g[4] * B) * 8
-    state = torch.full((nst,), fill, dtype=torch.uint8, device=DEV)
+    if state is None:
+        state = torch.full((nst,), fill, dtype=torch.uint8, device=DEV)
+    assert state.dtype == torch.uint8 and state.numel() == nst
     out = torch.full((2,), float("nan") if fill else 0.0, dtype=torch.float32, device=DEV)
     rc = L.fr_fine_losses_forward(h.ptr(zt), h.ptr(ct), B, H, W, h.ptr(out[0:]), h.ptr(out[1:]), h.ptr(state), nst, st)
     assert rc == 0, rc

@@ -49,8 +49,9 @@ def _dev(a):
     return t if t.numel() else torch.zeros((4,), dtype=t.dtype, device=DEV)
 
 
-def build_gram(pc_shape, pc_exp, fill=None):
-    """fr_geometry_gram_build through the raw C ABI -> G [Kp,Kp] float64 (numpy).  fill: a byte both buffers are filled with first."""
+def build_gram(pc_shape, pc_exp, fill=None, G=None, ws=None):
+    """fr_geometry_gram_build through the raw C ABI -> G [Kp,Kp] float64 (numpy).  fill: a byte both buffers are filled with first.
+    G, ws: uint8 device tensors of exactly the stated sizes to build into, as the caller placed and filled them."""
     h = _h()
     L = h.lib()
     N, ns, ne = pc_shape.shape[0] // 3, pc_shape.shape[1], pc_exp.shape[1]
@@ -59,7 +60,8 @@ def build_gram(pc_shape, pc_exp, fill=None):
     assert nb == kp * kp * 8 and nws > 0
     mk = (lambda n: torch.full((n,), fill, dtype=torch.uint8, device=DEV)) if fill is not None else \
         (lambda n: torch.empty((n,), dtype=torch.uint8, device=DEV))
-    G, ws = mk(nb), mk(nws)
+    G, ws = mk(nb) if G is None else G, mk(nws) if ws is None else ws
+    assert G.numel() == nb and ws.numel() == nws
     ps, pe = _dev(pc_shape), _dev(pc_exp)
     rc = L.fr_geometry_gram_build(h.ptr(ps), h.ptr(pe), N, ns, ne, h.ptr(G), nb, h.ptr(ws), nws, _st())
     assert rc == 0, rc
@@ -76,7 +78,7 @@ def rig(N, ns, ne):
     return pc_shape, pc_exp, G
 
 
-def loss_fwd_bwd(G, diff, N, ns, ne, grad_losses=(1.0,), stream=None):
+def loss_fwd_bwd(G, diff, N, ns, ne, grad_losses=(1.0,), stream=None, state=None):
     """fr_geometry_loss_forward + one fr_geometry_loss_backward per grad_loss through the raw C ABI -> (loss fp32, [grad_diff])"""
     h = _h()
     L = h.lib()
@@ -84,7 +86,9 @@ def loss_fwd_bwd(G, diff, N, ns, ne, grad_losses=(1.0,), stream=None):
     st = ctypes.c_void_p((stream or torch.cuda.current_stream(DEV)).cuda_stream)
     Gt, dt = torch.tensor(G, device=DEV), torch.as_tensor(diff, device=DEV)      # (G may be read-only: a copy)
     nst = L.fr_geometry_loss_state_bytes(B, ns, ne)
-    state = torch.full((nst,), 0xFF, dtype=torch.uint8, device=DEV)
+    if state is None:
+        state = torch.full((nst,), 0xFF, dtype=torch.uint8, device=DEV)
+    assert state.dtype == torch.uint8 and state.numel() == nst
     loss = torch.full((), float("nan"), dtype=torch.float32, device=DEV)
     assert L.fr_geometry_loss_forward(h.ptr(dt), h.ptr(Gt), B, N, ns, ne, h.ptr(loss), h.ptr(state), nst, st) == 0
     grads = []

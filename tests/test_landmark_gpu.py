@@ -50,12 +50,14 @@ def _bits64(a):
     return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
-def c_build(mu, pcs, pce, idx, N, ns, ne):
+def c_build(mu, pcs, pce, idx, N, ns, ne, img=None):
     h, L = _h(), _h().lib()
     K = len(idx)
     nb = L.fr_landmark_basis_bytes(K, ns, ne)
     assert nb == 4 * 3 * K * (2 * (ns + ne) + 1)
-    img = torch.full((nb // 4,), 7.0, dtype=torch.float32, device=DEV)
+    if img is None:
+        img = torch.full((nb // 4,), 7.0, dtype=torch.float32, device=DEV)
+    assert img.dtype == torch.float32 and img.numel() * 4 == nb
     rc = L.fr_landmark_basis_build(h.ptr(mu), h.ptr(pcs), h.ptr(pce), h.ptr(_t(idx, np.int32)), N, ns, ne, K, h.ptr(img), nb, _stream())
     assert rc == 0, rc
     return img

@@ -69,7 +69,7 @@ def _bits_equal(a, b):
     return (a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))
 
 
-def c_step(c, P, target, weight=None, ridge=None, center=None, damp=None, mask=RS.ALL_POSE, coef=0, im=IM):
+def c_step(c, P, target, weight=None, ridge=None, center=None, damp=None, mask=RS.ALL_POSE, coef=0, im=IM, ws=None):
     """the raw call: tensors in, (delta, cost, ok) prefilled with a sentinel"""
     h, L = _h(), _h().lib()
     B, K, ns, ne = int(P.shape[0]), c["K"], c["ns"], c["ne"]
@@ -77,7 +77,10 @@ def c_step(c, P, target, weight=None, ridge=None, center=None, damp=None, mask=R
     cost = torch.full((B, 2), SENT, dtype=torch.float64, device=DEV)
     ok = torch.full((B,), 7, dtype=torch.int32, device=DEV)
     nws = L.fr_landmark_solve_workspace_bytes(B, ns, ne)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    else:
+        assert ws.dtype == torch.uint8 and ws.numel() == nws, (ws.numel(), nws)     # (exactly the stated bytes)
     wb = 1 if weight is not None and weight.dim() == 2 else 0
     rc = L.fr_landmark_solve_step(h.ptr(P), h.ptr(c["img"]), c["img"].numel() * 4, h.ptr(target), h.ptr(weight), wb, h.ptr(ridge),
                                   h.ptr(center), h.ptr(damp), mask, coef, B, K, ns, ne, im, h.ptr(delta), h.ptr(cost), h.ptr(ok),

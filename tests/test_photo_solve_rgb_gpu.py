@@ -59,14 +59,17 @@ def _stream():
 
 
 # ---- the raw calls: numpy in, numpy out --------------------------------------------------------------------------------------------------
-def raw_light(inp, tex, weight=None, gate=None, ridge=0.0, gain=1.0, offset=0.0, fill=7.0):
+def raw_light(inp, tex, weight=None, gate=None, ridge=0.0, gain=1.0, offset=0.0, fill=7.0, ws=None):
     L = _L()
     B, H, W = inp["normal"].shape[:3]
     light = torch.full((B, 3, 9), fill, dtype=torch.float32, device=DEV)
     M = torch.full((B, 3, 16, 16), fill, dtype=torch.float64, device=DEV)
     st = torch.full((B, 3, 4), fill, dtype=torch.float64, device=DEV)
     nws = L.fr_photo_solve_rgb_workspace_bytes(B, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    else:
+        assert ws.dtype == torch.uint8 and ws.numel() == nws, (ws.numel(), nws)     # (exactly the stated bytes)
     d = [_dev(x) for x in (tex, inp["normal"], inp["tri_ind"], inp["target"], weight, gate)]
     rc = L.fr_photo_light_lse_rgb_forward(*[_p(x) for x in d], B, H, W, gain, offset, ridge, _p(light), _p(M), _p(st), _p(ws), nws,
                                           _stream())
@@ -75,7 +78,7 @@ def raw_light(inp, tex, weight=None, gate=None, ridge=0.0, gain=1.0, offset=0.0,
     return light.cpu().numpy(), st.cpu().numpy(), M.cpu().numpy()
 
 
-def raw_albedo(inp, light, weight=None, ridge=0.0, gain=1.0, offset=0.0, fill=7.0):
+def raw_albedo(inp, light, weight=None, ridge=0.0, gain=1.0, offset=0.0, fill=7.0, ws=None, basis=None):
     L = _L()
     B, H, W = inp["normal"].shape[:3]
     T, K = inp["basis"].shape[0], inp["basis"].shape[2] - 1
@@ -83,8 +86,11 @@ def raw_albedo(inp, light, weight=None, ridge=0.0, gain=1.0, offset=0.0, fill=7.
     M = torch.full((B, 16, 16), fill, dtype=torch.float64, device=DEV)
     st = torch.full((B, 4), fill, dtype=torch.float64, device=DEV)
     nws = L.fr_photo_solve_rgb_workspace_bytes(B, H, W)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
-    basis = _dev(inp["basis"], torch.float64)
+    if ws is None:
+        ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    else:
+        assert ws.dtype == torch.uint8 and ws.numel() == nws, (ws.numel(), nws)     # (exactly the stated bytes)
+    basis = _dev(inp["basis"], torch.float64) if basis is None else basis      # (basis: a device image to read instead)
     d = [_dev(x) for x in (inp["tri_ind"], inp["normal"], light, inp["target"], weight)]
     rc = L.fr_albedo_lse_rgb_forward(_p(basis), *[_p(x) for x in d], B, T, H, W, K, gain, offset, ridge, _p(alpha), _p(M), _p(st),
                                      _p(ws), nws, _stream())

@@ -54,12 +54,15 @@ def _geom(N):
     return list(out)
 
 
-def pose_c(G, V, P, R=None, ns=RP.NS, ne=RP.NE, im=IM, want_gp=True, want_R=True, fill=7.0):
+def pose_c(G, V, P, R=None, ns=RP.NS, ne=RP.NE, im=IM, want_gp=True, want_R=True, fill=7.0, ws=None):
     """fr_decode_pose_backward on torch's current stream -> (grad_params pre-filled with `fill`, grad_R), not synchronised"""
     h, L = _h(), _h().lib()
     B, N = int(P.shape[0]), int(G.shape[2])
     nws = L.fr_decode_pose_backward_workspace_bytes(B, N)
-    ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=DEV)
+    else:
+        assert ws.dtype == torch.uint8 and ws.numel() == nws, (ws.numel(), nws)     # (exactly the stated bytes)
     gp = torch.full((B, 7 + ns + ne), fill, dtype=torch.float32, device=DEV) if want_gp else None
     gR = torch.full((B, 3, 3), fill, dtype=torch.float32, device=DEV) if want_R else None
     rc = L.fr_decode_pose_backward(h.ptr(G), h.ptr(V), h.ptr(P), h.ptr(R), B, N, ns, ne, im, h.ptr(gp), h.ptr(gR), h.ptr(ws), nws,
@@ -171,7 +174,7 @@ class Scene:
         assert float((outs[3] >= 0).float().mean()) > 0.05
         return outs[2], outs[3], hand
 
-    def bwd(self, depth, tri_ind, hand, R=None, pose=True):
+    def bwd(self, depth, tri_ind, hand, R=None, pose=True, ws=None):
         h, L, n = _h(), _h().lib(), self.net
         B, S = self.B, self.S
         gp = torch.full((B, n.ndim), 7.0, dtype=torch.float32, device=DEV)
@@ -179,12 +182,14 @@ class Scene:
                   h.ptr(n.mu), h.ptr(self.image_t), h.ptr(R), B, self.N, self.ns, self.ne, self.ntri, S, S, float(S), h.ptr(gp))
         if not pose:
             nws = L.fr_decode_render_backward_workspace_bytes(B, self.N, self.ns, self.ne, S, S)
-            ws = torch.empty((nws,), dtype=torch.uint8, device=DEV)
+            ws = torch.empty((nws,), dtype=torch.uint8, device=DEV) if ws is None else ws
+            assert ws.numel() == nws
             assert L.fr_decode_render_backward(*common, h.ptr(ws), nws, _stream()) == 0
             torch.cuda.synchronize()
             return gp, None
         nws = L.fr_decode_render_backward_pose_workspace_bytes(B, self.N, self.ns, self.ne, S, S)
-        ws = torch.empty((nws,), dtype=torch.uint8, device=DEV)
+        ws = torch.empty((nws,), dtype=torch.uint8, device=DEV) if ws is None else ws
+        assert ws.numel() == nws
         gR = torch.full((B, 3, 3), 7.0, dtype=torch.float32, device=DEV)
         assert L.fr_decode_render_backward_pose(*common, h.ptr(ws), nws, _stream(), h.ptr(hand), hand.numel() * 4, h.ptr(gR)) == 0
         torch.cuda.synchronize()

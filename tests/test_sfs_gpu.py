@@ -44,13 +44,15 @@ def _sp():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def fwd(t, rcond=RS.RCOND, shape=None):
+def fwd(t, rcond=RS.RCOND, shape=None, state=None):
     """fr_sfs_intensity_forward on torch's current stream (device tensors; not synchronised) -> (intensity [B,H,W,1] pre-filled with
-    NaN, state [10,H,W] float64 pre-filled with NaN)"""
+    NaN, state [10,H,W] float64 pre-filled with NaN unless `state` is given)"""
     h, L = _h(), _h().lib()
     B, H, W = shape or tuple(t["normal"].shape[:3])
     nst = L.fr_sfs_state_bytes(H, W)
-    state = torch.full((10, H, W), float("nan"), dtype=torch.float64, device=DEV)
+    if state is None:
+        state = torch.full((10, H, W), float("nan"), dtype=torch.float64, device=DEV)
+    assert state.numel() * 8 == nst
     out = torch.full((B, H, W, 1), float("nan"), device=DEV)
     rc = L.fr_sfs_intensity_forward(h.ptr(t["abedo"]), h.ptr(t["normal"]), h.ptr(t["im_gray"]), h.ptr(t["abedo_new"]),
                                     h.ptr(t["normal_new"]), B, H, W, rcond, h.ptr(out), h.ptr(state), nst, _sp())

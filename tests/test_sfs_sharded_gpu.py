@@ -87,21 +87,25 @@ def one_bwd(g, t, state, shape, which=(True, True, True)):
     return o
 
 
-def moments(t, shape):
+def moments(t, shape, m=None):
     h, L = _h(), _h().lib()
     B, H, W = shape
-    m = torch.full((9, H, W), NAN, dtype=torch.float64, device=DEV)
+    if m is None:
+        m = torch.full((9, H, W), NAN, dtype=torch.float64, device=DEV)
+    assert m.numel() * 8 == L.fr_sfs_moments_bytes(H, W)
     rc = L.fr_sfs_moments(h.ptr(t["abedo"]), h.ptr(t["normal"]), h.ptr(t["im_gray"]), B, H, W, h.ptr(m), L.fr_sfs_moments_bytes(H, W),
                           _sp())
     assert rc == 0, rc
     return m
 
 
-def solve_shade(parts, t, shape):
+def solve_shade(parts, t, shape, state=None):
     h, L = _h(), _h().lib()
     B, H, W = shape
     assert parts.is_contiguous() and parts.dtype == torch.float64 and parts.numel() == parts.shape[0] * 9 * H * W
-    state = torch.full((10, H, W), NAN, dtype=torch.float64, device=DEV)
+    if state is None:
+        state = torch.full((10, H, W), NAN, dtype=torch.float64, device=DEV)
+    assert state.numel() == 10 * H * W
     out = torch.full((B, H, W, 1), NAN, device=DEV)
     rc = L.fr_sfs_solve_shade(h.ptr(parts), int(parts.shape[0]), h.ptr(t["abedo_new"]), h.ptr(t["normal_new"]), B, H, W, RS.RCOND,
                               h.ptr(out), h.ptr(state), state.numel() * 8, _sp())
@@ -109,10 +113,12 @@ def solve_shade(parts, t, shape):
     return out, state
 
 
-def backward_q(g, t, shape):
+def backward_q(g, t, shape, q=None):
     h, L = _h(), _h().lib()
     B, H, W = shape
-    q = torch.full((3, H, W), NAN, dtype=torch.float64, device=DEV)
+    if q is None:
+        q = torch.full((3, H, W), NAN, dtype=torch.float64, device=DEV)
+    assert q.numel() * 8 == L.fr_sfs_q_bytes(H, W)
     rc = L.fr_sfs_backward_q(h.ptr(g), h.ptr(t["abedo_new"]), h.ptr(t["normal_new"]), B, H, W, h.ptr(q), L.fr_sfs_q_bytes(H, W), _sp())
     assert rc == 0, rc
     return q
