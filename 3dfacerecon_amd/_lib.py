@@ -18,9 +18,10 @@ LIB_PATH = os.path.join(_PKG_DIR, "libfr_hotpath.so")
 SOURCES = ["fr_capi.hip", "fr_render.hip", "fr_decode.hip", "fr_decode_q.hip", "fr_decode_bwd.hip", "fr_render_bwd.hip", "fr_render_nbwd.hip",
            "fr_render_tbwd.hip", "fr_sfs.hip", "fr_depth_normals.hip", "fr_geometry.hip", "fr_fine_losses.hip", "fr_depth_interp.hip",
            "fr_albedo_lse.hip", "fr_synth.hip", "fr_photo.hip", "fr_mesh.hip", "fr_coverage.hip", "fr_landmark.hip",
-           "fr_landmark_solve.hip", "fr_landmark_contour.hip", "fr_photo_solve.hip"]
+           "fr_landmark_solve.hip", "fr_landmark_contour.hip", "fr_photo_solve.hip", "fr_attr_interp.hip"]
 HEADERS = [os.path.join(_CSRC, "fr_common.h"), os.path.join(_CSRC, "fr_decode_shared.h"), os.path.join(_CSRC, "fr_sfs_pinv.h"),
            os.path.join(_CSRC, "fr_owner_scatter.h"), os.path.join(_CSRC, "fr_shade.h"), os.path.join(_CSRC, "fr_landmark_shared.h"),
+           os.path.join(_CSRC, "fr_point_weight.h"),
            os.path.join(_PKG_DIR, "..", "include", "fr_hotpath.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]  # single-lane LDS atomics stay single instructions
@@ -224,6 +225,10 @@ SIGNATURES = {
     "fr_mesh_visible":                                "i:ppiiiiipp",
     "fr_mesh_lift":                                   "i:pippppiiiiipipp",
     "fr_mesh_vertex_normals":                         "i:pipppiiipip",
+    "fr_attr_interp_forward":                         "i:pipippiiiiipp",
+    "fr_attr_interp_backward":                        "i:ppipipppipiiiiiippp",
+    "fr_mesh_vertex_normals_backward":                "i:pipipppiiippiip",
+    "fr_debug_attr_interp_bwd_geom":                  "v:iiiiI",
     "fr_coverage_forward":                            "i:pippiiiiipp",
     "fr_coverage_backward_workspace_bytes":           "z:iiii",
     "fr_coverage_backward":                           "i:pppipppiiiiiipzp",

@@ -9,44 +9,9 @@
 //                            nine fp32 terms, the three record planes of the normal backward.
 //   dinterp_owner_kernel     owner_rows3: the normal backward's owner, instantiated here for this file's records.
 #include "fr_owner_scatter.h"
+#include "fr_point_weight.h"
 
 namespace fr {
-
-// get_point_weight in its source order (fp64 on the widened fp32 inputs; this TU is compiled without contraction, so every
-// product and sum rounds on its own).  P: [vertex][xyz]; (px, py) = (column, row).
-struct PointWeight {
-    double v0x, v0y, v1x, v1y;
-    double dot00, dot01, dot11, inv;
-    double w[3];   // (1 - u - v, v, u)
-    bool flat;     // den == 0: no plane, the op's own h stands
-};
-__device__ __forceinline__ PointWeight point_weight(const float (&P)[3][3], int px, int py) {
-    PointWeight s;
-    const double x1 = (double)P[0][0], y1 = (double)P[0][1];
-    s.v0x = (double)P[2][0] - x1; s.v0y = (double)P[2][1] - y1;
-    s.v1x = (double)P[1][0] - x1; s.v1y = (double)P[1][1] - y1;
-    const double v2x = (double)px - x1, v2y = (double)py - y1;
-    s.dot00 = s.v0x * s.v0x + s.v0y * s.v0y;
-    s.dot01 = s.v0x * s.v1x + s.v0y * s.v1y;
-    const double dot02 = s.v0x * v2x + s.v0y * v2y;
-    s.dot11 = s.v1x * s.v1x + s.v1y * s.v1y;
-    const double dot12 = s.v1x * v2x + s.v1y * v2y;
-    const double den = s.dot00 * s.dot11 - s.dot01 * s.dot01;
-    s.flat = den == 0;
-    s.inv = s.flat ? 0.0 : 1 / den;
-    const double u = (s.dot11 * dot02 - s.dot01 * dot12) * s.inv;
-    const double v = (s.dot00 * dot12 - s.dot01 * dot02) * s.inv;
-    s.w[0] = (1 - u) - v; s.w[1] = v; s.w[2] = u;
-    return s;
-}
-
-// the nine vertex coordinates of an ok pixel
-__device__ __forceinline__ void gather_tri(const float* __restrict__ vb, long long vpitch, const int (&id)[3], float (&P)[3][3]) {
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) P[k][c] = vb[(size_t)c * vpitch + id[k]];
-}
 
 struct DinterpFwdArgs {
     const float* vertex;    // [B,3,vpitch]
@@ -99,10 +64,9 @@ __device__ __forceinline__ void dinterp_terms(const float (&P)[3][3], float g, i
         for (int k = 0; k < 3; k++) { t[3 * k] = 0.0f; t[3 * k + 1] = 0.0f; t[3 * k + 2] = z; }
         return;
     }
-    const double gux = (s.dot11 * s.v0x - s.dot01 * s.v1x) * s.inv, guy = (s.dot11 * s.v0y - s.dot01 * s.v1y) * s.inv;
-    const double gvx = (s.dot00 * s.v1x - s.dot01 * s.v0x) * s.inv, gvy = (s.dot00 * s.v1y - s.dot01 * s.v0y) * s.inv;
+    const WeightSlopes q = weight_slopes(s);
     const double z1 = (double)P[0][2], d2 = (double)P[1][2] - z1, d3 = (double)P[2][2] - z1;
-    const double Ax = d2 * gvx + d3 * gux, Ay = d2 * gvy + d3 * guy;   // the plane's screen-space slope
+    const double Ax = d2 * q.gvx + d3 * q.gux, Ay = d2 * q.gvy + d3 * q.guy;   // the plane's screen-space slope
     const double G = (double)g;
 #pragma unroll
     for (int k = 0; k < 3; k++) {

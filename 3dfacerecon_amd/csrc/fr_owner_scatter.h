@@ -1,5 +1,5 @@
 // The owner-scatter scheme of the render backwards, stated once.  fr_render_bwd.hip (depth), fr_render_nbwd.hip (normal),
-// fr_render_tbwd.hip (texture) and fr_depth_interp.hip (interpolated depth) are built from these pieces; none of the pieces knows which gradient it serves -- what differs
+// fr_render_tbwd.hip (texture), fr_depth_interp.hip (interpolated depth) and fr_attr_interp.hip (interpolated attributes) are built from these pieces; none of the pieces knows which gradient it serves -- what differs
 // between them enters as a template parameter, a value or a functor.
 //
 // The scheme: a pixel covered by triangle t adds fp32 terms to the three vertices of t.  The reference is a serial loop (one

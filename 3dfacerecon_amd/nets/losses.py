@@ -249,6 +249,36 @@ def photometric_loss(face_net, vertices_proj, im_gray, light, alpha, weight=None
     return sse.sum() / count.sum().clamp_min(1)
 
 
+def photometric_loss_smooth(face_net, vertices_proj, picture, light, alpha, weight=None, gain=1.0, offset=0.0):
+    """photometric_loss over SMOOTH planes (opt-in; photometric_loss itself is unchanged): the render gives tri_ind alone, held
+    fixed, and the two planes shaded are FaceRecNet.smooth_planes -- the per-face albedo and the vertex normals interpolated at the
+    pixel, not the winning facet's.  The gradient reaches vertices_proj through x and y (both planes) and through the vertex
+    normals (x, y and z), and light and alpha as there.  `picture` is im_gray [B,H,W,1] with light [B,4] or im_rgb [B,H,W,3] with
+    light [B,3,9]; it should itself be shaded from smooth planes (examples/photo_fit.py --smooth does so).  -> a 0-dim float64
+    tensor, normalised as photometric_loss."""
+    fn = face_net
+    if fn.mu_tex is None or fn.pc_tex is None:
+        raise ValueError("the asset dict has no texture model (mu_tex / pc_tex)")
+    colour = light.dim() == 3
+    channels = int(picture.shape[-1]) if picture.dim() == 4 else 1
+    if colour != (channels == 3) or (colour and tuple(light.shape[1:]) != (3, 9)):
+        raise ValueError("light [B,4] goes with a one-channel picture and light [B,3,9] with im_rgb [B,H,W,3]; got light %s and a "
+                         "picture %s" % (tuple(light.shape), tuple(picture.shape)))
+    ops = _ops()
+    tex = ops.synth_texture(fn.mu_tex, fn.pc_tex, alpha)
+    ver = vertices_proj.float()
+    with torch.no_grad():
+        B, H, W = int(picture.shape[0]), int(picture.shape[1]), int(picture.shape[2])
+        image = torch.zeros((B, H, W, 3), dtype=torch.float32, device=ver.device)
+        tri_ind = ops.render_depth(ver.detach(), fn.tri, fn.vertex_code, image)[3]
+    tex_img, normal = fn.smooth_planes(ver, tex, tri_ind)
+    if colour:
+        sse, count = ops.photo_loss_rgb(tex_img, normal, tri_ind, light, picture.detach(), weight, gain, offset)
+        return sse.sum() / (3 * count.sum()).clamp_min(1)
+    sse, count = ops.photo_loss(tex_img, normal, tri_ind, light, picture.detach(), weight, gain, offset)
+    return sse.sum() / count.sum().clamp_min(1)
+
+
 def silhouette_loss(face_net, vertices_proj, target_mask):
     """The mean squared difference between the soft silhouette of the face of vertices_proj [B,3,N] (FaceRecNet.soft_mask: one
     render for tri_ind, then rendering_layer/ops.py::soft_coverage) and target_mask ([B,H,W,1] or [B,H,W], e.g. the `mask` of

@@ -449,6 +449,24 @@ class FaceRecNet:
                 self._adjacency = _ops().MeshAdjacency(adj_start, adj_tri, self.nvert, int(self.tri.shape[1]), self.device)
             return self._adjacency
 
+    def smooth_planes(self, ver, texture, tri_ind, normals=True, tex=True):
+        """The smooth counterparts (tex_img, normal) [B,H,W,3] of a render's flat planes, over that render's tri_ind [B,H,W,1]
+        (held fixed), in the layouts photo_loss, photo_loss_rgb, synth_shade* and the SfS route take:
+        tex_img  rendering_layer/ops.py::attr_interpolate of `texture` ([B,3,N], or a shared [3,N] / [1,3,N]) at the pixel, where
+                 the render has the mean of the triangle's three vertices;
+        normal   attr_interpolate of vertex_normals(ver, grad=True) over the cached adjacency(), where the render has the winner's
+                 facet normal.  It is not normalised (the consumers normalise, csrc/fr_shade.h) and (+0, +0, +0) off the face.
+        Gradients reach `texture`, and `ver` [B,3,N] through x and y (both planes) and through the vertex normals (all three
+        rows).  normals=False / tex=False: that plane is None and costs nothing."""
+        ops = _ops()
+        ver = ver.float()
+        tri_ind = tri_ind.detach()
+        tex_img = ops.attr_interpolate(ver, texture, self.tri, tri_ind) if tex else None
+        normal = None
+        if normals:
+            normal = ops.attr_interpolate(ver, ops.vertex_normals(ver, self.tri, self.adjacency(), grad=True), self.tri, tri_ind)
+        return tex_img, normal
+
     def landmark_basis(self, idx):
         """The compact image of the basis rows of the vertices `idx` (a sequence or tensor of ids in [0, N); duplicates are legal)
         as a rendering_layer/ops.py::LandmarkBasis, built on first use per id tuple and cached under the lock gram() uses: 187 KB

@@ -805,6 +805,91 @@ def depth_interpolate(ver, tri, tri_ind):
     return _DepthInterpolate.apply(ver, tri, tri_ind)
 
 
+def _attr_interp_scratch(B, H, W):
+    """(int32 elements of `records`, uint32 elements of `partial`) of fr_attr_interp_backward (include/fr_hotpath.h)"""
+    npix = H * W
+    return 2 * B * 3 * npix * 4, 2 * B * ((npix + 1023) // 1024) * 2
+
+
+class _AttrInterpolate(torch.autograd.Function):
+    """fr_attr_interp_forward / _backward (include/fr_hotpath.h, "smooth planes") as one autograd node."""
+
+    @staticmethod
+    def forward(ctx, ver, attr, tri, tri_ind):
+        h = _host()
+        if isinstance(tri_ind, torch.Tensor) and tri_ind.requires_grad:
+            raise ValueError("attr_interpolate: tri_ind requires grad, but the winning triangles are held fixed (detach it)")
+        ver_c = h.require_gpu_f32(ver, "ver")
+        attr_c = h.require_gpu_f32(attr, "attr")
+        tri_c = h.require_gpu_f32(tri, "tri")
+        ti_c = h.require_gpu_f32(tri_ind, "tri_ind")
+        _check_ver(ver_c)
+        _check_tri(tri_c)
+        if tuple(attr_c.shape) != tuple(ver_c.shape):
+            raise ValueError("attr_interpolate expects attr [B,3,nver] like ver %s (got %s)" % (tuple(ver_c.shape), tuple(attr_c.shape)))
+        if ti_c.dim() != 4 or ti_c.shape[0] != ver_c.shape[0] or ti_c.shape[3] != 1:
+            raise ValueError("attr_interpolate expects tri_ind [B,H,W,1] with the vertex's batch (got %s)" % (tuple(ti_c.shape),))
+        if tri_c.device != ver_c.device or ti_c.device != ver_c.device or attr_c.device != ver_c.device:
+            raise ValueError("attr_interpolate: ver, attr, tri and tri_ind must be on one device")
+        B, H, W = int(ti_c.shape[0]), int(ti_c.shape[1]), int(ti_c.shape[2])
+        nver, ntri = int(ver_c.shape[2]), int(tri_c.shape[1])
+        dev = ver_c.device
+        out = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = h.lib().fr_attr_interp_forward(h.ptr(ver_c), nver, h.ptr(attr_c), nver, h.ptr(tri_c), h.ptr(ti_c), B, nver, ntri, H, W,
+                                                h.ptr(out), h.stream_ptr(dev))
+        h.check(rc, "fr_attr_interp_forward")
+        ctx.save_for_backward(ver_c, attr_c, tri_c, ti_c)
+        ctx.dims = (B, nver, ntri, H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need_ver, need_attr = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_ver or need_attr):
+            return None, None, None, None
+        h = _host()
+        ver_c, attr_c, tri_c, ti_c = ctx.saved_tensors
+        B, nver, ntri, H, W = ctx.dims
+        dev = ver_c.device
+        if B * H * W == 0 or nver == 0:   # the entry point writes nothing for an empty image
+            z = lambda need: torch.zeros((B, 3, nver), dtype=torch.float32, device=dev) if need else None   # noqa: E731
+            return z(need_ver), z(need_attr), None, None
+        vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=dev) if need_ver else None
+        attr_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=dev) if need_attr else None
+        g_c = h.require_gpu_f32(g, "grad")
+        nrec, npart = _attr_interp_scratch(B, H, W)
+        # (both are dead once the launches are enqueued: one buffer per stream, under the pool's hold; `partial` behind `records`,
+        # whose byte count is a multiple of 16)
+        with torch.cuda.device(dev), _KINDS_POOL.hold("attr_interp_bwd", dev, 4 * (nrec + npart)) as ent:
+            base = ent.buf.data_ptr()
+            rc = h.lib().fr_attr_interp_backward(h.ptr(g_c), h.ptr(ver_c), nver, h.ptr(attr_c), nver, h.ptr(tri_c), h.ptr(ti_c),
+                                                 h.ptr(attr_grad), 0, h.ptr(vertex_grad), 0, B, nver, ntri, H, W,
+                                                 ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * nrec), h.stream_ptr(dev))
+        h.check(rc, "fr_attr_interp_backward")
+        return vertex_grad, attr_grad, None, None
+
+
+def attr_interpolate(ver, attr, tri, tri_ind):
+    """A three-channel per-vertex attribute interpolated at the pixel -> [B,H,W,3]: per pixel whose tri_ind ([B,H,W,1], e.g.
+    render_depth's fourth output) names a triangle (p1, p2, p3) of `tri` [3,ntri], w1 attr[p1] + w2 attr[p2] + w3 attr[p3] with the
+    barycentric weights of depth_interpolate (fr_attr_interp_forward: float64, one gather pass); (+0, +0, +0) where no triangle
+    wins, the render's flat texture lookup (the mean of the three) for a triangle without area.  Which triangle wins is not
+    re-decided, and nothing is normalised: a plane of interpolated normals is normalised by its consumer.  `ver` is [B,3,nver];
+    `attr` is [B,3,nver], or a shared [3,nver] / [1,3,nver], which is expanded to the batch and made dense first -- its gradient is
+    therefore torch's sum of the per-face gradients over the faces, in torch's order.  Gradients go to `attr` and to the x and y
+    rows of `ver` (the z row is +0): moving a vertex sideways slides the attribute under the pixel (fr_attr_interp_backward:
+    bit-reproducible; only the gradients autograd needs are formed); a tri_ind that requires grad is refused.  The node saves
+    `ver`, `attr`, `tri` and `tri_ind`."""
+    if isinstance(attr, torch.Tensor) and isinstance(ver, torch.Tensor) and ver.dim() == 3:
+        if attr.dim() == 2:
+            attr = attr.unsqueeze(0)
+        if attr.dim() == 3 and attr.shape[0] == 1 and ver.shape[0] != 1:
+            attr = attr.expand(ver.shape[0], -1, -1)
+        attr = attr.contiguous()
+    return _AttrInterpolate.apply(ver, attr, tri, tri_ind)
+
+
 class _SoftCoverage(torch.autograd.Function):
     """fr_coverage_forward / _backward (include/fr_hotpath.h, "soft coverage") as one autograd node."""
 
@@ -963,14 +1048,54 @@ class MeshAdjacency:
         self.adj_tri = torch.as_tensor(t.astype(np.int32), device=device)
 
 
-def vertex_normals(vertex, tri, adjacency):
+class _VertexNormals(torch.autograd.Function):
+    """fr_mesh_vertex_normals / _backward (include/fr_hotpath.h, "smooth planes") as one autograd node over a checked adjacency."""
+
+    @staticmethod
+    def forward(ctx, vertex, tri, adjacency):
+        normal = vertex_normals(vertex, tri, adjacency)
+        ctx.save_for_backward(_host().require_gpu_f32(vertex.detach(), "vertex"), _host().require_gpu_f32(tri.detach(), "tri"))
+        ctx.adjacency = adjacency
+        return normal
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        h = _host()
+        ver_c, tri_c = ctx.saved_tensors
+        adj = ctx.adjacency
+        B, nver, ntri = int(ver_c.shape[0]), int(ver_c.shape[2]), int(tri_c.shape[1])
+        dev = ver_c.device
+        if B == 0 or nver == 0:   # the entry point writes nothing
+            return torch.zeros((B, 3, nver), dtype=torch.float32, device=dev), None, None
+        g_c = h.require_gpu_f32(g, "normal_grad")
+        vertex_grad = torch.empty((B, 3, nver), dtype=torch.float32, device=dev)
+        # (h is dead once the two launches are enqueued: one per stream, under the pool's hold)
+        with torch.cuda.device(dev), _KINDS_POOL.hold("vertex_normals_bwd", dev, 8 * B * 3 * nver) as ent:
+            rc = h.lib().fr_mesh_vertex_normals_backward(h.ptr(g_c), nver, h.ptr(ver_c), nver, h.ptr(tri_c), h.ptr(adj.adj_start),
+                                                         h.ptr(adj.adj_tri), B, nver, ntri, h.ptr(ent.buf), h.ptr(vertex_grad), nver,
+                                                         0, h.stream_ptr(dev))
+        h.check(rc, "fr_mesh_vertex_normals_backward")
+        return vertex_grad, None, None
+
+
+def vertex_normals(vertex, tri, adjacency, grad=False):
     """Per-vertex unit normals [B,3,nver] fp32 of a vertex tensor [B,3,nver] over the triangles `tri` [3,ntri]: the area-weighted
     sum of (P2 - P1) x (P3 - P1) -- the render's orientation -- over the vertex's triangles in the order of `adjacency`, normalised;
     exactly (0, 0, 0) for a vertex without a triangle or whose sum vanishes (fr_mesh_vertex_normals: float64 chains in table
     order, one gather pass, bit-exact against numpy).  adjacency: a MeshAdjacency (checked once, e.g. FaceRecNet.adjacency()) or
-    the (adj_start, adj_tri) pair of utils/mesh_io.vertex_adjacency (checked and uploaded by this call).  Outside autograd: the
-    inputs are read as constants, the result does not require grad.  Runs on the current stream."""
+    the (adj_start, adj_tri) pair of utils/mesh_io.vertex_adjacency (checked and uploaded by this call).  grad=False (default):
+    outside autograd -- the inputs are read as constants, the result does not require grad.  grad=True: an autograd node with the
+    same forward bits whose gradient goes to `vertex` (fr_mesh_vertex_normals_backward: two float64 gathers, bit-exact against
+    numpy; the forward's rounding to fp32 is not differentiated, and a vertex whose normal is (0, 0, 0) passes nothing on); the
+    node saves `vertex`, `tri` and the adjacency.  Runs on the current stream."""
     h = _host()
+    if grad:
+        if not hasattr(adjacency, "adj_start"):
+            adj_start, adj_tri = adjacency
+            adjacency = MeshAdjacency(adj_start, adj_tri, int(vertex.shape[2]), int(tri.shape[1]), vertex.device)
+        return _VertexNormals.apply(vertex, tri, adjacency)
     ver_c = h.require_gpu_f32(vertex.detach() if isinstance(vertex, torch.Tensor) else vertex, "vertex")
     tri_c = h.require_gpu_f32(tri.detach() if isinstance(tri, torch.Tensor) else tri, "tri")
     _check_ver(ver_c)

@@ -9,6 +9,7 @@ HIP backward).
     python examples/photo_fit.py --small --fit-pose      # also fit t3d, f and the angles, from the truth perturbed
     python examples/photo_fit.py --small --colour        # the picture in colour: RGB albedo, second-order lighting per channel
     python examples/photo_fit.py --small --colour --closed-form 8 --steps 0   # ... light and alpha by alternating least squares
+    python examples/photo_fit.py --small --colour --smooth   # ... shaded from interpolated albedo and vertex normals, target included
     python examples/photo_fit.py --small --fit-pose --landmarks 68                    # ... with the landmark term beside the two
     python examples/photo_fit.py --small --fit-pose --landmarks 68 --landmarks-only   # pose from the landmarks alone: no render
     python examples/photo_fit.py --small --fit-pose --landmarks 68 --landmarks-only --landmark-init 6 --steps 0   # ... by the solver
@@ -76,6 +77,9 @@ def build_parser():
     ap.add_argument("--closed-form", type=int, nargs="?", const=8, default=0, metavar="ITERS",
                     help="with --colour: first fit light and alpha by ITERS alternations of the two linear least squares "
                          "(photo_solve_rgb); --steps 0 gives the solve alone")
+    ap.add_argument("--smooth", action="store_true", help="shade from smooth planes (FaceRecNet.smooth_planes: the albedo and the vertex "
+                                                          "normals interpolated at the pixel) in place of the render's flat ones, "
+                                                          "the target picture included")
     ap.add_argument("--landmarks", type=int, default=0, help="K > 0: add the landmark term over K vertices (utils/synth.landmark_ids)")
     ap.add_argument("--landmark-lambda", type=float, default=1.0)
     ap.add_argument("--landmarks-only", action="store_true", help="fit to the landmark term alone (needs --landmarks and --fit-pose or "
@@ -172,6 +176,18 @@ def main():
                     line_dir=torch.as_tensor(line_dir, device=dev), im_size=S)
     # --contour-fixed: every line keeps its rim vertex alone, so the correspondence cannot slide
     fit_lines = None if lines is None else (lines[:, :1] if args.contour_fixed else lines)
+    if args.smooth:
+        if args.landmarks_only or args.closed_form:
+            raise SystemExit("--smooth shades the render's planes: not with --landmarks-only or --closed-form")
+        # the batch's picture shows flat planes: shade the same face, light and albedo again from the smooth ones
+        ops = pkg("rendering_layer.ops")
+        with torch.no_grad():
+            tex_gt = ops.synth_texture(face.mu_tex, face.pc_tex, b["alpha"])
+            planes = face.smooth_planes(face.vertices_transform(b["params"]), tex_gt, b["tri_ind"])
+            if args.colour:
+                b["im_rgb"], b["im_gray"], _ = ops.synth_shade_rgb(*planes, b["tri_ind"], b["light"], gain=stream.gain, offset=stream.offset)
+            else:
+                b["im_gray"], _ = ops.synth_shade(*planes, b["tri_ind"], b["light"], gain=stream.gain, offset=stream.offset)
     im, params, light_gt, alpha_gt = b["im_gray"], b["params"], b["light"], b["alpha"]
     noise = make_noise(args.seed, dev)
     light = (light_gt + noise(light_gt, args.light_noise)).requires_grad_(True)
@@ -216,7 +232,8 @@ def main():
         if args.landmarks_only:
             return args.landmark_lambda * landmark_term(p)
         ver = vertices(p)
-        L = losses.photometric_loss(face, ver, b["im_rgb"] if args.colour else im, light, alpha, gain=stream.gain, offset=stream.offset)
+        term = losses.photometric_loss_smooth if args.smooth else losses.photometric_loss
+        L = term(face, ver, b["im_rgb"] if args.colour else im, light, alpha, gain=stream.gain, offset=stream.offset)
         if pose is not None:
             L = L + args.silhouette_lambda * losses.silhouette_loss(face, ver, b["mask"]).double()
         if lm_idx is not None:
@@ -281,7 +298,8 @@ def main():
     if pose is not None:
         after.update(pose_errors())
     print(json.dumps({"program": "photo_fit", "faces": B, "im_size": S, "steps": args.steps, "lr": args.lr, "fit_shape": bool(args.fit_shape),
-                      "fit_pose": bool(args.fit_pose), "colour": bool(args.colour), "landmarks": int(args.landmarks),
+                      "fit_pose": bool(args.fit_pose), "colour": bool(args.colour), "smooth": bool(args.smooth),
+                      "landmarks": int(args.landmarks),
                       "landmarks_only": bool(args.landmarks_only), "landmark_init": init, "closed_form": closed, "contour": contour, "yaw": args.yaw,
                       "first": first, "last": last, "ratio": last / first if first else None, "errors_before": before,
                       "errors_after": after, "finite": bool(torch.isfinite(light).all() and torch.isfinite(alpha).all())}))

@@ -1274,7 +1274,8 @@ void fr_debug_photo_solve_rgb_geom(int B, int H, int W, int* out);
 /* ---- fine mesh: the fine depth map lifted onto the vertices, visibility, vertex normals (opt-in, forward only) ----------------------
  * FineNet's output is a [B,H,W,1] plane and the coarse decode a [B,3,N] vertex tensor; the reference leaves them unjoined
  * (nets/network.py:451-453, "how to inversely convert predicted fine depth into new vertices?") and keeps the coarse vertices.  The
- * map between the two is the rasteriser's tri_ind.  Three entry points, none with a backward:
+ * map between the two is the rasteriser's tri_ind.  Three entry points, none with a backward (the vertex normals' is stated with the
+ * smooth planes below, its one consumer):
  *   vertex [B,3,vertex_pitch] (vertex_pitch >= nver, as in the interpolated depth);  tri [3,ntri], float-stored ids;  tri_ind,
  *   fine_depth, coarse_depth dense [B,H,W] (a trailing channel of 1 is the caller's);  visible, state uint8 [B,nver];  vertex_out,
  *   normal [B,3,out_pitch] (out_pitch >= nver; the columns from nver on are not written).  x is the column, y the row.
@@ -1326,6 +1327,92 @@ int fr_mesh_lift(const float* vertex, int vertex_pitch, const float* tri_ind, co
                  unsigned char* state, void* stream);
 int fr_mesh_vertex_normals(const float* vertex, int vertex_pitch, const float* tri, const int* adj_start, const int* adj_tri, int B,
                            int nver, int ntri, float* normal, int out_pitch, void* stream);
+
+/* ---- smooth planes: interpolated vertex attributes with a backward, and the backward of the vertex normals (opt-in) -------------------
+ * Every plane the render forward hands to the shading chain is flat per triangle: tex_img is (t[p1] + t[p2] + t[p3]) / 3, normal the
+ * winner's facet normal; only depth has a barycentric variant (the interpolated depth above).  These entry points are the third
+ * primitive beside "rasterise" and "shade": INTERPOLATE a three-channel per-vertex attribute at the pixel, by the interpolated depth's
+ * weights, with gradients to the attribute and to the vertex positions -- and the adjoint of fr_mesh_vertex_normals, so that a plane
+ * of interpolated vertex normals is differentiable down to the vertices.  Post-passes over a forward's tri_ind: which triangle wins a
+ * pixel is not theirs to say.  No existing plane, flag or bit changes.
+ *   vertex [B,3,vertex_pitch], attr [B,3,attr_pitch] (pitches >= nver, as in the interpolated depth);  tri [3,ntri], float-stored ids;
+ *   tri_ind dense [B,H,W,1];  out, grad dense [B,H,W,3];  attr_grad, vertex_grad dense [B,3,nver];
+ *   records int32 [2,B,3,H W,4], 16-byte aligned;  partial uint32 [2,B,ceil(H W / 1024),2], 8-byte aligned;
+ *   normal_grad [B,3,grad_pitch], vertex_grad of the normals' backward [B,3,out_pitch] (pitches >= nver);  h float64 [B,3,nver].
+ * NAMES.  The stream parameter is called `stream`, as in the sections above; tests/test_attr_interp_cpu.py holds the return codes.
+ * WHICH PIXEL.  A pixel is OK exactly as in the interpolated depth (tri_ind names t in [0, ntri) and all three ids (p1, p2, p3) of t
+ * lie in [0, nver)); NaN, -1, a value >= ntri or a bad id is not OK.  a_kc = attr[b][c][p_k].
+ * FORWARD.  w and den are the interpolated depth's, by the same lines in the same order (csrc/fr_point_weight.h), in float64 on the
+ * widened fp32 inputs, every product and sum rounded on its own.  Per channel c = 0, 1, 2:
+ *   den != 0:  out_c = fl32((w1 a_1c + w2 a_2c) + w3 a_3c)
+ *   den == 0:  out_c = the render's own texture lookup, in fp32: fl32(fl32(fl32(a_1c + a_2c) + a_3c) / 3.0f)
+ *   not OK:    out_c = +0
+ * Every element of out is written.  With attr = vertex, channel 2 is fr_depth_interp_forward's depth bit for bit on OK pixels.
+ * (tests/ref_attr_interp.py is this in numpy.)  Nothing is normalised: a consumer of a normal plane normalises (csrc/fr_shade.h does).
+ * BACKWARD.  tri_ind is held fixed and the forward's fp32 rounding is treated as the identity.  G_c = (double)grad_c.  For an OK pixel
+ * with den != 0, with gu, gv of the interpolated depth's backward:
+ *   attribute terms   term_c(p_k) = fl32(G_c w_k)
+ *   vertex terms      A_c = ((a_2c - a_1c) gvx + (a_3c - a_1c) gux,  (a_2c - a_1c) gvy + (a_3c - a_1c) guy)     channel c's slope
+ *                     S = ((G_0 A_0x + G_1 A_1x) + G_2 A_2x,  (G_0 A_0y + G_1 A_1y) + G_2 A_2y)
+ *                     term_x(p_k) = fl32(-(w_k Sx))      term_y(p_k) = fl32(-(w_k Sy))      term_z(p_k) = +0
+ * For an OK pixel with den == 0 the attribute terms are fl32(fl32(g_c * 1.0f) / 3.0f) for each of the three vertices and all nine
+ * vertex terms are +0.  Each (face, row, vertex) sum of terms is formed exactly as the interpolated depth's backward forms its own
+ * (the same record planes, the same owner workgroups, csrc/fr_owner_scatter.h), ONE SET OF RECORDS AND MAXIMA PER OUTPUT: 64-bit
+ * fixed point on a grid of 2^(e - 39 + shift), e = floor(log2 M), M the face's largest finite |term| of THAT output; integer
+ * addition in LDS; one rounding to fp32.  No float atomics, bit-reproducible, independent of the launch geometry and of the batch a
+ * face is in, and an output requested alone has the bits it has when both are requested;
+ * |result - exact sum| <= 2^-24 |sum| + n 2^(shift - 39) M for n terms.  A face with a non-finite term in an output takes fp32 LDS
+ * atomics for that output, as there.  The z row of vertex_grad is exactly +0 (accumulate 0).
+ *   attr_grad, vertex_grad: either may be NULL (not requested: its terms are not formed), not both.  attr_accumulate,
+ *                 vertex_accumulate 0: every element is written (exactly +0 where no OK pixel names the vertex); 1: each element
+ *                 becomes fl32(old + new), one add.
+ *   records, partial: caller-owned, per call in flight; set 0 is the attribute's, set 1 the vertex's.  The call needs neither
+ *                 cleared, writes nothing outside the stated shapes, and their contents after the call are unspecified.  The forward
+ *                 needs none.
+ * Checks of fr_attr_interp_*, all before any HIP call, in the order and with the codes of fr_depth_interp_*: (1) a negative size, an
+ * accumulate flag outside {0, 1} or a pitch below nver is FR_ERR_INVALID_ARG; (2) B == 0 or an empty image is FR_OK with nothing
+ * launched and nothing written (so is the backward with nver == 0); (3) a NULL tri_ind or out, both gradients NULL -- or, where
+ * triangles exist, a NULL tri, vertex, attr or grad -- is FR_ERR_INVALID_ARG; ntri >= 2^24 or more than 2^31 - 1 pixels per face is
+ * FR_ERR_UNSUPPORTED; (4) where triangles exist, a records or partial that is NULL or misaligned is FR_ERR_WORKSPACE; (5) more than
+ * 2^31 - 1 workgroups in a launch is FR_ERR_UNSUPPORTED.  With ntri == 0 the forward writes +0 everywhere and the backward zeros
+ * (or, under accumulate, nothing).  Nothing is allocated or synchronised; reentrant under the rules at the top of this file.
+ * VERTEX NORMALS, BACKWARD.  The adjoint of fr_mesh_vertex_normals as two gathers (no atomics, one fixed chain per element), in
+ * float64 with every operation rounded on its own.  The forward's single rounding of N / s to fp32 is not differentiated.
+ *   launch 1, per (face, vertex u): N and s are the forward's three chains and their length, recomputed.  Where the forward wrote
+ *             (+0, +0, +0) (s is 0 or not finite), h_u = (0, 0, 0).  Else n^ = N / s per component, g = (double)normal_grad[b][.][u],
+ *             d = (n^x gx + n^y gy) + n^z gz, and h_u = (g - n^ d) / s per component.
+ *   launch 2, per (face, vertex v): the triangles adj_tri[adj_start[v] .. adj_start[v + 1]) in table order, those with an id outside
+ *             [0, nver) skipped as in the forward.  Hs = h[p1], + h[p2] if p2 != p1, + h[p3] if p3 is neither (every distinct vertex
+ *             of a triangle counted it once).  For each position k = 1, 2, 3 in this order with p_k == v, the three chains (from
+ *             +0.0) add  (P2 - P3) x Hs (k = 1),  (P3 - P1) x Hs (k = 2),  Hs x (P2 - P1) (k = 3), each cross product p x q as
+ *             (py qz - pz qy, pz qx - px qz, px qy - py qx) -- the forward's order.  vertex_grad = the chains rounded to fp32 once;
+ *             accumulate 1: fl32(old + that).
+ * h is caller-owned typed scratch, 8-byte aligned, per call in flight; the call needs it not cleared and leaves its contents
+ * unspecified.  The table conventions and the host-side table check are the forward's.  Checks, in this order: (1) a negative size,
+ * a pitch below nver or accumulate outside {0, 1} is FR_ERR_INVALID_ARG; (2) B == 0 or nver == 0 is FR_OK with nothing launched;
+ * (3) a NULL normal_grad, vertex, vertex_grad -- or, where triangles exist, a NULL tri, adj_start, adj_tri -- is FR_ERR_INVALID_ARG;
+ * (4) ntri >= 2^24 or more than 2^31 - 1 workgroups of 256 vertices is FR_ERR_UNSUPPORTED; (5) an h that is NULL or misaligned is
+ * FR_ERR_WORKSPACE.
+ * Kernels (csrc/fr_attr_interp.hip, csrc/fr_mesh.hip): the interpolation's forward is one gather pass, one lane per pixel (three id
+ * gathers, six coordinate and nine attribute gathers out of L2, three stores; no LDS, no atomics); its backward one records pass
+ * (256 threads x 4 pixels, every gather issued before the first use) that writes the terms of the requested outputs, then the shared
+ * owner once per requested output.
+ * Time: tools/attr_interp_probe.py (profiles/attr_interp.json) measures every call at 32 and 64 faces of the full mesh at 200 x 200
+ * beside the bytes each must move, a 512 MiB copy, fr_depth_interp_* on the same inputs and the same operators from stock torch ops
+ * (DESIGN.md 4.4u). */
+int fr_attr_interp_forward(const float* vertex, int vertex_pitch, const float* attr, int attr_pitch, const float* tri,
+                           const float* tri_ind, int B, int nver, int ntri, int H, int W, float* out, void* stream);
+int fr_attr_interp_backward(const float* grad, const float* vertex, int vertex_pitch, const float* attr, int attr_pitch,
+                            const float* tri, const float* tri_ind, float* attr_grad, int attr_accumulate, float* vertex_grad,
+                            int vertex_accumulate, int B, int nver, int ntri, int H, int W, int* records, unsigned int* partial,
+                            void* stream);
+int fr_mesh_vertex_normals_backward(const float* normal_grad, int grad_pitch, const float* vertex, int vertex_pitch, const float* tri,
+                                    const int* adj_start, const int* adj_tri, int B, int nver, int ntri, double* h,
+                                    float* vertex_grad, int out_pitch, int accumulate, void* stream);
+
+/* The attribute interpolation backward's launch geometry (no GPU needed; the launcher reads the same function): out[6] as
+ * fr_debug_depth_interp_bwd_geom; both outputs share it.  Used by tests/test_attr_interp_gpu.py. */
+void fr_debug_attr_interp_bwd_geom(int B, int nver, int H, int W, int* out);
 
 /* ---- soft coverage: an antialiased silhouette with an x, y backward (opt-in) ---------------------------------------------------------
  * Every gradient above holds tri_ind fixed and every plane is flat per triangle in the screen plane: when a face moves sideways or is
