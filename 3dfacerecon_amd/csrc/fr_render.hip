@@ -30,41 +30,53 @@
 //
 // Bound: HBM -- 1.28 MB of output planes per face is the dominant algorithmic traffic.
 #include "fr_common.h"
+#include <stddef.h>
 
 namespace fr {
 
-struct RenderArgs {
+// The leading 128 bytes are the emit kernel's whole argument set, and their first 88 everything it reads before its first vector
+// load: adjacent and 64-byte aligned, so a workgroup's entry is one wide scalar fetch, not a chain of narrow ones.
+struct alignas(64) RenderArgs {
     const float* vertex;   // [B,3,vpitch] rows (vpitch == nver: the dense tensor of the op surface)
-    long long vpitch;      // floats between consecutive coordinate rows of `vertex`
-    const float* tri;      // [3,ntri]
-    const float* texture;  // [tex_batch,3,nver]
-    float* depth;          // [B,H,W,1]
-    float* tex_img;        // [B,H,W,3]
-    float* normal;         // [B,H,W,3]
-    float* tri_ind;        // [B,H,W,1]
-    int B, nver, ntri, H, W;
-    int rows;              // rows per strip
-    int strips;            // strips per face
+    long long face_stride_b;  // bytes between consecutive faces of `vertex` (3 * vpitch * 4)
+    long long vpitch_b;    // bytes between consecutive coordinate rows of `vertex` (vpitch * 4)
+    const int4* tri4_lane; // tri4 + nseg*SEG + 1: the triangle table in the emit kernel's lane order; [-1] is the header slot
     long long tex_stride;  // 0 (shared texture) or 3*nver
+    int nseg;
+    uint32_t nseg_magic;   // lid / nseg == umulhi(2 * lid, nseg_magic) >> nseg_shift for every lid < B * nseg (emit_index_magic
+    uint32_t nseg_shift;   // proves it on the host; a grid it cannot prove it for does not take the binned path)
+    int emit_q, emit_r;    // (B * nseg) / 8 and % 8: the emit grid's XCD remap constants
+    int strips;            // strips per face
+    float wm1, hm1;        // (float)(W-1), (float)(H-1)
+    int use_filter;        // A/B knob FR_EMIT_FILTER: 0 sends every pixel through the fp64 sequence
+    int nver, ntri;
+    uint32_t rows_magic;   // ceil(2^32 / rows): y / rows == umulhi(y, magic) for y, rows < 2^16
+    const float* texture;  // [tex_batch,3,nver]
+    float4* tritex_ws;     // [tex_batch][ntri] per-triangle texture mean (one copy when the texture is shared)
+    const int4* tri4;      // [nseg*SEG] pre-validated triangles {4*p1, 4*p2, 4*p3, valid} by id, [1] header, [nseg*SEG] the same in
+                           // the emit kernel's lane order, .w = valid | local index << 1 (pack_tri_kernel)
     // binned path workspace
     uint4* recs;           // [B][nseg][SEG][2] 16-byte records, each followed by its un-normalised normal (xyz as a float4): the
                            // resolver reads both, so they share a 32-byte half line
     uint16_t* segoff;      // [B][OFF_STRIDE][nseg] bucket offsets, bucket-major: the resolver's thread = segment reads of one bucket
                            // are one coalesced line (segment-major, every thread touched its own 128-byte line)
-    float4* tritex_ws;     // [tex_batch][ntri] per-triangle texture mean (one copy when the texture is shared)
-    int nseg;
+    // ---- byte 128: what only the resolver and the scan path read ----
+    long long vpitch;      // floats between consecutive coordinate rows of `vertex`
+    const float* tri;      // [3,ntri]
+    float* depth;          // [B,H,W,1]
+    float* tex_img;        // [B,H,W,3]
+    float* normal;         // [B,H,W,3]
+    float* tri_ind;        // [B,H,W,1]
+    int B, H, W;
+    int rows;              // rows per strip
     // fused rendering-layer outputs (fr_rendering_layer_forward; network.py:185-199 folded into the resolver)
     const float* im_gray;  // [B,H,W,1]
     float* net_in;         // [B,H,W,7] = [mask*im | pncc x3 | normalised normal x3]  (network.py:122)
     float* depth_img;      // [B,H,W,1] = max(depth, 1e-6)
-    float wm1, hm1;        // (float)(W-1), (float)(H-1)
-    uint32_t rows_magic;   // ceil(2^32 / rows): y / rows == umulhi(y, magic) for y, rows < 2^16
     int resolve_opt;       // A/B knob FR_RESOLVE_OPT: 1 = single-trip bins keep records + normals in registers
-    int use_filter;        // A/B knob FR_EMIT_FILTER: 0 sends every pixel through the fp64 sequence
-    const int4* tri4;      // [nseg*SEG] pre-validated triangles {4*p1, 4*p2, 4*p3, valid} by id, [1] header, [nseg*SEG] the same in
-                           // the emit kernel's lane order, .w = valid | local index << 1 (pack_tri_kernel)
-    uint32_t nseg_magic;   // ceil(2^32 / nseg): lid / nseg == umulhi(lid, magic) (launcher checks the range)
 };
+static_assert(offsetof(RenderArgs, rows_magic) + 4 == 88 && offsetof(RenderArgs, segoff) + 8 == 128 &&
+              offsetof(RenderArgs, vpitch) == 128, "the emit kernel's arguments are the leading 128 bytes");
 
 constexpr int SEG = 504;         // triangles (and record capacity) per segment: 504 * 40 B of queue + counters <= 20 KiB,
                                  // so eight emit workgroups share a CU's 160 KiB of LDS (8 waves per SIMD)
@@ -74,11 +86,12 @@ constexpr int SMALL_W = 8, SMALL_H = 4;  // hit-mask window: bit = dy*8 + dx
 
 // XCD-aware block remap (bijective for any grid): blocks that share blockIdx%8 share an XCD/L2, so give each
 // XCD a contiguous run of bins -- all work on a face then meets that face's vertices (and records) in one L2.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (bid >> 3);
+// (q = nwg / 8, r = nwg % 8: XCD x owns q + 1 blocks if x < r, else q, so its run starts at x * q + min(x, r) -- no branch)
+__device__ __forceinline__ int xcd_remap_qr(int bid, int q, int r) {
+    const int xcd = bid & 7;
+    return xcd * q + min(xcd, r) + (bid >> 3);
 }
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) { return xcd_remap_qr(bid, nwg >> 3, nwg & 7); }
 
 // three consecutive floats as ONE 12-byte store (global_store_dwordx3): a scattered per-pixel normal costs one
 // cache-line transaction per lane instead of three, and a lane-contiguous plane write one instruction instead of three
@@ -535,6 +548,9 @@ struct NoEmitProbe {
     template <int ID> __device__ __forceinline__ void stamp() {}
     __device__ __forceinline__ void finish(int) {}
 };
+// A predicate as a lane mask, and a lane's own bit of one (wave64; every lane is active where the emit kernel uses them).
+__device__ __forceinline__ unsigned long long lanes(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ bool lane_of(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 constexpr int EMIT_BLOCK = 256;
 constexpr int TPT = 2;                 // triangles per thread in phase A
 constexpr int EMIT_ACTIVE = SEG / TPT; // threads that own triangles in phase A (252 of 256)
@@ -560,7 +576,7 @@ __device__ __forceinline__ void emit_body(const RenderArgs& a, const int lid, un
     unsigned long long& qn2 = *reinterpret_cast<unsigned long long*>(lds + EMIT_LDS_QN2);
     const int tid = threadIdx.x;
     if constexpr (PR::abl == 1) return;   // (ablation: empty workgroups)
-    const int b = a.nseg_magic ? (int)__umulhi((uint32_t)lid, a.nseg_magic) : lid / a.nseg;  // lid / nseg
+    const int b = (int)(__umulhi((uint32_t)lid << 1, a.nseg_magic) >> a.nseg_shift);  // lid / nseg (emit_index_magic)
     const int seg = lid - b * a.nseg;
     const int S = a.strips;
     if (tid < 2 * S) cnt[tid] = 0;
@@ -569,29 +585,32 @@ __device__ __forceinline__ void emit_body(const RenderArgs& a, const int lid, un
     // there anyway, and an LDS-only barrier -- no vmcnt(0) fence -- leaves the gathers in flight)
 
     const int nver = a.nver, ntri = a.ntri;
-    const float* __restrict__ vx = a.vertex + (size_t)b * 3 * a.vpitch;
-    const float* __restrict__ vy = vx + a.vpitch;
-    const float* __restrict__ vz = vy + a.vpitch;
+    const char* const vbase = reinterpret_cast<const char*>(a.vertex) + (unsigned long long)(uint32_t)b * (unsigned long long)a.face_stride_b;
+    const float* __restrict__ vx = reinterpret_cast<const float*>(vbase);
+    const float* __restrict__ vy = reinterpret_cast<const float*>(vbase + a.vpitch_b);
+    const float* __restrict__ vz = reinterpret_cast<const float*>(vbase + 2 * a.vpitch_b);
 
     // ---------------- phase A: pre-validated ids, gathers, bbox reject ----------------
     {
-        const int4 hdr = a.tri4[(size_t)a.nseg * SEG];  // uniform: which (nver, ntri) the table was packed for
-        const int table_ok = (int)(hdr.x == TRI4_MAGIC) & (int)(hdr.y == nver) & (int)(hdr.z == ntri);
-        bool surv[TPT], single[TPT];
+        // Predicates are kept as LANE MASKS (64-bit scalars, one bit per lane) from the compares to the compaction: each ballot of
+        // a compare is that compare's own result register, the logic between them is scalar, and a lane reads its bit back with
+        // the inverse ballot (the mask used as the condition).  As bools they went through 0/1 vector registers at every join.
+        unsigned long long surv[TPT], single[TPT], valid[TPT];
         int4 e[TPT];
         float x1[TPT], x2[TPT], x3[TPT], y1[TPT], y2[TPT], y3[TPT], z1[TPT], z2[TPT], z3[TPT];
-        bool valid[TPT];
         // the segment's triangles in the lane order pack_tri_kernel chose: position -> {offsets, valid | local index << 1}
-        const int4* __restrict__ tri4p = a.tri4 + ((size_t)a.nseg * SEG + 1) + (size_t)seg * SEG;
+        const int4* __restrict__ tri4p = a.tri4_lane + (size_t)(uint32_t)seg * SEG;
         int tl[TPT];
 #pragma unroll
         for (int u = 0; u < TPT; u++) {
             // one unconditional 16-byte load (saddr + 32-bit offset form); no short-circuit on .w, or the compiler
             // splits the load and serialises the two halves
             e[u] = *reinterpret_cast<const int4*>(reinterpret_cast<const char*>(tri4p) + (size_t)((uint32_t)min(u * EMIT_ACTIVE + tid, SEG - 1) << 4));
-            valid[u] = ((int)(tid < EMIT_ACTIVE) & e[u].w & table_ok) != 0;   // (a valid entry has t < ntri: pack_tri_kernel)
             tl[u] = e[u].w >> 1;
         }
+        // The header slot says which (nver, ntri) the table was packed for.  It is fetched here, behind the table loads, and first
+        // looked at below the barrier: its arrival is awaited with the zeroed counters', not in front of the table -> gather chain.
+        const int4 hdr = a.tri4_lane[-1];  // uniform
         if constexpr (PR::abl == 2) {   // (ablation: the table loads only)
             if (e[0].x + e[1].y == 0x7fffffff) qd[tid].x = 1;
             return;
@@ -611,44 +630,41 @@ __device__ __forceinline__ void emit_body(const RenderArgs& a, const int lid, un
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // counters zeroed (first used by the compaction below)
         pr.template stamp<0>();
+        const bool table_ok = (hdr.x == TRI4_MAGIC) & (hdr.y == nver) & (hdr.z == ntri);
+        const unsigned long long owners = lanes(tid < EMIT_ACTIVE) & (table_ok ? ~0ull : 0ull);
+        const unsigned long long precull = (a.use_filter & 2) ? ~0ull : 0ull;
 #pragma unroll
         for (int u = 0; u < TPT; u++) {
+            valid[u] = owners & lanes((e[u].w & 1) != 0);   // (a valid entry has t < ntri: pack_tri_kernel)
             // bbox = ceil(min) .. floor(max) per axis and the whole-triangle reject of render_depth_op.cc:276-283, in the
             // float domain.  A NaN coordinate makes PointInTri false for every pixel whatever the bbox (all dot products
             // turn NaN), so the NaN-ignoring v_min3/v_max3 are equivalent to the reference's macros here; the
             // comparisons reject NaN / +-inf / out-of-int-range bounds exactly where (int) gives INT_MIN on x86.
             const float fx0 = ceilf(fminf(fminf(x1[u], x2[u]), x3[u])), fx1 = floorf(fmaxf(fmaxf(x1[u], x2[u]), x3[u]));
             const float fy0 = ceilf(fminf(fminf(y1[u], y2[u]), y3[u])), fy1 = floorf(fmaxf(fmaxf(y1[u], y2[u]), y3[u]));
-            surv[u] = valid[u] && (fx0 >= 0.0f) && (fy0 >= 0.0f) && (fx1 <= a.wm1) && (fy1 <= a.hm1) && !(fx1 < fx0) &&
-                      !(fy1 < fy0);
-            single[u] = (fx0 == fx1) && (fy0 == fy1);
+            surv[u] = valid[u] & lanes(fx0 >= 0.0f) & lanes(fy0 >= 0.0f) & lanes(fx1 <= a.wm1) & lanes(fy1 <= a.hm1) &
+                      lanes(!(fx1 < fx0)) & lanes(!(fy1 < fy0));
+            single[u] = lanes(fx0 == fx1) & lanes(fy0 == fy1);
             // A bbox with a single pixel centre (78 % of the survivors on a sub-pixel mesh) misses that centre 70 % of the
             // time.  The certified fp32 inside test of phase B (same expressions, same pixel, see there) is cheap
             // enough to run here, on the sparse lanes: a triangle it certifies as a MISS can emit nothing and is dropped
             // before the compaction, so that phase B runs on less than half the lanes; anything it cannot certify stays.  (Flagging
             // the certified HITS so that phase B skips their test measured no further gain.)
-            if ((a.use_filter & 2) && surv[u] && single[u]) {
+            // (Evaluated on every lane, with no branch and no short-circuit: some lane of a wave nearly always needs it, so a
+            // per-lane branch saves no issue slot.)
+            {
                 const float v0x = x3[u] - x1[u], v0y = y3[u] - y1[u], v1x = x2[u] - x1[u], v1y = y2[u] - y1[u];
                 const float D = __builtin_fmaf(v0x, v1y, -(v0y * v1x));   // (fused: one rounding fewer than the bound assumes)
                 const float M0 = fmaxf(fmaxf(fabsf(v0x), fabsf(v0y)), fmaxf(fabsf(v1x), fabsf(v1y)));
                 const float S = M0 * M0;
                 const float v2x = fx0 - x1[u], v2y = fy0 - y1[u];
                 const float A = __builtin_fmaf(v2x, v1y, -(v2y * v1x)), Bq = __builtin_fmaf(v0x, v2y, -(v0y * v2x)), C = (D - A) - Bq;
-                const bool certain = (M0 < 1073741824.0f) && (M0 > 9.094947017729282e-13f) && (fabsf(D) >= 0.00390625f * S) &&
-                                     fminf(fminf(fabsf(A), fabsf(Bq)), fabsf(C)) >= 1.52587890625e-05f * S;
-                const bool in = D > 0.0f ? fminf(fminf(A, Bq), C) > 0.0f : fmaxf(fmaxf(A, Bq), C) < 0.0f;
-                if (certain && !in) surv[u] = false;
-            }
-            // per-triangle texture mean ((t1+t2)+t3)/3 in fp32 (render_depth_op.cc:223) when the texture is shared by the
-            // batch: computed once, by face 0's workgroups, for every valid triangle
-            if (a.tex_stride == 0 && b == 0 && valid[u]) {
-                float tm[3];
-#pragma unroll
-                for (int j = 0; j < 3; j++) {
-                    const float* tj = a.texture + (size_t)j * nver;
-                    tm[j] = div3((ld_boff(tj, e[u].x) + ld_boff(tj, e[u].y)) + ld_boff(tj, e[u].z));
-                }
-                a.tritex_ws[seg * SEG + tl[u]] = make_float4(tm[0], tm[1], tm[2], 0.0f);
+                const unsigned long long certain = lanes(M0 < 1073741824.0f) & lanes(M0 > 9.094947017729282e-13f) &
+                                                   lanes(fabsf(D) >= 0.00390625f * S) &
+                                                   lanes(fminf(fminf(fabsf(A), fabsf(Bq)), fabsf(C)) >= 1.52587890625e-05f * S);
+                const unsigned long long dpos = lanes(D > 0.0f);
+                const unsigned long long in = (dpos & lanes(fminf(fminf(A, Bq), C) > 0.0f)) | (~dpos & lanes(fmaxf(fmaxf(A, Bq), C) < 0.0f));
+                surv[u] &= ~(precull & single[u] & certain & ~in);
             }
         }
         pr.template stamp<1>();   // gathers back, bbox + pre-cull done
@@ -660,8 +676,8 @@ __device__ __forceinline__ void emit_body(const RenderArgs& a, const int lid, un
         // zero-init barrier at kernel entry: 12.4 k vs 12.2 k cycles of wave life in the stamped build, and 45-46 vs 42.5-44 us
         // for the kernel in three bench sessions each.)
         static_assert(TPT == 2, "compaction below is written for two triangles per thread");
-        const unsigned long long ms0 = __ballot(surv[0] && single[0]), ms1 = __ballot(surv[1] && single[1]);
-        const unsigned long long mm0 = __ballot(surv[0] && !single[0]), mm1 = __ballot(surv[1] && !single[1]);
+        const unsigned long long ms0 = surv[0] & single[0], ms1 = surv[1] & single[1];
+        const unsigned long long mm0 = surv[0] & ~single[0], mm1 = surv[1] & ~single[1];
         const uint32_t cs0 = (uint32_t)__popcll(ms0), cs1 = (uint32_t)__popcll(ms1);
         const uint32_t cm0 = (uint32_t)__popcll(mm0), cm1 = (uint32_t)__popcll(mm1);
         unsigned long long wb = 0;
@@ -671,14 +687,33 @@ __device__ __forceinline__ void emit_body(const RenderArgs& a, const int lid, un
         const uint32_t bbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wb >> 32));
 #pragma unroll
         for (int u = 0; u < TPT; u++) {
-            if (surv[u]) {
-                const unsigned long long m = single[u] ? (u ? ms1 : ms0) : (u ? mm1 : mm0);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                const uint32_t slot = single[u] ? fbase + (u ? cs0 : 0u) + rank
-                                                : (uint32_t)(SEG - 1) - (bbase + (u ? cm0 : 0u) + rank);
+            if (lane_of(surv[u])) {
+                // rank within either class straight from the (scalar) masks; the lane's own class picks the slot
+                const unsigned long long ms = u ? ms1 : ms0, mm = u ? mm1 : mm0;
+                const uint32_t rs = __builtin_amdgcn_mbcnt_hi((uint32_t)(ms >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ms, 0u));
+                const uint32_t rm = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
+                const uint32_t slot = lane_of(single[u]) ? fbase + (u ? cs0 : 0u) + rs
+                                                : (uint32_t)(SEG - 1) - (bbase + (u ? cm0 : 0u) + rm);
                 qa[slot] = make_float4(x1[u], y1[u], x2[u], y2[u]);
                 qb[slot] = make_float4(x3[u], y3[u], z1[u], z2[u]);
                 qd[slot] = make_uint2(__float_as_uint(z3[u]), (uint32_t)tl[u]);
+            }
+        }
+        // per-triangle texture mean ((t1+t2)+t3)/3 in fp32 (render_depth_op.cc:223) when the texture is shared by the
+        // batch: computed once, by face 0's workgroups, for every valid triangle.  (Behind the compaction: between the compares
+        // and it, the branch kept every compare's mask live across itself, past the scalar registers eight waves per SIMD allow.)
+        if (a.tex_stride == 0 && b == 0) {
+#pragma unroll
+            for (int u = 0; u < TPT; u++) {
+                if (lane_of(valid[u])) {
+                    float tm[3];
+#pragma unroll
+                    for (int j = 0; j < 3; j++) {
+                        const float* tj = a.texture + (size_t)j * nver;
+                        tm[j] = div3((ld_boff(tj, e[u].x) + ld_boff(tj, e[u].y)) + ld_boff(tj, e[u].z));
+                    }
+                    a.tritex_ws[seg * SEG + tl[u]] = make_float4(tm[0], tm[1], tm[2], 0.0f);
+                }
             }
         }
     }
@@ -841,7 +876,7 @@ __global__ __launch_bounds__(EMIT_BLOCK) void raster_emit_kernel(RenderArgs a) {
     PR pr;
     pr.begin();
     __shared__ __attribute__((aligned(16))) unsigned char lds[EMIT_LDS_BYTES];
-    emit_body<PR>(a, xcd_remap(blockIdx.x, gridDim.x), lds, pr);
+    emit_body<PR>(a, xcd_remap_qr(blockIdx.x, a.emit_q, a.emit_r), lds, pr);   // (grid = B * nseg: prepare_render)
 }
 
 // ---- binned path, kernel 2: per (face, strip) LDS resolve + output ----------------------------------------
@@ -1264,6 +1299,26 @@ struct RenderGeom {
 };
 constexpr size_t kLdsMax = 160 * 1024;
 
+// Constants of the emit kernel's division-free lid -> face: lid / nseg == umulhi(2 * lid, magic) >> shift for EVERY lid < nlid.
+// With magic = ceil(2^(31 + shift) / nseg) and e = magic * nseg - 2^(31 + shift) (0 <= e < nseg), the right-hand side is
+// floor(lid / nseg + lid * e / (nseg * 2^(31 + shift))); lid / nseg has a fractional part of at most (nseg - 1) / nseg, so the
+// floor is exact while lid * e < 2^(31 + shift).  That is checked here for the largest lid of the grid, and the smallest shift that
+// passes is taken (nseg a power of two, 1 included: e = 0, shift = 0).  false = no 32-bit magic proves it: not launched.
+bool emit_index_magic(long long nlid, int nseg, uint32_t* magic, uint32_t* shift) {
+    if (nseg < 1 || nlid < 1 || nlid > 0x7FFFFFFFll) return false;   // 2 * lid must fit 32 bits
+    for (uint32_t sh = 0; sh < 32; sh++) {
+        const unsigned long long two = 1ull << (31 + sh);
+        const unsigned long long m = (two + (unsigned)nseg - 1) / (unsigned)nseg;
+        if (m > 0xFFFFFFFFull) break;
+        const unsigned long long e = m * (unsigned)nseg - two;
+        if (e * (unsigned long long)(nlid - 1) < two) {   // (e < 2^31, nlid <= 2^31: no overflow)
+            *magic = (uint32_t)m; *shift = sh;
+            return true;
+        }
+    }
+    return false;
+}
+
 // bins: enough workgroups to cover the 256 CUs a few times over, never more rows than fit in LDS
 RenderGeom render_geom(int B, int ntri, int H, int W, int rows_override) {
     RenderGeom g{};
@@ -1290,8 +1345,10 @@ RenderGeom render_geom(int B, int ntri, int H, int W, int rows_override) {
     // shorter than the window (a very wide image, or the override) it could span three and the emit kernel's bucket
     // choice would drop hits -- such shapes take the scan path instead.
     const bool window_fits = rows >= fr::SMALL_H || g.strips <= 1;
+    uint32_t magic, shift;
     g.binned_ok = rows_max >= 1 && window_fits && g.strips <= fr::MAX_STRIPS && H <= 0xFFFF && W <= 0xFFFF &&
-                  (long long)B * g.nseg <= 0x7FFFFFFFll;
+                  (long long)B * g.nseg <= 0x7FFFFFFFll &&
+                  ((long long)B * g.nseg < 1 || emit_index_magic((long long)B * g.nseg, g.nseg, &magic, &shift));
     return g;
 }
 RenderGeom render_geom(int B, int ntri, int H, int W) { return render_geom(B, ntri, H, W, fr::opt(fr::OPT_RENDER_ROWS)); }
@@ -1400,6 +1457,8 @@ static int prepare_render(const float* vertex, const float* tri, const float* te
     if ((long long)B * g.strips > 0x7FFFFFFFll) return FR_ERR_UNSUPPORTED;
     a.vertex = vertex; a.tri = tri; a.texture = texture;
     a.vpitch = vpitch > 0 ? vpitch : nver;
+    a.vpitch_b = a.vpitch * (long long)sizeof(float);
+    a.face_stride_b = 3 * a.vpitch_b;
     a.depth = depth; a.tex_img = tex_img; a.normal = normal; a.tri_ind = tri_ind;
     a.B = B; a.nver = nver; a.ntri = ntri; a.H = H; a.W = W;
     a.rows = g.rows; a.strips = g.strips;
@@ -1412,7 +1471,8 @@ static int prepare_render(const float* vertex, const float* tri, const float* te
     a.resolve_opt = opt(OPT_RESOLVE_OPT);
     a.use_filter = opt(OPT_EMIT_FILTER);  // bit 0: certified fp32 inside test, bit 1: single-pixel pre-cull in phase A
     a.rows_magic = g.rows > 1 ? (uint32_t)((0x100000000ull + (unsigned)g.rows - 1) / (unsigned)g.rows) : 0u;
-    a.tri4 = nullptr; a.nseg_magic = 0;
+    a.tri4 = nullptr; a.tri4_lane = nullptr;
+    a.nseg_magic = 0; a.nseg_shift = 0; a.emit_q = 0; a.emit_r = 0;
     const bool binned = g.binned_ok && ntri > 0 && opt(OPT_RENDER_IMPL) != 1;
     *binned_out = binned;
     if (fused && !binned) return FR_ERR_UNSUPPORTED;  // the caller falls back to the unfused op + elementwise post-processing
@@ -1425,9 +1485,10 @@ static int prepare_render(const float* vertex, const float* tri, const float* te
     a.segoff = reinterpret_cast<uint16_t*>(wsp + g.recs_bytes + g.nrm_bytes);
     a.tritex_ws = reinterpret_cast<float4*>(wsp + g.recs_bytes + g.segoff_bytes + g.nrm_bytes);
     a.tri4 = reinterpret_cast<int4*>(wsp + g.recs_bytes + g.segoff_bytes + 2 * g.nrm_bytes);
-    // lid / nseg through the 2^32 reciprocal is exact while lid * (magic * nseg - 2^32) < 2^32, i.e. B * nseg^2 < 2^32
-    a.nseg_magic = ((unsigned long long)B * g.nseg * g.nseg < 0x100000000ull && g.nseg > 1)
-                       ? (uint32_t)((0x100000000ull + (unsigned)g.nseg - 1) / (unsigned)g.nseg) : 0u;
+    a.tri4_lane = a.tri4 + ((size_t)g.nseg * SEG + 1);
+    const long long nlid = (long long)B * g.nseg;   // the emit grid
+    if (nlid > 0 && !emit_index_magic(nlid, g.nseg, &a.nseg_magic, &a.nseg_shift)) return FR_ERR_UNSUPPORTED;  // (binned_ok: never)
+    a.emit_q = (int)(nlid >> 3); a.emit_r = (int)(nlid & 7);
     return FR_OK;
 }
 
